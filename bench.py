@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py — requests/s matched by the MI355X WAF batch matcher on BASELINE.json's workload.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
 
 With N > 1 as a plain command it re-executes itself under `python -m torch.distributed.run --nnodes=1 --nproc-per-node N
 --master-addr 127.0.0.1` (one rank per GPU); launched by torch.distributed.run it reads RANK / LOCAL_RANK / WORLD_SIZE / MASTER_*.
@@ -12,16 +12,24 @@ synthetic requests that is already resident in HBM. Default workload: BASELINE.j
 ("1k-rule WAF") is quoted on; it fits one GPU. With N GPUs every rank evaluates its own slab of the same seeded stream (weak
 scaling); the only collective is the RCCL all-reduce of the four action counters (`rccl_ranks` = the world size that all-reduce saw).
 `--config 5` is BASELINE.json configs[4]: 4096 rules over 5 + 64 string fields (header-field extension), 1M-request batches,
-with per-batch latency percentiles; the default run carries a short leg of it as `config5`.
+with per-batch latency percentiles; the `--full` run carries a short leg of it as `config5`.
 
+A plain run does only what the headline figure needs: generate, compile, tune, upload, W warmup + K timed steps, the result line.
 Prints ONE JSON line on rank 0 (contract in the task statement) including
   roofline       HBM roofline of the dominant kernel (filter_kernel: the launch that streams the request bytes), from HIP events
                  recorded on the launch stream during the timed steps; algorithmic bytes per SURVEY.md §8(d) / DESIGN.md §6
+`--full` adds the side measurements and checks, each a run of its own after the headline's timed steps:
   traffic_modes  the same engine UNTUNED (no traffic sample) and on the ADVERSARIAL variant of the stream (near misses of the rule
                  literals, maximum-length fields), next to the headline (tuned on a benign sample disjoint from the timed batch)
   config5        BASELINE.json configs[4] on this GPU: requests/s, per-batch latency p50 / p99, adversarial, untuned
   cpu_baseline   the CPU oracle ("port": a restatement of the reference's interpreter loop, NOT the Rust binary) timed on this
                  box's host cores over a bounded sample of the same request stream (rank 0, N=1 only)
+  and the measured copy bandwidth, PCIe-inclusive host batches, the native micro-batcher, the residual-rule leg, the RCCL check.
+
+`--dump-outputs DIR` writes what the timed path handed its caller in the last timed step (rank 0's slab): the four action counters
+(`action_counts.npy`, float64) and each request's verdict (`verdict_action.npy`, `verdict_rule_idx.npy`, float32; rule_idx
+sentinels as signed values, e.g. -1 = no rule). A batch of more than DUMP_MAX_REQUESTS requests is sampled: the sorted indices
+np.random.default_rng(DUMP_SEED).choice(n, DUMP_MAX_REQUESTS, replace=False). Same arguments, same inputs: the stream is seeded.
 """
 from __future__ import annotations
 
@@ -38,6 +46,8 @@ sys.path.insert(0, ROOT)
 HBM_PEAK_GBS = 8000.0  # MI355X HBM3E spec peak (MI355X_MICROARCH.md); ~5.4-6.3 TB/s is the measured copy ceiling
 DEFAULT_N = {1: 10_000, 2: 1_000_000, 3: 10_000_000, 5: 1_000_000}
 TUNE_N = 32768
+DUMP_MAX_REQUESTS = 4_000_000  # two float32 verdict columns: 32 MB
+DUMP_SEED = 0
 
 
 def effective_cpus():
@@ -309,6 +319,24 @@ def slab_of(scaling, n_arg, rank, world):
     return n_arg, n_arg * world, rank * n_arg
 
 
+def dump_outputs(path, out, counts):
+    """--dump-outputs: the verdicts of the last timed step (`out`, (n, 2) int32 on the device: action, rule_idx) — a fixed seeded
+    sample of DUMP_MAX_REQUESTS of them when the batch is larger — and its four action counters, as .npy files under `path`."""
+    import numpy as np
+    import torch
+
+    n = out.shape[0]
+    if n > DUMP_MAX_REQUESTS:
+        idx = np.sort(np.random.default_rng(DUMP_SEED).choice(n, DUMP_MAX_REQUESTS, replace=False))
+        v = out[torch.from_numpy(idx).to(out.device)].cpu().numpy()
+    else:
+        v = out.cpu().numpy()
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "verdict_action.npy"), v[:, 0].astype(np.float32))
+    np.save(os.path.join(path, "verdict_rule_idx.npy"), v[:, 1].astype(np.float32))  # (sentinels 0xFFFFFFFx as int32: -1, -2, -3)
+    np.save(os.path.join(path, "action_counts.npy"), np.asarray(counts, dtype=np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -323,17 +351,23 @@ def main():
     ap.add_argument("--engine-flags", type=lambda x: int(x, 0), default=0, help="extra pwaf_options.flags for A/B runs (e.g. 2048 = PWAF_OPT_DENSE_VERDICT: the round-4 column file); same verdicts")
     ap.add_argument("--adversarial", action="store_true", help="time the adversarial variant of the stream as the HEADLINE batch (the tuning sample stays benign)")
     ap.add_argument("--no-extra-modes", action="store_true", help="skip the untuned and adversarial side runs (traffic_modes)")
-    ap.add_argument("--no-config5", action="store_true", help="skip the short BASELINE configs[4] leg of the default run")
+    ap.add_argument("--no-config5", action="store_true", help="skip the short BASELINE configs[4] leg of the --full run")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-pcie", action="store_true", help="skip the host-batch (PCIe-inclusive) and micro-batcher measurements")
+    ap.add_argument("--full", action="store_true", help="after the headline: the untuned / adversarial / saturated / two-in-flight runs, the config 5 leg, "
+                                                        "the residual-rule leg, the copy-bandwidth probe, PCIe-inclusive and micro-batcher calls, the CPU baseline "
+                                                        "and oracle checks, the RCCL single-rank check (a plain run times the headline only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the verdicts and action counters of the last timed step as .npy files under DIR")
     ap.add_argument("--verbose", action="store_true", help="per-kernel timings on stderr")
     ap.add_argument("--cpu-seconds", type=float, default=15.0)
     ap.add_argument("--residual", type=int, default=None, help="also time the same workload with K extra rules outside the column compiler's subset (arithmetic on lengths / ports, "
                                                             "concatenation, lists of request values, orderings between fields), evaluated by their specialized device program "
-                                                            "(DESIGN.md 3.5): `residual` object. Default: 8 in the full run, none with --no-extra-modes; 0 skips the leg")
+                                                            "(DESIGN.md 3.5): `residual` object. Default: 8 with --full, none with --no-extra-modes or without --full; 0 skips the leg")
     ap.add_argument("--inflight", type=int, default=1, help="batches in flight: step i is issued on stream i mod INFLIGHT (pwaf_evaluate_device is re-entrant: every call takes "
                                                             "its own scratch context), so one batch's small latency-bound kernels run under the next batch's streaming kernels")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     if args.gpus > 1 and "RANK" not in os.environ:
         self_launch(sys.argv[1:], args.gpus)  # does not return
@@ -370,7 +404,7 @@ def main():
     if n == 0:
         raise SystemExit(f"rank {rank}: an empty slab ({total} requests over {world} GPUs)")
     threads = max(1, effective_cpus()[0] // world)
-    extras = world == 1 and not args.no_extra_modes and not os.environ.get("PWAF_BENCH_NO_TUNE")
+    extras = args.full and world == 1 and not args.no_extra_modes and not os.environ.get("PWAF_BENCH_NO_TUNE")
 
     def phase(msg):
         if args.verbose and rank == 0:
@@ -418,7 +452,10 @@ def main():
     value = total * args.steps / elapsed
     head = R.mode_summary(elapsed, ktimes, args.steps)
     head["host_enqueue_ms_per_step"] = round(R.issue_ms, 3)
-    headline_out = R.outs[0][: min(n, 1_000_000)].clone()  # verdicts of the headline batch (the side runs below overwrite the buffer)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, R.outs[(args.steps - 1) % inflight], final_counts)
+    if args.full:
+        headline_out = R.outs[0][: min(n, 1_000_000)].clone()  # verdicts of the headline batch (the side runs below overwrite the buffer)
 
     if extras and inflight == 1:
         # the same batch with TWO batches in flight (step i on stream i mod 2; pwaf_evaluate_device is re-entrant: every call takes its
@@ -495,6 +532,8 @@ def main():
                            "the oracle evaluates ~14k requests/s",
         },
     }
+    if not args.full:
+        result["config"]["parity_note"] = "not oracle-checked in a plain run: --full checks a prefix of the timed batch against the CPU oracle"
 
     if rank == 0:
         kinds, _ = R.stream_kernels(ktimes)
@@ -568,33 +607,34 @@ def main():
         }
         result["traffic_modes"] = traffic_modes
         # ---- SURVEY §8(d) extras: the part's measured copy bandwidth, bytes per clock and CU ----
-        try:
-            src = torch.empty(1 << 28, dtype=torch.uint8, device=dev)
-            dst = torch.empty_like(src)
-            dst.copy_(src)
-            torch.cuda.synchronize(dev)
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            for _ in range(8):
+        if args.full:
+            try:
+                src = torch.empty(1 << 28, dtype=torch.uint8, device=dev)
+                dst = torch.empty_like(src)
                 dst.copy_(src)
-            e1.record()
-            torch.cuda.synchronize(dev)
-            copy_gbs = 8 * 2 * src.numel() / (e0.elapsed_time(e1) / 1e3) / 1e9  # read + write traffic of a device-to-device copy
-            del src, dst
-            props = torch.cuda.get_device_properties(dev)
-            result["roofline"]["peak_measured_copy_gbs"] = copy_gbs
-            result["roofline"]["frac_of_measured_copy"] = achieved / copy_gbs
-            # (2.4 GHz: the MI355X peak engine clock of MI355X_MICROARCH.md; torch does not expose the running clock)
-            result["roofline"]["bytes_per_clk_per_cu_at_2p4ghz"] = achieved * 1e9 / (props.multi_processor_count * 2.4e9)
-        except Exception as exc:  # informational only
-            result["roofline"]["peak_measured_copy_gbs"] = None
-            print(f"copy-bandwidth probe failed: {exc}", file=sys.stderr)
+                torch.cuda.synchronize(dev)
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                for _ in range(8):
+                    dst.copy_(src)
+                e1.record()
+                torch.cuda.synchronize(dev)
+                copy_gbs = 8 * 2 * src.numel() / (e0.elapsed_time(e1) / 1e3) / 1e9  # read + write traffic of a device-to-device copy
+                del src, dst
+                props = torch.cuda.get_device_properties(dev)
+                result["roofline"]["peak_measured_copy_gbs"] = copy_gbs
+                result["roofline"]["frac_of_measured_copy"] = achieved / copy_gbs
+                # (2.4 GHz: the MI355X peak engine clock of MI355X_MICROARCH.md; torch does not expose the running clock)
+                result["roofline"]["bytes_per_clk_per_cu_at_2p4ghz"] = achieved * 1e9 / (props.multi_processor_count * 2.4e9)
+            except Exception as exc:  # informational only
+                result["roofline"]["peak_measured_copy_gbs"] = None
+                print(f"copy-bandwidth probe failed: {exc}", file=sys.stderr)
 
-        if world == 1 and args.config == 5:
+        if world == 1 and args.full and args.config == 5:
             # per-batch latency (BASELINE.json configs[4]): one synchronised call per batch, device-resident
             phase("latency calls")
             result["latency_ms"] = {"batch": n, "calls": 40, "device_resident": R.batch_latency(dbatch, 40)}
-        if world == 1 and not args.no_pcie:
+        if world == 1 and args.full and not args.no_pcie:
             # host batch in, verdicts out through pwaf_evaluate_batch: H2D + kernels + D2H, on a bounded slice of the same batch
             phase("host-batch (PCIe-inclusive) calls")
             m = min(n, 1_000_000)
@@ -689,7 +729,7 @@ def main():
             except Exception as exc:  # the headline line must survive a failure of the side leg
                 result["config5"] = {"error": repr(exc)}
         # ---- CPU baseline: the oracle (port of the reference's per-request interpreter loop) on host cores ----
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             from oracle import pyoracle
 
             phase("cpu baseline")
@@ -738,7 +778,7 @@ def main():
             result["config"]["parity_note"] = (f"{100.0 * sample_n / n:.2f} % of the timed batch ({sample_n} requests, a prefix) oracle-checked in this line; "
                                                "a 20k random sample of the same batch in tests/test_gpu_prefilter.py")
         result["timing_notes"] = {"generate_s": round(t_gen, 2), "compile_upload_tune_s": round(t_compile, 2)}
-        if world == 1 and shard.collective_world() == 0:
+        if world == 1 and args.full and shard.collective_world() == 0:
             # a plain single process: the RCCL wiring exercised once, outside the timed region — a process group of one rank, the final
             # counters all-reduced (the sum over one rank is the counters themselves)
             try:

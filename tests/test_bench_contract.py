@@ -47,3 +47,39 @@ def test_quoted_traffic_is_the_committed_pmc_file():
     # of the same kernel — the two agree to a fraction of a percent)
     assert sk and abs(r["traffic"] - now) / now < 0.01, (r["traffic"], now)
     assert 0.95 < r["traffic"] / r["alg_bytes_per_launch"] < 1.10  # no wasted re-reads in the streaming kernel (and it cannot read less than it must)
+
+
+def test_dump_outputs_writes_the_verdicts_and_counters_as_float_arrays(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: the last step's verdicts (a fixed seeded sample above DUMP_MAX_REQUESTS) and its four action counters,
+    float32 / float64, exact for the rule_idx sentinels; the same sample on every call."""
+    import numpy as np
+    import torch
+
+    import bench
+
+    out = torch.arange(2 * 5000, dtype=torch.int32).reshape(5000, 2)
+    out[:, 0] %= 4
+    out[7, 1] = -1  # PWAF_RULE_NONE as the device writes it
+    bench.dump_outputs(str(tmp_path / "all"), out[:10], [6, 2, 1, 1])
+    assert (np.load(tmp_path / "all" / "verdict_action.npy") == out[:10, 0].numpy()).all()
+    r = np.load(tmp_path / "all" / "verdict_rule_idx.npy")
+    assert r.dtype == np.float32 and r[7] == -1 and (r == out[:10, 1].numpy()).all()
+    c = np.load(tmp_path / "all" / "action_counts.npy")
+    assert c.dtype == np.float64 and c.tolist() == [6, 2, 1, 1]
+    monkeypatch.setattr(bench, "DUMP_MAX_REQUESTS", 1000)
+    bench.dump_outputs(str(tmp_path / "a"), out, [0, 0, 0, 0])
+    bench.dump_outputs(str(tmp_path / "b"), out, [0, 0, 0, 0])
+    a, b = np.load(tmp_path / "a" / "verdict_rule_idx.npy"), np.load(tmp_path / "b" / "verdict_rule_idx.npy")
+    assert a.shape == (1000,) and (a == b).all() and (np.diff(a) > 0).all()  # sorted indices, odd values 2k+1 unique per request
+
+
+def test_bench_options_full_and_dump_outputs():
+    """A plain run times the headline only; the side legs are behind --full. --steps is validated."""
+    import subprocess
+    import sys
+
+    bench_py = os.path.join(ROOT, "bench.py")
+    h = subprocess.run([sys.executable, bench_py, "--help"], capture_output=True, text=True, check=True).stdout
+    assert "--full" in h and "--dump-outputs" in h
+    r = subprocess.run([sys.executable, bench_py, "--steps", "0"], capture_output=True, text=True)
+    assert r.returncode == 2 and "--steps" in r.stderr

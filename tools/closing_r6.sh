@@ -8,7 +8,7 @@ case $1 in
 A)
   O=$R/gpurun_out/r6_final; mkdir -p $O
   python -m pytest tests -m gpu -x -q > $O/gputests.log 2>&1; echo "rc=$?" >> $O/gputests.log; tail -2 $O/gputests.log
-  python bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench.json 2> $O/bench.err; tail -c 300 $O/bench.json
+  python bench.py --gpus 1 --steps 20 --warmup 5 --full > $O/bench.json 2> $O/bench.err; tail -c 300 $O/bench.json
   bash tools/profile_round.sh r6_c3
   # which request sizes the L2 sends to the fabric, per kernel (FETCH_SIZE = requests x 64 B whatever their size)
   cd /tmp; export TMPDIR=/tmp

@@ -12,7 +12,7 @@ python bench.py $A --adversarial > $O/b_adv.json 2> $O/b_adv.err
 python -c "
 import json
 d=json.load(open('$O/b_adv.json')); print('adv', round(d['ms_per_step'],4), d['traffic_modes'])" | cut -c1-900
-python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-pcie > $O/b_full.json 2> $O/b_full.err
+python bench.py --steps 20 --warmup 5 --full --no-cpu-baseline --no-pcie > $O/b_full.json 2> $O/b_full.err
 python -c "
 import json
 d=json.load(open('$O/b_full.json')); tm=d['traffic_modes']
