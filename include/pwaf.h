@@ -31,9 +31,10 @@
 extern "C" {
 #endif
 
-#define PWAF_ABI_VERSION 3u /* 2: pwaf_batch carries header columns; strict rule compilation by default (PWAF_OPT_LENIENT, PWAF_W_PARTIAL);
+#define PWAF_ABI_VERSION 4u /* 2: pwaf_batch carries header columns; strict rule compilation by default (PWAF_OPT_LENIENT, PWAF_W_PARTIAL);
                             * residual rules; pwaf_request carries header values; pwaf_node_evaluate_device; pwaf_program_tune
-                            * 3: page-locked host memory for batch columns (pwaf_host_alloc / _register); no struct changed */
+                            * 3: page-locked host memory for batch columns (pwaf_host_alloc / _register); no struct changed
+                            * 4: request records, non-blocking queue; no existing struct changed */
 
 /* ---- status codes ------------------------------------------------------------------ */
 #define PWAF_OK 0
@@ -44,6 +45,7 @@ extern "C" {
 #define PWAF_E_DEVICE (-5)       /* HIP error / no GPU: host may fail open                    */
 #define PWAF_E_BATCH (-6)        /* malformed batch (offsets not monotone, bad country, ...)  */
 #define PWAF_E_NOMEM (-7)
+#define PWAF_E_BUSY (-8)         /* non-blocking queue full: nothing was queued, submit again later (ABI 4)            */
 #define PWAF_W_PARTIAL 1          /* (positive: a warning, the object WAS created) with PWAF_OPT_LENIENT some rule is not evaluated */
 
 /* ---- verdict vocabulary (rules::Action, rules/rules.rs:30-35) ------------------------ */
@@ -369,6 +371,73 @@ int pwaf_batcher_create(pwaf_engine *engine, uint32_t max_batch, uint32_t max_de
 int pwaf_batcher_evaluate(pwaf_batcher *, const pwaf_request *req, pwaf_verdict *out);
 int pwaf_batcher_stats(pwaf_batcher *, uint64_t *n_batches, uint64_t *n_requests);
 void pwaf_batcher_destroy(pwaf_batcher *);
+
+/* ---- request records (ABI 4) ---------------------------------------------------------------------
+ * A record holds ONE request, self-contained: what a host writes while it handles requests one at a time (pingoo's listener has them one
+ * per hyper closure, http_listener.rs:133-274). Records live in one buffer, each at a 16-byte aligned offset:
+ *   pwaf_record_head                                  (36 bytes)
+ *   uint32_t len[n_values]                            value lengths
+ *   zero padding up to the next 16-byte boundary of the record
+ *   the values' bytes back to back                    (no padding between values)
+ *   zero padding up to `size`
+ * Value order: host, url, path, method, user_agent (PWAF_FIELD_*), then the engine's header columns in pwaf_engine_header_name order.
+ * 5 <= n_values <= 5 + pwaf_engine_header_count; the values a record does not carry read as "" (the rule of pwaf_request.headers).
+ * A buffer of records is evaluated by pwaf_evaluate_records; pwaf_async_submit writes them itself. */
+typedef struct pwaf_record_head {
+    uint32_t size;     /* whole record in bytes, a multiple of 16 */
+    uint16_t n_values; /* value lengths that follow the head */
+    uint16_t port;     /* client.remote_port */
+    uint8_t ip[16];    /* IPv4 in bytes 0..3 (network order) */
+    uint32_t asn;      /* with has_geoip */
+    uint8_t country[2];/* with has_geoip: two letters 'A'..'Z' */
+    uint8_t flags;     /* PWAF_FLAG_* */
+    uint8_t ip_is_v6;
+    uint8_t has_geoip; /* 0 or 1, the same for every record of one call */
+    uint8_t reserved[3];
+} pwaf_record_head;
+
+/* Synchronous evaluation of n records of a HOST buffer. Verdict i (out: n entries, host memory) belongs to the record at byte offset
+ * rec_off[i] of buf (any order; records may be shared or skipped). The host reads only the record heads and lengths: it validates every
+ * record and refuses the whole call with PWAF_E_BATCH, naming the record's index, when an offset is not 16-byte aligned, a record runs past
+ * buf_bytes, its lengths overflow its size, n_values is out of range, a country is not two letters A-Z, has_geoip differs between records
+ * or a column would exceed 4 GiB; nothing is launched then. The value bytes travel to the device as they are — one copy straight from
+ * page-locked memory (pwaf_host_alloc / pwaf_host_register), else staged through the engine's own page-locked block — and
+ * unpack_records_kernel writes the device batch's columns. Overflow-pool retries as in pwaf_evaluate_batch. `counts` is nullable. */
+int pwaf_evaluate_records(pwaf_engine *, const uint8_t *buf, size_t buf_bytes, const uint32_t *rec_off, uint32_t n, pwaf_verdict *out,
+                          pwaf_counts *counts);
+
+/* ---- non-blocking request queue (ABI 4) -------------------------------------------------------------
+ * The call shape of an async host (the reference's rule loop runs inside an async hyper closure, http_listener.rs:133-274): submit a
+ * request with a tag and go on; collect {tag, verdict, status} completions later. pwaf_async_submit copies the request ONCE, as a record,
+ * into page-locked segment memory (lock-free slot reservation; it never waits for the device). A batch closes at max_batch requests, when
+ * its oldest request has waited max_delay_us, or on pwaf_async_flush; requests with and without GeoIP go to separate batches. (A batch
+ * whose deadline passes while an earlier batch of its GeoIP class still waits for a dispatcher keeps filling until that one is taken.) Two
+ * dispatcher threads run pwaf_evaluate_records on closed segments and publish completions, in any order, then signal the eventfd.
+ * Consumer pattern (race-free): wait until pwaf_async_fd is readable, read(2) it, then pwaf_async_poll until it returns 0.
+ * A batch that fails completes each of its requests with that status and the verdict {ALLOW, PWAF_RULE_NONE}: the host applies its own
+ * failure policy. Destroy it before the engine. */
+typedef struct pwaf_async pwaf_async;
+typedef struct pwaf_completion {
+    uint64_t tag;         /* as given to pwaf_async_submit */
+    pwaf_verdict verdict; /* {ALLOW, PWAF_RULE_NONE} when status != PWAF_OK */
+    int32_t status;       /* PWAF_OK or the failing batch's PWAF_E_* */
+    uint32_t reserved;
+} pwaf_completion;
+/* max_in_flight: requests submitted but not yet handed out by pwaf_async_poll; past it submit answers PWAF_E_BUSY. */
+int pwaf_async_create(pwaf_engine *, uint32_t max_batch, uint32_t max_delay_us, uint32_t max_in_flight, pwaf_async **out);
+/* PWAF_OK: exactly one completion carrying `tag` will follow. PWAF_E_BUSY: max_in_flight reached or no segment has room; nothing was
+ * queued. PWAF_E_INVALID_ARG / PWAF_E_BATCH: the request itself is malformed (pwaf_batcher_evaluate's checks) or larger than a segment. */
+int pwaf_async_submit(pwaf_async *, const pwaf_request *req, uint64_t tag);
+/* Non-blocking: moves up to cap completions into out and returns how many. Safe from any thread; concurrent pollers get disjoint ones. */
+size_t pwaf_async_poll(pwaf_async *, pwaf_completion *out, size_t cap);
+/* eventfd (EFD_NONBLOCK | EFD_CLOEXEC) owned by the queue: readable after completions were published. */
+int pwaf_async_fd(pwaf_async *);
+/* Closes the open batches now (does not wait for them). */
+int pwaf_async_flush(pwaf_async *);
+int pwaf_async_stats(pwaf_async *, uint64_t *n_batches, uint64_t *n_requests, uint64_t *in_flight);
+/* Refuses new submits, evaluates every accepted request, waits for threads still inside submit / poll, frees the queue. Completions
+ * nobody polled are dropped. */
+void pwaf_async_destroy(pwaf_async *);
 
 /* ---- measurement ------------------------------------------------------------------------- */
 typedef struct pwaf_kernel_time {

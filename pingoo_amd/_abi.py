@@ -5,7 +5,7 @@ Kept in one place so the product wrapper (pingoo_amd.engine) and the test-side o
 """
 import ctypes as C
 
-ABI_VERSION = 3
+ABI_VERSION = 4
 
 OK = 0
 E_INVALID_ARG = -1
@@ -15,6 +15,7 @@ E_LIST = -4
 E_DEVICE = -5
 E_BATCH = -6
 E_NOMEM = -7
+E_BUSY = -8
 
 ACTION_ALLOW, ACTION_BLOCK, ACTION_CAPTCHA, ACTION_BYPASS = 0, 1, 2, 3
 RULE_NONE = 0xFFFFFFFF
@@ -129,6 +130,27 @@ class Request(C.Structure):
         ("n_headers", C.c_uint32),
         ("headers", C.c_void_p),  # pwaf_span[n_headers]
     ]
+
+
+class RecordHead(C.Structure):
+    """pwaf_record_head (ABI 4): the fixed part of one request record; lengths and values follow (include/pwaf.h)."""
+
+    _fields_ = [
+        ("size", C.c_uint32),
+        ("n_values", C.c_uint16),
+        ("port", C.c_uint16),
+        ("ip", C.c_uint8 * 16),
+        ("asn", C.c_uint32),
+        ("country", C.c_uint8 * 2),
+        ("flags", C.c_uint8),
+        ("ip_is_v6", C.c_uint8),
+        ("has_geoip", C.c_uint8),
+        ("reserved", C.c_uint8 * 3),
+    ]
+
+
+class Completion(C.Structure):
+    _fields_ = [("tag", C.c_uint64), ("verdict", Verdict), ("status", C.c_int32), ("reserved", C.c_uint32)]
 
 
 class Span(C.Structure):

@@ -234,6 +234,59 @@ class RequestBatch:
         v.country = None if self.country is None else self.country[lo:hi]
         return v
 
+    def to_records(self, order=None, header_names: Optional[Sequence[str]] = None):
+        """The batch as request records (include/pwaf.h pwaf_record_head; pwaf_evaluate_records) -> (buf uint8, rec_off uint32): request i's
+        record starts at buf[rec_off[i]]. `order`: a permutation — the records are laid out in that order in memory (rec_off still maps request
+        i to its own record). Values: the five fields, then `header_names` (default: the batch's own header names); a record ends after its
+        last non-empty value, so records carry fewer values where the trailing headers are empty."""
+        names = list(self.headers) if header_names is None else list(header_names)
+        n, n_cols = self.n, _abi.N_FIELDS + len(names)
+        empty = (np.zeros(_abi.ARENA_PAD, dtype=np.uint8), np.zeros(n + 1, dtype=np.uint32))
+        cols = list(zip(self.data, self.offsets)) + [self.headers.get(nm, empty) for nm in names]
+        lens = np.zeros((n, n_cols), dtype=np.int64)
+        for f, (_, o) in enumerate(cols):
+            lens[:, f] = np.diff(o.astype(np.int64))
+        nv = np.full(n, _abi.N_FIELDS, dtype=np.int64)
+        if n_cols > _abi.N_FIELDS:
+            nz = lens[:, _abi.N_FIELDS:] != 0
+            last = n_cols - _abi.N_FIELDS - np.argmax(nz[:, ::-1], axis=1)  # 1 + index of the last non-empty header
+            nv = np.where(nz.any(axis=1), _abi.N_FIELDS + last, _abi.N_FIELDS)
+        head = C.sizeof(_abi.RecordHead)
+        vo = (head + 4 * nv + 15) & ~15
+        size = (vo + lens.sum(axis=1) + 15) & ~15
+        perm = np.arange(n, dtype=np.int64) if order is None else np.asarray(order, dtype=np.int64)
+        assert len(perm) == n and np.array_equal(np.sort(perm), np.arange(n)), "order must be a permutation of the requests"
+        start = np.zeros(n, dtype=np.int64)
+        start[perm] = np.concatenate([[0], np.cumsum(size[perm])[:-1]]) if n else np.zeros(0, dtype=np.int64)
+        total = int(size.sum())
+        assert total < 1 << 32, "records of more than 4 GiB"
+        buf = np.zeros(total, dtype=np.uint8)
+        heads = np.zeros(n, dtype=np.dtype([("size", "<u4"), ("n_values", "<u2"), ("port", "<u2"), ("ip", "u1", (16,)), ("asn", "<u4"), ("country", "u1", (2,)),
+                                            ("flags", "u1"), ("ip_is_v6", "u1"), ("has_geoip", "u1"), ("reserved", "u1", (3,))]))
+        assert heads.dtype.itemsize == head
+        heads["size"], heads["n_values"], heads["port"], heads["ip"] = size, nv, self.port, self.ip
+        heads["flags"], heads["ip_is_v6"] = self.flags, self.ip_is_v6
+        if self.asn is not None:
+            heads["asn"], heads["has_geoip"] = self.asn, 1
+            heads["country"] = self.country.view(np.uint8).reshape(n, 2)
+        buf[(start[:, None] + np.arange(head)).ravel()] = heads.view(np.uint8).reshape(n, head).ravel()
+        k = np.arange(n_cols)
+        keep = k[None, :] < nv[:, None]
+        lpos = start[:, None] + head + 4 * k[None, :]
+        lb = lens.astype("<u4").view(np.uint8).reshape(n, n_cols, 4)
+        buf[(lpos[keep][:, None] + np.arange(4)).ravel()] = lb[keep].ravel()
+        at = start + vo  # where the record's next value goes
+        for f, (d, o) in enumerate(cols):
+            o64 = o.astype(np.int64)
+            ln = lens[:, f]
+            nb = int(ln.sum())
+            if nb:
+                src = np.repeat(o64[:-1], ln) + (np.arange(nb) - np.repeat(np.cumsum(ln) - ln, ln))
+                dst = np.repeat(at, ln) + (np.arange(nb) - np.repeat(np.cumsum(ln) - ln, ln))
+                buf[dst] = d[src]
+            at = at + ln
+        return buf, start.astype(np.uint32)
+
     def algorithmic_bytes(self) -> int:
         """sum(field bytes) + 4*(5+1) offset bytes + 22 B numerics + 8 B verdict per request
         (+6 B when GeoIP is precomputed on the host)."""

@@ -22,6 +22,7 @@
 #include "frontend.h"
 #include "kernels.h"
 #include "program.h"
+#include "records.h"
 
 using namespace pwaf;
 
@@ -189,6 +190,11 @@ struct Scratch {
     // a device-to-host copy into pageable memory is a blocking staged copy).
     PinBuf pin_in, pin_out, pin_status;
     DevBuf packed;
+    // pwaf_evaluate_records: rec_meta = [record offsets | column offsets | column places | counters, verdicts | the records' bytes] on the
+    // device (rec_pin: its page-locked image up to the verdicts, and the records when the caller's memory is pageable), rec_cols = the
+    // unpacked batch (column arenas, fixed columns), rec_back = counters and verdicts on their way back
+    DevBuf rec_meta, rec_cols;
+    PinBuf rec_pin, rec_back;
     // Streams and events are created on first use: every HIP stream takes a share of the few hardware queues of its priority
     // class, and a context (or its own stream) a caller never uses must not cost the caller's streams their concurrency (measured:
     // three idle contexts' streams made two caller streams share one queue — no overlap between two batches in flight).
@@ -222,6 +228,10 @@ struct Scratch {
         for (auto &b : stage_field_off) b.release();
         packed.release();
         for (PinBuf *b : {&pin_in, &pin_out, &pin_status}) b->release();
+        rec_meta.release();
+        rec_cols.release();
+        rec_pin.release();
+        rec_back.release();
         if (stream) (void)hipStreamDestroy(stream);
         if (side) (void)hipStreamDestroy(side);
         for (hipEvent_t ev : {ev_fork, ev_join, done})
@@ -2526,6 +2536,158 @@ int pwaf_host_register(void *p, size_t bytes) {
 int pwaf_host_unregister(void *p) {
     if (!p) return fail(PWAF_E_INVALID_ARG, "NULL argument");
     HIP_TRY(hipHostUnregister(p));
+    return PWAF_OK;
+}
+
+// ---- request records (ABI 4) ----
+namespace {
+// The caller's [p, p + bytes) lies in ONE page-locked allocation (pwaf_host_alloc / pwaf_host_register): the copy engine can read it
+// directly. Anything else (pageable memory, a range across two registrations) is staged.
+bool page_locked(const void *p, size_t bytes) {
+    hipPointerAttribute_t a{}, b{};
+    if (hipPointerGetAttributes(&a, p) != hipSuccess || hipPointerGetAttributes(&b, (const char *)p + bytes - 1) != hipSuccess) {
+        (void)hipGetLastError();
+        return false;
+    }
+    return a.type == hipMemoryTypeHost && b.type == hipMemoryTypeHost && a.devicePointer && b.devicePointer &&
+           (const char *)b.devicePointer - (const char *)a.devicePointer == (ptrdiff_t)(bytes - 1);
+}
+}  // namespace
+
+static_assert(pwaf::records::kMaxValues == PWAF_N_FIELDS + kMaxHeaders, "records.h kMaxValues must follow program.h kMaxHeaders");
+
+int pwaf_evaluate_records(pwaf_engine *e, const uint8_t *buf, size_t buf_bytes, const uint32_t *rec_off, uint32_t n, pwaf_verdict *out, pwaf_counts *counts) {
+    namespace R = pwaf::records;
+    if (!e || (n && (!buf || !rec_off || !out))) return fail(PWAF_E_INVALID_ARG, "NULL argument");
+    if (e->n_fields > R::kMaxValues) return fail(PWAF_E_UNSUPPORTED, "the engine has more columns than a record can carry");
+    if (n == 0) {
+        if (counts) memset(counts, 0, sizeof *counts);
+        return PWAF_OK;
+    }
+    // the host reads the heads and lengths only: validation (nothing is launched for a malformed call) and the column offsets
+    const uint32_t n_cols = e->n_fields;
+    std::vector<uint64_t> totals(n_cols);
+    uint32_t bad = 0;
+    int geo = 0;
+    uint64_t lo = 0, hi = 0;
+    const int chk = R::validate(buf, buf_bytes, rec_off, n, n_cols, totals.data(), &bad, &geo, &lo, &hi);
+    if (chk != R::kOk) return fail(PWAF_E_BATCH, "record " + std::to_string(bad) + " (offset " + std::to_string(rec_off[bad]) + "): " + R::check_message(chk));
+    HIP_TRY(hipSetDevice(e->device));
+    std::unique_lock<std::mutex> lock;
+    bool must_wait;
+    Scratch &S = acquire_context(e, true, nullptr, lock, must_wait);
+    int rc;
+    if ((rc = S.ensure(true))) return rc;
+    hipStream_t s = S.stream;
+    if (must_wait) HIP_TRY(hipStreamWaitEvent(s, S.done, 0));
+    // rec_meta: [record offsets (relative to lo)] [column offsets, n + 1 per column] [column places] [counters | verdicts] [records]
+    size_t need = 0;
+    auto take = [&](size_t bytes) { const size_t at = need; need = (need + bytes + 255) & ~(size_t)255; return at; };
+    const size_t off_stride = ((size_t)n + 1 + 63) & ~(size_t)63;
+    const size_t at_recoff = take((size_t)n * 4), at_off = take(off_stride * 4 * n_cols), at_colat = take((size_t)n_cols * 8);
+    const size_t at_counts = take(sizeof(pwaf_counts)), up_bytes = need, at_out = take((size_t)n * sizeof(pwaf_verdict));
+    const size_t span = (size_t)(hi - lo), at_rec = take(span);
+    const bool direct = page_locked(buf + lo, span);
+    if ((rc = S.rec_meta.reserve(need)) || (rc = S.rec_pin.reserve(direct ? up_bytes : need)) || (rc = S.rec_back.reserve(at_rec - at_counts))) return rc;
+    uint8_t *const h = (uint8_t *)S.rec_pin.p;
+    uint32_t *const h_recoff = (uint32_t *)(h + at_recoff);
+    for (uint32_t i = 0; i < n; i++) h_recoff[i] = (uint32_t)(rec_off[i] - lo);
+    R::column_offsets(buf, rec_off, n, n_cols, (uint32_t *)(h + at_off), off_stride);
+    // rec_cols: [column arenas, each with its PWAF_ARENA_PAD] [ip] [v6] [port] [flags] [asn] [country]
+    size_t cneed = 0;
+    auto ctake = [&](size_t bytes) { const size_t at = cneed; cneed = (cneed + bytes + 255) & ~(size_t)255; return at; };
+    uint64_t *const colat = (uint64_t *)(h + at_colat);
+    for (uint32_t f = 0; f < n_cols; f++) colat[f] = ctake(totals[f] + PWAF_ARENA_PAD);
+    const size_t c_ip = ctake((size_t)n * 16), c_v6 = ctake(n), c_port = ctake((size_t)n * 2), c_flags = ctake(n);
+    const size_t c_asn = geo ? ctake((size_t)n * 4) : 0, c_cc = geo ? ctake((size_t)n * 2) : 0;
+    if ((rc = S.rec_cols.reserve(cneed))) return rc;
+    memset(h + at_counts, 0, sizeof(pwaf_counts));
+    uint8_t *const d = (uint8_t *)S.rec_meta.p;
+    uint8_t *const dc = (uint8_t *)S.rec_cols.p;
+    HIP_TRY(hipMemcpyAsync(d, h, up_bytes, hipMemcpyHostToDevice, s));
+    if (direct) {
+        HIP_TRY(hipMemcpyAsync(d + at_rec, buf + lo, span, hipMemcpyHostToDevice, s));
+    } else {
+        memcpy(h + at_rec, buf + lo, span);
+        HIP_TRY(hipMemcpyAsync(d + at_rec, h + at_rec, span, hipMemcpyHostToDevice, s));
+    }
+    R::UnpackArgs ua{};
+    ua.rec = d + at_rec;
+    ua.rec_off = (const uint32_t *)(d + at_recoff);
+    ua.n = n;
+    ua.n_cols = n_cols;
+    ua.arena = dc;
+    ua.col_at = (const uint64_t *)(d + at_colat);
+    ua.off = (const uint32_t *)(d + at_off);
+    ua.off_stride = (uint32_t)off_stride;
+    ua.ip = dc + c_ip;
+    ua.ip_is_v6 = dc + c_v6;
+    ua.port = (uint16_t *)(dc + c_port);
+    ua.flags = dc + c_flags;
+    ua.asn = geo ? (uint32_t *)(dc + c_asn) : nullptr;
+    ua.country = geo ? (uint16_t *)(dc + c_cc) : nullptr;
+    if (R::launch_unpack_records(ua, s)) {
+        (void)hipStreamSynchronize(s);  // (the copies in flight read the caller's buffer)
+        return fail(PWAF_E_DEVICE, "unpack_records_kernel launch failed");
+    }
+    // the device batch the kernel writes: an ordinary DEVICE batch with every column's size known on the host
+    pwaf_batch db{};
+    db.struct_size = sizeof db;
+    db.n = n;
+    db.memory = PWAF_MEM_DEVICE;
+    std::vector<pwaf_strcol> hdr_cols(n_cols - PWAF_N_FIELDS);
+    std::vector<uint32_t> hdr_bytes(n_cols - PWAF_N_FIELDS);
+    for (uint32_t f = 0; f < n_cols; f++) {
+        const pwaf_strcol c{dc + colat[f], (const uint32_t *)(d + at_off) + (size_t)f * off_stride};
+        if (f < PWAF_N_FIELDS) {
+            db.field[f] = c;
+            db.field_bytes[f] = (uint32_t)totals[f];
+        } else {
+            hdr_cols[f - PWAF_N_FIELDS] = c;
+            hdr_bytes[f - PWAF_N_FIELDS] = (uint32_t)totals[f];
+        }
+    }
+    db.n_headers = (uint32_t)hdr_cols.size();
+    db.headers = hdr_cols.empty() ? nullptr : hdr_cols.data();
+    db.header_bytes = hdr_bytes.empty() ? nullptr : hdr_bytes.data();
+    db.ip = ua.ip;
+    db.ip_is_v6 = ua.ip_is_v6;
+    db.port = ua.port;
+    db.flags = ua.flags;
+    db.asn = ua.asn;
+    db.country = ua.country;
+    const std::vector<uint32_t> col_begin(n_cols, 0);
+    pwaf_counts *const d_counts = (pwaf_counts *)(d + at_counts);
+    pwaf_verdict *const d_out = (pwaf_verdict *)(d + at_out);
+    if ((rc = S.pin_status.reserve(16))) return rc;
+    volatile uint32_t *const st = (volatile uint32_t *)S.pin_status.p;
+    // run, bring counters + verdicts back, wait once; a batch that exhausted the scan overflow pool runs again with the pool it asked for
+    // (pwaf_evaluate_batch's retry: the unpacked columns stay where they are)
+    for (int attempt = 0;; attempt++) {
+        if (attempt) HIP_TRY(hipMemsetAsync(d_counts, 0, sizeof *d_counts, s));
+        S.retry = attempt > 0;
+        int r = run_pipeline(e, S, db, d_out, d_counts, nullptr, nullptr, s, true, &col_begin, true);
+        S.retry = false;
+        S.used = true;
+        S.last = s;
+        S.last_own = true;
+        if (!r) {
+            hipError_t he = hipMemcpyAsync((void *)&st[0], (uint32_t *)S.status.p + 1, 4, hipMemcpyDeviceToHost, s);
+            if (he == hipSuccess) he = hipMemcpyAsync((void *)&st[1], S.ctrl.p, 4, hipMemcpyDeviceToHost, s);
+            if (he == hipSuccess) he = hipMemcpyAsync(S.rec_back.p, d_counts, at_rec - at_counts, hipMemcpyDeviceToHost, s);
+            if (he != hipSuccess) r = fail(PWAF_E_DEVICE, std::string("hipMemcpyAsync: ") + hipGetErrorString(he));
+        }
+        (void)hipEventRecord(S.done, s);
+        const hipError_t se = hipStreamSynchronize(s);
+        if (r) return r;
+        if (se != hipSuccess) return fail(PWAF_E_DEVICE, std::string("hipStreamSynchronize: ") + hipGetErrorString(se));
+        if (!st[0]) break;
+        HIP_TRY(hipMemsetAsync((uint32_t *)S.status.p + 1, 0, 4, s));
+        if (attempt >= 2 || st[1] >= 0x7FFFFFF0u) return fail(PWAF_E_NOMEM, "scan overflow pool exhausted: verdicts of this batch are incomplete");
+        S.pool_entries = (uint64_t)st[1] + st[1] / 4 + 1024;
+    }
+    memcpy(out, (const char *)S.rec_back.p + (at_out - at_counts), (size_t)n * sizeof(pwaf_verdict));
+    if (counts) memcpy(counts, S.rec_back.p, sizeof(pwaf_counts));
     return PWAF_OK;
 }
 

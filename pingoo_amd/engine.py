@@ -16,6 +16,7 @@ from __future__ import annotations
 
 import ctypes as C
 import enum
+import ipaddress
 import os
 from dataclasses import dataclass, field
 from typing import Dict, Iterable, List, Optional, Sequence, Tuple
@@ -139,6 +140,16 @@ def lib():
     L.pwaf_batcher_stats.argtypes = [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
     L.pwaf_batcher_destroy.argtypes = [vp]
     L.pwaf_batcher_destroy.restype = None
+    L.pwaf_evaluate_records.argtypes = [vp, vp, C.c_size_t, vp, C.c_uint32, vp, vp]
+    L.pwaf_async_create.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(vp)]
+    L.pwaf_async_submit.argtypes = [vp, C.POINTER(_abi.Request), C.c_uint64]
+    L.pwaf_async_poll.argtypes = [vp, C.POINTER(_abi.Completion), C.c_size_t]
+    L.pwaf_async_poll.restype = C.c_size_t
+    L.pwaf_async_fd.argtypes = [vp]
+    L.pwaf_async_flush.argtypes = [vp]
+    L.pwaf_async_stats.argtypes = [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+    L.pwaf_async_destroy.argtypes = [vp]
+    L.pwaf_async_destroy.restype = None
     L.pwaf_geoip_from_mmdb.argtypes = [C.c_char_p, C.c_size_t, C.POINTER(C.POINTER(_abi.GeoipEntry)), C.POINTER(C.c_size_t)]
     L.pwaf_geoip_from_file_image.argtypes = [C.c_char_p, C.c_char_p, C.c_size_t, C.POINTER(C.POINTER(_abi.GeoipEntry)), C.POINTER(C.c_size_t)]
     L.pwaf_zstd_decompress.argtypes = [C.c_char_p, C.c_size_t, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]
@@ -427,6 +438,20 @@ class RuleEngine:
             return out, np.array(list(counts.by_action), dtype=np.uint64)
         return out
 
+    def evaluate_records(self, buf: np.ndarray, rec_off: np.ndarray, with_counts: bool = False):
+        """Request records (RequestBatch.to_records, include/pwaf.h pwaf_record_head) in, VERDICT_DTYPE array out: verdict i belongs to the
+        record at buf[rec_off[i]] (pwaf_evaluate_records). `buf` may be page-locked (pwaf_host_alloc / _register) or not."""
+        buf = np.ascontiguousarray(buf, dtype=np.uint8)
+        rec_off = np.ascontiguousarray(rec_off, dtype=np.uint32)
+        out = np.zeros(len(rec_off), dtype=VERDICT_DTYPE)
+        counts = _abi.Counts()
+        rc = lib().pwaf_evaluate_records(self._h, buf.ctypes.data, buf.nbytes, rec_off.ctypes.data, len(rec_off), out.ctypes.data, C.addressof(counts))
+        if rc != 0:
+            _raise(rc, lib().pwaf_last_error().decode(errors="replace"))
+        if with_counts:
+            return out, np.array(list(counts.by_action), dtype=np.uint64)
+        return out
+
     def evaluate(self, request: Request) -> Verdict:
         """RuleEngine::evaluate(Request) -> Action (pwaf_evaluate_one): a batch of one through the same device path."""
         st, _keep = _request_struct(request, self.header_names)
@@ -705,6 +730,119 @@ def native_batcher_latency(engine: "RuleEngine", batch: RequestBatch, threads: i
     pct = lambda p: xs[min(n - 1, int(round(p / 100.0 * (n - 1))))]  # noqa: E731
     return {"caller_threads": threads, "callers": "native (std::thread, tools/batcher_bench.cpp)", "requests": n, "failed": failed, "max_batch": max_batch, "deadline_us": max_delay_us,
             "batches": nb, "requests_per_s": n / secs.value if secs.value > 0 else 0.0, "latency_ms": {"p50": pct(50), "p99": pct(99), "max": xs[-1]}}
+
+
+class AsyncBatcher:
+    """Non-blocking request queue over a RuleEngine (pwaf_async_*): `submit(request, tag)` queues a request and returns at once (False:
+    the queue is full — pwaf_async_submit's PWAF_E_BUSY — nothing was queued); `poll(cap)` hands out finished requests as (tag, Verdict,
+    status) tuples. Wait for `fileno()` to be readable (select / an event loop), read it (`drain_fd()`), then poll until it returns [].
+    Safe from many threads (ctypes drops the GIL)."""
+
+    def __init__(self, engine: "RuleEngine", max_batch: int = 4096, max_delay_us: int = 200, max_in_flight: int = 65536):
+        self._engine = engine  # keeps the engine alive
+        h = C.c_void_p()
+        rc = lib().pwaf_async_create(engine._h, max_batch, max_delay_us, max_in_flight, C.byref(h))
+        if rc != 0:
+            _raise(rc, lib().pwaf_last_error().decode(errors="replace"))
+        self._h = h
+
+    def submit(self, request: Request, tag: int) -> bool:
+        st, _keep = _request_struct(request, self._engine.header_names)
+        rc = lib().pwaf_async_submit(self._h, C.byref(st), tag)
+        if rc == _abi.E_BUSY:
+            return False
+        if rc != 0:
+            _raise(rc, lib().pwaf_last_error().decode(errors="replace"))
+        return True
+
+    def poll(self, cap: int = 4096) -> List[Tuple[int, Verdict, int]]:
+        arr = (_abi.Completion * cap)()
+        k = lib().pwaf_async_poll(self._h, arr, cap)
+        return [(arr[i].tag, verdict_from_record({"action": arr[i].verdict.action, "rule_idx": arr[i].verdict.rule_idx}), arr[i].status) for i in range(k)]
+
+    def fileno(self) -> int:
+        return lib().pwaf_async_fd(self._h)
+
+    def drain_fd(self) -> None:
+        """Reads the eventfd (resets its counter); a no-op when nothing was signalled."""
+        try:
+            os.read(self.fileno(), 8)
+        except BlockingIOError:
+            pass
+
+    def flush(self) -> None:
+        lib().pwaf_async_flush(self._h)
+
+    def stats(self) -> Tuple[int, int, int]:
+        """(batches evaluated, requests evaluated, requests submitted and not yet polled)."""
+        nb, nr, fl = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+        lib().pwaf_async_stats(self._h, C.byref(nb), C.byref(nr), C.byref(fl))
+        return nb.value, nr.value, fl.value
+
+    def close(self):
+        """Refuses new submits, evaluates every accepted request and frees the queue (completions nobody polled are dropped)."""
+        if self._h:
+            lib().pwaf_async_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def _native_requests(engine: "RuleEngine", batch: RequestBatch, pool: int):
+    """The first `pool` requests of `batch` as pwaf_request structs (with the engine's header values) + what keeps their bytes alive."""
+    pool = min(pool, batch.n)
+    reqs = (_abi.Request * pool)()
+    keep = []
+    names = engine.header_names
+    for i in range(pool):
+        hdrs = {h: batch.header_bytes(h, i) for h in names} if names else None
+        geo = {} if batch.asn is None else {"asn": int(batch.asn[i]), "country": int(batch.country[i]).to_bytes(2, "little").decode("latin-1")}
+        ipb = bytes(batch.ip[i])
+        ip = str(ipaddress.ip_address(ipb if batch.ip_is_v6[i] else ipb[:4]))
+        r = Request(host=batch.field_bytes(0, i), url=batch.field_bytes(1, i), path=batch.field_bytes(2, i), method=batch.field_bytes(3, i), user_agent=batch.field_bytes(4, i),
+                    ip=ip, remote_port=int(batch.port[i]), captcha_verified=bool(batch.flags[i] & _abi.FLAG_CAPTCHA_VERIFIED), headers=hdrs, **geo)
+        st, k = _request_struct(r, names)
+        reqs[i] = st
+        keep.append(k)
+    return reqs, keep
+
+
+def native_async_throughput(engine: "RuleEngine", batch: RequestBatch, threads: int = 4, in_flight: int = 2048, per_thread: int = 200_000, max_batch: int = 8192,
+                            max_delay_us: int = 200, pool: int = 4096) -> dict:
+    """Requests/s and submit->completion latency through the non-blocking queue as a NATIVE host sees it: tools/libasync_bench.so (C++,
+    built on first use: `threads` submitter threads keeping `in_flight` requests each in flight over the first `pool` requests of `batch`,
+    one poller on the eventfd). Every verdict is checked against pwaf_evaluate_batch on the same requests. Measurement only."""
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    src, path = os.path.join(root, "tools", "async_bench.cpp"), os.path.join(root, "tools", "libasync_bench.so")
+    if not os.path.exists(path) or os.path.getmtime(src) > os.path.getmtime(path):
+        import subprocess
+
+        subprocess.run(["g++", "-std=c++17", "-O2", "-fPIC", "-shared", "-pthread", "-I", os.path.join(root, "include"), src, "-o", path], check=True)
+    ab = C.CDLL(path)
+    ab.ab_run.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(_abi.Request), C.c_size_t, C.POINTER(_abi.Verdict), C.c_int, C.c_int, C.c_uint64,
+                          C.c_uint32, C.c_uint32, C.c_char_p, C.c_size_t]
+    reqs, _keep = _native_requests(engine, batch, pool)
+    n = len(reqs)
+    sub = batch.slice(0, n)
+    want = engine.evaluate_batch(sub)
+    wv = (_abi.Verdict * n)()
+    C.memmove(wv, want.ctypes.data, n * C.sizeof(_abi.Verdict))
+    out = C.create_string_buffer(4096)
+    L = lib()
+    fns = (C.c_void_p * 7)(*[C.cast(getattr(L, f), C.c_void_p).value for f in ("pwaf_async_create", "pwaf_async_submit", "pwaf_async_poll", "pwaf_async_fd",
+                                                                                 "pwaf_async_flush", "pwaf_async_stats", "pwaf_async_destroy")])
+    # a short unmeasured run first: the engine's per-call contexts grow their device and page-locked buffers to the batch sizes the queue makes
+    ab.ab_run(fns, engine._h, None, reqs, n, wv, threads, in_flight, min(per_thread, 20_000), max_batch, max_delay_us, out, len(out))
+    rc = ab.ab_run(fns, engine._h, None, reqs, n, wv, threads, in_flight, per_thread, max_batch, max_delay_us, out, len(out))
+    import json
+
+    res = json.loads(out.value.decode())
+    res["rc"] = rc
+    return res
 
 
 def geoip_from_mmdb(content: bytes, path: str = "geoip.mmdb") -> np.ndarray:
