@@ -21,6 +21,7 @@
 
 #include "frontend.h"
 #include "kernels.h"
+#include "lscan_split.h"
 #include "program.h"
 #include "records.h"
 
@@ -276,6 +277,7 @@ struct pwaf_engine {
     uint32_t n_ungated = 0, n_gated = 0, n_filtered = 0;
     std::vector<uint8_t> owns_factors;  // per pass: some of its atoms are prefilter factors of gap passes
     uint32_t n_gap = 0;                 // gated gap passes (list slots [0, kGapLists), one factor-mask bit each)
+    std::vector<uint32_t> lscan_launches[2];  // per list-scan phase: the descriptors of each launch_scan_gated call (lscan_split.h)
     DevBuf pass_table;                  // PassInfo per pass
     std::vector<uint32_t> hlen_fields;  // header columns whose length some rule compares (comparison variable 7 + k)
     uint32_t n_fields = PWAF_N_FIELDS;  // 5 + header columns
@@ -607,6 +609,13 @@ void set_trie_args(const pwaf_engine *e, VerdictArgs &v) {
     v.ipres_packed = (e->n_classes <= 65536u && n_sets <= 65536u) ? 1u : 0u;
 }
 
+#ifdef PWAF_PROFILING
+bool skip_identity_walks() {  // timing experiment (wrong results): the identity passes are not walked
+    static const bool skip = getenv("PWAF_SKIP_IDENTITY") != nullptr;
+    return skip;
+}
+#endif
+
 // Decides which passes are list-driven and uploads what that needs: a pass behind a bigram prefilter walks the filter's candidate
 // list, a gated gap pass the list fed by its prefilter factors (owned by earlier passes). Called at creation and again when
 // pwaf_engine_tune has rebuilt the filters from a traffic sample.
@@ -710,6 +719,19 @@ int assign_lists(pwaf_engine *e) {
         d.share_owner = owner;
         e->groups[owner].shared_bits |= 1u << d.gate;
         if (e->groups[owner].need_slot < 0) e->groups[owner].need_slot = (int)e->n_need++;
+    }
+    // the list-scan launches of every batch (lscan_split.h): per phase, consecutive calls of at most 256 descriptors each
+    for (int phase = 0; phase < 2; phase++) {
+        std::vector<uint32_t> per_pass(e->groups.size(), 0);
+        for (size_t k = 0; k < e->groups.size(); k++) {
+            const DevGroup &d = e->groups[k];
+            lsplit::PassKind pk{d.identity, d.gate >= 0, d.filtered, d.confirm, d.confirm_walk, !(P.flags & PWAF_OPT_NO_DENSE_SWITCH)};
+#ifdef PWAF_PROFILING
+            if (skip_identity_walks()) pk.identity = false;
+#endif
+            per_pass[k] = lsplit::descriptors(pk, phase);
+        }
+        e->lscan_launches[phase] = lsplit::split(per_pass.data(), per_pass.size());
     }
     {
         // the verdict kernel's pass table: first column + where the pass's visited bitmap lives
@@ -1388,8 +1410,7 @@ int run_pipeline(pwaf_engine *e, Scratch &S, const pwaf_batch &db /* device poin
             }
             if (d.confirm && !d.confirm_walk) continue;  // every atom of the pass is a literal the confirm tier decided: nothing to walk
 #ifdef PWAF_PROFILING
-            static const bool skip_identity = getenv("PWAF_SKIP_IDENTITY") != nullptr;  // timing experiment (wrong results)
-            if (skip_identity && d.identity) continue;
+            if (skip_identity_walks() && d.identity) continue;
 #endif
             ListScanArgs a = list_args(gi, lshapes[phase]);
             if (phase == 0 && d.confirm && dense_flag_of[gi] != nullptr) {  // the R-tier walk over the confirm tier's walk list: idle when the pass is walked whole
@@ -1403,6 +1424,11 @@ int run_pipeline(pwaf_engine *e, Scratch &S, const pwaf_batch &db /* device poin
             }
             la[phase].push_back(a);
         }
+    for (int phase = 0; phase < 2; phase++) {  // (the launches assign_lists planned must take exactly these descriptors)
+        size_t planned = 0;
+        for (const uint32_t c : e->lscan_launches[phase]) planned += c;
+        if (planned != la[phase].size()) return fail(PWAF_E_DEVICE, "list-scan launch plan does not match the batch's descriptors");
+    }
     ColPtrChunk ptrs{};  // residual kernel: the batch's string columns as arrays of pointers
     if (P.n_residual) {
         const size_t nc = e->n_fields;
@@ -1411,7 +1437,7 @@ int run_pipeline(pwaf_engine *e, Scratch &S, const pwaf_batch &db /* device poin
     }
     // device layout of `args`: [all filtered passes] [stride-1 passes] [stride-2 passes] [confirm passes] [list passes of phase 0] [of
     // phase 1] [column pointers] — the uploaded part — then the work-item plans the plan kernels write (confirm: count + 2 words; list
-    // scans: per phase 2 * count + 1)
+    // scans: per launch 2 * count + 1)
     const uint32_t nf = (uint32_t)fall.size(), nc_conf = (uint32_t)call.size();
     const FilterArgs *d_all = nullptr, *d_s1 = nullptr, *d_s2 = nullptr;
     const ConfirmArgs *d_c = nullptr;
@@ -1424,7 +1450,7 @@ int run_pipeline(pwaf_engine *e, Scratch &S, const pwaf_batch &db /* device poin
                      a_c = part((size_t)nc_conf * sizeof(ConfirmArgs)), a_l0 = part((la[0].size() + 1) * sizeof(ListScanArgs)), a_l1 = part((la[1].size() + 1) * sizeof(ListScanArgs)),
                      a_ptrs = part((size_t)ptrs.count * sizeof(void *));
         const size_t up_bytes = ab;
-        const size_t a_cplan = part(((size_t)nc_conf + 2) * 4), a_lplan = part((2 * (la[0].size() + la[1].size()) + 4) * 4);
+        const size_t a_cplan = part(((size_t)nc_conf + 2) * 4), a_lplan = part((lsplit::plan_words(e->lscan_launches[0]) + lsplit::plan_words(e->lscan_launches[1])) * 4);
         if ((rc = S.args.reserve(ab))) return rc;
         char *const abase = (char *)S.args.p;
         d_all = (const FilterArgs *)(abase + a_all);
@@ -1493,17 +1519,19 @@ int run_pipeline(pwaf_engine *e, Scratch &S, const pwaf_batch &db /* device poin
     if ((rc = launch_attr_side())) return rc;  // (no filtered pass: beside the list scans / the verdict kernel's predecessors)
     // ---- 3. list-driven DFA passes ----
     {
-        uint32_t *plan_at = l_plan;  // work-item prefix sums, one set per phase
+        uint32_t *plan_at = l_plan;  // work-item prefix sums, one set per launch
         for (int phase = 0; phase < 2; phase++) {
-            const uint32_t cnt = (uint32_t)la[phase].size();
-            if (!cnt) continue;
-            if ((rc = mark(nullptr, 0))) return rc;
-            int he = launch_scan_gated(la[phase].data(), cnt, d_la[phase], plan_at, lshapes[phase], stream);
-            plan_at += 2 * cnt + 1;  // (prefix sums, then the entries per work item of every pass)
-            if (he) return fail(PWAF_E_DEVICE, std::string("gated scan kernel launch failed: ") + hipGetErrorString((hipError_t)he));
-            char nm[48];
-            snprintf(nm, sizeof nm, "lscan_x%u", cnt);
-            if ((rc = mark(nm, 0xFDu))) return rc;
+            uint32_t first = 0;  // (a phase of more than 256 descriptors runs as several launches, one after the other on the stream)
+            for (const uint32_t cnt : e->lscan_launches[phase]) {
+                if ((rc = mark(nullptr, 0))) return rc;
+                int he = launch_scan_gated(la[phase].data() + first, cnt, d_la[phase] + first, plan_at, lshapes[phase], stream);
+                plan_at += 2 * cnt + 1;  // (prefix sums, then the entries per work item of every pass)
+                first += cnt;
+                if (he) return fail(PWAF_E_DEVICE, std::string("gated scan kernel launch failed: ") + hipGetErrorString((hipError_t)he));
+                char nm[48];
+                snprintf(nm, sizeof nm, "lscan_x%u", cnt);
+                if ((rc = mark(nm, 0xFDu))) return rc;
+            }
         }
     }
     if (!P.fcmp.empty()) {

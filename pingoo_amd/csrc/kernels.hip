@@ -2527,7 +2527,7 @@ __global__ __launch_bounds__(SP ? 768 : 1024, (SP && BR == 1) ? 6 : 1) void verd
                     for (int q = 0; q < 4; q++) lit[q] = k + q < lit_off + lit_cnt ? (LT ? l_lits[k + q] : a.lits[k + q]) : 0u;
                     unsigned long long cw[4];
 #pragma unroll
-                    for (int q = 0; q < 4; q++) cw[q] = col_word(lit[q] & LIT_ATOM_MASK);
+                    for (int q = 0; q < 4; q++) cw[q] = (lit[q] & LIT_LAZY) ? 0ull : col_word(lit[q] & LIT_ATOM_MASK);  // (no LAZY literal reaches this kernel — engine.cpp packs them for verdict2 only — but its low bits are no column)
 #pragma unroll
                     for (int q = 0; q < 4; q++) {
                         acc_and &= (lit[q] & LIT_NEG) ? ~cw[q] : cw[q];
@@ -3042,7 +3042,9 @@ __global__ __launch_bounds__(768, BR == 1 ? 6 : 1) void verdict2_kernel(VerdictA
                     for (int q = 0; q < 4; q++) lit[q] = k + q < lit_off + lit_cnt ? (LT ? l_lits[k + q] : a.lits[k + q]) : 0u;
                     unsigned long long cw[4];
 #pragma unroll
-                    for (int q = 0; q < 4; q++) cw[q] = col_word(lit[q] & LIT_ATOM_MASK);  // (a lazy literal's index is below n_cols too: the read is harmless)
+                    // (a LAZY literal's low bits are its constant, operator and slot, not a column — up to 0x7FFFF: it must not index slot[]
+                    // or the spill array; its word is not used below)
+                    for (int q = 0; q < 4; q++) cw[q] = (lit[q] & LIT_LAZY) ? 0ull : col_word(lit[q] & LIT_ATOM_MASK);
 #pragma unroll
                     for (int q = 0; q < 4; q++) {
                         // a LAZY comparison atom reads as TRUE here, negated or not: what comes out is a superset of the rule's matches

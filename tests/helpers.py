@@ -331,3 +331,152 @@ def as_the_engine_sees(rules, prog, allow=0):
     REWRITTEN["unsupported"] += len(bad)
     assert len(bad) <= allow, [(i, prog.rule_status(i)[1]) for i in sorted(bad)]
     return [(n, "false" if i in bad else e, a) for i, (n, e, a) in enumerate(rules)], bad
+
+
+# ---------------------------------------------------------------------------------------------------------
+# rule sets pinned to an exact number of scan passes (the engine's capacity limits: 250 passes, 256 list-scan descriptors per launch,
+# the verdict kernels' 64-pass bitmap, 32 gated gap passes). The pass count is not monotone in the rule count, so the search walks rule
+# counts one compile at a time, and word seeds when it circles, until the count is exact.
+# ---------------------------------------------------------------------------------------------------------
+CONSONANTS = "bcdfghjklmnpqrstvwxz"
+PASS_KINDS = ("confirm_walk", "confirm_literal", "gap", "identity")
+_PASS_RATE = {"confirm_walk": 0.66, "confirm_literal": 0.33, "gap": 0.5, "identity": 1.0}  # passes per rule, measured (the search's first guess)
+_PASS_OPTS = {"confirm_walk": dict(max_table_bytes=1024), "confirm_literal": dict(max_table_bytes=1024), "gap": {}, "identity": dict(max_table_bytes=1024)}
+GAP_MAX = 30
+
+
+def pass_words(seed: int, n: int):
+    """n distinct six-consonant words (no vowel: no English word, no token of the other generators)"""
+    rng = random.Random(0x5EED00 + seed)
+    seen, out = set(), []
+    while len(out) < n:
+        w = "".join(rng.choice(CONSONANTS) for _ in range(6))
+        if w not in seen:
+            seen.add(w)
+            out.append(w)
+    return out
+
+
+def kind_rules(kind: str, n: int, seed: int = 0, prefix: str = ""):
+    """n rules of one kind and, per rule, the field it reads and the values that make its literals occur:
+    confirm_walk    url.matches("<w1>[0-9]+<w2>"): a literal factor and a non-literal middle (a confirm tier that walks)
+    confirm_literal url.contains("<w>"): the confirm tier decides the literal (no walk)
+    gap             url.matches("<w1>.{0,30}<w2>"): a counted gap (a gated gap pass fed by the literal passes' factors)
+    identity        method.matches("<C>[A-Z]{5}$"): no literal factor of two bytes (a method pass walks every request)"""
+    B_ = [B, CAP, [CAP, B]]
+    rules, tokens = [], []
+    if kind == "identity":
+        if n > 26 * 3:
+            raise ValueError("at most 78 identity rules")
+        for k in range(n):
+            c, m = chr(ord("A") + k % 26), 5 + k // 26
+            rules.append((f"{prefix}i{k}", f'http_request.method.matches("{c}[A-Z]{{{m}}}$")', [B]))
+            tokens.append(("method", [c + "QZX" * 3, "x" + c + "Q" * m, c + "Q" * (m - 1), (c + "Z" * m)[:-1] + "0"]))
+        return rules, tokens
+    w = pass_words(seed * 7 + PASS_KINDS.index(kind), 2 * n)
+    for k in range(n):
+        a, b = w[2 * k], w[2 * k + 1]
+        acts = B_[k % 3] if isinstance(B_[k % 3], list) else [B_[k % 3]]
+        if kind == "confirm_walk":
+            rules.append((f"{prefix}c{k}", f'http_request.url.matches("{a}[0-9]+{b}")', acts))
+            tokens.append(("url", [f"{a}{k % 97}{b}", f"{a}{b}", f"{a[:-1]}7{b}", f"{a}12x{b}", f"{'_' * (k % 16)}{a}0{b}"]))
+        elif kind == "confirm_literal":
+            rules.append((f"{prefix}l{k}", f'http_request.url.contains("{a}")', acts))
+            tokens.append(("url", [a, a[:-1], a[1:], f"{'_' * (k % 16)}{a}", a[:3] + "/" + a[3:]]))
+        elif kind == "gap":
+            rules.append((f"{prefix}g{k}", f'http_request.url.matches("{a}.{{0,{GAP_MAX}}}{b}")', acts))
+            tokens.append(("url", [a + b, a + "x" * (GAP_MAX - 1) + b, a + "y" * GAP_MAX + b, a + "z" * (GAP_MAX + 1) + b, f"{'_' * (k % 16)}{a}-{b}", a[:-1] + "-" + b]))
+        else:
+            raise ValueError(kind)
+    return rules, tokens
+
+
+class PinnedSet:
+    """A rule set and what it compiles to: n_passes (scan passes), n_gated (gated gap passes), n_filtered, n_confirm (passes with a
+    confirm tier), n_walk (those of them that walk), opts (the compile options it was pinned with), tokens (per rule: its field and
+    the values that make its literals occur — whole, truncated, padded so that they straddle 16-byte chunks)."""
+
+    def __init__(self, rules, tokens, opts, program):
+        from table_walker import Tables
+
+        self.rules, self.tokens, self.opts, self.program = rules, tokens, opts, program
+        s = program.stats()
+        self.n_passes, self.n_gated, self.n_filtered = s["n_dfa_groups"], s["n_gated_groups"], s["n_filtered_groups"]
+        groups = Tables(program.dump()).groups
+        self.n_confirm = sum(1 for g in groups if g.get("confirm"))
+        self.n_walk = sum(1 for g in groups if g.get("confirm") and g.get("confirm_walk"))
+
+    def pass_of_input(self, value: bytes, first: int = 0):
+        """the filtered passes from `first` on that the value flags (pwaf_program_confirm_field: the device's own prefilter code)"""
+        from pingoo_amd.engine import PwafError
+
+        out = []
+        for g in range(first, self.n_passes):
+            try:
+                if self.program.confirm_field(g, value)[1]:
+                    out.append(g)
+            except PwafError:
+                pass  # (a pass without a prefilter)
+        return out
+
+
+_PINNED = {}
+
+
+def pinned_passes(kind: str, n: int, seed: int = 0, extra=(), max_seeds: int = 4, max_tries: int = 14) -> PinnedSet:
+    """A deterministic rule set of `kind` (PASS_KINDS) that compiles, together with the fixed rules `extra` (e.g. kind_rules of another
+    kind), to exactly n scan passes — n GATED gap passes for kind "gap". Fails naming the nearest counts found when n is unreachable."""
+    from pingoo_amd.engine import CompiledProgram, UnsupportedExpression
+
+    key = (kind, n, seed, repr(list(extra)))
+    if key in _PINNED:
+        return _PINNED[key]
+    opts = dict(_PASS_OPTS[kind])
+    seen = {}
+    for s in range(seed, seed + max_seeds):
+        r, tried = max(1, round(n / _PASS_RATE[kind])), set()
+        for _ in range(max_tries):
+            if r in tried or r < 1:
+                break  # (circling: next word seed)
+            tried.add(r)
+            rules, tokens = kind_rules(kind, r, s)
+            try:
+                prog = CompiledProgram(list(extra) + rules, **opts)
+            except UnsupportedExpression:
+                seen[(s, r)] = 251  # (refused: more than 250 passes)
+                r -= max(1, round(r * 0.02))
+                continue
+            st = prog.stats()
+            c = st["n_gated_groups"] if kind == "gap" else st["n_dfa_groups"]
+            seen[(s, r)] = c
+            if c == n:
+                ps = PinnedSet(list(extra) + rules, [("", [])] * len(extra) + tokens, opts, prog)
+                _PINNED[key] = ps
+                return ps
+            step = round((n - c) / _PASS_RATE[kind] / 2)  # (half the estimate: near the count, one rule at a time)
+            r += max(-16, min(16, step if step else (1 if n > c else -1)))
+    near = sorted(set(seen.values()), key=lambda c: (abs(c - n), c))[:4]
+    raise AssertionError(f"no {kind} rule set compiles to exactly {n} passes (seeds {seed}..{seed + max_seeds - 1}); nearest counts found: {near}")
+
+
+def pinned_requests(rng: random.Random, ps: PinnedSet, n: int, hit: float = 0.3, rules=None):
+    """Requests whose url / method carry the tokens of the set's rules (of `rules`, indices, when given) next to benign filler."""
+    idx = [k for k in (rules if rules is not None else range(len(ps.tokens))) if ps.tokens[k][1]]
+    reqs = []
+    for _ in range(n):
+        url, method = [], "GET"
+        for _ in range(rng.randint(0, 4)):
+            if idx and rng.random() < hit:
+                f, vals = ps.tokens[rng.choice(idx)]
+                v = rng.choice(vals)
+                if f == "method":
+                    method = v
+                else:
+                    url.append(v)
+            else:
+                url.append(rstr(rng, 1, 12, "abcdefxyz/.=-_0123456789"))
+        u = "/" + rng.choice(["", "?", "/", "&"]).join(url)
+        reqs.append(Request(host="h.example", url=u, path=u.split("?")[0], method=method, user_agent="ua/" + rstr(rng, 0, 6),
+                            ip=f"{rng.randint(1, 3)}.{rng.randint(0, 3)}.0.{rng.randint(0, 255)}", remote_port=rng.randint(0, 65535),
+                            captcha_verified=rng.random() < 0.3))
+    return reqs
