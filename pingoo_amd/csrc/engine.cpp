@@ -11,11 +11,11 @@
 #include <cstdio>
 #include <algorithm>
 #include <cstring>
-#include <functional>
 #include <map>
 #include <memory>
 #include <mutex>
 #include <string>
+#include <type_traits>
 #include <unordered_map>
 #include <vector>
 
@@ -48,6 +48,49 @@ namespace {
         hipError_t _e = (expr);                                                                                \
         if (_e != hipSuccess) return fail(PWAF_E_DEVICE, std::string(#expr) + ": " + hipGetErrorString(_e));   \
     } while (0)
+
+// The measurement switches of the batch path, read from the environment ONCE, and only by a -DPWAF_PROFILING build (tools/*.sh,
+// docs/experiments/): every other build runs with the defaults written here. Timing experiments and debugging aids — several give
+// wrong results; none is a product setting.
+struct Switches {
+    bool sync_each = false;           // PWAF_SYNC_EACH, debugging aid: wait after every launch and print how it ended (which launch faults)
+    uint32_t debug_skip = 0;          // PWAF_DEBUG_SKIP: VerdictArgs::debug_skip
+    bool attr_prio = false;           // PWAF_ATTR_PRIO: bit 31 of the same
+    int placement = 2;                // PWAF_PLACEMENT=0..3, PWAF_ATTR_INLINE (= 1), PWAF_ATTR_EARLY (= 3): where the attribute path runs (BatchRun::ipres_stage)
+    bool skip_ipres = false;          // PWAF_SKIP_IPRES, PWAF_SKIP_ATTR
+    bool skip_attr = false;           // PWAF_SKIP_ATTR
+    long list_shape = -1;             // PWAF_LIST_SHAPE = phase 0 | phase 1 << 4: the list scans' workgroup shapes (same results); -1: not given
+    uint32_t filter_debug_skip = 0;   // PWAF_FILTER_DEBUG_SKIP: FilterArgs::debug
+    bool attr_after_compact = false;  // PWAF_ATTR_AFTER_COMPACT: the attribute path forks behind resolve / compact instead of the prefilter
+    bool dump_counts = false;         // PWAF_DUMP_COUNTS, debugging aid: the device-side list lengths of every batch
+    bool skip_identity = false;       // PWAF_SKIP_IDENTITY: the identity passes are not walked
+    bool side_priority_high = false;  // PWAF_SIDE_PRIORITY_HIGH: the side stream at the highest priority instead of the lowest
+    bool no_packed_staging = false;   // PWAF_NO_PACKED_STAGING, A/B: the column-by-column path for every host batch
+};
+Switches read_switches() {
+    Switches s;
+#ifdef PWAF_PROFILING
+    const auto set = [](const char *name) { return getenv(name) != nullptr; };
+    s.sync_each = set("PWAF_SYNC_EACH");
+    if (set("PWAF_DEBUG_SKIP")) s.debug_skip = (uint32_t)strtoul(getenv("PWAF_DEBUG_SKIP"), nullptr, 0);
+    s.attr_prio = set("PWAF_ATTR_PRIO");
+    s.placement = set("PWAF_PLACEMENT") ? atoi(getenv("PWAF_PLACEMENT")) : set("PWAF_ATTR_INLINE") ? 1 : set("PWAF_ATTR_EARLY") ? 3 : 2;
+    s.skip_attr = set("PWAF_SKIP_ATTR");
+    s.skip_ipres = set("PWAF_SKIP_IPRES") || s.skip_attr;
+    if (set("PWAF_LIST_SHAPE")) s.list_shape = (long)(uint32_t)atoi(getenv("PWAF_LIST_SHAPE"));
+    if (set("PWAF_FILTER_DEBUG_SKIP")) s.filter_debug_skip = (uint32_t)atoi(getenv("PWAF_FILTER_DEBUG_SKIP"));
+    s.attr_after_compact = set("PWAF_ATTR_AFTER_COMPACT");
+    s.dump_counts = set("PWAF_DUMP_COUNTS");
+    s.skip_identity = set("PWAF_SKIP_IDENTITY");
+    s.side_priority_high = set("PWAF_SIDE_PRIORITY_HIGH");
+    s.no_packed_staging = set("PWAF_NO_PACKED_STAGING");
+#endif
+    return s;
+}
+const Switches &switches() {
+    static const Switches sw = read_switches();
+    return sw;
+}
 
 struct DevBuf {
     void *p = nullptr;
@@ -206,9 +249,7 @@ struct Scratch {
         if (!side) {
             int least = 0, greatest = 0;
             (void)hipDeviceGetStreamPriorityRange(&least, &greatest);
-#ifdef PWAF_PROFILING
-            if (getenv("PWAF_SIDE_PRIORITY_HIGH")) least = greatest;  // timing experiment
-#endif
+            if (switches().side_priority_high) least = greatest;  // timing experiment
             if (hipStreamCreateWithPriority(&side, hipStreamNonBlocking, least) != hipSuccess || hipEventCreateWithFlags(&ev_fork, hipEventDisableTiming) != hipSuccess ||
                 hipEventCreateWithFlags(&ev_join, hipEventDisableTiming) != hipSuccess || hipEventCreateWithFlags(&done, hipEventDisableTiming) != hipSuccess)
                 return fail(PWAF_E_DEVICE, "hipStreamCreate / hipEventCreate failed");
@@ -609,13 +650,6 @@ void set_trie_args(const pwaf_engine *e, VerdictArgs &v) {
     v.ipres_packed = (e->n_classes <= 65536u && n_sets <= 65536u) ? 1u : 0u;
 }
 
-#ifdef PWAF_PROFILING
-bool skip_identity_walks() {  // timing experiment (wrong results): the identity passes are not walked
-    static const bool skip = getenv("PWAF_SKIP_IDENTITY") != nullptr;
-    return skip;
-}
-#endif
-
 // Decides which passes are list-driven and uploads what that needs: a pass behind a bigram prefilter walks the filter's candidate
 // list, a gated gap pass the list fed by its prefilter factors (owned by earlier passes). Called at creation and again when
 // pwaf_engine_tune has rebuilt the filters from a traffic sample.
@@ -726,9 +760,7 @@ int assign_lists(pwaf_engine *e) {
         for (size_t k = 0; k < e->groups.size(); k++) {
             const DevGroup &d = e->groups[k];
             lsplit::PassKind pk{d.identity, d.gate >= 0, d.filtered, d.confirm, d.confirm_walk, !(P.flags & PWAF_OPT_NO_DENSE_SWITCH)};
-#ifdef PWAF_PROFILING
-            if (skip_identity_walks()) pk.identity = false;
-#endif
+            if (switches().skip_identity) pk.identity = false;
             per_pass[k] = lsplit::descriptors(pk, phase);
         }
         e->lscan_launches[phase] = lsplit::split(per_pass.data(), per_pass.size());
@@ -785,107 +817,42 @@ Scratch &acquire_context(pwaf_engine *e, bool own, hipStream_t caller, std::uniq
     return *e->ctx[k];
 }
 
-int run_pipeline(pwaf_engine *e, Scratch &S, const pwaf_batch &db /* device pointers */, pwaf_verdict *d_out, pwaf_counts *d_counts, uint32_t *d_match_idx,
-                 uint32_t *d_n_matches, hipStream_t stream, bool totals_known = false, const std::vector<uint32_t> *col_begin = nullptr, bool sync_status = false) {
-    const Program &P = *e->prog.p;
-    const uint32_t n = db.n, n_groups = (n + 63) / 64;
-    if (n == 0) return PWAF_OK;
-    const uint32_t residual_pass = (uint32_t)e->groups.size() + (P.fcmp.empty() ? 0u : 1u);
-    const uint32_t n_passes = residual_pass + (P.n_residual ? 1u : 0u);  // (+ the pseudo passes of the field-against-field atoms and of the residual rules)
-    int rc;
-    // scratch sized for the worst case the 288 GB part can afford: one 4-byte hit record per (pass, request) and an overflow
-    // pool of 8 entries per request (exhaustion is reported through the status word, never silently)
-    // (a batch that exhausts the pool sets the context's sticky status word; the synchronous entry points then grow the pool to
-    // what the batch asked for — the allocator keeps counting past the cap — and run the batch again)
-    const uint64_t pool_cap64 = std::max<uint64_t>(std::max<uint64_t>(1u << 20, (uint64_t)n * 8), S.pool_entries);
-    const uint32_t pool_cap = (uint32_t)std::min<uint64_t>(pool_cap64, 0x7FFFFFF0u);
-    S.pool_entries = pool_cap;
-    // two sticky status words per context: [0] device-resident batches (reported and cleared by pwaf_engine_device_status),
-    // [1] the synchronous entry points (read and cleared by their own retry loop) — a synchronous batch on the same context can no
-    // longer swallow the overflow bit of an earlier asynchronous one
-    if (!S.status.p) {
-        if ((rc = S.status.reserve(8))) return rc;
-        HIP_TRY(hipMemsetAsync(S.status.p, 0, 8, stream));
-    }
-    uint32_t *const status_word = (uint32_t *)S.status.p + (sync_status ? 1 : 0);
-    if ((rc = S.rec.reserve((size_t)std::max(1u, n_passes) * n * 4))) return rc;
-    // the attribute kernel's output: per group a header and room for EVERY non-scan atom (worst case: no overflow path), plus 64
-    // pairs of slack so the verdict kernel may read a full wave's worth unconditionally
-    const uint32_t pair_stride = std::max(1u, e->n_bit_atoms + e->n_cmp_atoms + e->n_short);
-    if ((rc = S.attr.reserve(((size_t)n_groups * pair_stride + 64) * 16 + (size_t)n_groups * 4))) return rc;
-    if ((rc = S.pool.reserve((size_t)pool_cap * sizeof(PoolEntry)))) return rc;
-    const size_t n_slots = (size_t)std::max(kGapLists, e->n_gated);
-    const size_t ctrl_words = 2 + n_slots + e->n_filtered;  // [0] pool allocator, [1] status word, one length per list slot, one pair count per filtered pass
-    // visited bitmaps of the list-driven passes (one bit per request, whole 64-request groups): zeroed per batch — 1/32 of what
-    // zeroing the hit records themselves would write. They share ONE zeroed block with the control words and the confirm tier's walk bitmaps.
-    const uint32_t bit_words = 2 * n_groups;
-    uint32_t n_conf = 0;
-    for (const DevGroup &d : e->groups) n_conf += (d.filtered && d.confirm) ? 1u : 0u;
-    bool zero_deferred = false;
-    size_t zero_bytes = 0;
-    int arg_slot_used = -1;
-    {
-        size_t zb = 0;
-        auto part = [&](size_t bytes) { const size_t at = zb; zb = (zb + bytes + 255) & ~(size_t)255; return at; };
-        const size_t z_ctrl = part(4 * ctrl_words), z_cand = part((size_t)e->n_filtered * bit_words * 4), z_visit = part((size_t)e->n_visit * bit_words * 4),
-                     z_walk = part((size_t)n_conf * bit_words * 4);
-        if ((rc = S.zero_block.reserve(zb))) return rc;
-        // (cleared by the descriptor upload's launch when nothing needs it before that: no pass that streams every request — those run first and
-        // count into the control words)
-        zero_deferred = e->n_filtered != 0;
-        for (const DevGroup &d : e->groups) zero_deferred = zero_deferred && (d.gate >= 0 || d.identity || d.short_lit);
-        zero_bytes = zb;
-        if (!zero_deferred) HIP_TRY(hipMemsetAsync(S.zero_block.p, 0, zb, stream));
-        char *const zbase = (char *)S.zero_block.p;
-        S.ctrl.p = zbase + z_ctrl;
-        S.cand_bits.p = zbase + z_cand;
-        S.visit_bits.p = zbase + z_visit;
-        S.walk_bits.p = zbase + z_walk;
-    }
-    // string columns by field id: the five fixed fields, then one column per header name the rule set mentions (EXTENSION); a header
-    // the batch does not carry reads as the empty string for every request
-    std::vector<pwaf_strcol> cols(e->n_fields);
-    std::vector<uint32_t> col_bytes(e->n_fields, 0);
-    for (int f = 0; f < PWAF_N_FIELDS; f++) {
-        cols[(size_t)f] = db.field[f];
-        col_bytes[(size_t)f] = db.field_bytes[f];
-    }
-    bool missing_header = false;
-    for (uint32_t f = PWAF_N_FIELDS; f < e->n_fields; f++) {
-        const uint32_t k = f - PWAF_N_FIELDS;
-        if (k < db.n_headers && db.headers != nullptr && db.headers[k].data != nullptr && db.headers[k].offsets != nullptr) {
-            cols[f] = db.headers[k];
-            col_bytes[f] = db.header_bytes ? db.header_bytes[k] : 0u;
-        } else {
-            missing_header = true;
-        }
-    }
-    if (missing_header) {
-        if (S.zero_off.cap < (size_t)(n + 1) * 4 + PWAF_ARENA_PAD) {
-            if ((rc = S.zero_off.reserve((size_t)(n + 1) * 4 + PWAF_ARENA_PAD))) return rc;
-            HIP_TRY(hipMemsetAsync(S.zero_off.p, 0, S.zero_off.cap, stream));
-        }
-        for (uint32_t f = PWAF_N_FIELDS; f < e->n_fields; f++)
-            if (cols[f].data == nullptr) {
-                cols[f].data = (const uint8_t *)S.zero_off.p;
-                cols[f].offsets = (const uint32_t *)S.zero_off.p;
-                col_bytes[f] = 0;
-            }
-    }
-    std::vector<uint8_t> col_known(e->n_fields, totals_known ? 1 : 0);
-    for (uint32_t f = 0; f < e->n_fields; f++)
-        if (col_bytes[f] != 0 || cols[f].data == (const uint8_t *)S.zero_off.p) col_known[f] = 1;
-    if (e->n_gated && (rc = S.gate_lists.reserve((size_t)e->n_gated * n * 4))) return rc;
-    if (e->n_need && (rc = S.need.reserve((size_t)e->n_need * n * 4))) return rc;
+// ---- one batch through the pipeline: run_pipeline at the end of this section is the driver, BatchRun holds the
+//      steps ----
 
-    // Profiling: HIP events on the launch stream. On the main stream the event that ends one kernel also starts the next
-    // (half the events; the few microseconds of launch gap or memset in between are charged to the later kernel).
-    // (evaluate calls are re-entrant, the timing tables are not — a profiled call holds this lock while it enqueues)
-    std::unique_lock<std::mutex> prof_lock;
-    if (e->profiling) prof_lock = std::unique_lock<std::mutex>(e->prof_mu);
-    size_t ev_i = e->profiling ? e->n_timed : 0;
+// Parts of one block (the zeroed block, the descriptor block, the staging blocks of the host entry points), each on a 256-byte boundary.
+struct Layout {
+    size_t used = 0;
+    size_t take(size_t bytes) { const size_t at = used; used = (used + bytes + 255) & ~(size_t)255; return at; }
+    size_t size() const { return used; }
+};
+
+// Slabs a filter pass streams: its arena cut into kStreamSlab pieces, less the whole slabs in front of the batch's own bytes.
+uint32_t slab_count(uint32_t total, uint32_t slab0) { return (uint32_t)(((uint64_t)total + kStreamSlab - 1) / kStreamSlab) - slab0; }
+uint32_t slabs_of(const FilterArgs &f) { return slab_count(f.total, f.slab0); }
+// (request, flagged chunk) pairs of a pass with a confirm tier: at most one per chunk of the arena plus one per request (a chunk that
+// straddles two requests counts for both)
+uint32_t pair_cap_of(uint32_t slabs, uint32_t n) { return (uint32_t)std::min<uint64_t>(0xFFFFFFF0u, (uint64_t)slabs * (kStreamSlab / 16) + n + 64); }
+
+// Kernel times (pwaf_engine_set_profiling): HIP events on the launch stream. On the main stream the event that ends one kernel also
+// starts the next (half the events; the few microseconds of launch gap or memset in between are charged to the later kernel).
+// (evaluate calls are re-entrant, the timing tables are not — a profiled call holds prof_mu while it enqueues)
+struct KernelTimer {
+    pwaf_engine *e;
+    hipStream_t stream;
+    std::unique_lock<std::mutex> lock;
+    size_t ev_i = 0;
     long last_main = -1;  // index of the last event recorded on `stream` during this call
-    auto record = [&](hipStream_t on) -> int {
+    long open_begin = -1;
+    bool streaming = false;  // the marks of a launch that streams request bytes (level 2 records no others)
+    const bool sync_each = switches().sync_each;
+    KernelTimer(pwaf_engine *e_, hipStream_t stream_) : e(e_), stream(stream_) {
+        if (!e->profiling) return;
+        lock = std::unique_lock<std::mutex>(e->prof_mu);
+        ev_i = e->n_timed;
+    }
+    bool off() const { return !e->profiling || (e->profiling == 2 && !streaming); }
+    int record(hipStream_t on) {
         if (e->ev.size() < ev_i + 1) {
             hipEvent_t x;
             HIP_TRY(hipEventCreate(&x));
@@ -894,142 +861,320 @@ int run_pipeline(pwaf_engine *e, Scratch &S, const pwaf_batch &db /* device poin
         HIP_TRY(hipEventRecord(e->ev[ev_i], on));
         ev_i++;
         return PWAF_OK;
-    };
-    long open_begin = -1;
-    bool stream_mark = false;  // the marks of a launch that streams request bytes (level 2 records no others)
-    auto mark = [&](const char *name, uint64_t alg_bytes, hipStream_t on = nullptr) -> int {
-#ifdef PWAF_PROFILING
-        static const bool sync_each = getenv("PWAF_SYNC_EACH") != nullptr;  // debugging aid: which launch faults
-        if (sync_each && name) {
-            hipError_t se = hipStreamSynchronize(on ? on : stream);
+    }
+    // `side`: the launch goes to that stream instead of the batch's
+    int begin(hipStream_t side = nullptr) {
+        if (off()) return PWAF_OK;
+        if (!side && last_main >= 0) { open_begin = last_main; return PWAF_OK; }
+        const int rc = record(side ? side : stream);
+        if (rc) return rc;
+        open_begin = (long)ev_i - 1;
+        if (!side) last_main = open_begin;
+        return PWAF_OK;
+    }
+    int end(const char *name, uint64_t alg_bytes, hipStream_t side = nullptr) {
+        if (sync_each) {
+            hipError_t se = hipStreamSynchronize(side ? side : stream);
             fprintf(stderr, "[pwaf] %s done: %s\n", name, hipGetErrorString(se));
         }
-#endif
-        if (!e->profiling || (e->profiling == 2 && !stream_mark)) return PWAF_OK;
-        int rc2;
-        if (!name) {  // begin
-            if (!on && last_main >= 0) { open_begin = last_main; return PWAF_OK; }
-            if ((rc2 = record(on ? on : stream))) return rc2;
-            open_begin = (long)ev_i - 1;
-            if (!on) last_main = open_begin;
-            return PWAF_OK;
-        }
-        if ((rc2 = record(on ? on : stream))) return rc2;
-        if (!on) last_main = (long)ev_i - 1;
+        if (off()) return PWAF_OK;
+        const int rc = record(side ? side : stream);
+        if (rc) return rc;
+        if (!side) last_main = (long)ev_i - 1;
         pwaf_kernel_time t{};
         snprintf(t.name, sizeof t.name, "%s", name);
         t.alg_bytes = alg_bytes;
         e->times.push_back(t);
         e->time_ev.push_back({(size_t)open_begin, ev_i - 1});
         return PWAF_OK;
-    };
+    }
+    void commit() { e->n_timed = ev_i; }
+};
 
+// The page-locked descriptor slot a batch wrote (Scratch::arg_slot): it may be rewritten only after the copy launch that read it has
+// run, so WHATEVER way the batch leaves the pipeline its event is recorded behind what was enqueued. A batch that enqueued everything
+// records it itself (record(): after the verdict launch — a record between two kernels keeps the second from starting while the first
+// drains); every other exit leaves it to the destructor.
+struct ArgSlotMark {
+    Scratch &S;
+    hipStream_t stream;
+    int slot = -1;
+    int record() {
+        if (slot < 0) return PWAF_OK;
+        const int k = slot;
+        slot = -1;
+        S.arg_pending[k] = true;  // (an event whose record failed reads as complete: the next user of the slot does not wait)
+        HIP_TRY(hipEventRecord(S.arg_ev[k], stream));  // (the copy launch that read the slot ran before everything recorded here)
+        return PWAF_OK;
+    }
+    ~ArgSlotMark() { (void)record(); }
+};
+
+struct BatchRun {
+    pwaf_engine *e;
+    Scratch &S;
+    const Program &P;
+    const pwaf_batch &db;  // device pointers
+    hipStream_t stream;
+    const std::vector<uint32_t> *col_begin;  // per field, where the batch's own bytes begin in the arena (a slab view of a larger batch); null: at 0
+    const Switches &sw;
+    KernelTimer prof;
+    ArgSlotMark arg_slot;
+    uint32_t n, n_groups, residual_pass, n_passes, bit_words, pair_stride;
+    size_t n_slots, ctrl_words;
+    uint32_t pool_cap = 0;
+    uint32_t *status_word = nullptr;
+    bool zero_deferred = false;  // the zeroed block is cleared by the descriptor upload's launch
+    size_t zero_bytes = 0;
+    std::vector<pwaf_strcol> cols;
+    std::vector<uint32_t> col_bytes;  // arena sizes (0 = not known yet: learn_arena_sizes)
+    std::vector<uint8_t> col_known;
     VerdictArgs v{};
-    v.n = n;
-    v.n_groups = n_groups;
-    v.force_global_tables = (P.flags & PWAF_OPT_GLOBAL_VERDICT_TABLES) ? 1u : 0u;
-    v.sparse_mode = verdict_mode(P.flags);
-    if (v.sparse_mode >= 3) {
-        // the entry list: entries per wave in LDS, and the per-wave spill array (by column) for a group that appends more
-        const VerdictShape vs = verdict_shape(P.n_cols, (uint32_t)P.rules.size(), e->n_trig, (uint32_t)P.lits.size(), v.force_global_tables != 0, (int)v.sparse_mode, n_passes);
-        v.v_cap = vs.v_cap;
-        if ((rc = S.verdict_spill.reserve((size_t)verdict_blocks_sp(vs, e->n_cus) * vs.waves * P.n_cols * 8))) return rc;
-        v.spill = (unsigned long long *)S.verdict_spill.p;
-    } else if (v.sparse_mode) {
-        // the sparse column file: value slots per wave, and the per-wave spill array for a group that dirties more columns than that
-        const VerdictShape vs = verdict_shape(P.n_cols, (uint32_t)P.rules.size(), e->n_trig, (uint32_t)P.lits.size(), v.force_global_tables != 0, (int)v.sparse_mode, n_passes);
-        v.v_cap = vs.v_cap;
-        if (vs.v_cap < P.n_cols) {
-            if ((rc = S.verdict_spill.reserve((size_t)verdict_blocks_sp(vs, e->n_cus) * vs.waves * (P.n_cols - vs.v_cap) * 8))) return rc;
-            v.spill = (unsigned long long *)S.verdict_spill.p;
+    bool ipres_launched = false, attr_launched = false;
+    ListShape lshapes[2];  // (the shape is per PHASE: the filtered passes' candidate lists are long, the gap passes' short)
+    // the descriptors of every launch of the batch (prefilter, resolve, confirm tier, list scans, residual kernel): built on the host,
+    // uploaded ONCE
+    std::vector<uint32_t> filter_index;  // a filtered pass's index among the filtered passes (its candidate / valid bitmap)
+    std::vector<FilterArgs> fall;        // every filtered pass, in pass order
+    std::vector<FilterArgs> by_stride[2];
+    std::vector<ConfirmArgs> call;
+    std::vector<ListScanArgs> la[2];
+    ColPtrChunk ptrs{};  // residual kernel: the batch's string columns as arrays of pointers
+    uint64_t alg_bytes[3] = {0, 0, 0};  // per sampling stride
+    // ... and where they live in Scratch::args, with the work-item plans the plan kernels write behind them
+    const FilterArgs *d_all = nullptr, *d_s1 = nullptr, *d_s2 = nullptr;
+    const ConfirmArgs *d_c = nullptr;
+    const ListScanArgs *d_la[2] = {nullptr, nullptr};
+    uint32_t *c_plan = nullptr, *l_plan = nullptr;
+
+    BatchRun(pwaf_engine *e_, Scratch &S_, const pwaf_batch &db_, hipStream_t stream_, const std::vector<uint32_t> *col_begin_)
+        : e(e_), S(S_), P(*e_->prog.p), db(db_), stream(stream_), col_begin(col_begin_), sw(switches()), prof(e_, stream_), arg_slot{S_, stream_} {
+        n = db.n;
+        n_groups = (n + 63) / 64;
+        residual_pass = (uint32_t)e->groups.size() + (P.fcmp.empty() ? 0u : 1u);
+        n_passes = residual_pass + (P.n_residual ? 1u : 0u);  // (+ the pseudo passes of the field-against-field atoms and of the residual rules)
+        // visited bitmaps of the list-driven passes (one bit per request, whole 64-request groups): zeroed per batch — 1/32 of what
+        // zeroing the hit records themselves would write. They share ONE zeroed block with the control words and the confirm tier's walk bitmaps.
+        bit_words = 2 * n_groups;
+        // the attribute kernel's output: per group a header and room for EVERY non-scan atom (worst case: no overflow path)
+        pair_stride = std::max(1u, e->n_bit_atoms + e->n_cmp_atoms + e->n_short);
+        n_slots = (size_t)std::max(kGapLists, e->n_gated);
+        ctrl_words = 2 + n_slots + e->n_filtered;  // [0] pool allocator, [1] status word, one length per list slot, one pair count per filtered pass
+    }
+
+    // ---- scratch, columns, the verdict kernel's arguments ----
+
+    int reserve_scratch(bool sync_status) {
+        int rc;
+        // scratch sized for the worst case the 288 GB part can afford: one 4-byte hit record per (pass, request) and an overflow
+        // pool of 8 entries per request (exhaustion is reported through the status word, never silently)
+        // (a batch that exhausts the pool sets the context's sticky status word; the synchronous entry points then grow the pool to
+        // what the batch asked for — the allocator keeps counting past the cap — and run the batch again)
+        const uint64_t pool_cap64 = std::max<uint64_t>(std::max<uint64_t>(1u << 20, (uint64_t)n * 8), S.pool_entries);
+        pool_cap = (uint32_t)std::min<uint64_t>(pool_cap64, 0x7FFFFFF0u);
+        S.pool_entries = pool_cap;
+        // two sticky status words per context: [0] device-resident batches (reported and cleared by pwaf_engine_device_status),
+        // [1] the synchronous entry points (read and cleared by their own retry loop) — a synchronous batch on the same context can no
+        // longer swallow the overflow bit of an earlier asynchronous one
+        if (!S.status.p) {
+            if ((rc = S.status.reserve(8))) return rc;
+            HIP_TRY(hipMemsetAsync(S.status.p, 0, 8, stream));
         }
+        status_word = (uint32_t *)S.status.p + (sync_status ? 1 : 0);
+        if ((rc = S.rec.reserve((size_t)std::max(1u, n_passes) * n * 4))) return rc;
+        // (attr: plus 64 pairs of slack so the verdict kernel may read a full wave's worth unconditionally)
+        if ((rc = S.attr.reserve(((size_t)n_groups * pair_stride + 64) * 16 + (size_t)n_groups * 4))) return rc;
+        if ((rc = S.pool.reserve((size_t)pool_cap * sizeof(PoolEntry)))) return rc;
+        uint32_t n_conf = 0;
+        for (const DevGroup &d : e->groups) n_conf += (d.filtered && d.confirm) ? 1u : 0u;
+        Layout z;
+        const size_t z_ctrl = z.take(4 * ctrl_words), z_cand = z.take((size_t)e->n_filtered * bit_words * 4), z_visit = z.take((size_t)e->n_visit * bit_words * 4),
+                     z_walk = z.take((size_t)n_conf * bit_words * 4);
+        zero_bytes = z.size();
+        if ((rc = S.zero_block.reserve(zero_bytes))) return rc;
+        // (cleared by the descriptor upload's launch when nothing needs it before that: no pass that streams every request — those run first and
+        // count into the control words)
+        zero_deferred = e->n_filtered != 0;
+        for (const DevGroup &d : e->groups) zero_deferred = zero_deferred && (d.gate >= 0 || d.identity || d.short_lit);
+        if (!zero_deferred) HIP_TRY(hipMemsetAsync(S.zero_block.p, 0, zero_bytes, stream));
+        char *const zbase = (char *)S.zero_block.p;
+        S.ctrl.p = zbase + z_ctrl;
+        S.cand_bits.p = zbase + z_cand;
+        S.visit_bits.p = zbase + z_visit;
+        S.walk_bits.p = zbase + z_walk;
+        if (e->n_gated && (rc = S.gate_lists.reserve((size_t)e->n_gated * n * 4))) return rc;
+        if (e->n_need && (rc = S.need.reserve((size_t)e->n_need * n * 4))) return rc;
+        return PWAF_OK;
     }
-#ifdef PWAF_PROFILING
-    {
-        static const uint32_t skip = getenv("PWAF_DEBUG_SKIP") ? (uint32_t)strtoul(getenv("PWAF_DEBUG_SKIP"), nullptr, 0) : 0u;
-        v.debug_skip = skip;  // timing experiments only: results are wrong when non-zero
-        static const bool attr_prio = getenv("PWAF_ATTR_PRIO") != nullptr;
-        if (attr_prio) v.debug_skip |= 0x80000000u;
+
+    // string columns by field id: the five fixed fields, then one column per header name the rule set mentions (EXTENSION); a header
+    // the batch does not carry reads as the empty string for every request
+    int resolve_columns(bool totals_known) {
+        int rc;
+        cols.resize(e->n_fields);
+        col_bytes.assign(e->n_fields, 0);
+        for (int f = 0; f < PWAF_N_FIELDS; f++) {
+            cols[(size_t)f] = db.field[f];
+            col_bytes[(size_t)f] = db.field_bytes[f];
+        }
+        bool missing_header = false;
+        for (uint32_t f = PWAF_N_FIELDS; f < e->n_fields; f++) {
+            const uint32_t k = f - PWAF_N_FIELDS;
+            if (k < db.n_headers && db.headers != nullptr && db.headers[k].data != nullptr && db.headers[k].offsets != nullptr) {
+                cols[f] = db.headers[k];
+                col_bytes[f] = db.header_bytes ? db.header_bytes[k] : 0u;
+            } else {
+                missing_header = true;
+            }
+        }
+        if (missing_header) {
+            if (S.zero_off.cap < (size_t)(n + 1) * 4 + PWAF_ARENA_PAD) {
+                if ((rc = S.zero_off.reserve((size_t)(n + 1) * 4 + PWAF_ARENA_PAD))) return rc;
+                HIP_TRY(hipMemsetAsync(S.zero_off.p, 0, S.zero_off.cap, stream));
+            }
+            for (uint32_t f = PWAF_N_FIELDS; f < e->n_fields; f++)
+                if (cols[f].data == nullptr) {
+                    cols[f].data = (const uint8_t *)S.zero_off.p;
+                    cols[f].offsets = (const uint32_t *)S.zero_off.p;
+                    col_bytes[f] = 0;
+                }
+        }
+        col_known.assign(e->n_fields, totals_known ? 1 : 0);
+        for (uint32_t f = 0; f < e->n_fields; f++)
+            if (col_bytes[f] != 0 || cols[f].data == (const uint8_t *)S.zero_off.p) col_known[f] = 1;
+        return PWAF_OK;
     }
-#endif
-    for (int f = 0; f < PWAF_N_FIELDS; f++) v.off[f] = db.field[f].offsets;
-    v.ip = db.ip;
-    v.ip_is_v6 = db.ip_is_v6;
-    v.port = db.port;
-    v.flags = db.flags;
-    v.asn = db.asn;
-    v.country = db.country;
-    v.n_cols = P.n_cols;
-    v.n_passes = n_passes;
-    v.rec = (const uint32_t *)S.rec.p;
-    v.passes = (const PassInfo *)e->pass_table.p;
-    if (P.n_residual && e->residual_jit.function) {
-        v.res_words = (P.n_residual + 31u) / 32u;
-        v.res_base = P.residual_base;
-        if ((rc = S.res_words.reserve((size_t)v.res_words * n * 4))) return rc;
-        v.res_match = (const uint32_t *)S.res_words.p;
+
+    int fill_verdict_args(pwaf_verdict *d_out, pwaf_counts *d_counts, uint32_t *d_match_idx, uint32_t *d_n_matches) {
+        int rc;
+        v.n = n;
+        v.n_groups = n_groups;
+        v.force_global_tables = (P.flags & PWAF_OPT_GLOBAL_VERDICT_TABLES) ? 1u : 0u;
+        v.sparse_mode = verdict_mode(P.flags);
+        if (v.sparse_mode) {
+            // >= 3, the entry list: entries per wave in LDS, and the per-wave spill array (by column) for a group that appends more;
+            // else the sparse column file: value slots per wave, and the spill array for a group that dirties more columns than that
+            const VerdictShape vs = verdict_shape(P.n_cols, (uint32_t)P.rules.size(), e->n_trig, (uint32_t)P.lits.size(), v.force_global_tables != 0, (int)v.sparse_mode, n_passes);
+            v.v_cap = vs.v_cap;
+            const bool entry_list = v.sparse_mode >= 3;
+            const uint32_t spill_cols = entry_list ? P.n_cols : P.n_cols - std::min(vs.v_cap, P.n_cols);
+            if (entry_list || spill_cols) {
+                if ((rc = S.verdict_spill.reserve((size_t)verdict_blocks_sp(vs, e->n_cus) * vs.waves * spill_cols * 8))) return rc;
+                v.spill = (unsigned long long *)S.verdict_spill.p;
+            }
+        }
+        v.debug_skip = sw.debug_skip | (sw.attr_prio ? 0x80000000u : 0u);  // timing experiments only: results are wrong when non-zero
+        for (int f = 0; f < PWAF_N_FIELDS; f++) v.off[f] = db.field[f].offsets;
+        v.ip = db.ip;
+        v.ip_is_v6 = db.ip_is_v6;
+        v.port = db.port;
+        v.flags = db.flags;
+        v.asn = db.asn;
+        v.country = db.country;
+        v.n_cols = P.n_cols;
+        v.n_passes = n_passes;
+        v.rec = (const uint32_t *)S.rec.p;
+        v.passes = (const PassInfo *)e->pass_table.p;
+        if (P.n_residual && e->residual_jit.function) {
+            v.res_words = (P.n_residual + 31u) / 32u;
+            v.res_base = P.residual_base;
+            if ((rc = S.res_words.reserve((size_t)v.res_words * n * 4))) return rc;
+            v.res_match = (const uint32_t *)S.res_words.p;
+        }
+        v.cand_bits = (const uint32_t *)S.cand_bits.p;
+        v.visit_bits = (const uint32_t *)S.visit_bits.p;
+        v.bit_words = bit_words;
+        v.n_hlen = (uint32_t)e->hlen_fields.size();
+        for (size_t k = 0; k < e->hlen_fields.size(); k++) v.hoff[k] = cols[e->hlen_fields[k]].offsets;
+        v.gpairs = (uint4 *)S.attr.p;
+        v.ghdr = (uint32_t *)((char *)S.attr.p + ((size_t)n_groups * pair_stride + 64) * 16);
+        v.pair_stride = pair_stride;
+        v.attr_blocks = e->n_cus;
+        v.pool = (const PoolEntry *)S.pool.p;
+        v.cmp = (const CmpAtomDev *)e->num_atoms.p;
+        v.n_cmp = e->n_cmp_atoms;
+        v.cmp_vars = e->cmp_vars;
+        v.lazy = (const CmpAtomDev *)e->lazy_atoms.p;
+        v.n_lazy = e->n_lazy;
+        v.n_lazy_var = (uint32_t)e->lazy_vars.size();
+        for (size_t k = 0; k < e->lazy_vars.size(); k++) v.lazy_var[k] = e->lazy_vars[k];
+        v.n_short = e->n_short;
+        v.short_atoms = (const ShortAtom *)e->short_atoms.p;
+        if (e->n_short) {
+            v.short_data = cols[(size_t)e->short_field].data;
+            v.short_off = cols[(size_t)e->short_field].offsets;
+        }
+        v.n_trig = e->n_trig;
+        v.n_lits = (uint32_t)P.lits.size();
+        v.bit_col = (const uint32_t *)e->bit_atoms.p;
+        v.trig_off = (const uint32_t *)e->trig_off.p;
+        v.trig_rules = (const uint16_t *)e->trig_rules.p;
+        v.always_rules = (const uint32_t *)e->always_rules.p;
+        for (int var = 0; var < 2; var++) {
+            v.iu_vals[var] = (const int64_t *)e->iu_vals[var].p;
+            v.iu_masks[var] = (const uint32_t *)e->iu_masks[var].p;
+            v.iu_n[var] = e->iu_n[var];
+            v.iu_words[var] = e->iu_words[var];
+        }
+        v.country_masks = (const uint32_t *)e->country_luts.p;
+        v.cc_words = e->cc_words;
+        v.rules = (const DevRule *)e->rules.p;
+        v.n_rules = (uint32_t)P.rules.size();
+        v.lits = (const uint32_t *)e->lits.p;
+        set_trie_args(e, v);
+        if ((rc = S.ipres.reserve((size_t)n * (v.ipres_packed ? 4 : 8) + 64))) return rc;
+        v.ipres = (uint32_t *)S.ipres.p;
+        v.out = d_out;
+        v.counts = (unsigned long long *)d_counts;
+        v.match_idx = d_match_idx;
+        v.n_matches = d_n_matches;
+        return PWAF_OK;
     }
-    v.cand_bits = (const uint32_t *)S.cand_bits.p;
-    v.visit_bits = (const uint32_t *)S.visit_bits.p;
-    v.bit_words = bit_words;
+
     // A pass with heads writes records outside its candidate list too: zeroed here, read densely. (A confirm tier MERGES hits into zeroed
     // records: resolve_kernel zeroes the records of the requests that have a flagged chunk — the only ones a hit can land in.) Passes are
     // laid out so that the filtered ones are neighbours: runs of passes to zero take ONE memset each.
-    for (size_t k = 0; k < e->groups.size();) {
-        auto zeroed = [&](size_t q) { return e->groups[q].filtered && !e->groups[q].filter.heads.empty(); };
-        if (!zeroed(k)) { k++; continue; }
-        size_t k1 = k;
-        while (k1 < e->groups.size() && zeroed(k1)) k1++;
-        HIP_TRY(hipMemsetAsync((uint32_t *)S.rec.p + k * (size_t)n, 0, (k1 - k) * (size_t)n * 4, stream));
-        k = k1;
+    int zero_head_records() {
+        for (size_t k = 0; k < e->groups.size();) {
+            size_t k1 = k;
+            while (k1 < e->groups.size() && e->groups[k1].filtered && !e->groups[k1].filter.heads.empty()) k1++;
+            if (k1 == k) { k++; continue; }
+            HIP_TRY(hipMemsetAsync((uint32_t *)S.rec.p + k * (size_t)n, 0, (k1 - k) * (size_t)n * 4, stream));
+            k = k1;
+        }
+        return PWAF_OK;
     }
-    v.n_hlen = (uint32_t)e->hlen_fields.size();
-    for (size_t k = 0; k < e->hlen_fields.size(); k++) v.hoff[k] = cols[e->hlen_fields[k]].offsets;
-    v.gpairs = (uint4 *)S.attr.p;
-    v.ghdr = (uint32_t *)((char *)S.attr.p + ((size_t)n_groups * pair_stride + 64) * 16);
-    v.pair_stride = pair_stride;
-    v.attr_blocks = e->n_cus;
-    v.pool = (const PoolEntry *)S.pool.p;
-    v.cmp = (const CmpAtomDev *)e->num_atoms.p;
-    v.n_cmp = e->n_cmp_atoms;
-    v.cmp_vars = e->cmp_vars;
-    v.lazy = (const CmpAtomDev *)e->lazy_atoms.p;
-    v.n_lazy = e->n_lazy;
-    v.n_lazy_var = (uint32_t)e->lazy_vars.size();
-    for (size_t k = 0; k < e->lazy_vars.size(); k++) v.lazy_var[k] = e->lazy_vars[k];
-    v.n_short = e->n_short;
-    v.short_atoms = (const ShortAtom *)e->short_atoms.p;
-    if (e->n_short) {
-        v.short_data = cols[(size_t)e->short_field].data;
-        v.short_off = cols[(size_t)e->short_field].offsets;
+
+    void pick_list_shapes() {
+        uint32_t variant[2] = {2, 0};  // long candidate lists: 1024 threads over 144 KiB of hot rows (measured: benign 0.169 -> 0.143 ms, adversarial 4.43 -> 3.87 ms); short gap lists: 3 x 48 KiB
+        // With a confirm tier on every filtered pass the phase-0 lists are short walk lists: the small workgroup shape (512 threads,
+        // 48 KiB) starts on whatever wave slots the attribute kernels leave free — the 1024-thread / 144 KiB shape had to wait for a whole
+        // free CU (measured: 0.04 ms alone, 0.17 ms beside the side stream).
+        bool all_confirm = e->n_filtered != 0;
+        for (const DevGroup &d : e->groups) all_confirm = all_confirm && (!d.filtered || d.confirm);
+        if (all_confirm) variant[0] = 0;
+        if (sw.list_shape >= 0) {  // PWAF_LIST_SHAPE, timing experiments (same results): phase 0 | phase 1 << 4
+            variant[0] = (uint32_t)sw.list_shape & 15u;
+            variant[1] = (uint32_t)sw.list_shape >> 4;
+        }
+        for (int phase = 0; phase < 2; phase++) lshapes[phase] = list_shape(variant[phase]);
     }
-    v.n_trig = e->n_trig;
-    v.n_lits = (uint32_t)P.lits.size();
-    v.bit_col = (const uint32_t *)e->bit_atoms.p;
-    v.trig_off = (const uint32_t *)e->trig_off.p;
-    v.trig_rules = (const uint16_t *)e->trig_rules.p;
-    v.always_rules = (const uint32_t *)e->always_rules.p;
-    for (int var = 0; var < 2; var++) {
-        v.iu_vals[var] = (const int64_t *)e->iu_vals[var].p;
-        v.iu_masks[var] = (const uint32_t *)e->iu_masks[var].p;
-        v.iu_n[var] = e->iu_n[var];
-        v.iu_words[var] = e->iu_words[var];
+
+    // ---- launching ----
+
+    // One launch between its two marks. `what` names it in the error text; `side`: it goes to that stream instead of the batch's.
+    template <class Launch>
+    int timed(const char *name, uint64_t bytes, const char *what, Launch &&launch, hipStream_t side = nullptr) {
+        const int rc = prof.begin(side);
+        if (rc) return rc;
+        const int he = launch();
+        if (he) return fail(PWAF_E_DEVICE, std::string(what) + " launch failed: " + hipGetErrorString((hipError_t)he));
+        return prof.end(name, bytes, side);
     }
-    v.country_masks = (const uint32_t *)e->country_luts.p;
-    v.cc_words = e->cc_words;
-    v.rules = (const DevRule *)e->rules.p;
-    v.n_rules = (uint32_t)P.rules.size();
-    v.lits = (const uint32_t *)e->lits.p;
-    set_trie_args(e, v);
-    if ((rc = S.ipres.reserve((size_t)n * (v.ipres_packed ? 4 : 8) + 64))) return rc;
-    v.ipres = (uint32_t *)S.ipres.p;
-    v.out = d_out;
-    v.counts = (unsigned long long *)d_counts;
-    v.match_idx = d_match_idx;
-    v.n_matches = d_n_matches;
+
     // The attribute path — ipres_kernel (address lookups: one scattered 16-byte gather per request, bound by the texture addresser) and
     // attr_kernel (rows, transposes, comparisons: bound by vector-ALU issue) — does not depend on the scans. Placement (measured on
-    // MI355X, 10M requests; `PWAF_PLACEMENT` in profiling builds):
+    // MI355X, 10M requests; `PWAF_PLACEMENT` in profiling builds, every other build takes 2: Switches::placement):
     //   0  ipres on the side stream from the START of the batch, attr_kernel on the main stream after the prefilter    1.838 ms / step
     //   1  both on the main stream after the prefilter (every kernel alone)                                              1.861
     //   2  both on the side stream, forked after the prefilter                                        <- default          1.779
@@ -1038,72 +1183,226 @@ int run_pipeline(pwaf_engine *e, Scratch &S, const pwaf_batch &db /* device poin
     // roofline is quoted on, so it runs undisturbed.
     // Kernels that run beside each other take about as long as one after the other here (the step is the SUM of what its kernels
     // cost alone, give or take 2 %), so the placement only matters where the two really use different units.
-    int placement = 2;
-#ifdef PWAF_PROFILING
-    static const int forced_placement = getenv("PWAF_PLACEMENT") ? atoi(getenv("PWAF_PLACEMENT")) : (getenv("PWAF_ATTR_INLINE") ? 1 : getenv("PWAF_ATTR_EARLY") ? 3 : 2);
-    placement = forced_placement;
-#endif
-    bool ipres_launched = false, attr_launched = false;
-    auto launch_ipres_stage = [&](hipStream_t q) -> int {
+    // One of the two kernels on `q`: the batch's stream, or the side stream, which then leaves ev_join behind for join_side.
+    template <class Launch>
+    int side_stage(hipStream_t q, const char *name, uint64_t code, const char *what, Launch &&launch) {
+        const hipStream_t side = q != stream ? q : nullptr;
+        const int rc = timed(name, code, what, launch, side);
+        if (rc) return rc;
+        if (side) HIP_TRY(hipEventRecord(S.ev_join, q));
+        return PWAF_OK;
+    }
+    int ipres_stage(hipStream_t q) {
         if (ipres_launched) return PWAF_OK;
         ipres_launched = true;
-        int rc2, he = 0;
-        if (q != stream) {
+        if (q != stream) {  // fork: the side stream starts behind what the batch has enqueued so far
             HIP_TRY(hipEventRecord(S.ev_fork, stream));
             HIP_TRY(hipStreamWaitEvent(q, S.ev_fork, 0));
         }
-        if ((rc2 = mark(nullptr, 0, q != stream ? q : nullptr))) return rc2;
-#ifdef PWAF_PROFILING
-        static const bool skip_ipres = getenv("PWAF_SKIP_IPRES") != nullptr || getenv("PWAF_SKIP_ATTR") != nullptr;  // timing experiments only: every address resolves to class 0 / set 0
-        if (skip_ipres) HIP_TRY(hipMemsetAsync(v.ipres, 0, (size_t)n * (v.ipres_packed ? 4 : 8), q));
-        else
-#endif
-        he = launch_ipres(v, q);
-        if (he) return fail(PWAF_E_DEVICE, std::string("ipres kernel launch failed: ") + hipGetErrorString((hipError_t)he));
-        if ((rc2 = mark("ipres", 0xFAu, q != stream ? q : nullptr))) return rc2;
-        if (q != stream) HIP_TRY(hipEventRecord(S.ev_join, q));
-        return PWAF_OK;
-    };
-    auto launch_attr_stage = [&](hipStream_t q) -> int {
+        // (PWAF_SKIP_IPRES, timing experiments only: every address resolves to class 0 / set 0)
+        return side_stage(q, "ipres", 0xFAu, "ipres kernel", [&] { return sw.skip_ipres ? (int)hipMemsetAsync(v.ipres, 0, (size_t)n * (v.ipres_packed ? 4 : 8), q) : launch_ipres(v, q); });
+    }
+    int attr_stage(hipStream_t q) {
         if (attr_launched) return PWAF_OK;
         attr_launched = true;
-        int rc2, he = 0;
-        if (q == stream && (placement == 0)) HIP_TRY(hipStreamWaitEvent(stream, S.ev_join, 0));  // the side stream's ipres results
-        if ((rc2 = mark(nullptr, 0, q != stream ? q : nullptr))) return rc2;
-#ifdef PWAF_PROFILING
-        static const bool skip_attr = getenv("PWAF_SKIP_ATTR") != nullptr;  // timing experiments only: every non-scan predicate reads false
-        if (skip_attr) HIP_TRY(hipMemsetAsync(v.ghdr, 0, (size_t)n_groups * 4, q));
-        else
-#endif
-        he = launch_attr(v, q);
-        if (he) return fail(PWAF_E_DEVICE, std::string("attribute kernel launch failed: ") + hipGetErrorString((hipError_t)he));
-        if ((rc2 = mark("attr", 0xFEu, q != stream ? q : nullptr))) return rc2;
-        if (q != stream) HIP_TRY(hipEventRecord(S.ev_join, q));
-        return PWAF_OK;
-    };
+        if (q == stream && sw.placement == 0) HIP_TRY(hipStreamWaitEvent(stream, S.ev_join, 0));  // the side stream's ipres results
+        // (PWAF_SKIP_ATTR, timing experiments only: every non-scan predicate reads false)
+        return side_stage(q, "attr", 0xFEu, "attribute kernel", [&] { return sw.skip_attr ? (int)hipMemsetAsync(v.ghdr, 0, (size_t)n_groups * 4, q) : launch_attr(v, q); });
+    }
     // batch start: what forks here
-    if (placement == 0 && (rc = launch_ipres_stage(S.side))) return rc;
-    if (placement == 3 && ((rc = launch_ipres_stage(S.side)) || (rc = launch_attr_stage(S.side)))) return rc;
-    // after the prefilter (or, without one, before the list scans)
-    auto launch_attr_side = [&]() -> int {
-        int rc2;
-        if (placement == 0) return launch_attr_stage(stream);
-        if (placement == 1) { if ((rc2 = launch_ipres_stage(stream))) return rc2; return launch_attr_stage(stream); }
-        if (placement == 2) { if ((rc2 = launch_ipres_stage(S.side))) return rc2; return launch_attr_stage(S.side); }
+    int attr_at_start() {
+        int rc;
+        if (sw.placement == 0) return ipres_stage(S.side);
+        if (sw.placement == 3) return (rc = ipres_stage(S.side)) ? rc : attr_stage(S.side);
         return PWAF_OK;
-    };
+    }
+    // after the prefilter (or, without one, before the list scans); what has been launched is not launched again
+    int attr_after_filter() {
+        int rc;
+        switch (sw.placement) {
+        case 0: return attr_stage(stream);
+        case 1: return (rc = ipres_stage(stream)) ? rc : attr_stage(stream);
+        case 2: return (rc = ipres_stage(S.side)) ? rc : attr_stage(S.side);
+        default: return PWAF_OK;
+        }
+    }
+    // before the verdict kernel
+    int join_side() {
+        if (sw.placement >= 2) HIP_TRY(hipStreamWaitEvent(stream, S.ev_join, 0));  // (the attribute kernel ran on the side stream)
+        return PWAF_OK;
+    }
 
-    static const char *fn[5] = {"host", "url", "path", "method", "user_agent"};
-    auto scan_args = [&](size_t gi) -> ScanArgs {
+    // ---- 1. plain passes: the DFA walks every request (short fields go through the list-scan kernel below) ----
+    int launch_plain_scans() {
+        static const char *fn[5] = {"host", "url", "path", "method", "user_agent"};
+        for (size_t gi = 0; gi < e->groups.size(); gi++) {
+            const DevGroup &d = e->groups[gi];
+            if (d.gate >= 0 || d.identity || d.short_lit) continue;
+            const ScanArgs a = scan_args(gi);
+            char nm[48];
+            if (d.field < PWAF_N_FIELDS) snprintf(nm, sizeof nm, "scan_%s_g%zu", fn[d.field], gi);
+            else snprintf(nm, sizeof nm, "scan_hdr%u_g%zu", d.field - PWAF_N_FIELDS, gi);
+            prof.streaming = true;
+            // algorithmic bytes: the field's bytes + its offsets (0 bytes when the arena size is unknown)
+            const int rc = timed(nm, (uint64_t)col_bytes[d.field] + 4ull * (n + 1), "scan kernel", [&] { return launch_scan(a, stream); });
+            prof.streaming = false;
+            if (rc) return rc;
+        }
+        return PWAF_OK;
+    }
+
+    // ---- 2a. bigram prefilters of every filtered pass in one launch (the arenas as flat byte streams), hit segments -> candidate
+    //          bitmaps / pair lists ----
+    int launch_filter_stage() {
+        prof.streaming = true;
+        // algorithmic bytes: every streamed arena once + its offsets. The mark's name tells the bench which strides the launch mixed.
+        const int rc = timed(by_stride[1].empty() ? "filter_s1" : by_stride[0].empty() ? "filter_s2" : "filter_mix", alg_bytes[1] + alg_bytes[2], "filter kernel", [&] {
+            return launch_filter(by_stride[0].data(), (uint32_t)by_stride[0].size(), d_s1, by_stride[1].data(), (uint32_t)by_stride[1].size(), d_s2, stream);
+        });
+        prof.streaming = false;
+        return rc;
+    }
+    int launch_resolve_stage() {
+        bool any_list = false;  // (a pass with a confirm tier has no candidate bitmap to turn into a list: its flagged chunks are the work list)
+        for (const DevGroup &d : e->groups) any_list = any_list || (d.filtered && !d.confirm);
+        return timed("resolve+compact", 0xFCu, "resolve / compact kernel", [&] {
+            const int he = launch_resolve(fall.data(), (uint32_t)fall.size(), d_all, stream);
+            return !he && any_list ? launch_compact(fall.data(), (uint32_t)fall.size(), d_all, stream) : he;
+        });
+    }
+    // ---- 2b. confirm tier ----
+    int launch_confirm_stage() {
+        if (call.empty()) return PWAF_OK;
+        return timed("confirm", 0xF8u, "confirm kernel", [&] { return launch_confirm(call.data(), (uint32_t)call.size(), d_c, c_plan, e->n_cus, stream); });
+    }
+    // ---- 3. list-driven DFA passes: the launches assign_lists planned ----
+    int launch_list_scans() {
+        uint32_t *plan_at = l_plan;  // work-item prefix sums, one set per launch
+        for (int phase = 0; phase < 2; phase++) {
+            uint32_t first = 0;  // (a phase of more than 256 descriptors runs as several launches, one after the other on the stream)
+            for (const uint32_t cnt : e->lscan_launches[phase]) {
+                char nm[48];
+                snprintf(nm, sizeof nm, "lscan_x%u", cnt);
+                const int rc = timed(nm, 0xFDu, "gated scan kernel", [&] { return launch_scan_gated(la[phase].data() + first, cnt, d_la[phase] + first, plan_at, lshapes[phase], stream); });
+                if (rc) return rc;
+                plan_at += 2 * cnt + 1;  // (prefix sums, then the entries per work item of every pass)
+                first += cnt;
+            }
+        }
+        return PWAF_OK;
+    }
+    // field-against-field atoms: the last (pseudo) pass; its hit records are written for every request
+    int launch_fcmp_stage() {
+        if (P.fcmp.empty()) return PWAF_OK;
+        FcmpArgs fa{};
+        std::vector<uint32_t> slots;  // field ids in use, by slot
+        for (size_t k = 0; k < P.fcmp.size(); k++) {
+            uint32_t sl[2];
+            const uint32_t fld[2] = {P.fcmp[k].a, P.fcmp[k].b};
+            for (int q = 0; q < 2; q++) {
+                size_t at = std::find(slots.begin(), slots.end(), fld[q]) - slots.begin();
+                if (at == slots.size()) slots.push_back(fld[q]);
+                sl[q] = (uint32_t)at;
+            }
+            fa.atoms[k] = P.fcmp[k].op | (sl[0] << 8) | (sl[1] << 16);
+        }
+        for (size_t q = 0; q < slots.size() && q < kMaxFcmpFields; q++) {
+            fa.data[q] = cols[slots[q]].data;
+            fa.off[q] = cols[slots[q]].offsets;
+        }
+        fa.n = n;
+        fa.n_atoms = (uint32_t)P.fcmp.size();
+        fa.rec = (uint32_t *)S.rec.p + e->groups.size() * (size_t)n;
+        set_pool(fa);
+        return timed("fcmp", 0xFBu, "field comparison kernel", [&] { return launch_fcmp(fa, stream); });
+    }
+    // rules the column compiler could not take: interpreted per request (residual.h), results = the hit records of the last pseudo pass
+    template <class Args>
+    int residual_inputs(Args &a) {  // what both forms of the residual kernel read
+        a.data = (const uint8_t *const *)S.res_cols.p;
+        a.off = (const uint32_t *const *)((const char *)S.res_cols.p + (size_t)e->n_fields * 8);
+        a.blob = (const uint8_t *)e->residual_blob.p;
+        a.n = n;
+        a.n_rules = P.n_residual;
+        a.ip = db.ip;
+        a.ip_is_v6 = db.ip_is_v6;
+        a.port = db.port;
+        a.asn = db.asn;
+        a.country = db.country;
+        a.has_geo = (P.has_geo && P.residual_needs_geo) ? 1u : 0u;
+        a.geo_root4 = (const uint32_t *)e->geo_rec_root4.p;
+        a.geo_root6 = (const uint32_t *)e->geo_rec_root6.p;
+        a.geo_nodes = (const uint32_t *)e->geo_rec_nodes.p;
+        a.geo_recs = (const GeoRec *)e->geo_recs.p;
+        a.rule_errors = (unsigned long long *)e->residual_errors.p;
+        if (S.retry) {  // (pwaf_engine_rule_errors counts REQUESTS: a batch run again for a larger pool must not count its errors twice)
+            const int rc = S.err_sink.reserve((size_t)P.n_residual * 8);
+            if (rc) return rc;
+            a.rule_errors = (unsigned long long *)S.err_sink.p;
+        }
+        return PWAF_OK;
+    }
+    int launch_residual_stage() {
+        if (!P.n_residual) return PWAF_OK;
+        int rc;
+        if (e->residual_jit.function) {
+            // the SPECIALIZED form: the same programs as straight-line device code (compiled at creation); the verdict kernel reads the result words
+            ResidualJitArgs ja{};
+            if ((rc = residual_inputs(ja))) return rc;
+            ja.match_words = (uint32_t *)S.res_words.p;
+            return timed("residual_jit", 0xF9u, "specialized residual kernel", [&] { return launch_residual_jit(e->residual_jit, ja, e->n_cus, stream); });
+        }
+        ResidualArgs ra{};
+        if ((rc = residual_inputs(ra))) return rc;
+        ra.rec = (uint32_t *)S.rec.p + (size_t)residual_pass * n;
+        set_pool(ra);
+        return timed("residual", 0xF9u, "residual kernel", [&] { return launch_residual(ra, stream); });
+    }
+    int launch_verdict_stage() { return timed("verdict", 0xFFu, "verdict kernel", [&] { return launch_verdict(v, stream); }); }
+    // PWAF_DUMP_COUNTS, debugging aid: the device-side list lengths of this batch
+    int dump_counts() {
+        std::vector<uint32_t> cw(ctrl_words);
+        HIP_TRY(hipStreamSynchronize(stream));
+        HIP_TRY(hipMemcpy(cw.data(), S.ctrl.p, 4 * ctrl_words, hipMemcpyDeviceToHost));
+        fprintf(stderr, "[pwaf] n %u pool %u status %u |", n, cw[0], cw[1]);
+        for (size_t k = 0; k < e->groups.size(); k++) {
+            const DevGroup &d = e->groups[k];
+            if (d.gate >= 0) fprintf(stderr, " pass %zu field %u %s list %u", k, d.field, d.filtered ? (d.confirm ? "confirm" : "filtered") : "gap", cw[2 + (size_t)d.gate]);
+        }
+        for (uint32_t k = 0; k < e->n_filtered; k++) fprintf(stderr, " pairs[%u] %u", k, cw[2 + n_slots + k]);
+        fprintf(stderr, "\n");
+        return PWAF_OK;
+    }
+
+    // ---- the descriptors: host arithmetic over DevGroup, the scratch pointers and the columns ----
+
+    // where a kernel appends hit records that do not fit the pass's own: the overflow pool
+    template <class Args>
+    void set_pool(Args &a) const {
+        a.pool = (PoolEntry *)S.pool.p;
+        a.pool_count = (uint32_t *)S.ctrl.p;
+        a.pool_cap = pool_cap;
+        a.status = status_word;
+    }
+    // A pass that owns prefilter factors feeds the gated gap passes' request lists as its requests finish. (enq_bits: a gap pass's visited
+    // bitmap, indexed by its list slot — set when the request is enqueued; scan_kernel's requests are enqueued once by construction.)
+    bool feeds_gates(size_t gi) const { return e->n_gap && e->owns_factors[gi]; }
+    template <class Args>
+    void set_gate_feed(Args &a, const DevGroup &d) const {
+        a.colmask_local = (const uint32_t *)e->colmask.p + d.atom_base;
+        a.n_local = d.n_local;
+        a.gate_lists = (uint32_t *)S.gate_lists.p;
+        a.gate_count = (uint32_t *)S.ctrl.p + 2;
+        if constexpr (!std::is_same<Args, ScanArgs>::value) {
+            a.enq_bits = (uint32_t *)S.visit_bits.p;
+            a.enq_words = bit_words;
+        }
+    }
+
+    ScanArgs scan_args(size_t gi) const {
         const DevGroup &d = e->groups[gi];
         ScanArgs a{};
-        if (e->n_gap && e->owns_factors[gi]) {
-            // this pass owns prefilter factors: it feeds the gated gap passes' request lists as requests finish
-            a.colmask_local = (const uint32_t *)e->colmask.p + d.atom_base;
-            a.n_local = d.n_local;
-            a.gate_lists = (uint32_t *)S.gate_lists.p;
-            a.gate_count = (uint32_t *)S.ctrl.p + 2;
-        }
+        if (feeds_gates(gi)) set_gate_feed(a, d);
         a.data = cols[d.field].data;
         a.off = cols[d.field].offsets;
         a.n = n;
@@ -1124,34 +1423,154 @@ int run_pipeline(pwaf_engine *e, Scratch &S, const pwaf_batch &db /* device poin
         a.n_classes = d.n_classes;
         a.n_hot = d.n_hot;
         a.rec = (uint32_t *)S.rec.p + gi * (size_t)n;
-        a.pool = (PoolEntry *)S.pool.p;
-        a.pool_count = (uint32_t *)S.ctrl.p;
-        a.pool_cap = pool_cap;
-        a.status = status_word;
+        set_pool(a);
         return a;
-    };
-    // (the shape is per PHASE: the filtered passes' candidate lists are long, the gap passes' short)
-    uint32_t list_variant[2] = {2, 0};  // long candidate lists: 1024 threads over 144 KiB of hot rows (measured: benign 0.169 -> 0.143 ms, adversarial 4.43 -> 3.87 ms); short gap lists: 3 x 48 KiB
-#ifdef PWAF_PROFILING
-    static const uint32_t forced_shape = getenv("PWAF_LIST_SHAPE") ? (uint32_t)atoi(getenv("PWAF_LIST_SHAPE")) : 0u;  // timing experiments (same results): phase 0 | phase 1 << 4
-    if (getenv("PWAF_LIST_SHAPE")) {
-        list_variant[0] = forced_shape & 15u;
-        list_variant[1] = forced_shape >> 4;
     }
-#endif
-    {
-        // With a confirm tier on every filtered pass the phase-0 lists are short walk lists: the small workgroup shape (512 threads,
-        // 48 KiB) starts on whatever wave slots the attribute kernels leave free — the 1024-thread / 144 KiB shape had to wait for a whole
-        // free CU (measured: 0.04 ms alone, 0.17 ms beside the side stream).
-        bool all_confirm = e->n_filtered != 0;
-        for (const DevGroup &d : e->groups) all_confirm = all_confirm && (!d.filtered || d.confirm);
-#ifdef PWAF_PROFILING
-        if (!getenv("PWAF_LIST_SHAPE"))
-#endif
-        if (all_confirm) list_variant[0] = 0;
+
+    // arena sizes: a host batch's offsets were read while staging; a device batch says so itself or is asked (one small copy)
+    int learn_arena_sizes() {
+        bool ask = false;
+        for (const DevGroup &d : e->groups)
+            if (d.filtered && !col_known[d.field]) {
+                HIP_TRY(hipMemcpyAsync(&col_bytes[d.field], cols[d.field].offsets + n, 4, hipMemcpyDeviceToHost, stream));
+                ask = true;
+            }
+        if (ask) HIP_TRY(hipStreamSynchronize(stream));
+        return PWAF_OK;
     }
-    const ListShape lshapes[2] = {list_shape(list_variant[0]), list_shape(list_variant[1])};
-    auto list_args = [&](size_t gi, const ListShape &lshape, bool full_table = false) -> ListScanArgs {
+
+    uint32_t slab0_of(uint32_t field) const { return col_begin ? (*col_begin)[field] / kStreamSlab : 0u; }
+
+    // FilterArgs of every filtered pass (fall, in pass order; by_stride: the same split for the fused launch), sized scratch included
+    int build_filter_args() {
+        int rc;
+        filter_index.assign(e->groups.size(), 0);
+        if (!e->n_filtered) return PWAF_OK;
+        const uint32_t words = (n + 31) / 32, n_cblocks = (words + kCompactWords - 1) / kCompactWords;
+        uint64_t sub_entries = 0, n_slabs_all = 0, pair_bytes = 0;
+        for (const DevGroup &d : e->groups)
+            if (d.filtered) {
+                const uint64_t slabs = slab_count(col_bytes[d.field], slab0_of(d.field));
+                n_slabs_all += slabs;
+                sub_entries += slabs * (kStreamSlab / 512);  // chunk bitmap words
+                if (d.confirm) pair_bytes += (uint64_t)pair_cap_of((uint32_t)slabs, n) * sizeof(uint2);
+            }
+        if ((rc = S.chunk_bits.reserve((size_t)sub_entries * 4))) return rc;
+        if ((rc = S.cand_cnt.reserve((size_t)(2 * n_slabs_all + (uint64_t)e->n_filtered * n_cblocks) * 4))) return rc;  // per pass: flag counts per slab, pair-list starts per slab, candidates per compact workgroup
+        if (pair_bytes && (rc = S.pairs.reserve((size_t)pair_bytes))) return rc;
+        const bool dense_switch = !(P.flags & PWAF_OPT_NO_DENSE_SWITCH);
+        uint32_t fi = 0;
+        uint64_t sub_at = 0, cnt_at = 0, pair_at = 0;
+        for (size_t gi = 0; gi < e->groups.size(); gi++) {
+            const DevGroup &d = e->groups[gi];
+            if (!d.filtered) continue;
+            fall.emplace_back();
+            FilterArgs &f = fall.back();
+            f.data = cols[d.field].data;
+            f.off = cols[d.field].offsets;
+            f.n = n;
+            f.total = col_bytes[d.field];
+            f.init = d.filter.init;
+            f.mul = d.filter.mul;
+            f.stride = d.filter.stride;
+            f.debug = sw.filter_debug_skip;
+            f.table = (const uint32_t *)d.ftable.p;
+            f.n_heads = (uint32_t)std::min<size_t>(2, d.filter.heads.size());
+            for (uint32_t h = 0; h < f.n_heads; h++) {
+                const FilterHead &fh = d.filter.heads[h];
+                uint8_t lit[16] = {0}, msk[16] = {0};
+                memcpy(lit, fh.bytes, fh.len);
+                memset(msk, 0xFF, fh.len);
+                memcpy(f.head_w[h], lit, 16);
+                memcpy(f.head_m[h], msk, 16);
+                f.head_len[h] = fh.len | ((uint32_t)fh.exact << 8);
+                f.head_code[h] = h == 0 ? (uint32_t)fh.local + 1u : ((uint32_t)fh.local + 1u) << 15;
+            }
+            f.slab0 = slab0_of(d.field);
+            const uint32_t slabs = slabs_of(f);
+            f.rec = (uint32_t *)S.rec.p + gi * (size_t)n;
+            f.chunk_bits = (uint32_t *)S.chunk_bits.p + sub_at;
+            f.sub_count = (uint32_t *)S.cand_cnt.p + cnt_at;
+            f.pair_base = f.sub_count + slabs;
+            f.block_count = f.pair_base + slabs;
+            f.bitmap = (uint32_t *)S.cand_bits.p + (size_t)fi * bit_words;
+            filter_index[gi] = fi;
+            f.list = (uint32_t *)S.gate_lists.p + (size_t)d.gate * n;
+            f.list_count = (uint32_t *)S.ctrl.p + 2 + d.gate;
+            if (d.confirm) {
+                f.pair_cap = pair_cap_of(slabs, n);
+                f.pairs = (uint2 *)((char *)S.pairs.p + pair_at);
+                f.pair_count = (uint32_t *)S.ctrl.p + 2 + n_slots + fi;
+                pair_at += (uint64_t)f.pair_cap * sizeof(uint2);
+                if (dense_switch) {
+                    // more than half of the arena's 16-byte chunks flagged: confirming them one by one costs more than walking every request
+                    // (measured, round 5: the saturated stream took 22 ms in the confirm tier against 9 ms for the plain DFA over the same bytes;
+                    // the hostile stream of the 1k-rule set flags a quarter of its chunks and stays on the confirm tier: 1.3 ms against 3.9)
+                    f.dense_flag = f.pair_count;  // (the count filter_kernel leaves there, against dense_thresh)
+                    f.dense_thresh = (uint32_t)std::min<uint64_t>(0xFFFFFFFEu, (uint64_t)slabs * (kStreamSlab / 16) / 2);
+                }
+            }
+            f.first_block = 0;
+            sub_at += (uint64_t)slabs * (kStreamSlab / 512);
+            cnt_at += 2 * slabs + n_cblocks;
+            alg_bytes[f.stride == 2 ? 2 : 1] += (uint64_t)f.total + 4ull * (n + 1);
+            fi++;
+        }
+        // the fused filter launch takes the stride-1 passes and the stride-2 passes as two tables, first_block numbered within each
+        for (const FilterArgs &f : fall) {
+            std::vector<FilterArgs> &sub = by_stride[f.stride == 2 ? 1 : 0];
+            const uint32_t block = sub.empty() ? 0u : sub.back().first_block + (slabs_of(sub.back()) + kFilterWaves - 1) / kFilterWaves;
+            sub.push_back(f);
+            sub.back().first_block = block;
+        }
+        return PWAF_OK;
+    }
+
+    // confirm tier: what the flagged chunks of every candidate really hold (literal atoms decided; walk flags). `wi`: the pass's walk bitmap
+    ConfirmArgs confirm_args(const FilterArgs &f, const DevGroup &d, size_t gi, uint32_t wi) const {
+        ConfirmArgs c{};
+        c.data = f.data;
+        c.off = f.off;
+        c.n = n;
+        c.total = f.total;
+        c.pairs = f.pairs;
+        c.pair_count = f.pair_count;
+        c.pair_cap = f.pair_cap;
+        c.mul = f.mul;
+        c.stride = f.stride;
+        c.init = f.init;
+        c.ftable = f.table;
+        c.c_head = (const uint32_t *)d.c_head.p;
+        c.c_entries = (const ConfirmEntry *)d.c_entries.p;
+        c.c_bytes = (const uint8_t *)d.c_bytes.p;
+        c.c_classes = (const uint32_t *)d.c_classes.p;
+        c.n_entries = (uint32_t)d.filter.confirm.entries.size();
+        c.n_bytes = (uint32_t)d.filter.confirm.bytes.size() & ~3u;
+        c.n_class_words = (uint32_t)d.filter.confirm.classes.size();
+        c.rec = f.rec;
+        c.valid_bits = f.bitmap;
+        c.dense_flag = f.dense_flag;
+        c.dense_thresh = f.dense_thresh;
+        c.walk_bits = (uint32_t *)S.walk_bits.p + (size_t)wi * bit_words;
+        if (d.confirm_walk) {
+            c.walk_list = f.list;
+            c.walk_count = f.list_count;
+        }
+        set_pool(c);
+        if (feeds_gates(gi)) {
+            set_gate_feed(c, d);
+            c.shared_bits = d.shared_bits;
+        }
+        return c;
+    }
+    void build_confirm_args() {
+        for (size_t gi = 0; gi < e->groups.size(); gi++) {
+            const DevGroup &d = e->groups[gi];
+            if (d.filtered && d.confirm) call.push_back(confirm_args(fall[filter_index[gi]], d, gi, (uint32_t)call.size()));
+        }
+    }
+
+    ListScanArgs list_args(size_t gi, const ListShape &lshape, bool full_table = false) const {
         const DevGroup &d = e->groups[gi];
         ListScanArgs a{};
         const DevGroup &src = d.share_owner >= 0 ? e->groups[(size_t)d.share_owner] : d;  // whose list this pass walks
@@ -1164,13 +1583,8 @@ int run_pipeline(pwaf_engine *e, Scratch &S, const pwaf_batch &db /* device poin
             a.need_in = (const uint32_t *)S.need.p + (size_t)src.need_slot * n;
             a.need_bit = (uint32_t)d.gate;
         }
-        if (e->n_gap && e->owns_factors[gi]) {
-            a.colmask_local = (const uint32_t *)e->colmask.p + d.atom_base;
-            a.n_local = d.n_local;
-            a.gate_lists = (uint32_t *)S.gate_lists.p;
-            a.gate_count = (uint32_t *)S.ctrl.p + 2;
-            a.enq_bits = (uint32_t *)S.visit_bits.p;  // (a gap pass's visited bitmap, indexed by its list slot: set when the request is enqueued)
-            a.enq_words = bit_words;
+        if (feeds_gates(gi)) {
+            set_gate_feed(a, d);
             if (d.need_slot >= 0) {
                 a.need_out = (uint32_t *)S.need.p + (size_t)d.need_slot * n;
                 a.shared_bits = d.shared_bits;
@@ -1187,279 +1601,102 @@ int run_pipeline(pwaf_engine *e, Scratch &S, const pwaf_batch &db /* device poin
         a.umap = F.scalar_mode ? (const uint8_t *)F.flat_classmap.p + kUmapAt : nullptr;
         a.ill_class = F.ill_class;
         a.n_classes = F.n_classes;
-        {
-            // rows [0, n_full) and the delta records behind them, when this launch's LDS share holds the layout the tables were built for
-            const uint32_t row_bytes = 2u * (F.n_classes + 3u), hb = list_hot_bytes(lshape);
-            if (F.n_delta && (uint64_t)F.n_full * row_bytes + 48u + 8ull * F.n_delta <= hb) {
-                a.n_hot = F.n_full;
-                a.n_delta = F.n_delta;
-                a.delta = (const uint64_t *)F.delta.p;
-            } else {
-                a.n_hot = std::min<uint32_t>(F.n_delta ? F.n_full : F.n_states, (hb - 48u) / row_bytes);  // (states are in visit order: the first rows are the hot ones; 48 bytes stay free for the sentinel cell and lscan_async's dummy record)
-            }
+        // rows [0, n_full) and the delta records behind them, when this launch's LDS share holds the layout the tables were built for
+        const uint32_t row_bytes = 2u * (F.n_classes + 3u), hb = list_hot_bytes(lshape);
+        if (F.n_delta && (uint64_t)F.n_full * row_bytes + 48u + 8ull * F.n_delta <= hb) {
+            a.n_hot = F.n_full;
+            a.n_delta = F.n_delta;
+            a.delta = (const uint64_t *)F.delta.p;
+        } else {
+            a.n_hot = std::min<uint32_t>(F.n_delta ? F.n_full : F.n_states, (hb - 48u) / row_bytes);  // (states are in visit order: the first rows are the hot ones; 48 bytes stay free for the sentinel cell and lscan_async's dummy record)
         }
         a.emit_off = (const uint32_t *)F.emit_off.p;
         a.emit_list = (const uint16_t *)F.emit_list.p;
         a.end_off = (const uint32_t *)F.end_off.p;
         a.end_list = (const uint16_t *)F.end_list.p;
         a.rec = (uint32_t *)S.rec.p + gi * (size_t)n;
-        a.pool = (PoolEntry *)S.pool.p;
-        a.pool_count = (uint32_t *)S.ctrl.p;
-        a.pool_cap = pool_cap;
-        a.status = status_word;
+        set_pool(a);
         a.n_cus = e->n_cus;
         return a;
-    };
-    // ---- 1. plain passes: the DFA walks every request (short fields go through the list-scan kernel below) ----
-    for (size_t gi = 0; gi < e->groups.size(); gi++) {
-        const DevGroup &d = e->groups[gi];
-        if (d.gate >= 0 || d.identity || d.short_lit) continue;
-        const ScanArgs a = scan_args(gi);
-        char nm[48];
-        if (d.field < PWAF_N_FIELDS) snprintf(nm, sizeof nm, "scan_%s_g%zu", fn[d.field], gi);
-        else snprintf(nm, sizeof nm, "scan_hdr%u_g%zu", d.field - PWAF_N_FIELDS, gi);
-        stream_mark = true;
-        if ((rc = mark(nullptr, 0))) return rc;
-        int he = launch_scan(a, stream);
-        if (he) return fail(PWAF_E_DEVICE, std::string("scan kernel launch failed: ") + hipGetErrorString((hipError_t)he));
-        if ((rc = mark(nm, (uint64_t)col_bytes[d.field] + 4ull * (n + 1)))) return rc;  // algorithmic bytes: the field's bytes + its offsets (0 bytes when the arena size is unknown)
-        stream_mark = false;
     }
-    // ---- 2. the descriptors of every launch of the batch (prefilter, resolve, confirm tier, list scans, residual kernel): built here,
-    //         uploaded ONCE ----
-    std::vector<uint32_t> &totals = col_bytes;
-    // the flag-density switch (kernels.h: ListScanArgs::dense_flag): per pass with a confirm tier, the device word that says "walked whole this batch"
-    std::vector<const uint32_t *> dense_flag_of(e->groups.size(), nullptr);
-    std::vector<uint32_t> dense_thresh_of(e->groups.size(), 0);
-    std::vector<uint32_t> filter_index(e->groups.size(), 0);  // a filtered pass's index among the filtered passes (its candidate / valid bitmap)
-    const bool dense_switch = !(P.flags & PWAF_OPT_NO_DENSE_SWITCH);
-    std::vector<FilterArgs> fall;        // every filtered pass, in pass order
-    std::vector<FilterArgs> by_stride[2];
-    std::vector<ConfirmArgs> call;
-    std::vector<ListScanArgs> la[2];
-    uint64_t alg_bytes[3] = {0, 0, 0};  // per sampling stride
-    if (e->n_filtered) {
-        // arena sizes: a host batch's offsets were read while staging; a device batch says so itself or is asked (one small copy)
-        bool ask = false;
-        for (const DevGroup &d : e->groups)
-            if (d.filtered && !col_known[d.field]) ask = true;
-        if (ask) {
-            for (const DevGroup &d : e->groups)
-                if (d.filtered && !col_known[d.field]) HIP_TRY(hipMemcpyAsync(&totals[d.field], cols[d.field].offsets + n, 4, hipMemcpyDeviceToHost, stream));
-            HIP_TRY(hipStreamSynchronize(stream));
-        }
-        const uint32_t words = (n + 31) / 32, n_cblocks = (words + kCompactWords - 1) / kCompactWords;
-        uint64_t sub_entries = 0, n_slabs_all = 0;
-        for (const DevGroup &d : e->groups)
-            if (d.filtered) {
-                const uint64_t slabs = ((uint64_t)totals[d.field] + kStreamSlab - 1) / kStreamSlab - (col_begin ? (*col_begin)[d.field] / kStreamSlab : 0u);
-                n_slabs_all += slabs;
-                sub_entries += slabs * (kStreamSlab / 512);  // chunk bitmap words
-            }
-        if ((rc = S.chunk_bits.reserve((size_t)sub_entries * 4))) return rc;
-        if ((rc = S.cand_cnt.reserve((size_t)(2 * n_slabs_all + (uint64_t)e->n_filtered * n_cblocks) * 4))) return rc;  // per pass: flag counts per slab, pair-list starts per slab, candidates per compact workgroup
-        uint32_t fi = 0;
-        uint64_t sub_at = 0, cnt_at = 0, pair_at = 0;
-        {
-            uint64_t pair_bytes = 0;
-            for (const DevGroup &d : e->groups)
-                if (d.filtered && d.confirm) {
-                    const uint64_t slabs = ((uint64_t)totals[d.field] + kStreamSlab - 1) / kStreamSlab - (col_begin ? (*col_begin)[d.field] / kStreamSlab : 0u);
-                    pair_bytes += std::min<uint64_t>(0xFFFFFFF0u, slabs * (kStreamSlab / 16) + n + 64) * sizeof(uint2);
-                }
-            if (pair_bytes && (rc = S.pairs.reserve((size_t)pair_bytes))) return rc;
-        }
-        for (size_t gi = 0; gi < e->groups.size(); gi++) {
-            const DevGroup &d = e->groups[gi];
-            if (!d.filtered) continue;
-            fall.emplace_back();
-            FilterArgs &f = fall.back();
-            f = FilterArgs{};
-            f.data = cols[d.field].data;
-            f.off = cols[d.field].offsets;
-            f.n = n;
-            f.total = totals[d.field];
-            f.init = d.filter.init;
-            f.mul = d.filter.mul;
-            f.stride = d.filter.stride;
-#ifdef PWAF_PROFILING
-            static const uint32_t fdebug = getenv("PWAF_FILTER_DEBUG_SKIP") ? (uint32_t)atoi(getenv("PWAF_FILTER_DEBUG_SKIP")) : 0u;
-            f.debug = fdebug;
-#endif
-            f.table = (const uint32_t *)d.ftable.p;
-            f.n_heads = (uint32_t)std::min<size_t>(2, d.filter.heads.size());
-            for (uint32_t h = 0; h < f.n_heads; h++) {
-                const FilterHead &fh = d.filter.heads[h];
-                uint8_t lit[16] = {0}, msk[16] = {0};
-                memcpy(lit, fh.bytes, fh.len);
-                memset(msk, 0xFF, fh.len);
-                memcpy(f.head_w[h], lit, 16);
-                memcpy(f.head_m[h], msk, 16);
-                f.head_len[h] = fh.len | ((uint32_t)fh.exact << 8);
-                f.head_code[h] = h == 0 ? (uint32_t)fh.local + 1u : ((uint32_t)fh.local + 1u) << 15;
-            }
-            f.slab0 = col_begin ? (*col_begin)[d.field] / kStreamSlab : 0u;
-            const uint32_t slabs = (uint32_t)(((uint64_t)f.total + kStreamSlab - 1) / kStreamSlab) - f.slab0;
-            f.rec = (uint32_t *)S.rec.p + gi * (size_t)n;
-            f.chunk_bits = (uint32_t *)S.chunk_bits.p + sub_at;
-            f.sub_count = (uint32_t *)S.cand_cnt.p + cnt_at;
-            f.pair_base = f.sub_count + slabs;
-            f.block_count = f.pair_base + slabs;
-            f.bitmap = (uint32_t *)S.cand_bits.p + (size_t)fi * bit_words;
-            filter_index[gi] = fi;
-            f.list = (uint32_t *)S.gate_lists.p + (size_t)d.gate * n;
-            f.list_count = (uint32_t *)S.ctrl.p + 2 + d.gate;
-            if (d.confirm) {
-                // (request, flagged chunk) pairs: at most one per chunk of the arena plus one per request (a chunk that straddles two requests counts for both)
-                f.pair_cap = (uint32_t)std::min<uint64_t>(0xFFFFFFF0u, (uint64_t)slabs * (kStreamSlab / 16) + n + 64);
-                f.pairs = (uint2 *)((char *)S.pairs.p + pair_at);
-                f.pair_count = (uint32_t *)S.ctrl.p + 2 + n_slots + fi;
-                pair_at += (uint64_t)f.pair_cap * sizeof(uint2);
-                if (dense_switch) {
-                    // more than half of the arena's 16-byte chunks flagged: confirming them one by one costs more than walking every request
-                    // (measured, round 5: the saturated stream took 22 ms in the confirm tier against 9 ms for the plain DFA over the same bytes;
-                    // the hostile stream of the 1k-rule set flags a quarter of its chunks and stays on the confirm tier: 1.3 ms against 3.9)
-                    f.dense_flag = f.pair_count;  // (the count filter_kernel leaves there, against dense_thresh)
-                    f.dense_thresh = (uint32_t)std::min<uint64_t>(0xFFFFFFFEu, (uint64_t)slabs * (kStreamSlab / 16) / 2);
-                    dense_flag_of[gi] = f.dense_flag;
-                    dense_thresh_of[gi] = f.dense_thresh;
-                }
-            }
-            f.first_block = 0;
-            sub_at += (uint64_t)slabs * (kStreamSlab / 512);
-            cnt_at += 2 * slabs + n_cblocks;
-            alg_bytes[f.stride == 2 ? 2 : 1] += (uint64_t)f.total + 4ull * (n + 1);
-            fi++;
-        }
-        // the fused filter launch takes the stride-1 passes and the stride-2 passes as two tables, first_block numbered within each
-        for (const FilterArgs &f : fall) {
-            std::vector<FilterArgs> &sub = by_stride[f.stride == 2 ? 1 : 0];
-            const uint32_t block = sub.empty() ? 0u : sub.back().first_block + ((uint32_t)(((uint64_t)sub.back().total + kStreamSlab - 1) / kStreamSlab) - sub.back().slab0 + kFilterWaves - 1) / kFilterWaves;
-            sub.push_back(f);
-            sub.back().first_block = block;
-        }
-        // confirm tier: what the flagged chunks of every candidate really hold (literal atoms decided; walk flags)
-        uint32_t wi = 0;
-        fi = 0;
-        for (size_t gi = 0; gi < e->groups.size(); gi++) {
-            const DevGroup &d = e->groups[gi];
-            if (!d.filtered) continue;
-            const FilterArgs &f = fall[fi++];
-            if (!d.confirm) continue;
-            ConfirmArgs c{};
-            c.data = f.data;
-            c.off = f.off;
-            c.n = n;
-            c.total = f.total;
-            c.pairs = f.pairs;
-            c.pair_count = f.pair_count;
-            c.pair_cap = f.pair_cap;
-            c.mul = f.mul;
-            c.stride = f.stride;
-            c.init = f.init;
-            c.ftable = f.table;
-            c.c_head = (const uint32_t *)d.c_head.p;
-            c.c_entries = (const ConfirmEntry *)d.c_entries.p;
-            c.c_bytes = (const uint8_t *)d.c_bytes.p;
-            c.c_classes = (const uint32_t *)d.c_classes.p;
-            c.n_entries = (uint32_t)d.filter.confirm.entries.size();
-            c.n_bytes = (uint32_t)d.filter.confirm.bytes.size() & ~3u;
-            c.n_class_words = (uint32_t)d.filter.confirm.classes.size();
-            c.rec = f.rec;
-            c.valid_bits = f.bitmap;
-            c.dense_flag = f.dense_flag;
-            c.dense_thresh = f.dense_thresh;
-            c.walk_bits = (uint32_t *)S.walk_bits.p + (size_t)wi++ * bit_words;
-            if (d.confirm_walk) {
-                c.walk_list = f.list;
-                c.walk_count = f.list_count;
-            }
-            c.pool = (PoolEntry *)S.pool.p;
-            c.pool_count = (uint32_t *)S.ctrl.p;
-            c.pool_cap = pool_cap;
-            c.status = status_word;
-            if (e->n_gap && e->owns_factors[gi]) {
-                c.colmask_local = (const uint32_t *)e->colmask.p + d.atom_base;
-                c.n_local = d.n_local;
-                c.gate_lists = (uint32_t *)S.gate_lists.p;
-                c.gate_count = (uint32_t *)S.ctrl.p + 2;
-                c.enq_bits = (uint32_t *)S.visit_bits.p;
-                c.enq_words = bit_words;
-                c.shared_bits = d.shared_bits;
-            }
-            call.push_back(c);
-        }
+    // The flag-density switch (kernels.h: ListScanArgs::dense_flag): the FilterArgs of a pass whose confirm tier has it — they name the
+    // device word that says "walked whole this batch" and its threshold — else null.
+    const FilterArgs *dense_of(size_t gi) const {
+        const FilterArgs *f = e->groups[gi].filtered ? &fall[filter_index[gi]] : nullptr;
+        return f && f->dense_flag ? f : nullptr;
+    }
+    static void set_dense(ListScanArgs &a, const FilterArgs &f, uint32_t mode) {
+        a.dense_flag = f.dense_flag;
+        a.dense_thresh = f.dense_thresh;
+        a.dense_mode = mode;
     }
     // list-driven DFA passes: first those behind a prefilter (they may feed the gap passes' lists), then the gap passes
-    for (int phase = 0; phase < 2; phase++)
-        for (size_t gi = 0; gi < e->groups.size(); gi++) {
-            const DevGroup &d = e->groups[gi];
-            if (d.identity ? phase != 0 : (d.gate < 0 || d.filtered != (phase == 0))) continue;
-            if (phase == 0 && d.confirm && dense_flag_of[gi] != nullptr) {
-                // the pass's dense alternative: EVERY request through the full table (the whole-pass walk of PWAF_OPT_NO_CONFIRM, over the
-                // identity list), records and valid bits written for all; gets work only when the device set the pass's flag
-                ListScanArgs a = list_args(gi, lshapes[phase], /*full_table=*/true);
-                a.req_list = nullptr;
-                a.n_list = nullptr;
-                a.merge_rec = 0;
-                a.visited = (uint32_t *)S.cand_bits.p + (size_t)filter_index[gi] * bit_words;
-                a.dense_flag = dense_flag_of[gi];
-                a.dense_thresh = dense_thresh_of[gi];
-                a.dense_mode = 1;
+    void build_list_args() {
+        for (int phase = 0; phase < 2; phase++)
+            for (size_t gi = 0; gi < e->groups.size(); gi++) {
+                const DevGroup &d = e->groups[gi];
+                if (d.identity ? phase != 0 : (d.gate < 0 || d.filtered != (phase == 0))) continue;
+                const FilterArgs *const dense = phase == 0 && d.confirm ? dense_of(gi) : nullptr;
+                const FilterArgs *const owner_dense = d.share_owner >= 0 ? dense_of((size_t)d.share_owner) : nullptr;
+                if (dense) {
+                    // the pass's dense alternative: EVERY request through the full table (the whole-pass walk of PWAF_OPT_NO_CONFIRM, over the
+                    // identity list), records and valid bits written for all; gets work only when the device set the pass's flag
+                    ListScanArgs a = list_args(gi, lshapes[phase], /*full_table=*/true);
+                    a.req_list = nullptr;
+                    a.n_list = nullptr;
+                    a.merge_rec = 0;
+                    a.visited = (uint32_t *)S.cand_bits.p + (size_t)filter_index[gi] * bit_words;
+                    set_dense(a, *dense, 1);
+                    la[phase].push_back(a);
+                }
+                if (d.confirm && !d.confirm_walk) continue;  // every atom of the pass is a literal the confirm tier decided: nothing to walk
+                if (sw.skip_identity && d.identity) continue;
+                ListScanArgs a = list_args(gi, lshapes[phase]);
+                if (dense) set_dense(a, *dense, 2);  // the R-tier walk over the confirm tier's walk list: idle when the pass is walked whole
+                else if (owner_dense) set_dense(a, *owner_dense, 3);  // a gap pass riding the owner's list through need masks
                 la[phase].push_back(a);
             }
-            if (d.confirm && !d.confirm_walk) continue;  // every atom of the pass is a literal the confirm tier decided: nothing to walk
-#ifdef PWAF_PROFILING
-            if (skip_identity_walks() && d.identity) continue;
-#endif
-            ListScanArgs a = list_args(gi, lshapes[phase]);
-            if (phase == 0 && d.confirm && dense_flag_of[gi] != nullptr) {  // the R-tier walk over the confirm tier's walk list: idle when the pass is walked whole
-                a.dense_flag = dense_flag_of[gi];
-                a.dense_thresh = dense_thresh_of[gi];
-                a.dense_mode = 2;
-            } else if (d.share_owner >= 0 && dense_flag_of[(size_t)d.share_owner] != nullptr) {  // a gap pass riding the owner's list through need masks
-                a.dense_flag = dense_flag_of[(size_t)d.share_owner];
-                a.dense_thresh = dense_thresh_of[(size_t)d.share_owner];
-                a.dense_mode = 3;
-            }
-            la[phase].push_back(a);
-        }
-    for (int phase = 0; phase < 2; phase++) {  // (the launches assign_lists planned must take exactly these descriptors)
-        size_t planned = 0;
-        for (const uint32_t c : e->lscan_launches[phase]) planned += c;
-        if (planned != la[phase].size()) return fail(PWAF_E_DEVICE, "list-scan launch plan does not match the batch's descriptors");
     }
-    ColPtrChunk ptrs{};  // residual kernel: the batch's string columns as arrays of pointers
-    if (P.n_residual) {
+    int check_list_plan() const {  // (the launches assign_lists planned must take exactly these descriptors)
+        for (int phase = 0; phase < 2; phase++) {
+            size_t planned = 0;
+            for (const uint32_t c : e->lscan_launches[phase]) planned += c;
+            if (planned != la[phase].size()) return fail(PWAF_E_DEVICE, "list-scan launch plan does not match the batch's descriptors");
+        }
+        return PWAF_OK;
+    }
+    void build_column_pointers() {
+        if (!P.n_residual) return;
         const size_t nc = e->n_fields;
         ptrs.count = (uint32_t)(2 * nc);
         for (size_t f = 0; f < nc; f++) { ptrs.p[f] = cols[f].data; ptrs.p[nc + f] = cols[f].offsets; }
     }
-    // device layout of `args`: [all filtered passes] [stride-1 passes] [stride-2 passes] [confirm passes] [list passes of phase 0] [of
+
+    // ---- placement and upload ----
+    // Device layout of Scratch::args: [all filtered passes] [stride-1 passes] [stride-2 passes] [confirm passes] [list passes of phase 0] [of
     // phase 1] [column pointers] — the uploaded part — then the work-item plans the plan kernels write (confirm: count + 2 words; list
-    // scans: per launch 2 * count + 1)
-    const uint32_t nf = (uint32_t)fall.size(), nc_conf = (uint32_t)call.size();
-    const FilterArgs *d_all = nullptr, *d_s1 = nullptr, *d_s2 = nullptr;
-    const ConfirmArgs *d_c = nullptr;
-    const ListScanArgs *d_la[2] = {nullptr, nullptr};
-    uint32_t *c_plan = nullptr, *l_plan = nullptr;
-    {
-        size_t ab = 0;
-        auto part = [&](size_t bytes) { const size_t at = ab; ab = (ab + bytes + 255) & ~(size_t)255; return at; };
-        const size_t a_all = part((size_t)nf * sizeof(FilterArgs)), a_s1 = part(by_stride[0].size() * sizeof(FilterArgs)), a_s2 = part(by_stride[1].size() * sizeof(FilterArgs)),
-                     a_c = part((size_t)nc_conf * sizeof(ConfirmArgs)), a_l0 = part((la[0].size() + 1) * sizeof(ListScanArgs)), a_l1 = part((la[1].size() + 1) * sizeof(ListScanArgs)),
-                     a_ptrs = part((size_t)ptrs.count * sizeof(void *));
-        const size_t up_bytes = ab;
-        const size_t a_cplan = part(((size_t)nc_conf + 2) * 4), a_lplan = part((lsplit::plan_words(e->lscan_launches[0]) + lsplit::plan_words(e->lscan_launches[1])) * 4);
-        if ((rc = S.args.reserve(ab))) return rc;
+    // scans: per launch 2 * count + 1). The host writes the uploaded part into a page-locked slot; ONE copy launch moves it (and clears
+    // the zeroed block, when that was deferred).
+    int upload_descriptors() {
+        int rc;
+        struct Part { size_t at; const void *src; size_t bytes; };
+        const size_t b_all = fall.size() * sizeof(FilterArgs), b_s1 = by_stride[0].size() * sizeof(FilterArgs), b_s2 = by_stride[1].size() * sizeof(FilterArgs),
+                     b_c = call.size() * sizeof(ConfirmArgs), b_l0 = la[0].size() * sizeof(ListScanArgs), b_l1 = la[1].size() * sizeof(ListScanArgs),
+                     b_ptrs = (size_t)ptrs.count * sizeof(void *);
+        Layout L;  // (a list table keeps room for one descriptor more than it holds)
+        const Part up[7] = {{L.take(b_all), fall.data(), b_all}, {L.take(b_s1), by_stride[0].data(), b_s1}, {L.take(b_s2), by_stride[1].data(), b_s2}, {L.take(b_c), call.data(), b_c},
+                            {L.take(b_l0 + sizeof(ListScanArgs)), la[0].data(), b_l0}, {L.take(b_l1 + sizeof(ListScanArgs)), la[1].data(), b_l1}, {L.take(b_ptrs), ptrs.p, b_ptrs}};
+        const size_t up_bytes = L.size();
+        const size_t a_cplan = L.take((call.size() + 2) * 4), a_lplan = L.take((lsplit::plan_words(e->lscan_launches[0]) + lsplit::plan_words(e->lscan_launches[1])) * 4);
+        if ((rc = S.args.reserve(L.size()))) return rc;
         char *const abase = (char *)S.args.p;
-        d_all = (const FilterArgs *)(abase + a_all);
-        d_s1 = (const FilterArgs *)(abase + a_s1);
-        d_s2 = (const FilterArgs *)(abase + a_s2);
-        d_c = (const ConfirmArgs *)(abase + a_c);
-        d_la[0] = (const ListScanArgs *)(abase + a_l0);
-        d_la[1] = (const ListScanArgs *)(abase + a_l1);
-        S.res_cols.p = abase + a_ptrs;
+        d_all = (const FilterArgs *)(abase + up[0].at);
+        d_s1 = (const FilterArgs *)(abase + up[1].at);
+        d_s2 = (const FilterArgs *)(abase + up[2].at);
+        d_c = (const ConfirmArgs *)(abase + up[3].at);
+        d_la[0] = (const ListScanArgs *)(abase + up[4].at);
+        d_la[1] = (const ListScanArgs *)(abase + up[5].at);
+        S.res_cols.p = abase + up[6].at;
         c_plan = (uint32_t *)(abase + a_cplan);
         l_plan = (uint32_t *)(abase + a_lplan);
         if (up_bytes) {
@@ -1467,191 +1704,129 @@ int run_pipeline(pwaf_engine *e, Scratch &S, const pwaf_batch &db /* device poin
             if (S.arg_pending[slot]) HIP_TRY(hipEventSynchronize(S.arg_ev[slot]));  // (the copy launch that read this slot last has run: returns at once unless the caller is kArgSlots batches ahead)
             if ((rc = S.arg_slot[slot].reserve(up_bytes))) return rc;
             char *const hb = (char *)S.arg_slot[slot].p;
-            auto put = [&](size_t at, const void *src, size_t bytes) { if (bytes) memcpy(hb + at, src, bytes); };
-            put(a_all, fall.data(), (size_t)nf * sizeof(FilterArgs));
-            put(a_s1, by_stride[0].data(), by_stride[0].size() * sizeof(FilterArgs));
-            put(a_s2, by_stride[1].data(), by_stride[1].size() * sizeof(FilterArgs));
-            put(a_c, call.data(), (size_t)nc_conf * sizeof(ConfirmArgs));
-            put(a_l0, la[0].data(), la[0].size() * sizeof(ListScanArgs));
-            put(a_l1, la[1].data(), la[1].size() * sizeof(ListScanArgs));
-            put(a_ptrs, ptrs.p, (size_t)ptrs.count * sizeof(void *));
-            int he = upload_args_block(hb, S.args.p, up_bytes, zero_deferred ? S.zero_block.p : nullptr, zero_deferred ? zero_bytes : 0, stream);
+            for (const Part &p : up)
+                if (p.bytes) memcpy(hb + p.at, p.src, p.bytes);
+            arg_slot.slot = (int)slot;  // (from here on every way out of the pipeline records the slot's event)
+            const int he = upload_args_block(hb, S.args.p, up_bytes, zero_deferred ? S.zero_block.p : nullptr, zero_deferred ? zero_bytes : 0, stream);
             if (he) return fail(PWAF_E_DEVICE, std::string("descriptor upload failed: ") + hipGetErrorString((hipError_t)he));
-            zero_deferred = false;
-            arg_slot_used = (int)slot;  // (its event is recorded at the END of the batch: a record between two kernels keeps the second from starting while the first drains)
-        }
-        if (zero_deferred) {  // (nothing to upload: the block is cleared the old way)
+        } else if (zero_deferred) {  // (nothing to upload: the block is cleared the old way)
             HIP_TRY(hipMemsetAsync(S.zero_block.p, 0, zero_bytes, stream));
-            zero_deferred = false;
         }
+        zero_deferred = false;
+        return PWAF_OK;
     }
-    // ---- 2a. bigram prefilters of every filtered pass in one launch (the arenas as flat byte streams), hit segments -> candidate
-    //          bitmaps / pair lists ----
+};
+
+// One batch of device columns through every launch. Nothing between upload_descriptors and the end returns past
+// BatchRun's destructor: the descriptor slot's event is recorded whichever way the batch leaves (ArgSlotMark).
+int run_pipeline(pwaf_engine *e, Scratch &S, const pwaf_batch &db /* device pointers */, pwaf_verdict *d_out, pwaf_counts *d_counts, uint32_t *d_match_idx,
+                 uint32_t *d_n_matches, hipStream_t stream, bool totals_known = false, const std::vector<uint32_t> *col_begin = nullptr, bool sync_status = false) {
+    if (db.n == 0) return PWAF_OK;
+    BatchRun b(e, S, db, stream, col_begin);
+    int rc;
+    if ((rc = b.reserve_scratch(sync_status)) || (rc = b.resolve_columns(totals_known))) return rc;
+    if ((rc = b.fill_verdict_args(d_out, d_counts, d_match_idx, d_n_matches)) || (rc = b.zero_head_records())) return rc;
+    b.pick_list_shapes();
+    if ((rc = b.attr_at_start()) || (rc = b.launch_plain_scans())) return rc;
+    // every descriptor of the batch: built, checked against the launch plan, uploaded once
+    if ((rc = b.learn_arena_sizes()) || (rc = b.build_filter_args())) return rc;
+    b.build_confirm_args();
+    b.build_list_args();
+    b.build_column_pointers();
+    if ((rc = b.check_list_plan()) || (rc = b.upload_descriptors())) return rc;
     if (e->n_filtered) {
-        int he;
-        stream_mark = true;
-        if ((rc = mark(nullptr, 0))) return rc;
-        he = launch_filter(by_stride[0].data(), (uint32_t)by_stride[0].size(), d_s1, by_stride[1].data(), (uint32_t)by_stride[1].size(), d_s2, stream);
-        if (he) return fail(PWAF_E_DEVICE, std::string("filter kernel launch failed: ") + hipGetErrorString((hipError_t)he));
-        // algorithmic bytes: every streamed arena once + its offsets. The mark's name tells the bench which strides the launch mixed.
-        if ((rc = mark(by_stride[1].empty() ? "filter_s1" : by_stride[0].empty() ? "filter_s2" : "filter_mix", alg_bytes[1] + alg_bytes[2]))) return rc;
-        stream_mark = false;
-#ifdef PWAF_PROFILING
-        static const bool attr_after_compact = getenv("PWAF_ATTR_AFTER_COMPACT") != nullptr;  // timing experiment
-        if (!attr_after_compact)
-#endif
-        if ((rc = launch_attr_side())) return rc;
-        if ((rc = mark(nullptr, 0))) return rc;
-        he = launch_resolve(fall.data(), nf, d_all, stream);
-        bool any_list = false;  // (a pass with a confirm tier has no candidate bitmap to turn into a list: its flagged chunks are the work list)
-        for (const DevGroup &d : e->groups) any_list = any_list || (d.filtered && !d.confirm);
-        if (!he && any_list) he = launch_compact(fall.data(), nf, d_all, stream);
-        if (he) return fail(PWAF_E_DEVICE, std::string("resolve / compact kernel launch failed: ") + hipGetErrorString((hipError_t)he));
-        if ((rc = mark("resolve+compact", 0xFCu))) return rc;
-        // ---- 2b. confirm tier ----
-        if (!call.empty()) {
-            if ((rc = mark(nullptr, 0))) return rc;
-            he = launch_confirm(call.data(), nc_conf, d_c, c_plan, e->n_cus, stream);
-            if (he) return fail(PWAF_E_DEVICE, std::string("confirm kernel launch failed: ") + hipGetErrorString((hipError_t)he));
-            if ((rc = mark("confirm", 0xF8u))) return rc;
-        }
+        if ((rc = b.launch_filter_stage())) return rc;
+        if (!b.sw.attr_after_compact && (rc = b.attr_after_filter())) return rc;  // (PWAF_ATTR_AFTER_COMPACT: timing experiment)
+        if ((rc = b.launch_resolve_stage()) || (rc = b.launch_confirm_stage())) return rc;
     }
-    if ((rc = launch_attr_side())) return rc;  // (no filtered pass: beside the list scans / the verdict kernel's predecessors)
-    // ---- 3. list-driven DFA passes ----
-    {
-        uint32_t *plan_at = l_plan;  // work-item prefix sums, one set per launch
-        for (int phase = 0; phase < 2; phase++) {
-            uint32_t first = 0;  // (a phase of more than 256 descriptors runs as several launches, one after the other on the stream)
-            for (const uint32_t cnt : e->lscan_launches[phase]) {
-                if ((rc = mark(nullptr, 0))) return rc;
-                int he = launch_scan_gated(la[phase].data() + first, cnt, d_la[phase] + first, plan_at, lshapes[phase], stream);
-                plan_at += 2 * cnt + 1;  // (prefix sums, then the entries per work item of every pass)
-                first += cnt;
-                if (he) return fail(PWAF_E_DEVICE, std::string("gated scan kernel launch failed: ") + hipGetErrorString((hipError_t)he));
-                char nm[48];
-                snprintf(nm, sizeof nm, "lscan_x%u", cnt);
-                if ((rc = mark(nm, 0xFDu))) return rc;
-            }
-        }
-    }
-    if (!P.fcmp.empty()) {
-        // field-against-field atoms: the last (pseudo) pass; its hit records are written for every request
-        FcmpArgs fa{};
-        std::vector<uint32_t> slots;  // field ids in use, by slot
-        for (size_t k = 0; k < P.fcmp.size(); k++) {
-            uint32_t sl[2];
-            const uint32_t fld[2] = {P.fcmp[k].a, P.fcmp[k].b};
-            for (int q = 0; q < 2; q++) {
-                size_t at = std::find(slots.begin(), slots.end(), fld[q]) - slots.begin();
-                if (at == slots.size()) slots.push_back(fld[q]);
-                sl[q] = (uint32_t)at;
-            }
-            fa.atoms[k] = P.fcmp[k].op | (sl[0] << 8) | (sl[1] << 16);
-        }
-        for (size_t q = 0; q < slots.size() && q < kMaxFcmpFields; q++) {
-            fa.data[q] = cols[slots[q]].data;
-            fa.off[q] = cols[slots[q]].offsets;
-        }
-        fa.n = n;
-        fa.n_atoms = (uint32_t)P.fcmp.size();
-        fa.rec = (uint32_t *)S.rec.p + e->groups.size() * (size_t)n;
-        fa.pool = (PoolEntry *)S.pool.p;
-        fa.pool_count = (uint32_t *)S.ctrl.p;
-        fa.pool_cap = pool_cap;
-        fa.status = status_word;
-        if ((rc = mark(nullptr, 0))) return rc;
-        int he = launch_fcmp(fa, stream);
-        if (he) return fail(PWAF_E_DEVICE, std::string("field comparison kernel launch failed: ") + hipGetErrorString((hipError_t)he));
-        if ((rc = mark("fcmp", 0xFBu))) return rc;
-    }
-    if (P.n_residual) {
-        // rules the column compiler could not take: interpreted per request (residual.h), results = the hit records of the last pseudo pass
-        ResidualArgs ra{};
-        const size_t nc = e->n_fields;
-        ra.data = (const uint8_t *const *)S.res_cols.p;
-        ra.off = (const uint32_t *const *)((const char *)S.res_cols.p + nc * 8);
-        ra.blob = (const uint8_t *)e->residual_blob.p;
-        ra.n = n;
-        ra.n_rules = P.n_residual;
-        ra.ip = db.ip;
-        ra.ip_is_v6 = db.ip_is_v6;
-        ra.port = db.port;
-        ra.asn = db.asn;
-        ra.country = db.country;
-        ra.has_geo = (P.has_geo && P.residual_needs_geo) ? 1u : 0u;
-        ra.geo_root4 = (const uint32_t *)e->geo_rec_root4.p;
-        ra.geo_root6 = (const uint32_t *)e->geo_rec_root6.p;
-        ra.geo_nodes = (const uint32_t *)e->geo_rec_nodes.p;
-        ra.geo_recs = (const GeoRec *)e->geo_recs.p;
-        ra.rec = (uint32_t *)S.rec.p + (size_t)residual_pass * n;
-        ra.pool = (PoolEntry *)S.pool.p;
-        ra.pool_count = (uint32_t *)S.ctrl.p;
-        ra.pool_cap = pool_cap;
-        ra.status = status_word;
-        ra.rule_errors = (unsigned long long *)e->residual_errors.p;
-        if (S.retry) {  // (pwaf_engine_rule_errors counts REQUESTS: a batch run again for a larger pool must not count its errors twice)
-            if ((rc = S.err_sink.reserve((size_t)P.n_residual * 8))) return rc;
-            ra.rule_errors = (unsigned long long *)S.err_sink.p;
-        }
-        if ((rc = mark(nullptr, 0))) return rc;
-        if (e->residual_jit.function) {
-            // the SPECIALIZED form: the same programs as straight-line device code (compiled at creation); the verdict kernel reads the result words
-            ResidualJitArgs ja{};
-            ja.data = ra.data;
-            ja.off = ra.off;
-            ja.blob = ra.blob;
-            ja.n = n;
-            ja.n_rules = P.n_residual;
-            ja.ip = ra.ip;
-            ja.ip_is_v6 = ra.ip_is_v6;
-            ja.port = ra.port;
-            ja.asn = ra.asn;
-            ja.country = ra.country;
-            ja.has_geo = ra.has_geo;
-            ja.geo_root4 = ra.geo_root4;
-            ja.geo_root6 = ra.geo_root6;
-            ja.geo_nodes = ra.geo_nodes;
-            ja.geo_recs = ra.geo_recs;
-            ja.match_words = (uint32_t *)S.res_words.p;
-            ja.rule_errors = ra.rule_errors;
-            int hj = launch_residual_jit(e->residual_jit, ja, e->n_cus, stream);
-            if (hj) return fail(PWAF_E_DEVICE, std::string("specialized residual kernel launch failed: ") + hipGetErrorString((hipError_t)hj));
-            if ((rc = mark("residual_jit", 0xF9u))) return rc;
-        } else {
-            int he2 = launch_residual(ra, stream);
-            if (he2) return fail(PWAF_E_DEVICE, std::string("residual kernel launch failed: ") + hipGetErrorString((hipError_t)he2));
-            if ((rc = mark("residual", 0xF9u))) return rc;
-        }
-    }
-    if (placement >= 2) HIP_TRY(hipStreamWaitEvent(stream, S.ev_join, 0));  // (the attribute kernel ran on the side stream)
-    if ((rc = mark(nullptr, 0))) return rc;
-    int he = launch_verdict(v, stream);
-    if (he) return fail(PWAF_E_DEVICE, std::string("verdict kernel launch failed: ") + hipGetErrorString((hipError_t)he));
-    if ((rc = mark("verdict", 0xFFu))) return rc;
-#ifdef PWAF_PROFILING
-    {
-        static const bool dump_counts = getenv("PWAF_DUMP_COUNTS") != nullptr;  // debugging aid: the device-side list lengths of this batch
-        if (dump_counts) {
-            std::vector<uint32_t> cw(ctrl_words);
-            HIP_TRY(hipStreamSynchronize(stream));
-            HIP_TRY(hipMemcpy(cw.data(), S.ctrl.p, 4 * ctrl_words, hipMemcpyDeviceToHost));
-            fprintf(stderr, "[pwaf] n %u pool %u status %u |", n, cw[0], cw[1]);
-            for (size_t k = 0; k < e->groups.size(); k++) {
-                const DevGroup &d = e->groups[k];
-                if (d.gate >= 0) fprintf(stderr, " pass %zu field %u %s list %u", k, d.field, d.filtered ? (d.confirm ? "confirm" : "filtered") : "gap", cw[2 + (size_t)d.gate]);
-            }
-            for (uint32_t k = 0; k < e->n_filtered; k++) fprintf(stderr, " pairs[%u] %u", k, cw[2 + n_slots + k]);
-            fprintf(stderr, "\n");
-        }
-    }
-#endif
-    if (arg_slot_used >= 0) {
-        HIP_TRY(hipEventRecord(S.arg_ev[arg_slot_used], stream));  // (the copy launch that read the slot ran before everything recorded here)
-        S.arg_pending[arg_slot_used] = true;
-    }
-    e->n_timed = ev_i;
+    if ((rc = b.attr_after_filter())) return rc;  // (no filtered pass: beside the list scans / the verdict kernel's predecessors)
+    if ((rc = b.launch_list_scans()) || (rc = b.launch_fcmp_stage()) || (rc = b.launch_residual_stage())) return rc;
+    if ((rc = b.join_side()) || (rc = b.launch_verdict_stage())) return rc;
+    if (b.sw.dump_counts && (rc = b.dump_counts())) return rc;
+    if ((rc = b.arg_slot.record())) return rc;
+    b.prof.commit();
     return PWAF_OK;
 }
+
+// What a context remembers of its latest batch (acquire_context), and the event its next user waits for.
+hipError_t mark_context_used(Scratch &S, hipStream_t s, bool own) {
+    S.used = true;
+    S.last = s;
+    S.last_own = own;
+    return hipEventRecord(S.done, s);
+}
+
+int device_error(const char *call, hipError_t he) { return fail(PWAF_E_DEVICE, std::string(call) + ": " + hipGetErrorString(he)); }
+
+// The synchronous entry points' batch on the context's own stream: runs the pipeline and waits ONCE — the status words travel back
+// (into page-locked memory) behind the batch, together with whatever `after` enqueues (the verdicts on their way to the host). A batch
+// that exhausted the overflow pool is run again, at most twice, with a pool of the size it asked for (the staged columns stay where
+// they are). `counts_zero`: the first attempt's counters arrive zeroed (they are part of a staged block). Whatever fails, the stream is
+// drained before the call returns: what was enqueued may still read the caller's buffers.
+template <class After>
+int run_with_retry(pwaf_engine *e, Scratch &S, const pwaf_batch &db, pwaf_verdict *d_out, pwaf_counts *d_counts, bool known, const std::vector<uint32_t> *begins, bool counts_zero,
+                   After &&after) {
+    const hipStream_t s = S.stream;
+    int r = S.pin_status.reserve(16);
+    volatile uint32_t *const st = (volatile uint32_t *)S.pin_status.p;
+    for (int attempt = 0;; attempt++) {
+        hipError_t he = hipSuccess;
+        if (!r && d_counts && !(counts_zero && attempt == 0) && (he = hipMemsetAsync(d_counts, 0, sizeof *d_counts, s)) != hipSuccess) r = device_error("hipMemsetAsync", he);
+        if (!r) {
+            S.retry = attempt > 0;
+            r = run_pipeline(e, S, db, d_out, d_counts, nullptr, nullptr, s, known, begins, true);
+            S.retry = false;
+        }
+        if (!r) {
+            he = hipMemcpyAsync((void *)&st[0], (uint32_t *)S.status.p + 1, 4, hipMemcpyDeviceToHost, s);
+            if (he == hipSuccess) he = hipMemcpyAsync((void *)&st[1], S.ctrl.p, 4, hipMemcpyDeviceToHost, s);  // overflow entries the batch asked for
+            r = he != hipSuccess ? device_error("hipMemcpyAsync", he) : after();
+        }
+        const hipError_t re = mark_context_used(S, s, true), se = hipStreamSynchronize(s);
+        if (r) return r;
+        if (re != hipSuccess) return device_error("hipEventRecord", re);
+        if (se != hipSuccess) return device_error("hipStreamSynchronize", se);
+        if (!st[0]) return PWAF_OK;
+        HIP_TRY(hipMemsetAsync((uint32_t *)S.status.p + 1, 0, 4, s));
+        if (attempt >= 2 || st[1] >= 0x7FFFFFF0u) return fail(PWAF_E_NOMEM, "scan overflow pool exhausted: verdicts of this batch are incomplete");
+        S.pool_entries = (uint64_t)st[1] + st[1] / 4 + 1024;
+    }
+}
+
+// The device-side view of a batch whose columns the engine placed itself (a staged host batch, unpacked records): an ordinary DEVICE
+// batch with every column's size known on the host.
+struct DeviceBatch {
+    pwaf_batch db{};
+    std::vector<pwaf_strcol> hdr_cols;
+    std::vector<uint32_t> hdr_bytes;
+    DeviceBatch(uint32_t n, uint32_t n_fields) : hdr_cols(n_fields - PWAF_N_FIELDS, pwaf_strcol{nullptr, nullptr}), hdr_bytes(n_fields - PWAF_N_FIELDS, 0) {
+        db.struct_size = sizeof db;
+        db.n = n;
+        db.memory = PWAF_MEM_DEVICE;
+        db.n_headers = (uint32_t)hdr_cols.size();
+        db.headers = hdr_cols.empty() ? nullptr : hdr_cols.data();
+        db.header_bytes = hdr_bytes.empty() ? nullptr : hdr_bytes.data();
+    }
+    DeviceBatch(const DeviceBatch &) = delete;  // (db points into the vectors)
+    void set_col(uint32_t f, const void *data, const void *offsets, uint32_t bytes) {
+        const pwaf_strcol c{(const uint8_t *)data, (const uint32_t *)offsets};
+        if (f < PWAF_N_FIELDS) {
+            db.field[f] = c;
+            db.field_bytes[f] = bytes;
+        } else {
+            hdr_cols[f - PWAF_N_FIELDS] = c;
+            hdr_bytes[f - PWAF_N_FIELDS] = bytes;
+        }
+    }
+    void set_fixed(const void *ip, const void *ip_is_v6, const void *port, const void *flags, const void *asn, const void *country) {
+        db.ip = (const uint8_t *)ip;
+        db.ip_is_v6 = (const uint8_t *)ip_is_v6;
+        db.port = (const uint16_t *)port;
+        db.flags = (const uint8_t *)flags;
+        db.asn = (const uint32_t *)asn;
+        db.country = (const uint16_t *)country;
+    }
+};
 
 }  // namespace
 
@@ -2318,11 +2493,8 @@ int pwaf_evaluate_device(pwaf_engine *e, const pwaf_batch *in, pwaf_verdict *out
     if ((rc = S.ensure(false))) return rc;
     if (must_wait) HIP_TRY(hipStreamWaitEvent((hipStream_t)stream, S.done, 0));
     rc = run_pipeline(e, S, *in, out, counts, match_idx, n_matches, (hipStream_t)stream);
-    S.used = true;
-    S.last = (hipStream_t)stream;
-    S.last_own = false;
-    HIP_TRY(hipEventRecord(S.done, (hipStream_t)stream));
-    return rc;
+    const hipError_t he = mark_context_used(S, (hipStream_t)stream, false);
+    return he != hipSuccess ? device_error("hipEventRecord", he) : rc;
 }
 
 int pwaf_evaluate_batch(pwaf_engine *e, const pwaf_batch *in, pwaf_verdict *out, pwaf_counts *counts) {
@@ -2341,42 +2513,7 @@ int pwaf_evaluate_batch(pwaf_engine *e, const pwaf_batch *in, pwaf_verdict *out,
     if ((rc = S.ensure(true))) return rc;
     hipStream_t s = S.stream;
     if (must_wait) HIP_TRY(hipStreamWaitEvent(s, S.done, 0));
-    // Runs the pipeline and waits ONCE: the status words travel back (into page-locked memory) behind the batch, together with whatever
-    // `after` enqueues (the host batch's verdicts). A batch that exhausted the overflow pool is run again with a pool of the size it
-    // asked for. `counts_zero`: the first attempt's counters arrive zeroed (they are part of a staged block).
-    if ((rc = S.pin_status.reserve(16))) return rc;
-    volatile uint32_t *const st = (volatile uint32_t *)S.pin_status.p;
-    auto run_checked = [&](const pwaf_batch &db, pwaf_verdict *d_out, pwaf_counts *d_counts, bool known, const std::vector<uint32_t> *begins, const std::function<int()> &after,
-                           bool counts_zero) -> int {
-        for (int attempt = 0;; attempt++) {
-            if (d_counts && !(counts_zero && attempt == 0)) HIP_TRY(hipMemsetAsync(d_counts, 0, sizeof *d_counts, s));
-            S.retry = attempt > 0;
-            int r = run_pipeline(e, S, db, d_out, d_counts, nullptr, nullptr, s, known, begins, true);
-            S.retry = false;
-            S.used = true;
-            S.last = s;
-            S.last_own = true;
-            if (r) {
-                (void)hipEventRecord(S.done, s);
-                (void)hipStreamSynchronize(s);  // (whatever was enqueued may still read the caller's buffers)
-                return r;
-            }
-            HIP_TRY(hipMemcpyAsync((void *)&st[0], (uint32_t *)S.status.p + 1, 4, hipMemcpyDeviceToHost, s));
-            HIP_TRY(hipMemcpyAsync((void *)&st[1], S.ctrl.p, 4, hipMemcpyDeviceToHost, s));  // overflow entries the batch asked for
-            if (after && (r = after())) {
-                (void)hipEventRecord(S.done, s);
-                (void)hipStreamSynchronize(s);
-                return r;
-            }
-            HIP_TRY(hipEventRecord(S.done, s));
-            HIP_TRY(hipStreamSynchronize(s));
-            if (!st[0]) return PWAF_OK;
-            HIP_TRY(hipMemsetAsync((uint32_t *)S.status.p + 1, 0, 4, s));
-            if (attempt >= 2 || st[1] >= 0x7FFFFFF0u) return fail(PWAF_E_NOMEM, "scan overflow pool exhausted: verdicts of this batch are incomplete");
-            S.pool_entries = (uint64_t)st[1] + st[1] / 4 + 1024;
-        }
-    };
-    if (in->memory == PWAF_MEM_DEVICE) return run_checked(*in, out, counts, false, nullptr, nullptr, false);
+    if (in->memory == PWAF_MEM_DEVICE) return run_with_retry(e, S, *in, out, counts, false, nullptr, false, [] { return PWAF_OK; });
     // HOST batch: stage, validate what a device cannot report (while the copies are in flight, when the caller's memory is page-locked:
     // pwaf_host_alloc / pwaf_host_register), run, copy back
     const uint32_t n = in->n;
@@ -2411,51 +2548,32 @@ int pwaf_evaluate_batch(pwaf_engine *e, const pwaf_batch *in, pwaf_verdict *out,
         const pwaf_strcol *c = host_col(f);
         if (c && c->offsets[n] < c->offsets[0]) return fail(PWAF_E_BATCH, "field offsets are not monotone");
     }
-    pwaf_batch db = *in;
-    db.memory = PWAF_MEM_DEVICE;
-    std::vector<pwaf_strcol> hdr_cols(e->n_fields - PWAF_N_FIELDS, pwaf_strcol{nullptr, nullptr});
-    std::vector<uint32_t> hdr_bytes(e->n_fields - PWAF_N_FIELDS, 0);
+    DeviceBatch dv(n, e->n_fields);
     std::vector<uint32_t> col_begin(e->n_fields, 0);
-    auto set_col = [&](uint32_t f, const uint8_t *d_data, const uint32_t *d_off, uint32_t hi) {
-        const pwaf_strcol dc{d_data, d_off};
-        if (f < PWAF_N_FIELDS) {
-            db.field[f] = dc;
-            db.field_bytes[f] = hi;
-        } else {
-            hdr_cols[f - PWAF_N_FIELDS] = dc;
-            hdr_bytes[f - PWAF_N_FIELDS] = hi;
-        }
-    };
-    auto finish_headers = [&]() {
-        db.headers = hdr_cols.empty() ? nullptr : hdr_cols.data();
-        db.header_bytes = hdr_bytes.empty() ? nullptr : hdr_bytes.data();
-        db.n_headers = (uint32_t)hdr_cols.size();
-    };
 
     // ---- small batches: ONE packed block ----
     // [offsets + arena of every column] [ip] [v6] [port] [flags] [asn] [country] [counters] | [verdicts], each 256-byte aligned. The
     // micro-batcher's batches and pwaf_evaluate_one's single requests paid ~25 small copies from pageable memory (each a blocking staged
     // copy) and two waits per batch; now: memcpy into page-locked memory, one copy in, one out, one wait.
     static constexpr size_t kPackMax = 1u << 20;
-    size_t need = 0;
-    auto take = [&](size_t bytes) { const size_t at = need; need = (need + bytes + 255) & ~(size_t)255; return at; };
+    Layout pk;
     bool packable = true;
     std::vector<size_t> at_off(e->n_fields, 0), at_data(e->n_fields, 0);
     for (uint32_t f = 0; f < e->n_fields && packable; f++) {
         const pwaf_strcol *c = host_col(f);
         if (!c) continue;
         if (c->offsets[0] != 0) { packable = false; break; }  // (a slab view of a larger arena keeps its positions: the column-by-column path)
-        at_off[f] = take((size_t)(n + 1) * 4);
-        at_data[f] = take((size_t)c->offsets[n] + PWAF_ARENA_PAD);
-        if (need > kPackMax) packable = false;
+        at_off[f] = pk.take((size_t)(n + 1) * 4);
+        at_data[f] = pk.take((size_t)c->offsets[n] + PWAF_ARENA_PAD);
+        if (pk.size() > kPackMax) packable = false;
     }
-    const size_t at_ip = take((size_t)n * 16), at_v6 = take(n), at_port = take((size_t)n * 2), at_flags = take(n);
-    const size_t at_asn = in->asn ? take((size_t)n * 4) : 0, at_cc = in->asn ? take((size_t)n * 2) : 0;
-    const size_t at_counts = take(sizeof(pwaf_counts));  // (arrive zeroed with the inputs, return with the verdicts)
-    const size_t in_bytes = need;
-    const size_t at_out = take((size_t)n * sizeof(pwaf_verdict));
-    static const bool no_pack = getenv("PWAF_NO_PACKED_STAGING") != nullptr;  // A/B: the column-by-column path for every batch
-    if (packable && need <= kPackMax && !no_pack) {
+    const size_t at_ip = pk.take((size_t)n * 16), at_v6 = pk.take(n), at_port = pk.take((size_t)n * 2), at_flags = pk.take(n);
+    const size_t at_asn = in->asn ? pk.take((size_t)n * 4) : 0, at_cc = in->asn ? pk.take((size_t)n * 2) : 0;
+    const size_t at_counts = pk.take(sizeof(pwaf_counts));  // (arrive zeroed with the inputs, return with the verdicts)
+    const size_t in_bytes = pk.size();
+    const size_t at_out = pk.take((size_t)n * sizeof(pwaf_verdict));
+    const size_t need = pk.size();
+    if (packable && need <= kPackMax && !switches().no_packed_staging) {
         if ((rc = validate())) return rc;
         if ((rc = S.pin_in.reserve(in_bytes)) || (rc = S.pin_out.reserve(need - at_counts)) || (rc = S.packed.reserve(need))) return rc;
         uint8_t *const h = (uint8_t *)S.pin_in.p;
@@ -2467,32 +2585,26 @@ int pwaf_evaluate_batch(pwaf_engine *e, const pwaf_batch *in, pwaf_verdict *out,
             memcpy(h + at_off[f], c->offsets, (size_t)(n + 1) * 4);
             if (hi) memcpy(h + at_data[f], c->data, hi);
             memset(h + at_data[f] + hi, 0, PWAF_ARENA_PAD);
-            set_col(f, d + at_data[f], (const uint32_t *)(d + at_off[f]), hi);
+            dv.set_col(f, d + at_data[f], d + at_off[f], hi);
         }
-        finish_headers();
         memcpy(h + at_ip, in->ip, (size_t)n * 16);
         memcpy(h + at_v6, in->ip_is_v6, n);
         memcpy(h + at_port, in->port, (size_t)n * 2);
         memcpy(h + at_flags, in->flags, n);
-        db.ip = d + at_ip;
-        db.ip_is_v6 = d + at_v6;
-        db.port = (const uint16_t *)(d + at_port);
-        db.flags = d + at_flags;
         if (in->asn) {
             memcpy(h + at_asn, in->asn, (size_t)n * 4);
             memcpy(h + at_cc, in->country, (size_t)n * 2);
-            db.asn = (const uint32_t *)(d + at_asn);
-            db.country = (const uint16_t *)(d + at_cc);
         }
+        dv.set_fixed(d + at_ip, d + at_v6, d + at_port, d + at_flags, in->asn ? d + at_asn : nullptr, in->asn ? d + at_cc : nullptr);
         memset(h + at_counts, 0, sizeof(pwaf_counts));
         HIP_TRY(hipMemcpyAsync(S.packed.p, h, in_bytes, hipMemcpyHostToDevice, s));
         pwaf_verdict *const d_out = (pwaf_verdict *)((char *)S.packed.p + at_out);
         pwaf_counts *const d_counts = (pwaf_counts *)((char *)S.packed.p + at_counts);
         const size_t back = need - at_counts;
-        rc = run_checked(db, d_out, d_counts, true, &col_begin, [&]() -> int {
+        rc = run_with_retry(e, S, dv.db, d_out, d_counts, true, &col_begin, true, [&]() -> int {
             HIP_TRY(hipMemcpyAsync(S.pin_out.p, d_counts, back, hipMemcpyDeviceToHost, s));
             return PWAF_OK;
-        }, true);
+        });
         if (rc) return rc;
         memcpy(out, (const char *)S.pin_out.p + (at_out - at_counts), (size_t)n * sizeof(pwaf_verdict));
         if (counts) memcpy(counts, S.pin_out.p, sizeof(pwaf_counts));
@@ -2516,32 +2628,27 @@ int pwaf_evaluate_batch(pwaf_engine *e, const pwaf_batch *in, pwaf_verdict *out,
         if (hi > lo) HIP_TRY(hipMemcpyAsync((char *)S.stage_field_data[f].p + lo, c->data + lo, hi - lo, hipMemcpyHostToDevice, s));
         HIP_TRY(hipMemsetAsync((char *)S.stage_field_data[f].p + hi, 0, PWAF_ARENA_PAD, s));
         HIP_TRY(hipMemcpyAsync(S.stage_field_off[f].p, o, (size_t)(n + 1) * 4, hipMemcpyHostToDevice, s));
-        set_col(f, (const uint8_t *)S.stage_field_data[f].p, (const uint32_t *)S.stage_field_off[f].p, (uint32_t)hi);
+        dv.set_col(f, S.stage_field_data[f].p, S.stage_field_off[f].p, (uint32_t)hi);
     }
-    finish_headers();
-    auto stage = [&](DevBuf &b, const void *src, size_t bytes, const void **dst) -> int {
+    auto stage = [&](DevBuf &b, const void *src, size_t bytes) -> int {
         int r = b.reserve(bytes);
         if (r) return r;
         HIP_TRY(hipMemcpyAsync(b.p, src, bytes, hipMemcpyHostToDevice, s));
-        *dst = b.p;
         return PWAF_OK;
     };
-    if ((rc = stage(S.stage_ip, in->ip, (size_t)n * 16, (const void **)&db.ip))) return bail(rc);
-    if ((rc = stage(S.stage_v6, in->ip_is_v6, n, (const void **)&db.ip_is_v6))) return bail(rc);
-    if ((rc = stage(S.stage_port, in->port, (size_t)n * 2, (const void **)&db.port))) return bail(rc);
-    if ((rc = stage(S.stage_flags, in->flags, n, (const void **)&db.flags))) return bail(rc);
-    if (in->asn) {
-        if ((rc = stage(S.stage_asn, in->asn, (size_t)n * 4, (const void **)&db.asn))) return bail(rc);
-        if ((rc = stage(S.stage_country, in->country, (size_t)n * 2, (const void **)&db.country))) return bail(rc);
-    }
+    if ((rc = stage(S.stage_ip, in->ip, (size_t)n * 16)) || (rc = stage(S.stage_v6, in->ip_is_v6, n)) || (rc = stage(S.stage_port, in->port, (size_t)n * 2)) ||
+        (rc = stage(S.stage_flags, in->flags, n)))
+        return bail(rc);
+    if (in->asn && ((rc = stage(S.stage_asn, in->asn, (size_t)n * 4)) || (rc = stage(S.stage_country, in->country, (size_t)n * 2)))) return bail(rc);
+    dv.set_fixed(S.stage_ip.p, S.stage_v6.p, S.stage_port.p, S.stage_flags.p, in->asn ? S.stage_asn.p : nullptr, in->asn ? S.stage_country.p : nullptr);
     if ((rc = S.stage_out.reserve((size_t)n * sizeof(pwaf_verdict)))) return bail(rc);
     if ((rc = S.stage_counts.reserve(sizeof(pwaf_counts)))) return bail(rc);
     if ((rc = validate())) return bail(rc);
-    return run_checked(db, (pwaf_verdict *)S.stage_out.p, (pwaf_counts *)S.stage_counts.p, true, &col_begin, [&]() -> int {
+    return run_with_retry(e, S, dv.db, (pwaf_verdict *)S.stage_out.p, (pwaf_counts *)S.stage_counts.p, true, &col_begin, false, [&]() -> int {
         HIP_TRY(hipMemcpyAsync(out, S.stage_out.p, (size_t)n * sizeof(pwaf_verdict), hipMemcpyDeviceToHost, s));
         if (counts) HIP_TRY(hipMemcpyAsync(counts, S.stage_counts.p, sizeof(pwaf_counts), hipMemcpyDeviceToHost, s));
         return PWAF_OK;
-    }, false);
+    });
 }
 
 // Page-locked host memory for batch columns: the copy engine reads it directly (no staging copy inside the runtime, the calling thread
@@ -2609,12 +2716,11 @@ int pwaf_evaluate_records(pwaf_engine *e, const uint8_t *buf, size_t buf_bytes, 
     hipStream_t s = S.stream;
     if (must_wait) HIP_TRY(hipStreamWaitEvent(s, S.done, 0));
     // rec_meta: [record offsets (relative to lo)] [column offsets, n + 1 per column] [column places] [counters | verdicts] [records]
-    size_t need = 0;
-    auto take = [&](size_t bytes) { const size_t at = need; need = (need + bytes + 255) & ~(size_t)255; return at; };
+    Layout meta;
     const size_t off_stride = ((size_t)n + 1 + 63) & ~(size_t)63;
-    const size_t at_recoff = take((size_t)n * 4), at_off = take(off_stride * 4 * n_cols), at_colat = take((size_t)n_cols * 8);
-    const size_t at_counts = take(sizeof(pwaf_counts)), up_bytes = need, at_out = take((size_t)n * sizeof(pwaf_verdict));
-    const size_t span = (size_t)(hi - lo), at_rec = take(span);
+    const size_t at_recoff = meta.take((size_t)n * 4), at_off = meta.take(off_stride * 4 * n_cols), at_colat = meta.take((size_t)n_cols * 8);
+    const size_t at_counts = meta.take(sizeof(pwaf_counts)), up_bytes = meta.size(), at_out = meta.take((size_t)n * sizeof(pwaf_verdict));
+    const size_t span = (size_t)(hi - lo), at_rec = meta.take(span), need = meta.size();
     const bool direct = page_locked(buf + lo, span);
     if ((rc = S.rec_meta.reserve(need)) || (rc = S.rec_pin.reserve(direct ? up_bytes : need)) || (rc = S.rec_back.reserve(at_rec - at_counts))) return rc;
     uint8_t *const h = (uint8_t *)S.rec_pin.p;
@@ -2622,13 +2728,12 @@ int pwaf_evaluate_records(pwaf_engine *e, const uint8_t *buf, size_t buf_bytes, 
     for (uint32_t i = 0; i < n; i++) h_recoff[i] = (uint32_t)(rec_off[i] - lo);
     R::column_offsets(buf, rec_off, n, n_cols, (uint32_t *)(h + at_off), off_stride);
     // rec_cols: [column arenas, each with its PWAF_ARENA_PAD] [ip] [v6] [port] [flags] [asn] [country]
-    size_t cneed = 0;
-    auto ctake = [&](size_t bytes) { const size_t at = cneed; cneed = (cneed + bytes + 255) & ~(size_t)255; return at; };
+    Layout cl;
     uint64_t *const colat = (uint64_t *)(h + at_colat);
-    for (uint32_t f = 0; f < n_cols; f++) colat[f] = ctake(totals[f] + PWAF_ARENA_PAD);
-    const size_t c_ip = ctake((size_t)n * 16), c_v6 = ctake(n), c_port = ctake((size_t)n * 2), c_flags = ctake(n);
-    const size_t c_asn = geo ? ctake((size_t)n * 4) : 0, c_cc = geo ? ctake((size_t)n * 2) : 0;
-    if ((rc = S.rec_cols.reserve(cneed))) return rc;
+    for (uint32_t f = 0; f < n_cols; f++) colat[f] = cl.take(totals[f] + PWAF_ARENA_PAD);
+    const size_t c_ip = cl.take((size_t)n * 16), c_v6 = cl.take(n), c_port = cl.take((size_t)n * 2), c_flags = cl.take(n);
+    const size_t c_asn = geo ? cl.take((size_t)n * 4) : 0, c_cc = geo ? cl.take((size_t)n * 2) : 0;
+    if ((rc = S.rec_cols.reserve(cl.size()))) return rc;
     memset(h + at_counts, 0, sizeof(pwaf_counts));
     uint8_t *const d = (uint8_t *)S.rec_meta.p;
     uint8_t *const dc = (uint8_t *)S.rec_cols.p;
@@ -2659,61 +2764,17 @@ int pwaf_evaluate_records(pwaf_engine *e, const uint8_t *buf, size_t buf_bytes, 
         return fail(PWAF_E_DEVICE, "unpack_records_kernel launch failed");
     }
     // the device batch the kernel writes: an ordinary DEVICE batch with every column's size known on the host
-    pwaf_batch db{};
-    db.struct_size = sizeof db;
-    db.n = n;
-    db.memory = PWAF_MEM_DEVICE;
-    std::vector<pwaf_strcol> hdr_cols(n_cols - PWAF_N_FIELDS);
-    std::vector<uint32_t> hdr_bytes(n_cols - PWAF_N_FIELDS);
-    for (uint32_t f = 0; f < n_cols; f++) {
-        const pwaf_strcol c{dc + colat[f], (const uint32_t *)(d + at_off) + (size_t)f * off_stride};
-        if (f < PWAF_N_FIELDS) {
-            db.field[f] = c;
-            db.field_bytes[f] = (uint32_t)totals[f];
-        } else {
-            hdr_cols[f - PWAF_N_FIELDS] = c;
-            hdr_bytes[f - PWAF_N_FIELDS] = (uint32_t)totals[f];
-        }
-    }
-    db.n_headers = (uint32_t)hdr_cols.size();
-    db.headers = hdr_cols.empty() ? nullptr : hdr_cols.data();
-    db.header_bytes = hdr_bytes.empty() ? nullptr : hdr_bytes.data();
-    db.ip = ua.ip;
-    db.ip_is_v6 = ua.ip_is_v6;
-    db.port = ua.port;
-    db.flags = ua.flags;
-    db.asn = ua.asn;
-    db.country = ua.country;
+    DeviceBatch dv(n, n_cols);
+    for (uint32_t f = 0; f < n_cols; f++) dv.set_col(f, dc + colat[f], (const uint32_t *)(d + at_off) + (size_t)f * off_stride, (uint32_t)totals[f]);
+    dv.set_fixed(ua.ip, ua.ip_is_v6, ua.port, ua.flags, ua.asn, ua.country);
     const std::vector<uint32_t> col_begin(n_cols, 0);
     pwaf_counts *const d_counts = (pwaf_counts *)(d + at_counts);
-    pwaf_verdict *const d_out = (pwaf_verdict *)(d + at_out);
-    if ((rc = S.pin_status.reserve(16))) return rc;
-    volatile uint32_t *const st = (volatile uint32_t *)S.pin_status.p;
-    // run, bring counters + verdicts back, wait once; a batch that exhausted the scan overflow pool runs again with the pool it asked for
-    // (pwaf_evaluate_batch's retry: the unpacked columns stay where they are)
-    for (int attempt = 0;; attempt++) {
-        if (attempt) HIP_TRY(hipMemsetAsync(d_counts, 0, sizeof *d_counts, s));
-        S.retry = attempt > 0;
-        int r = run_pipeline(e, S, db, d_out, d_counts, nullptr, nullptr, s, true, &col_begin, true);
-        S.retry = false;
-        S.used = true;
-        S.last = s;
-        S.last_own = true;
-        if (!r) {
-            hipError_t he = hipMemcpyAsync((void *)&st[0], (uint32_t *)S.status.p + 1, 4, hipMemcpyDeviceToHost, s);
-            if (he == hipSuccess) he = hipMemcpyAsync((void *)&st[1], S.ctrl.p, 4, hipMemcpyDeviceToHost, s);
-            if (he == hipSuccess) he = hipMemcpyAsync(S.rec_back.p, d_counts, at_rec - at_counts, hipMemcpyDeviceToHost, s);
-            if (he != hipSuccess) r = fail(PWAF_E_DEVICE, std::string("hipMemcpyAsync: ") + hipGetErrorString(he));
-        }
-        (void)hipEventRecord(S.done, s);
-        const hipError_t se = hipStreamSynchronize(s);
-        if (r) return r;
-        if (se != hipSuccess) return fail(PWAF_E_DEVICE, std::string("hipStreamSynchronize: ") + hipGetErrorString(se));
-        if (!st[0]) break;
-        HIP_TRY(hipMemsetAsync((uint32_t *)S.status.p + 1, 0, 4, s));
-        if (attempt >= 2 || st[1] >= 0x7FFFFFF0u) return fail(PWAF_E_NOMEM, "scan overflow pool exhausted: verdicts of this batch are incomplete");
-        S.pool_entries = (uint64_t)st[1] + st[1] / 4 + 1024;
-    }
+    // (the counters arrive zeroed with the staged block; counters + verdicts come back in one copy)
+    rc = run_with_retry(e, S, dv.db, (pwaf_verdict *)(d + at_out), d_counts, true, &col_begin, true, [&]() -> int {
+        HIP_TRY(hipMemcpyAsync(S.rec_back.p, d_counts, at_rec - at_counts, hipMemcpyDeviceToHost, s));
+        return PWAF_OK;
+    });
+    if (rc) return rc;
     memcpy(out, (const char *)S.rec_back.p + (at_out - at_counts), (size_t)n * sizeof(pwaf_verdict));
     if (counts) memcpy(counts, S.rec_back.p, sizeof(pwaf_counts));
     return PWAF_OK;
