@@ -490,6 +490,13 @@ long pwaf_program_residual_compile(const pwaf_program *, const char *arch, char 
  * no prefilter. The reference has no counterpart: it evaluates every predicate on every request (pingoo/rules.rs:37-51). */
 int pwaf_program_confirm_field(const pwaf_program *, uint32_t group, const uint8_t *bytes, size_t len, uint32_t arena_offset,
                                uint16_t *atoms, size_t cap, size_t *n_atoms, int *flagged, int *walk);
+/* TEST HOOK (needs an engine, i.e. a device; reads host-side fields only): what the IPv4 lookup structures of this engine look like,
+ * so that a test can assert that the path it was written for exists. out[0] = escaped /24s of the DIR-24 table (a prefix longer
+ * than /24, or a class >= 65536 / membership set >= 32768), out[1] = entries of the run table behind the 16-byte records (0: the
+ * engine has no DIR-24 table), out[2] = 1 when a summary bitmap stands in front of the table, out[3] = its granularity (one bit per
+ * 2^out[3] /24s), out[4] = the table entry a clear summary bit stands for, out[5] = 1 when (class, set) travel packed in one word,
+ * out[6] = GeoIP classes, out[7] = membership sets. The reference has no counterpart (pingoo/geoip.rs, lists.rs scan per request). */
+int pwaf_engine_address_tables(const pwaf_engine *, uint32_t out[8]);
 int pwaf_program_stats(const pwaf_program *, pwaf_stats *out);
 
 /* ---- host-side field derivation (what the reference does before building RequestData) ------ */

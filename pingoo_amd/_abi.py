@@ -32,6 +32,8 @@ FLAG_CAPTCHA_VERIFIED = 1
 N_FIELDS = 5
 FIELD_NAMES = ("host", "url", "path", "method", "user_agent")
 ARENA_PAD = 16
+# pwaf_engine_address_tables (test hook): the meaning of out[0..7]
+ADDRESS_TABLE_FIELDS = ("escapes", "n_vals", "has_summary", "shift", "common", "packed", "classes", "sets")
 
 
 class RuleDesc(C.Structure):

@@ -19,6 +19,7 @@
 #include <unordered_map>
 #include <vector>
 
+#include "dirtable.h"
 #include "frontend.h"
 #include "kernels.h"
 #include "lscan_split.h"
@@ -312,6 +313,7 @@ struct pwaf_engine {
     DevBuf residual_blob, geo_rec_root4, geo_rec_root6, geo_rec_nodes;  // residual rules: the program image; the GeoIP trie with RECORD leaves (client.asn / country values)
     DevBuf pass_base, colmask, dir24 /* build-time only: released once compressed */, dir_chunks, dir_vals, dir_summary;
     uint32_t dir_sum_shift = 0, dir_common = 0;  // (VerdictArgs::dir_summary)
+    uint32_t dir_n_esc = 0, dir_n_vals = 0;      // (pwaf_engine_address_tables)
     uint32_t n_need = 0;   // sharing owners (need-mask arrays per batch)
     uint32_t n_visit = 0;  // gap passes (visited bitmaps per batch)
     std::vector<double> mean_len;  // per field, from the tuning sample (0 = unknown)
@@ -2291,76 +2293,22 @@ int pwaf_engine_create(const pwaf_rule_desc *rules, size_t n_rules, const pwaf_l
         if (ok) ok = hipMemset(cnt.p, 0, 4) == hipSuccess && launch_dir24(tv, e->dir24.p, e->dir_esc.p, cnt.p, nullptr) == 0 && hipDeviceSynchronize() == hipSuccess;
         cnt.release();
         if (!ok) { fail(PWAF_E_DEVICE, "DIR-24 table build failed"); return dev_fail(PWAF_E_DEVICE); }
-        // Compressed for the lookups (round 3): 10M uniformly random addresses against the flat 64 MiB table are 10M misses to HBM (the
-        // batch's own 3 GB of streaming flush every cache level in between). Consecutive /24s mostly share their entry (a /20 prefix
-        // covers 16 of them), so per /16 the 256 entries are stored as RUNS, 32 /24s per 16-byte record (8 records = one 128-byte line
-        // per /16): {bitmap of the /24s of this group where a run starts, the entry in force when the group begins, the entry of the
-        // first run that starts inside it, where the entries of further runs live in dir_vals}. One 16-byte gather answers every lookup
-        // whose /24 lies in the carried-in run or in the first run of its group (nearly all: ~12 runs per /16 over 8 groups); 8 MiB for
-        // any table: L2 / Infinity-Cache resident. (Measured: the lookup kernel is bound by the NUMBER of scattered load instructions —
-        // the texture addresser takes them one lane-address at a time — not by bytes or latency: four loads per lookup from one line
-        // took as long as four from different lines.)
+        // Compressed for the lookups: runs of equal entries, 32 /24s per 16-byte record, and a summary bitmap in front of them
+        // (csrc/dirtable.h: the layouts, the reasons and the code, shared with the CPU suite)
         {
             std::vector<uint32_t> d24((size_t)1 << 24);
             if (hipMemcpy(d24.data(), e->dir24.p, d24.size() * 4, hipMemcpyDeviceToHost) != hipSuccess) { fail(PWAF_E_DEVICE, "DIR-24 download failed"); return dev_fail(PWAF_E_DEVICE); }
-            std::vector<uint32_t> chunks((size_t)65536 * kDirChunkWords, 0), vals;
-            for (uint32_t x = 0; x < 65536; x++) {
-                const uint32_t *en = &d24[(size_t)x << 8];
-                for (uint32_t w = 0; w < 8; w++) {
-                    uint32_t *rec = &chunks[(size_t)x * kDirChunkWords + 4 * w];
-                    uint32_t bm = 0, n_starts = 0;
-                    for (uint32_t j = 32 * w; j < 32 * w + 32; j++)
-                        if (j == 0 || en[j] != en[j - 1]) {
-                            bm |= 1u << (j & 31);
-                            if (n_starts == 1) rec[3] = (uint32_t)vals.size();
-                            if (n_starts == 0) rec[2] = en[j];
-                            else vals.push_back(en[j]);
-                            n_starts++;
-                        }
-                    rec[0] = bm;
-                    rec[1] = w ? en[32 * w - 1] : 0u;  // (group 0 always starts a run at its first /24)
-                }
+            static_assert(dirtable::kChunkWords == kDirChunkWords, "dirtable.h and kernels.h disagree on the record layout");
+            dirtable::Compressed ct;
+            dirtable::compress(d24.data(), (P.flags & PWAF_OPT_NO_DIR_SUMMARY) != 0, ct);
+            if ((rc = upload(e->dir_chunks, ct.chunks)) || (rc = upload(e->dir_vals, ct.vals))) return dev_fail(rc);
+            if (!ct.summary.empty()) {
+                if ((rc = upload(e->dir_summary, ct.summary))) return dev_fail(rc);
+                e->dir_sum_shift = ct.shift;
+                e->dir_common = ct.common;
             }
-            if (vals.empty()) vals.push_back(0);
-            if ((rc = upload(e->dir_chunks, chunks)) || (rc = upload(e->dir_vals, vals))) return dev_fail(rc);
-            // The summary bitmap (round 6; kernels.h: VerdictArgs::dir_summary). Most of the address space holds ONE entry — for a WAF
-            // rule set the one that says "no list holds this address and no rule asks about its GeoIP record" — so one bit per block
-            // of /24s answers most lookups from a bitmap small enough to stay in every XCD's L2. Granularity: /20 ... /24 blocks,
-            // whichever minimises (fraction of the space that still needs the table) + (bitmap bytes / 8 MiB); no summary when more
-            // than half of the blocks need the table anyway. Skipped with PWAF_OPT_NO_DIR_SUMMARY (A/B runs and tests: same results).
-            if (!(P.flags & PWAF_OPT_NO_DIR_SUMMARY)) {
-                std::unordered_map<uint32_t, uint64_t> run_len;
-                for (size_t x = 0; x < d24.size();) {
-                    size_t y = x + 1;
-                    while (y < d24.size() && d24[y] == d24[x]) y++;
-                    run_len[d24[x]] += y - x;
-                    x = y;
-                }
-                uint32_t common = 0;
-                uint64_t best_len = 0;
-                for (const auto &kv : run_len)
-                    if (kv.second > best_len || (kv.second == best_len && kv.first < common)) { common = kv.first; best_len = kv.second; }
-                double best_cost = 1e9;
-                uint32_t best_shift = 0;
-                std::vector<uint32_t> best_bits;
-                for (uint32_t shift = 0; shift <= 4; shift++) {
-                    const size_t n_blk = d24.size() >> shift;
-                    std::vector<uint32_t> bits(n_blk / 32, 0);
-                    uint64_t set = 0;
-                    for (size_t b = 0; b < n_blk; b++) {
-                        bool other = false;
-                        for (size_t j = b << shift; j < ((b + 1) << shift) && !other; j++) other = d24[j] != common;
-                        if (other) { bits[b >> 5] |= 1u << (b & 31); set++; }
-                    }
-                    const double cost = (double)set / (double)n_blk + (double)(n_blk / 8) / (8.0 * 1024 * 1024);
-                    if (cost < best_cost && set * 2 <= n_blk) { best_cost = cost; best_shift = shift; best_bits.swap(bits); }
-                }
-                if (!best_bits.empty()) {
-                    if ((rc = upload(e->dir_summary, best_bits))) return dev_fail(rc);
-                    e->dir_sum_shift = best_shift;
-                    e->dir_common = common;
-                }
-            }
+            e->dir_n_esc = n_esc;
+            e->dir_n_vals = (uint32_t)ct.vals.size();
             e->dir24.release();
         }
     }
@@ -2393,6 +2341,21 @@ int pwaf_engine_residual_mode(const pwaf_engine *e) {
     return e->residual_jit.function ? 2 : 1;
 }
 const char *pwaf_engine_residual_fallback(const pwaf_engine *e) { return e ? e->residual_note.c_str() : ""; }
+int pwaf_engine_address_tables(const pwaf_engine *e, uint32_t out[8]) {
+    if (!e || !out) return fail(PWAF_E_INVALID_ARG, "pwaf_engine_address_tables: NULL argument");
+    const Program &P = *e->prog.p;
+    VerdictArgs v{};
+    set_trie_args(e, v);
+    out[0] = e->dir_n_esc;
+    out[1] = e->dir_chunks.p ? e->dir_n_vals : 0u;
+    out[2] = e->dir_summary.p ? 1u : 0u;
+    out[3] = e->dir_sum_shift;
+    out[4] = e->dir_common;
+    out[5] = v.ipres_packed;
+    out[6] = e->n_classes;
+    out[7] = P.set_words ? (uint32_t)(P.set_masks.size() / P.set_words) : 1u;
+    return PWAF_OK;
+}
 size_t pwaf_program_residual_source(const pwaf_program *p, int kind, char *buf, size_t cap) {
     if (!p || p->p->n_residual == 0) return 0;
     std::string text, why;

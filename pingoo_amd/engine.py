@@ -89,6 +89,7 @@ def lib():
     L.pwaf_program_confirm_field.argtypes = [vp, C.c_uint32, C.c_char_p, C.c_size_t, C.c_uint32, C.POINTER(C.c_uint16), C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_int), C.POINTER(C.c_int)]
     L.pwaf_engine_rule_errors.argtypes = [vp, C.POINTER(C.c_uint64), C.c_size_t]
     L.pwaf_engine_residual_mode.argtypes = [vp]
+    L.pwaf_engine_address_tables.argtypes = [vp, C.POINTER(C.c_uint32)]
     L.pwaf_engine_residual_fallback.argtypes = [vp]
     L.pwaf_engine_residual_fallback.restype = C.c_char_p
     L.pwaf_program_residual_source.argtypes = [vp, C.c_int, C.c_char_p, C.c_size_t]
@@ -407,6 +408,15 @@ class RuleEngine:
     @property
     def residual_fallback(self) -> str:
         return (lib().pwaf_engine_residual_fallback(self._h) or b"").decode(errors="replace")
+
+    def address_tables(self) -> dict:
+        """TEST HOOK (pwaf_engine_address_tables): the shape of this engine's IPv4 lookup structures, by the names of
+        _abi.ADDRESS_TABLE_FIELDS — escapes, run-table length, summary present / granularity / common entry, packed, classes, sets."""
+        out = (C.c_uint32 * len(_abi.ADDRESS_TABLE_FIELDS))()
+        rc = lib().pwaf_engine_address_tables(self._h, out)
+        if rc != 0:
+            _raise(rc, lib().pwaf_last_error().decode(errors="replace"))
+        return dict(zip(_abi.ADDRESS_TABLE_FIELDS, (int(x) for x in out)))
 
     def rule_errors(self, n_rules: int) -> List[int]:
         """Per caller rule: requests (over every batch so far) for which the rule's evaluation ended in an execution error — what the

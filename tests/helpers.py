@@ -168,7 +168,52 @@ def rexpr(rng: random.Random, lists, depth=0) -> str:
     return rpred(rng, lists)
 
 
-def fuzz_lists(rng: random.Random):
+def wide_v4(rng: random.Random) -> str:
+    """an IPv4 address from a space wide enough for every third octet (every 32-/24 group of a /16, every summary block) and small
+    enough in its first two octets that prefixes and clients still meet"""
+    return f"{rng.choice([0, 1, 2, 3, 3, 127, 200, 224, 255])}.{rng.choice([0, 1, 2, 3, 255])}.{rng.randint(0, 255)}.{rng.randint(0, 255)}"
+
+
+def wide_v6(rng: random.Random) -> str:
+    import ipaddress
+
+    if rng.random() < 0.2:
+        return rng.choice(["::", "::1", "ff02::1", "ffff:ffff:ffff:ffff:ffff:ffff:ffff:ffff", "2001:db8::"])
+    v = (0x20010DB8 << 96) | (rng.randint(0, 3) << 80)  # 2001:db8:0-3::/48, then a few bytes anywhere below
+    for _ in range(rng.randint(0, 3)):
+        v |= rng.randint(0, 255) << (8 * rng.randint(0, 9))
+    return str(ipaddress.IPv6Address(v))
+
+
+def wide_nets(rng: random.Random, n: int, v6_share: float = 0.25):
+    return [f"{wide_v6(rng)}/{rng.randint(0, 128)}" if rng.random() < v6_share else f"{wide_v4(rng)}/{rng.randint(0, 32)}" for _ in range(n)]
+
+
+def address_edges(lists, geo):
+    """first / last address of every prefix of the ip lists and the GeoIP entries, and the addresses just outside"""
+    import ipaddress
+
+    nets = [ipaddress.ip_network(s.strip(), strict=False) for t, items in (lists or {}).values() if t == _abi.LIST_IP for s in items]
+    for e in (geo if geo is not None else []):
+        raw = bytes(e["addr"])
+        nets.append(ipaddress.ip_network((raw if e["is_v6"] else raw[:4], int(e["prefix_len"])), strict=False))
+    out = []
+    for net in nets:
+        lo, hi, top = int(net.network_address), int(net.broadcast_address), (1 << net.max_prefixlen) - 1
+        cls = ipaddress.IPv6Address if net.version == 6 else ipaddress.IPv4Address
+        out += [str(cls(a)) for a in (lo, hi, max(lo - 1, 0), min(hi + 1, top))]
+    return out
+
+
+def fuzz_lists(rng: random.Random, wide: bool = False):
+    """wide: addresses with every third octet, prefix lengths 0...32 / 0...128 (the committed seeds keep the narrow draw)"""
+    if wide:
+        return {
+            "nets": (_abi.LIST_IP, wide_nets(rng, rng.randint(1, 12))),
+            "nets2": (_abi.LIST_IP, wide_nets(rng, rng.randint(0, 5), 0.1) + ["1.1.1.1", " 2.2.2.2 "]),
+            "words": (_abi.LIST_STRING, [rstr(rng, 0, 3) for _ in range(rng.randint(0, 6))]),
+            "asns": (_abi.LIST_INT, [str(rng.randint(0, 5)) for _ in range(rng.randint(0, 5))] + [" 64512 "]),
+        }
     nets = []
     for _ in range(rng.randint(1, 12)):
         if rng.random() < 0.75:
@@ -185,7 +230,8 @@ def fuzz_lists(rng: random.Random):
     }
 
 
-def fuzz_requests(rng: random.Random, n: int, with_geo: bool):
+def fuzz_requests(rng: random.Random, n: int, with_geo: bool, wide: bool = False, edges=()):
+    """wide: client addresses from the wide space, half of them from `edges` (address_edges of the lists and the GeoIP table)"""
     reqs = []
     for _ in range(n):
         alpha = UALPHA if rng.random() < 0.3 else ALPHA
@@ -193,7 +239,9 @@ def fuzz_requests(rng: random.Random, n: int, with_geo: bool):
         if rng.random() < 0.1:
             path = "/__pingoo/captcha" + path
         ua = rstr(rng, 0, 8, "abM/ ") if rng.random() < 0.9 else rng.choice(["", "x" * 255, "x" * 256, "x" * 290])
-        if rng.random() < 0.75:
+        if wide:
+            ip = rng.choice(edges) if edges and rng.random() < 0.5 else wide_v6(rng) if rng.random() < 0.25 else wide_v4(rng)
+        elif rng.random() < 0.75:
             ip = f"{rng.randint(1, 3)}.{rng.randint(0, 3)}.{rng.randint(0, 3)}.{rng.randint(0, 255)}"
         else:
             ip = rng.choice([f"2001:db8:{rng.randint(0, 3):x}::{rng.randint(0, 3):x}", "::1", "ff02::1", "127.0.0.1", "224.1.2.3", "1.1.1.1", "2.2.2.2"])
@@ -205,9 +253,12 @@ def fuzz_requests(rng: random.Random, n: int, with_geo: bool):
     return reqs
 
 
-def fuzz_geoip(rng: random.Random):
+def fuzz_geoip(rng: random.Random, wide: bool = False):
     from pingoo_amd import geoip_entries
 
+    if wide:
+        rows = [(net, rng.choice([0, 1, 2, 3, 64512]), rng.choice(COUNTRIES + ["xx", "F1"])) for net in wide_nets(rng, rng.randint(1, 14))]
+        return geoip_entries(rows + [("127.0.0.0/8", 3, "US")])
     rows = []
     for _ in range(rng.randint(1, 10)):
         if rng.random() < 0.7:

@@ -69,9 +69,19 @@ def test_syntax_accept_reject_parity_with_oracle():
 
 @pytest.mark.parametrize("seed", range(60))
 def test_fuzz_compiled_tables_match_oracle(seed):
-    rng = random.Random(1000 + seed)
-    lists = H.fuzz_lists(rng)
-    geo = H.fuzz_geoip(rng) if rng.random() < 0.7 else None
+    fuzz_compiled_tables_match_oracle(random.Random(1000 + seed), f"seed {seed}")
+
+
+@pytest.mark.parametrize("seed", range(40))
+def test_fuzz_compiled_tables_match_oracle_wide(seed):
+    """the same with addresses and prefixes from the wide space (helpers.fuzz_lists(wide=True)): every third octet, prefix lengths
+    0...32 / 0...128, half of the clients at prefix edges"""
+    fuzz_compiled_tables_match_oracle(random.Random(11000 + seed), f"wide seed {seed}", wide=True)
+
+
+def fuzz_compiled_tables_match_oracle(rng, label, wide=False):
+    lists = H.fuzz_lists(rng, wide)
+    geo = H.fuzz_geoip(rng, wide) if rng.random() < 0.7 else None
     with_geo = rng.random() < 0.3
     rules = []
     for k in range(rng.randint(1, 12)):
@@ -83,9 +93,9 @@ def test_fuzz_compiled_tables_match_oracle(seed):
     # (lenient only so that a rule NOBODY can take would show up as a count instead of an exception: the grammar produces none —
     # what the column compiler cannot take runs in the residual interpreter, evaluated here by its host build)
     seen, _ = H.as_the_engine_sees(rules, prog)
-    batch = RequestBatch.from_requests(H.fuzz_requests(rng, 48, with_geo))
+    batch = RequestBatch.from_requests(H.fuzz_requests(rng, 48, with_geo, wide, H.address_edges(lists, geo) if wide else ()))
     want = pyoracle.Oracle(seen, lists, geo, flags=flags).evaluate(batch)
-    H.assert_verdicts_equal(walk(prog, batch), want, batch, f"seed {seed}")
+    H.assert_verdicts_equal(walk(prog, batch), want, batch, label)
 
 
 def test_synthetic_workload_tables_match_oracle():

@@ -29,9 +29,19 @@ def test_golden_vectors_on_the_gpu(kat):
 
 @pytest.mark.parametrize("seed", range(40))
 def test_fuzz_gpu_matches_oracle(seed):
-    rng = random.Random(5000 + seed)
-    lists = H.fuzz_lists(rng)
-    geo = H.fuzz_geoip(rng) if rng.random() < 0.7 else None
+    fuzz_gpu_matches_oracle(random.Random(5000 + seed), f"seed {seed}")
+
+
+@pytest.mark.parametrize("seed", range(24))
+def test_fuzz_gpu_matches_oracle_wide(seed):
+    """the same with addresses and prefixes from the wide space (helpers.fuzz_lists(wide=True)): every third octet, prefix lengths
+    0...32 / 0...128, half of the clients at prefix edges"""
+    fuzz_gpu_matches_oracle(random.Random(15000 + seed), f"wide seed {seed}", wide=True)
+
+
+def fuzz_gpu_matches_oracle(rng, label, wide=False):
+    lists = H.fuzz_lists(rng, wide)
+    geo = H.fuzz_geoip(rng, wide) if rng.random() < 0.7 else None
     with_geo = rng.random() < 0.3
     rules = []
     for k in range(rng.randint(1, 14)):
@@ -41,13 +51,13 @@ def test_fuzz_gpu_matches_oracle(seed):
     flags = rng.choice([0, 0, _abi.OPT_NO_UA_GATE, _abi.OPT_NO_CAPTCHA_BYPASS])
     eng = RuleEngine(rules, lists, geo, flags=flags | _abi.OPT_LENIENT, lds_table_budget=rng.choice([0, 0, 1024, 2048]), max_table_bytes=rng.choice([0, 0, 4096]), max_dfa_states=rng.choice([0, 0, 60]))
     n = rng.choice([1, 63, 64, 65, 200, 777])
-    batch = RequestBatch.from_requests(H.fuzz_requests(rng, n, with_geo))
+    batch = RequestBatch.from_requests(H.fuzz_requests(rng, n, with_geo, wide, H.address_edges(lists, geo) if wide else ()))
     # nothing is dropped from the rule set: what the column compiler cannot take runs in the residual interpreter (residual_kernel); the
     # fuzz grammar produces no rule that neither takes (as_the_engine_sees asserts it: lenient only to count instead of raising)
     seen, _ = H.as_the_engine_sees(rules, eng.program)
     want = pyoracle.Oracle(seen, lists, geo, flags=flags).evaluate(batch)
     got, counts = eng.evaluate_batch(batch, with_counts=True)
-    H.assert_verdicts_equal(got, want, batch, f"seed {seed}")
+    H.assert_verdicts_equal(got, want, batch, label)
     assert counts.tolist() == np.bincount(want["action"], minlength=4).tolist()
     eng.close()
 
