@@ -15,6 +15,8 @@
  *   rule loop + gates                http_listener.rs:196-264  pwaf_evaluate_batch / _one
  *   Rule::match_request              pingoo/rules.rs:37-51     (inside the batch evaluation)
  *   GeoipDB::lookup                  pingoo/geoip.rs:73-91     (device trie, or caller-supplied asn/country)
+ *   geoip record -> RequestContext   http_listener.rs:143-157,183-191; upstream headers http_proxy_service.rs:174-189
+ *                                                              pwaf_geoip_lookup / pwaf_evaluate_*_geo (PWAF_OPT_GEO_ANSWERS)
  *   get_host / get_path / UA derive  http_listener.rs:140-165,284-296; http_utils.rs:114-116
  *                                                              pwaf_derive_host / _path / _user_agent
  *
@@ -34,7 +36,8 @@ extern "C" {
 #define PWAF_ABI_VERSION 4u /* 2: pwaf_batch carries header columns; strict rule compilation by default (PWAF_OPT_LENIENT, PWAF_W_PARTIAL);
                             * residual rules; pwaf_request carries header values; pwaf_node_evaluate_device; pwaf_program_tune
                             * 3: page-locked host memory for batch columns (pwaf_host_alloc / _register); no struct changed
-                            * 4: request records, non-blocking queue; no existing struct changed */
+                            * 4: request records, non-blocking queue; no existing struct changed
+                            *    + GeoIP answers: new symbols only */
 
 /* ---- status codes ------------------------------------------------------------------ */
 #define PWAF_OK 0
@@ -135,6 +138,9 @@ void pwaf_list_free(char **items, size_t n);
 #define PWAF_OPT_NO_DENSE_SWITCH 65536u /* A-B / testing: a pass whose prefilter flags most of the arena is still confirmed chunk by chunk (round 5), never walked whole (same verdicts) */
 #define PWAF_OPT_EAGER_CMP 32768u      /* A-B / testing: every length / port comparison is evaluated per group by the attribute kernel (round 5), none lazily by the verdict kernel (same verdicts) */
 #define PWAF_OPT_NO_DIR_SUMMARY 8192u  /* A-B / testing: IPv4 lookups always gather from the compressed DIR-24 table, without the summary bitmap in front of it (same verdicts) */
+#define PWAF_OPT_GEO_ANSWERS 256u     /* the engine also keeps RECORD tables and answers each request's GeoIP record: pwaf_geoip_lookup,
+                                       * pwaf_evaluate_*_geo, pwaf_async_create_geo (see "GeoIP answers" below). Without it those return
+                                       * PWAF_E_UNSUPPORTED and nothing about the engine differs: memory, creation time, launches, verdicts */
 #define PWAF_OPT_NO_RESIDUAL 64u      /* do not use the per-request residual interpreter (testing / benchmarking the column path alone) */
 #define PWAF_OPT_NO_RESIDUAL_JIT 1024u /* residual rules are INTERPRETED per request (residual_kernel) instead of running as the specialized
                                        * device program compiled by hiprtc when the engine is created (the default): same verdicts */
@@ -438,6 +444,46 @@ int pwaf_async_stats(pwaf_async *, uint64_t *n_batches, uint64_t *n_requests, ui
 /* Refuses new submits, evaluates every accepted request, waits for threads still inside submit / poll, frees the queue. Completions
  * nobody polled are dropped. */
 void pwaf_async_destroy(pwaf_async *);
+
+/* ---- GeoIP answers (ABI 4, additive; engines created with PWAF_OPT_GEO_ANSWERS) ----------------------
+ * The reference looks the client's record up once per request, before the gates (http_listener.rs:143-157), keeps asn / country in the
+ * RequestContext that travels with the request (:183-191), builds the rule and routing contexts from it (:207-219, :266-270) and sends
+ * it upstream as pingoo-client-country / pingoo-client-asn (services/http_proxy_service.rs:174-189). A host that lets the engine own the
+ * GeoIP table gets that record back here, next to the verdict: geo[i] is the record the rules of request i saw as client.asn /
+ * client.country. A batch, record or request that carries asn / country gets them echoed; otherwise it is the longest-prefix record
+ * of the engine's table (later duplicates win), and the default {0, "XX"} for a miss, a loopback or multicast address (geoip.rs:73-91;
+ * even below a covering prefix), a record whose country is not two letters A-Z, an engine without a table and an address family the
+ * table has no prefix of. ip_is_v6 alone decides the family. Gate verdicts (UA gate, captcha endpoint) get their record too.
+ * With `geo` == NULL the _geo functions are exactly the plain ones: no extra launch, no extra copy. `geo` lives where the verdicts
+ * live. Out of scope: the blocking pwaf_batcher_* and pwaf_node_* (a node's engines are reachable through pwaf_node_engine). */
+typedef struct pwaf_geo {
+    uint32_t asn;
+    uint8_t country[2];
+    uint16_t reserved; /* 0 */
+} pwaf_geo; /* 8 bytes == csrc/program.h: GeoRec */
+
+/* GeoipDB::lookup for n addresses and nothing else (georec_kernel alone). `memory` says where ip, ip_is_v6 and out live. HOST: staged,
+ * looked up, copied back, waited for (`stream` is ignored). DEVICE: enqueued on `stream` (hipStream_t; NULL = HIP's default); returns at once. */
+int pwaf_geoip_lookup(pwaf_engine *, const uint8_t *ip /* n x 16 */, const uint8_t *ip_is_v6 /* n */, uint32_t n, uint32_t memory,
+                      pwaf_geo *out /* n */, void *stream);
+/* The plain entry points with one more output: pwaf_evaluate_batch / _device / _records / _one. The record kernel runs on the context's
+ * side stream beside the address lookups; an overflow-pool retry runs it again. */
+int pwaf_evaluate_batch_geo(pwaf_engine *, const pwaf_batch *in, pwaf_verdict *out, pwaf_counts *counts, pwaf_geo *geo);
+int pwaf_evaluate_device_geo(pwaf_engine *, const pwaf_batch *in, pwaf_verdict *out, pwaf_counts *counts, uint32_t *match_idx,
+                             uint32_t *n_matches, pwaf_geo *geo, void *stream);
+int pwaf_evaluate_records_geo(pwaf_engine *, const uint8_t *buf, size_t buf_bytes, const uint32_t *rec_off, uint32_t n, pwaf_verdict *out,
+                              pwaf_counts *counts, pwaf_geo *geo);
+int pwaf_evaluate_one_geo(pwaf_engine *, const pwaf_request *req, pwaf_verdict *out, pwaf_geo *geo);
+/* A non-blocking queue whose completions carry the record: pwaf_async_poll_geo fills geo[k] beside out[k] (geo may be NULL). A failed
+ * batch completes with {0, "XX"}. pwaf_async_poll on such a queue hands out the completions and drops the records; pwaf_async_poll_geo
+ * on a queue made by pwaf_async_create returns 0, consumes nothing and sets pwaf_last_error. */
+int pwaf_async_create_geo(pwaf_engine *, uint32_t max_batch, uint32_t max_delay_us, uint32_t max_in_flight, pwaf_async **out);
+size_t pwaf_async_poll_geo(pwaf_async *, pwaf_completion *out, pwaf_geo *geo /* cap entries, parallel to out */, size_t cap);
+/* TEST HOOK (needs an engine; reads host-side fields only), like pwaf_engine_address_tables for the record tables: out[0] = 1 when an
+ * IPv4 record table exists, out[1] = /24s that escape to the trie (a prefix longer than /24), out[2] = entries of the run table,
+ * out[3] = 1 when a summary bitmap stands in front, out[4] = its granularity, out[5] = the table entry a clear summary bit stands for,
+ * out[6] = records, out[7] = 0. */
+int pwaf_engine_geo_answer_tables(const pwaf_engine *, uint32_t out[8]);
 
 /* ---- measurement ------------------------------------------------------------------------- */
 typedef struct pwaf_kernel_time {

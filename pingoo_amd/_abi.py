@@ -26,6 +26,7 @@ RULE_ACTION_BLOCK, RULE_ACTION_CAPTCHA = 1, 2
 LIST_STRING, LIST_INT, LIST_IP = 0, 1, 2
 OPT_NO_UA_GATE, OPT_NO_CAPTCHA_BYPASS, OPT_NO_PREFILTER, OPT_STRICT, OPT_FILTER_STRIDE2, OPT_LENIENT, OPT_NO_RESIDUAL, OPT_GLOBAL_VERDICT_TABLES, OPT_NO_CONFIRM, OPT_NO_RESIDUAL_JIT = 1, 2, 4, 8, 16, 32, 64, 128, 512, 1024
 OPT_DENSE_VERDICT, OPT_TINY_VERDICT_SLOTS, OPT_NO_DIR_SUMMARY, OPT_SPARSE_VERDICT, OPT_EAGER_CMP, OPT_NO_DENSE_SWITCH = 2048, 4096, 8192, 16384, 32768, 65536
+OPT_GEO_ANSWERS = 256  # the engine also answers each request's GeoIP record (pwaf_geoip_lookup, pwaf_evaluate_*_geo)
 W_PARTIAL = 1
 MEM_HOST, MEM_DEVICE = 0, 1
 FLAG_CAPTCHA_VERIFIED = 1
@@ -34,6 +35,8 @@ FIELD_NAMES = ("host", "url", "path", "method", "user_agent")
 ARENA_PAD = 16
 # pwaf_engine_address_tables (test hook): the meaning of out[0..7]
 ADDRESS_TABLE_FIELDS = ("escapes", "n_vals", "has_summary", "shift", "common", "packed", "classes", "sets")
+# pwaf_engine_geo_answer_tables (test hook): the meaning of out[0..7]
+GEO_ANSWER_TABLE_FIELDS = ("has_table", "escapes", "n_vals", "has_summary", "shift", "common", "records", "zero")
 
 
 class RuleDesc(C.Structure):
@@ -149,6 +152,12 @@ class RecordHead(C.Structure):
         ("has_geoip", C.c_uint8),
         ("reserved", C.c_uint8 * 3),
     ]
+
+
+class Geo(C.Structure):
+    """pwaf_geo: one GeoIP answer (PWAF_OPT_GEO_ANSWERS) — the record the rules saw as client.asn / client.country."""
+
+    _fields_ = [("asn", C.c_uint32), ("country", C.c_uint8 * 2), ("reserved", C.c_uint16)]
 
 
 class Completion(C.Structure):

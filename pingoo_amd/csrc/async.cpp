@@ -19,6 +19,11 @@
 // has waited max_delay_us — unless a batch of the same class is still waiting in the queue, in which case it keeps filling until that one
 // is taken — so a class that keeps the dispatchers busy cannot hold back the other class's deadline. A segment returns to its class's
 // free list only after pwaf_evaluate_records on it has returned.
+//
+// GeoIP answers. A queue made by pwaf_async_create_geo keeps a pwaf_geo per slot and per completion. The evaluator that fills them
+// (pwaf_evaluate_records_geo) reaches the queue as a function pointer (pwaf::async_create_with, called from engine.cpp): this file refers
+// to no engine symbol beyond pwaf_engine_header_count, pwaf_host_alloc / _free and pwaf_evaluate_records, so the CPU suite links it
+// against a stub engine.
 #include <sys/eventfd.h>
 #include <unistd.h>
 
@@ -40,6 +45,8 @@
 
 namespace pwaf {
 int fail(int code, const std::string &msg);
+using RecordsGeoFn = int (*)(pwaf_engine *, const uint8_t *, size_t, const uint32_t *, uint32_t, pwaf_verdict *, pwaf_counts *, pwaf_geo *);
+int async_create_with(pwaf_engine *engine, uint32_t max_batch, uint32_t max_delay_us, uint32_t max_in_flight, RecordsGeoFn eval_geo, pwaf_async **out);
 }
 using pwaf::fail;
 
@@ -60,11 +67,12 @@ inline uint32_t word_bytes(uint64_t w) { return (uint32_t)w; }
 
 struct Segment {
     int geo = 0;
-    uint8_t *mem = nullptr;  // page-locked: [records: cap_bytes] [rec_off: cap_n] [tags: cap_n] [verdicts: cap_n]
+    uint8_t *mem = nullptr;  // page-locked: [records: cap_bytes] [tags: cap_n] [verdicts: cap_n] [rec_off: cap_n] [GeoIP answers: cap_n, a geo queue's only]
     uint32_t cap_bytes = 0, cap_n = 0;
     uint32_t *rec_off = nullptr;
     uint64_t *tags = nullptr;
     pwaf_verdict *verdicts = nullptr;
+    pwaf_geo *geos = nullptr;  // a geo queue's segments: the record of every slot
     std::atomic<uint64_t> word{kClosed};
     std::atomic<uint32_t> written{0};
     std::atomic<int64_t> first_ns{0};  // when the batch's first request reserved its slot (Clock, since epoch)
@@ -77,6 +85,7 @@ int64_t now_ns() { return std::chrono::duration_cast<std::chrono::nanoseconds>(C
 
 struct pwaf_async {
     pwaf_engine *engine = nullptr;
+    pwaf::RecordsGeoFn eval_geo = nullptr;  // a geo queue (pwaf_async_create_geo): the evaluator that also answers the records
     uint32_t n_cols = PWAF_N_FIELDS;
     uint32_t max_batch = 0, max_in_flight = 0;
     int64_t max_delay_ns = 0;
@@ -96,6 +105,7 @@ struct pwaf_async {
     // completions
     std::mutex cmu;
     std::deque<pwaf_completion> done;
+    std::deque<pwaf_geo> done_geo;  // a geo queue's: parallel to `done`
     std::atomic<uint64_t> in_flight{0};  // submitted, not yet handed out by poll
     std::atomic<uint64_t> n_batches{0}, n_requests{0};
     std::atomic<bool> stopping{false};
@@ -155,6 +165,7 @@ struct pwaf_async {
                     c.verdict.rule_idx = PWAF_RULE_NONE;
                 }
                 done.push_back(c);
+                if (eval_geo) done_geo.push_back(rc == PWAF_OK ? s->geos[i] : pwaf_geo{0u, {'X', 'X'}, 0u});
             }
         }
         n_batches.fetch_add(1, std::memory_order_relaxed);
@@ -198,7 +209,8 @@ struct pwaf_async {
                 // the submitters that reserved before the close finish copying their records (a few hundred nanoseconds)
                 while (s->written.load(std::memory_order_acquire) < s->n) std::this_thread::yield();
                 try {
-                    publish(s, pwaf_evaluate_records(engine, s->mem, s->bytes, s->rec_off, s->n, s->verdicts, nullptr));
+                    publish(s, eval_geo ? eval_geo(engine, s->mem, s->bytes, s->rec_off, s->n, s->verdicts, nullptr, s->geos)
+                                        : pwaf_evaluate_records(engine, s->mem, s->bytes, s->rec_off, s->n, s->verdicts, nullptr));
                 } catch (const std::exception &) {  // (std::bad_alloc of the completion queue: nothing may escape a worker thread)
                 }
                 release(s);
@@ -213,15 +225,14 @@ struct pwaf_async {
     }
 };
 
-extern "C" {
-
-int pwaf_async_create(pwaf_engine *engine, uint32_t max_batch, uint32_t max_delay_us, uint32_t max_in_flight, pwaf_async **out) {
+int pwaf::async_create_with(pwaf_engine *engine, uint32_t max_batch, uint32_t max_delay_us, uint32_t max_in_flight, pwaf::RecordsGeoFn eval_geo, pwaf_async **out) {
     if (!engine || !out) return fail(PWAF_E_INVALID_ARG, "NULL argument");
     *out = nullptr;
     if (max_batch == 0 || max_in_flight == 0) return fail(PWAF_E_INVALID_ARG, "max_batch and max_in_flight must be at least 1");
     auto *q = new (std::nothrow) pwaf_async();
     if (!q) return fail(PWAF_E_NOMEM, "pwaf_async_create: out of memory");
     q->engine = engine;
+    q->eval_geo = eval_geo;
     q->n_cols = PWAF_N_FIELDS + pwaf_engine_header_count(engine);
     if (q->n_cols > pwaf::records::kMaxValues) {  // (submit's per-request arrays hold kMaxValues values)
         delete q;
@@ -243,7 +254,7 @@ int pwaf_async_create(pwaf_engine *engine, uint32_t max_batch, uint32_t max_dela
             s->geo = g;
             s->cap_bytes = (uint32_t)cap_bytes;
             s->cap_n = q->max_batch;
-            const size_t total = cap_bytes + (size_t)s->cap_n * (4 + 8 + sizeof(pwaf_verdict));
+            const size_t total = cap_bytes + (size_t)s->cap_n * (4 + 8 + sizeof(pwaf_verdict) + (eval_geo ? sizeof(pwaf_geo) : 0));
             void *p = nullptr;
             const int rc = pwaf_host_alloc(total, &p);
             if (rc != PWAF_OK) {
@@ -255,6 +266,7 @@ int pwaf_async_create(pwaf_engine *engine, uint32_t max_batch, uint32_t max_dela
             s->tags = (uint64_t *)(s->mem + cap_bytes);
             s->verdicts = (pwaf_verdict *)(s->tags + s->cap_n);
             s->rec_off = (uint32_t *)(s->verdicts + s->cap_n);
+            if (eval_geo) s->geos = (pwaf_geo *)(s->mem + cap_bytes + (size_t)s->cap_n * (4 + 8 + sizeof(pwaf_verdict)));
             q->all.push_back(s);
             q->free_list[g].push_back(s);
         }
@@ -265,6 +277,12 @@ int pwaf_async_create(pwaf_engine *engine, uint32_t max_batch, uint32_t max_dela
     for (auto &w : q->worker) w = std::thread([q] { q->run(); });
     *out = q;
     return PWAF_OK;
+}
+
+extern "C" {
+
+int pwaf_async_create(pwaf_engine *engine, uint32_t max_batch, uint32_t max_delay_us, uint32_t max_in_flight, pwaf_async **out) {
+    return pwaf::async_create_with(engine, max_batch, max_delay_us, max_in_flight, nullptr, out);
 }
 
 namespace {
@@ -365,8 +383,8 @@ int pwaf_async_submit(pwaf_async *q, const pwaf_request *r, uint64_t tag) {
     }
 }
 
-size_t pwaf_async_poll(pwaf_async *q, pwaf_completion *out, size_t cap) {
-    if (!q || !out || !cap) return 0;
+namespace {
+size_t poll_into(pwaf_async *q, pwaf_completion *out, pwaf_geo *geo, size_t cap) {
     Inside guard(q->inside);
     size_t k = 0;
     {
@@ -374,9 +392,28 @@ size_t pwaf_async_poll(pwaf_async *q, pwaf_completion *out, size_t cap) {
         k = std::min(cap, q->done.size());
         std::copy(q->done.begin(), q->done.begin() + (ptrdiff_t)k, out);
         q->done.erase(q->done.begin(), q->done.begin() + (ptrdiff_t)k);
+        if (q->eval_geo) {  // (a plain poll of a geo queue drops the records)
+            if (geo) std::copy(q->done_geo.begin(), q->done_geo.begin() + (ptrdiff_t)k, geo);
+            q->done_geo.erase(q->done_geo.begin(), q->done_geo.begin() + (ptrdiff_t)k);
+        }
     }
     q->in_flight.fetch_sub(k, std::memory_order_acq_rel);
     return k;
+}
+}  // namespace
+
+size_t pwaf_async_poll(pwaf_async *q, pwaf_completion *out, size_t cap) {
+    if (!q || !out || !cap) return 0;
+    return poll_into(q, out, nullptr, cap);
+}
+
+size_t pwaf_async_poll_geo(pwaf_async *q, pwaf_completion *out, pwaf_geo *geo, size_t cap) {
+    if (!q || !out || !cap) return 0;
+    if (!q->eval_geo) {
+        (void)fail(PWAF_E_UNSUPPORTED, "pwaf_async_poll_geo: the queue was not made by pwaf_async_create_geo (PWAF_OPT_GEO_ANSWERS)");
+        return 0;
+    }
+    return poll_into(q, out, geo, cap);
 }
 
 int pwaf_async_fd(pwaf_async *q) {

@@ -20,6 +20,7 @@
 #include <vector>
 
 #include "dirtable.h"
+#include "georec.h"
 #include "frontend.h"
 #include "kernels.h"
 #include "lscan_split.h"
@@ -230,6 +231,7 @@ struct Scratch {
     uint32_t arg_next = 0;
     std::vector<DevBuf> stage_field_data, stage_field_off;  // n_fields each
     DevBuf stage_ip, stage_v6, stage_port, stage_flags, stage_asn, stage_country, stage_out, stage_counts;
+    DevBuf stage_geo;  // the GeoIP answers of a large host batch / a host pwaf_geoip_lookup on their way back (PWAF_OPT_GEO_ANSWERS)
     // A SMALL host batch (the micro-batcher's, pwaf_evaluate_one's) travels as ONE block: every column packed into page-locked memory,
     // one asynchronous copy in, one out (pwaf_evaluate_batch). pin_status: the status words on their way back (never a pageable target:
     // a device-to-host copy into pageable memory is a blocking staged copy).
@@ -262,7 +264,7 @@ struct Scratch {
     }
     void release() {
         for (DevBuf *b : {&status, &ipres, &rec, &res_words, &err_sink, &pool, &verdict_spill, &zero_block, &gate_lists, &attr, &chunk_bits, &cand_cnt, &need, &pairs, &zero_off, &args, &stage_ip, &stage_v6, &stage_port, &stage_flags,
-                          &stage_asn, &stage_country, &stage_out, &stage_counts})
+                          &stage_asn, &stage_country, &stage_out, &stage_counts, &stage_geo})
             b->release();
         for (PinBuf &b : arg_slot) b.release();
         for (hipEvent_t ev : arg_ev)
@@ -314,6 +316,11 @@ struct pwaf_engine {
     DevBuf pass_base, colmask, dir24 /* build-time only: released once compressed */, dir_chunks, dir_vals, dir_summary;
     uint32_t dir_sum_shift = 0, dir_common = 0;  // (VerdictArgs::dir_summary)
     uint32_t dir_n_esc = 0, dir_n_vals = 0;      // (pwaf_engine_address_tables)
+    // PWAF_OPT_GEO_ANSWERS: the RECORD of every request (georec_kernel). The record-leaf trie and the records are geo_rec_* / geo_recs
+    // above (shared with the residual rules); the IPv4 table of record ids is the engine's own (csrc/georec.h)
+    bool geo_answers = false;
+    DevBuf georec_chunks, georec_vals, georec_summary;
+    uint32_t georec_shift = 0, georec_common = 0, georec_n_esc = 0, georec_n_vals = 0;
     uint32_t n_need = 0;   // sharing owners (need-mask arrays per batch)
     uint32_t n_visit = 0;  // gap passes (visited bitmaps per batch)
     std::vector<double> mean_len;  // per field, from the tuning sample (0 = unknown)
@@ -652,6 +659,25 @@ void set_trie_args(const pwaf_engine *e, VerdictArgs &v) {
     v.ipres_packed = (e->n_classes <= 65536u && n_sets <= 65536u) ? 1u : 0u;
 }
 
+// the table part of georec_kernel's arguments (PWAF_OPT_GEO_ANSWERS engines)
+void set_georec_args(const pwaf_engine *e, GeoRecArgs &g) {
+    g.has_geo = e->prog.p->has_geo ? 1u : 0u;
+    g.root4 = (const uint32_t *)e->geo_rec_root4.p;
+    g.root6 = (const uint32_t *)e->geo_rec_root6.p;
+    g.nodes = (const uint32_t *)e->geo_rec_nodes.p;
+    g.recs = (const GeoRec *)e->geo_recs.p;
+    g.chunks = (const uint32_t *)e->georec_chunks.p;
+    g.vals = (const uint32_t *)e->georec_vals.p;
+    g.summary = (const uint32_t *)e->georec_summary.p;
+    g.sum_shift = e->georec_shift;
+    g.common = e->georec_common;
+    g.n_cus = e->n_cus;
+}
+int need_geo_answers(const pwaf_engine *e, const char *fn) {
+    if (e->geo_answers) return PWAF_OK;
+    return fail(PWAF_E_UNSUPPORTED, std::string(fn) + ": the engine was not created with PWAF_OPT_GEO_ANSWERS");
+}
+
 // Decides which passes are list-driven and uploads what that needs: a pass behind a bigram prefilter walks the filter's candidate
 // list, a gated gap pass the list fed by its prefilter factors (owned by earlier passes). Called at creation and again when
 // pwaf_engine_tune has rebuilt the filters from a traffic sample.
@@ -933,6 +959,7 @@ struct BatchRun {
     std::vector<uint8_t> col_known;
     VerdictArgs v{};
     bool ipres_launched = false, attr_launched = false;
+    pwaf_geo *d_geo = nullptr;  // PWAF_OPT_GEO_ANSWERS: where the batch's GeoIP records go (null: none asked for, nothing launched)
     ListShape lshapes[2];  // (the shape is per PHASE: the filtered passes' candidate lists are long, the gap passes' short)
     // the descriptors of every launch of the batch (prefilter, resolve, confirm tier, list scans, residual kernel): built on the host,
     // uploaded ONCE
@@ -1202,7 +1229,18 @@ struct BatchRun {
             HIP_TRY(hipStreamWaitEvent(q, S.ev_fork, 0));
         }
         // (PWAF_SKIP_IPRES, timing experiments only: every address resolves to class 0 / set 0)
-        return side_stage(q, "ipres", 0xFAu, "ipres kernel", [&] { return sw.skip_ipres ? (int)hipMemsetAsync(v.ipres, 0, (size_t)n * (v.ipres_packed ? 4 : 8), q) : launch_ipres(v, q); });
+        const int rc = side_stage(q, "ipres", 0xFAu, "ipres kernel", [&] { return sw.skip_ipres ? (int)hipMemsetAsync(v.ipres, 0, (size_t)n * (v.ipres_packed ? 4 : 8), q) : launch_ipres(v, q); });
+        if (rc || !d_geo) return rc;
+        // the GeoIP answers: beside the address lookups, on the same stream (the side stream's join covers both)
+        GeoRecArgs ga{};
+        set_georec_args(e, ga);
+        ga.ip = db.ip;
+        ga.ip_is_v6 = db.ip_is_v6;
+        ga.asn = db.asn;
+        ga.country = db.country;
+        ga.n = n;
+        ga.out = (uint2 *)d_geo;
+        return side_stage(q, "georec", 25ull * n, "georec kernel", [&] { return launch_georec(ga, q); });
     }
     int attr_stage(hipStream_t q) {
         if (attr_launched) return PWAF_OK;
@@ -1722,9 +1760,11 @@ struct BatchRun {
 // One batch of device columns through every launch. Nothing between upload_descriptors and the end returns past
 // BatchRun's destructor: the descriptor slot's event is recorded whichever way the batch leaves (ArgSlotMark).
 int run_pipeline(pwaf_engine *e, Scratch &S, const pwaf_batch &db /* device pointers */, pwaf_verdict *d_out, pwaf_counts *d_counts, uint32_t *d_match_idx,
-                 uint32_t *d_n_matches, hipStream_t stream, bool totals_known = false, const std::vector<uint32_t> *col_begin = nullptr, bool sync_status = false) {
+                 uint32_t *d_n_matches, hipStream_t stream, bool totals_known = false, const std::vector<uint32_t> *col_begin = nullptr, bool sync_status = false,
+                 pwaf_geo *d_geo = nullptr) {
     if (db.n == 0) return PWAF_OK;
     BatchRun b(e, S, db, stream, col_begin);
+    b.d_geo = d_geo;
     int rc;
     if ((rc = b.reserve_scratch(sync_status)) || (rc = b.resolve_columns(totals_known))) return rc;
     if ((rc = b.fill_verdict_args(d_out, d_counts, d_match_idx, d_n_matches)) || (rc = b.zero_head_records())) return rc;
@@ -1767,7 +1807,7 @@ int device_error(const char *call, hipError_t he) { return fail(PWAF_E_DEVICE, s
 // drained before the call returns: what was enqueued may still read the caller's buffers.
 template <class After>
 int run_with_retry(pwaf_engine *e, Scratch &S, const pwaf_batch &db, pwaf_verdict *d_out, pwaf_counts *d_counts, bool known, const std::vector<uint32_t> *begins, bool counts_zero,
-                   After &&after) {
+                   After &&after, pwaf_geo *d_geo = nullptr) {
     const hipStream_t s = S.stream;
     int r = S.pin_status.reserve(16);
     volatile uint32_t *const st = (volatile uint32_t *)S.pin_status.p;
@@ -1776,7 +1816,7 @@ int run_with_retry(pwaf_engine *e, Scratch &S, const pwaf_batch &db, pwaf_verdic
         if (!r && d_counts && !(counts_zero && attempt == 0) && (he = hipMemsetAsync(d_counts, 0, sizeof *d_counts, s)) != hipSuccess) r = device_error("hipMemsetAsync", he);
         if (!r) {
             S.retry = attempt > 0;
-            r = run_pipeline(e, S, db, d_out, d_counts, nullptr, nullptr, s, known, begins, true);
+            r = run_pipeline(e, S, db, d_out, d_counts, nullptr, nullptr, s, known, begins, true, d_geo);
             S.retry = false;
         }
         if (!r) {
@@ -2279,6 +2319,32 @@ int pwaf_engine_create(const pwaf_rule_desc *rules, size_t n_rules, const pwaf_l
         }
     }
 #undef UP
+    if (P.flags & PWAF_OPT_GEO_ANSWERS) {
+        // GeoIP answers: the trie with RECORD leaves and the records (shared with the residual rules: uploaded once), and for IPv4 a table
+        // of record ids over the trie's first 24 bits, compressed like the class table (csrc/georec.h, csrc/dirtable.h)
+        e->geo_answers = true;
+        const std::vector<uint32_t> leaf0(65536, TRIE_LEAF);  // record 0 = the default {0, "XX"}
+        if (!e->geo_rec_root4.p) {
+            if ((rc = upload(e->geo_rec_root4, P.geo_trie.root4.empty() ? leaf0 : P.geo_trie.root4)) || (rc = upload(e->geo_rec_root6, P.geo_trie.root6.empty() ? leaf0 : P.geo_trie.root6)) ||
+                (rc = upload(e->geo_rec_nodes, P.geo_trie.nodes)))
+                return dev_fail(rc);
+            const std::vector<GeoRec> def{GeoRec{0u, (uint16_t)('X' | ('X' << 8)), 0u}};
+            if ((rc = upload(e->geo_recs, P.geo_recs.empty() ? def : P.geo_recs))) return dev_fail(rc);
+        }
+        if (P.has_geo && !P.geo_trie.root4.empty()) {
+            std::vector<uint32_t> d24;
+            e->georec_n_esc = georec::flatten(P.geo_trie.root4.data(), P.geo_trie.nodes.data(), d24);
+            dirtable::Compressed ct;
+            dirtable::compress(d24.data(), (P.flags & PWAF_OPT_NO_DIR_SUMMARY) != 0, ct);
+            if ((rc = upload(e->georec_chunks, ct.chunks)) || (rc = upload(e->georec_vals, ct.vals))) return dev_fail(rc);
+            if (!ct.summary.empty()) {
+                if ((rc = upload(e->georec_summary, ct.summary))) return dev_fail(rc);
+                e->georec_shift = ct.shift;
+                e->georec_common = ct.common;
+            }
+            e->georec_n_vals = (uint32_t)ct.vals.size();
+        }
+    }
     if ((P.has_geo && !P.geo_trie.root4.empty()) || (P.n_ip_lists && !P.ipset_trie.root4.empty())) {
         // DIR-24-8: one 64 MiB table (2^24 x 4 B) so that an IPv4 address resolves its GeoIP class AND its ip-list membership set with
         // a single gather; built on the device from the two tries that were just uploaded (first launch counts the escapes)
@@ -2322,7 +2388,7 @@ void pwaf_engine_destroy(pwaf_engine *e) {
     for (auto &g : e->groups) { for (DevBuf *b : {&g.tab, &g.classmap, &g.special, &g.list_off, &g.list, &g.ftable, &g.c_head, &g.c_entries, &g.c_bytes, &g.c_classes}) b->release(); g.fl.release(); g.rt.release(); }
     for (DevBuf *b : {&e->num_atoms, &e->lazy_atoms, &e->bit_atoms, &e->trig_off, &e->trig_rules, &e->always_rules, &e->iu_vals[0], &e->iu_vals[1], &e->iu_masks[0], &e->iu_masks[1], &e->country_luts, &e->rules, &e->lits,
                       &e->set_masks, &e->ip_root4, &e->ip_root6, &e->ip_nodes, &e->geo_root4, &e->geo_root6, &e->geo_nodes, &e->geo_recs, &e->residual_blob, &e->residual_errors, &e->geo_rec_root4, &e->geo_rec_root6, &e->geo_rec_nodes, &e->pass_base, &e->colmask, &e->dir24, &e->dir_chunks, &e->dir_vals, &e->dir_summary, &e->class_rows,
-                      &e->dir_esc, &e->leaf_root, &e->geo_leaf_root, &e->pass_table})
+                      &e->dir_esc, &e->leaf_root, &e->geo_leaf_root, &e->pass_table, &e->georec_chunks, &e->georec_vals, &e->georec_summary})
         b->release();
     if (e->residual_jit.module) {  // (a module belongs to the device it was loaded on)
         int cur = -1;
@@ -2354,6 +2420,19 @@ int pwaf_engine_address_tables(const pwaf_engine *e, uint32_t out[8]) {
     out[5] = v.ipres_packed;
     out[6] = e->n_classes;
     out[7] = P.set_words ? (uint32_t)(P.set_masks.size() / P.set_words) : 1u;
+    return PWAF_OK;
+}
+int pwaf_engine_geo_answer_tables(const pwaf_engine *e, uint32_t out[8]) {
+    if (!e || !out) return fail(PWAF_E_INVALID_ARG, "pwaf_engine_geo_answer_tables: NULL argument");
+    if (int rc = need_geo_answers(e, "pwaf_engine_geo_answer_tables")) return rc;
+    out[0] = e->georec_chunks.p ? 1u : 0u;
+    out[1] = e->georec_n_esc;
+    out[2] = e->georec_chunks.p ? e->georec_n_vals : 0u;
+    out[3] = e->georec_summary.p ? 1u : 0u;
+    out[4] = e->georec_shift;
+    out[5] = e->georec_common;
+    out[6] = (uint32_t)std::max<size_t>(1, e->prog.p->geo_recs.size());
+    out[7] = 0;
     return PWAF_OK;
 }
 size_t pwaf_program_residual_source(const pwaf_program *p, int kind, char *buf, size_t cap) {
@@ -2441,8 +2520,9 @@ int pwaf_program_confirm_field(const pwaf_program *p, uint32_t group, const uint
     return PWAF_OK;
 }
 
-int pwaf_evaluate_device(pwaf_engine *e, const pwaf_batch *in, pwaf_verdict *out, pwaf_counts *counts, uint32_t *match_idx, uint32_t *n_matches, void *stream) {
-    if (!e || !out) return fail(PWAF_E_INVALID_ARG, "NULL argument");
+}  // extern "C"
+namespace {
+int evaluate_device_impl(pwaf_engine *e, const pwaf_batch *in, pwaf_verdict *out, pwaf_counts *counts, uint32_t *match_idx, uint32_t *n_matches, pwaf_geo *geo, void *stream) {
     int rc = validate_batch_header(in);
     if (rc) return rc;
     if (in->memory != PWAF_MEM_DEVICE) return fail(PWAF_E_INVALID_ARG, "pwaf_evaluate_device needs a DEVICE batch");
@@ -2455,13 +2535,13 @@ int pwaf_evaluate_device(pwaf_engine *e, const pwaf_batch *in, pwaf_verdict *out
     Scratch &S = acquire_context(e, false, (hipStream_t)stream, lock, must_wait);
     if ((rc = S.ensure(false))) return rc;
     if (must_wait) HIP_TRY(hipStreamWaitEvent((hipStream_t)stream, S.done, 0));
-    rc = run_pipeline(e, S, *in, out, counts, match_idx, n_matches, (hipStream_t)stream);
+    rc = run_pipeline(e, S, *in, out, counts, match_idx, n_matches, (hipStream_t)stream, false, nullptr, false, geo);
     const hipError_t he = mark_context_used(S, (hipStream_t)stream, false);
     return he != hipSuccess ? device_error("hipEventRecord", he) : rc;
 }
 
-int pwaf_evaluate_batch(pwaf_engine *e, const pwaf_batch *in, pwaf_verdict *out, pwaf_counts *counts) {
-    if (!e || !out) return fail(PWAF_E_INVALID_ARG, "NULL argument");
+// `geo` (nullable; PWAF_OPT_GEO_ANSWERS engines only): the GeoIP record of every request, where `out` lives
+int evaluate_batch_impl(pwaf_engine *e, const pwaf_batch *in, pwaf_verdict *out, pwaf_counts *counts, pwaf_geo *geo) {
     int rc = validate_batch_header(in);
     if (rc) return rc;
     if (in->n == 0) {
@@ -2476,7 +2556,7 @@ int pwaf_evaluate_batch(pwaf_engine *e, const pwaf_batch *in, pwaf_verdict *out,
     if ((rc = S.ensure(true))) return rc;
     hipStream_t s = S.stream;
     if (must_wait) HIP_TRY(hipStreamWaitEvent(s, S.done, 0));
-    if (in->memory == PWAF_MEM_DEVICE) return run_with_retry(e, S, *in, out, counts, false, nullptr, false, [] { return PWAF_OK; });
+    if (in->memory == PWAF_MEM_DEVICE) return run_with_retry(e, S, *in, out, counts, false, nullptr, false, [] { return PWAF_OK; }, geo);
     // HOST batch: stage, validate what a device cannot report (while the copies are in flight, when the caller's memory is page-locked:
     // pwaf_host_alloc / pwaf_host_register), run, copy back
     const uint32_t n = in->n;
@@ -2535,6 +2615,7 @@ int pwaf_evaluate_batch(pwaf_engine *e, const pwaf_batch *in, pwaf_verdict *out,
     const size_t at_counts = pk.take(sizeof(pwaf_counts));  // (arrive zeroed with the inputs, return with the verdicts)
     const size_t in_bytes = pk.size();
     const size_t at_out = pk.take((size_t)n * sizeof(pwaf_verdict));
+    const size_t at_geo = geo ? pk.take((size_t)n * sizeof(pwaf_geo)) : 0;  // (returns with the verdicts)
     const size_t need = pk.size();
     if (packable && need <= kPackMax && !switches().no_packed_staging) {
         if ((rc = validate())) return rc;
@@ -2567,8 +2648,9 @@ int pwaf_evaluate_batch(pwaf_engine *e, const pwaf_batch *in, pwaf_verdict *out,
         rc = run_with_retry(e, S, dv.db, d_out, d_counts, true, &col_begin, true, [&]() -> int {
             HIP_TRY(hipMemcpyAsync(S.pin_out.p, d_counts, back, hipMemcpyDeviceToHost, s));
             return PWAF_OK;
-        });
+        }, geo ? (pwaf_geo *)((char *)S.packed.p + at_geo) : nullptr);
         if (rc) return rc;
+        if (geo) memcpy(geo, (const char *)S.pin_out.p + (at_geo - at_counts), (size_t)n * sizeof(pwaf_geo));
         memcpy(out, (const char *)S.pin_out.p + (at_out - at_counts), (size_t)n * sizeof(pwaf_verdict));
         if (counts) memcpy(counts, S.pin_out.p, sizeof(pwaf_counts));
         return PWAF_OK;
@@ -2606,12 +2688,81 @@ int pwaf_evaluate_batch(pwaf_engine *e, const pwaf_batch *in, pwaf_verdict *out,
     dv.set_fixed(S.stage_ip.p, S.stage_v6.p, S.stage_port.p, S.stage_flags.p, in->asn ? S.stage_asn.p : nullptr, in->asn ? S.stage_country.p : nullptr);
     if ((rc = S.stage_out.reserve((size_t)n * sizeof(pwaf_verdict)))) return bail(rc);
     if ((rc = S.stage_counts.reserve(sizeof(pwaf_counts)))) return bail(rc);
+    if (geo && (rc = S.stage_geo.reserve((size_t)n * sizeof(pwaf_geo)))) return bail(rc);
     if ((rc = validate())) return bail(rc);
     return run_with_retry(e, S, dv.db, (pwaf_verdict *)S.stage_out.p, (pwaf_counts *)S.stage_counts.p, true, &col_begin, false, [&]() -> int {
         HIP_TRY(hipMemcpyAsync(out, S.stage_out.p, (size_t)n * sizeof(pwaf_verdict), hipMemcpyDeviceToHost, s));
         if (counts) HIP_TRY(hipMemcpyAsync(counts, S.stage_counts.p, sizeof(pwaf_counts), hipMemcpyDeviceToHost, s));
+        if (geo) HIP_TRY(hipMemcpyAsync(geo, S.stage_geo.p, (size_t)n * sizeof(pwaf_geo), hipMemcpyDeviceToHost, s));
         return PWAF_OK;
-    });
+    }, geo ? (pwaf_geo *)S.stage_geo.p : nullptr);
+}
+}  // namespace
+
+extern "C" {
+
+int pwaf_evaluate_device(pwaf_engine *e, const pwaf_batch *in, pwaf_verdict *out, pwaf_counts *counts, uint32_t *match_idx, uint32_t *n_matches, void *stream) {
+    if (!e || !out) return fail(PWAF_E_INVALID_ARG, "NULL argument");
+    return evaluate_device_impl(e, in, out, counts, match_idx, n_matches, nullptr, stream);
+}
+int pwaf_evaluate_device_geo(pwaf_engine *e, const pwaf_batch *in, pwaf_verdict *out, pwaf_counts *counts, uint32_t *match_idx, uint32_t *n_matches, pwaf_geo *geo, void *stream) {
+    if (!e || !out) return fail(PWAF_E_INVALID_ARG, "NULL argument");
+    if (int rc = need_geo_answers(e, "pwaf_evaluate_device_geo")) return rc;
+    return evaluate_device_impl(e, in, out, counts, match_idx, n_matches, geo, stream);
+}
+
+int pwaf_evaluate_batch(pwaf_engine *e, const pwaf_batch *in, pwaf_verdict *out, pwaf_counts *counts) {
+    if (!e || !out) return fail(PWAF_E_INVALID_ARG, "NULL argument");
+    return evaluate_batch_impl(e, in, out, counts, nullptr);
+}
+int pwaf_evaluate_batch_geo(pwaf_engine *e, const pwaf_batch *in, pwaf_verdict *out, pwaf_counts *counts, pwaf_geo *geo) {
+    if (!e || !out) return fail(PWAF_E_INVALID_ARG, "NULL argument");
+    if (int rc = need_geo_answers(e, "pwaf_evaluate_batch_geo")) return rc;
+    return evaluate_batch_impl(e, in, out, counts, geo);
+}
+
+// The GeoIP records of n addresses, nothing else: georec_kernel alone. DEVICE memory: enqueued on `stream`; HOST memory: staged through a
+// context of the engine, launched on its stream, copied back, waited for.
+int pwaf_geoip_lookup(pwaf_engine *e, const uint8_t *ip, const uint8_t *ip_is_v6, uint32_t n, uint32_t memory, pwaf_geo *out, void *stream) {
+    if (!e || (n && (!ip || !ip_is_v6 || !out))) return fail(PWAF_E_INVALID_ARG, "pwaf_geoip_lookup: NULL argument");
+    if (memory != PWAF_MEM_HOST && memory != PWAF_MEM_DEVICE) return fail(PWAF_E_INVALID_ARG, "pwaf_geoip_lookup: memory is neither HOST nor DEVICE");
+    int rc = need_geo_answers(e, "pwaf_geoip_lookup");
+    if (rc) return rc;
+    if (n == 0) return PWAF_OK;
+    HIP_TRY(hipSetDevice(e->device));
+    GeoRecArgs ga{};
+    set_georec_args(e, ga);
+    ga.n = n;
+    if (memory == PWAF_MEM_DEVICE) {
+        ga.ip = ip;
+        ga.ip_is_v6 = ip_is_v6;
+        ga.out = (uint2 *)out;
+        KernelTimer prof(e, (hipStream_t)stream);
+        if ((rc = prof.begin())) return rc;
+        if (const int he = launch_georec(ga, stream)) return fail(PWAF_E_DEVICE, std::string("georec kernel launch failed: ") + hipGetErrorString((hipError_t)he));
+        if ((rc = prof.end("georec", 25ull * n))) return rc;
+        prof.commit();
+        return PWAF_OK;
+    }
+    std::unique_lock<std::mutex> lock;
+    bool must_wait;
+    Scratch &S = acquire_context(e, true, nullptr, lock, must_wait);
+    if ((rc = S.ensure(true))) return rc;
+    const hipStream_t s = S.stream;
+    if (must_wait) HIP_TRY(hipStreamWaitEvent(s, S.done, 0));
+    if ((rc = S.stage_ip.reserve((size_t)n * 16)) || (rc = S.stage_v6.reserve(n)) || (rc = S.stage_geo.reserve((size_t)n * sizeof(pwaf_geo)))) return rc;
+    ga.ip = (const uint8_t *)S.stage_ip.p;
+    ga.ip_is_v6 = (const uint8_t *)S.stage_v6.p;
+    ga.out = (uint2 *)S.stage_geo.p;
+    hipError_t he = hipMemcpyAsync(S.stage_ip.p, ip, (size_t)n * 16, hipMemcpyHostToDevice, s);
+    if (he == hipSuccess) he = hipMemcpyAsync(S.stage_v6.p, ip_is_v6, n, hipMemcpyHostToDevice, s);
+    if (he == hipSuccess) he = (hipError_t)launch_georec(ga, s);
+    if (he == hipSuccess) he = hipMemcpyAsync(out, S.stage_geo.p, (size_t)n * sizeof(pwaf_geo), hipMemcpyDeviceToHost, s);
+    const hipError_t re = mark_context_used(S, s, true), se = hipStreamSynchronize(s);  // (what was enqueued reads the caller's buffers)
+    if (he != hipSuccess) return device_error("pwaf_geoip_lookup", he);
+    if (re != hipSuccess) return device_error("hipEventRecord", re);
+    if (se != hipSuccess) return device_error("hipStreamSynchronize", se);
+    return PWAF_OK;
 }
 
 // Page-locked host memory for batch columns: the copy engine reads it directly (no staging copy inside the runtime, the calling thread
@@ -2654,9 +2805,11 @@ bool page_locked(const void *p, size_t bytes) {
 
 static_assert(pwaf::records::kMaxValues == PWAF_N_FIELDS + kMaxHeaders, "records.h kMaxValues must follow program.h kMaxHeaders");
 
-int pwaf_evaluate_records(pwaf_engine *e, const uint8_t *buf, size_t buf_bytes, const uint32_t *rec_off, uint32_t n, pwaf_verdict *out, pwaf_counts *counts) {
+}  // extern "C"
+namespace {
+// `geo` (nullable; host memory, n entries; PWAF_OPT_GEO_ANSWERS engines only): the GeoIP record of every request
+int evaluate_records_impl(pwaf_engine *e, const uint8_t *buf, size_t buf_bytes, const uint32_t *rec_off, uint32_t n, pwaf_verdict *out, pwaf_counts *counts, pwaf_geo *geo_out) {
     namespace R = pwaf::records;
-    if (!e || (n && (!buf || !rec_off || !out))) return fail(PWAF_E_INVALID_ARG, "NULL argument");
     if (e->n_fields > R::kMaxValues) return fail(PWAF_E_UNSUPPORTED, "the engine has more columns than a record can carry");
     if (n == 0) {
         if (counts) memset(counts, 0, sizeof *counts);
@@ -2683,6 +2836,7 @@ int pwaf_evaluate_records(pwaf_engine *e, const uint8_t *buf, size_t buf_bytes, 
     const size_t off_stride = ((size_t)n + 1 + 63) & ~(size_t)63;
     const size_t at_recoff = meta.take((size_t)n * 4), at_off = meta.take(off_stride * 4 * n_cols), at_colat = meta.take((size_t)n_cols * 8);
     const size_t at_counts = meta.take(sizeof(pwaf_counts)), up_bytes = meta.size(), at_out = meta.take((size_t)n * sizeof(pwaf_verdict));
+    const size_t at_geo = geo_out ? meta.take((size_t)n * sizeof(pwaf_geo)) : 0;  // (comes back with the verdicts)
     const size_t span = (size_t)(hi - lo), at_rec = meta.take(span), need = meta.size();
     const bool direct = page_locked(buf + lo, span);
     if ((rc = S.rec_meta.reserve(need)) || (rc = S.rec_pin.reserve(direct ? up_bytes : need)) || (rc = S.rec_back.reserve(at_rec - at_counts))) return rc;
@@ -2736,11 +2890,25 @@ int pwaf_evaluate_records(pwaf_engine *e, const uint8_t *buf, size_t buf_bytes, 
     rc = run_with_retry(e, S, dv.db, (pwaf_verdict *)(d + at_out), d_counts, true, &col_begin, true, [&]() -> int {
         HIP_TRY(hipMemcpyAsync(S.rec_back.p, d_counts, at_rec - at_counts, hipMemcpyDeviceToHost, s));
         return PWAF_OK;
-    });
+    }, geo_out ? (pwaf_geo *)(d + at_geo) : nullptr);
     if (rc) return rc;
     memcpy(out, (const char *)S.rec_back.p + (at_out - at_counts), (size_t)n * sizeof(pwaf_verdict));
+    if (geo_out) memcpy(geo_out, (const char *)S.rec_back.p + (at_geo - at_counts), (size_t)n * sizeof(pwaf_geo));
     if (counts) memcpy(counts, S.rec_back.p, sizeof(pwaf_counts));
     return PWAF_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int pwaf_evaluate_records(pwaf_engine *e, const uint8_t *buf, size_t buf_bytes, const uint32_t *rec_off, uint32_t n, pwaf_verdict *out, pwaf_counts *counts) {
+    if (!e || (n && (!buf || !rec_off || !out))) return fail(PWAF_E_INVALID_ARG, "NULL argument");
+    return evaluate_records_impl(e, buf, buf_bytes, rec_off, n, out, counts, nullptr);
+}
+int pwaf_evaluate_records_geo(pwaf_engine *e, const uint8_t *buf, size_t buf_bytes, const uint32_t *rec_off, uint32_t n, pwaf_verdict *out, pwaf_counts *counts, pwaf_geo *geo) {
+    if (!e || (n && (!buf || !rec_off || !out))) return fail(PWAF_E_INVALID_ARG, "NULL argument");
+    if (int rc = need_geo_answers(e, "pwaf_evaluate_records_geo")) return rc;
+    return evaluate_records_impl(e, buf, buf_bytes, rec_off, n, out, counts, geo);
 }
 
 // The host half of tuning (no device involved): walks every pass over the sample and rebuilds the bigram prefilters for this traffic.
@@ -3033,8 +3201,9 @@ int pwaf_engine_device_status(pwaf_engine *e) {
     return PWAF_OK;
 }
 
-int pwaf_evaluate_one(pwaf_engine *e, const pwaf_request *r, pwaf_verdict *out) {
-    if (!e || !r || !out) return fail(PWAF_E_INVALID_ARG, "NULL argument");
+}  // extern "C"
+namespace {
+int evaluate_one_impl(pwaf_engine *e, const pwaf_request *r, pwaf_verdict *out, pwaf_geo *geo) {
     if (r->n_headers && !r->headers) return fail(PWAF_E_INVALID_ARG, "n_headers without a headers array");
     const uint32_t n_hdr = e->n_fields - PWAF_N_FIELDS;  // header columns the rule set reads
     const uint32_t n_cols = PWAF_N_FIELDS + n_hdr;
@@ -3082,7 +3251,34 @@ int pwaf_evaluate_one(pwaf_engine *e, const pwaf_request *r, pwaf_verdict *out) 
         b.asn = &asn;
         b.country = &country;
     }
-    return pwaf_evaluate_batch(e, &b, out, nullptr);
+    return evaluate_batch_impl(e, &b, out, nullptr, geo);
+}
+}  // namespace
+
+extern "C" {
+
+int pwaf_evaluate_one(pwaf_engine *e, const pwaf_request *r, pwaf_verdict *out) {
+    if (!e || !r || !out) return fail(PWAF_E_INVALID_ARG, "NULL argument");
+    return evaluate_one_impl(e, r, out, nullptr);
+}
+int pwaf_evaluate_one_geo(pwaf_engine *e, const pwaf_request *r, pwaf_verdict *out, pwaf_geo *geo) {
+    if (!e || !r || !out) return fail(PWAF_E_INVALID_ARG, "NULL argument");
+    if (int rc = need_geo_answers(e, "pwaf_evaluate_one_geo")) return rc;
+    return evaluate_one_impl(e, r, out, geo);
+}
+
+}  // extern "C"
+namespace pwaf {  // async.cpp: the queue takes its records-with-answers evaluator as a pointer (it links against a stub engine in the CPU suite)
+using RecordsGeoFn = int (*)(pwaf_engine *, const uint8_t *, size_t, const uint32_t *, uint32_t, pwaf_verdict *, pwaf_counts *, pwaf_geo *);
+int async_create_with(pwaf_engine *engine, uint32_t max_batch, uint32_t max_delay_us, uint32_t max_in_flight, RecordsGeoFn eval_geo, pwaf_async **out);
+}  // namespace pwaf
+extern "C" {
+
+int pwaf_async_create_geo(pwaf_engine *e, uint32_t max_batch, uint32_t max_delay_us, uint32_t max_in_flight, pwaf_async **out) {
+    if (!e || !out) return fail(PWAF_E_INVALID_ARG, "NULL argument");
+    *out = nullptr;
+    if (int rc = need_geo_answers(e, "pwaf_async_create_geo")) return rc;
+    return pwaf::async_create_with(e, max_batch, max_delay_us, max_in_flight, &pwaf_evaluate_records_geo, out);
 }
 
 int pwaf_engine_set_profiling(pwaf_engine *e, int on) {

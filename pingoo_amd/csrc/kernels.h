@@ -475,6 +475,21 @@ int launch_verdict(const VerdictArgs &a, void *stream);
 int launch_ipres(const VerdictArgs &a, void *stream);  // address lookups -> a.ipres; then, on the same stream:
 int launch_attr(const VerdictArgs &a, void *stream);
 int launch_dir24(const VerdictArgs &a, void *out /* 2^24 x u32, or null: count only */, void *esc, void *esc_count, void *stream);
+// georec_kernel (PWAF_OPT_GEO_ANSWERS): the GeoIP RECORD of every request, 8 bytes each ({asn, country, 0} = pwaf_geo = GeoRec) — what
+// the rules saw as client.asn / client.country. The tables are the record-leaf trie and its own compressed IPv4 table (csrc/georec.h).
+struct GeoRecArgs {
+    const uint8_t *ip, *ip_is_v6;
+    const uint32_t *asn;      // the batch's own columns (both or neither): echoed, no lookup
+    const uint16_t *country;
+    uint32_t n, has_geo;
+    const uint32_t *root4, *root6, *nodes;  // leaves = record ids (an all-leaf root for a family without prefixes)
+    const GeoRec *recs;                     // never null: record 0 = {0, "XX"}
+    const uint32_t *chunks, *vals, *summary;  // the IPv4 table as dirtable::Compressed (chunks null: IPv4 walks the trie)
+    uint32_t sum_shift, common;
+    uint32_t n_cus;
+    uint2 *out;  // n x 8 bytes
+};
+int launch_georec(const GeoRecArgs &a, void *stream);
 uint32_t scan_lds_bytes(uint32_t n_hot, uint32_t stride, uint32_t n_gate_atoms);
 struct VerdictShape {
     uint32_t waves, lds_bytes, lds_tables;

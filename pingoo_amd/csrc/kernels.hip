@@ -3338,6 +3338,110 @@ __global__ __launch_bounds__(256) void ipres_kernel(VerdictArgs a) {
     }
 }
 
+// georec_kernel (PWAF_OPT_GEO_ANSWERS): the GeoIP RECORD of every request — what the reference keeps in its RequestContext and sends
+// upstream (http_listener.rs:143-157,183-191; http_proxy_service.rs:174-189). ipres_kernel's shape (one lane per request, no LDS, U = 4
+// requests per lane in lockstep, every phase's loads issued before any is used) over ONE table: the record-leaf trie and its own
+// compressed IPv4 table (csrc/georec.h: an entry is the record id, or DIR_ESCAPE | the trie node to continue from). One dependent
+// 8-byte gather of the record and one 8-byte store end it. A batch that carries asn / country columns gets them echoed.
+__global__ __launch_bounds__(256) void georec_kernel(GeoRecArgs a) {
+    constexpr uint32_t U = 4;
+    const uint32_t T = gridDim.x * 256u;
+    if (a.asn != nullptr) {
+        for (uint32_t i = blockIdx.x * 256u + threadIdx.x; i < a.n; i += T) a.out[i] = make_uint2(a.asn[i], (uint32_t)a.country[i]);
+        return;
+    }
+    const bool dir = a.chunks != nullptr;
+    for (uint32_t i0 = blockIdx.x * 256u + threadIdx.x; i0 < a.n; i0 += T * U) {
+        uint32_t idx[U], ipw[U][4], e[U], k[U], top16[U], v6b[U];
+        bool live[U], chunked[U];
+        uint4 raw[U];
+#pragma unroll
+        for (uint32_t u = 0; u < U; u++) {
+            idx[u] = i0 + u * T;
+            live[u] = idx[u] < a.n;
+            const uint32_t j = live[u] ? idx[u] : i0;
+            raw[u] = *reinterpret_cast<const uint4 *>(a.ip + (size_t)j * 16);
+            v6b[u] = a.ip_is_v6[j];
+        }
+        // family and exclusion (GeoipDB::lookup, pingoo/geoip.rs:73-91: loopback / multicast are "not found"), then phase 1: the 16-bit
+        // root (IPv6, or IPv4 without a table)
+#pragma unroll
+        for (uint32_t u = 0; u < U; u++) {
+            ipw[u][0] = raw[u].x; ipw[u][1] = raw[u].y; ipw[u][2] = raw[u].z; ipw[u][3] = raw[u].w;
+            const bool v6 = v6b[u] != 0;
+            bool walk = a.has_geo != 0;
+            if (!v6) {
+                const uint32_t b0 = ipw[u][0] & 0xFFu;
+                walk = walk && !(b0 == 127u || (b0 & 0xF0u) == 0xE0u);
+            } else {
+                const bool loopback = ipw[u][0] == 0 && ipw[u][1] == 0 && ipw[u][2] == 0 && ipw[u][3] == 0x01000000u;
+                walk = walk && !(loopback || (ipw[u][0] & 0xFFu) == 0xFFu);
+            }
+            top16[u] = (ip_byte(ipw[u], 0) << 8) | ip_byte(ipw[u], 1);
+            e[u] = TRIE_LEAF;  // record 0: the default
+            k[u] = 2;
+            chunked[u] = walk && !v6 && dir;
+            if (walk && !chunked[u]) e[u] = (v6 ? a.root6 : a.root4)[top16[u]];
+        }
+        // phase 1b: the summary bit of the address's block of /24s: 0 = the table's most common entry, no gather
+        uint32_t look[U];
+#pragma unroll
+        for (uint32_t u = 0; u < U; u++) {
+            look[u] = chunked[u] ? 1u : 0u;
+            if (chunked[u] && a.summary != nullptr) {
+                const uint32_t blk = ((top16[u] << 8) | ip_byte(ipw[u], 2)) >> a.sum_shift;
+                look[u] = (a.summary[blk >> 5] >> (blk & 31u)) & 1u;
+            }
+        }
+        // ONE 16-byte gather: the record of the address's group of 32 /24s
+        uint4 rec4[U];
+#pragma unroll
+        for (uint32_t u = 0; u < U; u++) {
+            rec4[u] = make_uint4(0u, 0u, 0u, 0u);
+            if (look[u]) rec4[u] = *reinterpret_cast<const uint4 *>(a.chunks + (size_t)top16[u] * kDirChunkWords + 4u * (ip_byte(ipw[u], 2) >> 5));
+        }
+        // phase 2: the run's entry — carried into the group, the first run inside it, or a further run from vals
+        uint32_t e24[U];
+#pragma unroll
+        for (uint32_t u = 0; u < U; u++) {
+            e24[u] = a.common;
+            if (look[u]) {
+                const uint32_t rank = (uint32_t)__builtin_popcount(rec4[u].x & (0xFFFFFFFFu >> (31u - (ip_byte(ipw[u], 2) & 31u))));
+                e24[u] = rank == 0 ? rec4[u].y : rank == 1 ? rec4[u].z : a.vals[rec4[u].w + rank - 2u];
+            }
+        }
+        // phase 4: an escape continues in the trie node the entry names, with the address's last byte
+#pragma unroll
+        for (uint32_t u = 0; u < U; u++)
+            if (chunked[u]) {
+                k[u] = 3;
+                e[u] = (e24[u] & DIR_ESCAPE) ? (e24[u] & ~DIR_ESCAPE) : (TRIE_LEAF | e24[u]);
+            }
+        // phase 5: the remaining trie levels (IPv6, escapes), all walks advancing together
+        for (;;) {
+            bool more = false;
+#pragma unroll
+            for (uint32_t u = 0; u < U; u++) more = more || !(e[u] & TRIE_LEAF);
+            if (!more) break;
+            uint32_t ne[U];
+#pragma unroll
+            for (uint32_t u = 0; u < U; u++) ne[u] = (e[u] & TRIE_LEAF) ? e[u] : a.nodes[(size_t)e[u] * 256 + ip_byte(ipw[u], k[u] < 16 ? k[u] : 15u)];
+#pragma unroll
+            for (uint32_t u = 0; u < U; u++) {
+                k[u]++;
+                e[u] = ne[u];
+            }
+        }
+        // the record itself: one 8-byte gather, one 8-byte store
+        uint2 r[U];
+#pragma unroll
+        for (uint32_t u = 0; u < U; u++) r[u] = reinterpret_cast<const uint2 *>(a.recs)[e[u] & ~TRIE_LEAF];
+#pragma unroll
+        for (uint32_t u = 0; u < U; u++)
+            if (live[u]) a.out[idx[u]] = make_uint2(r[u].x, r[u].y & 0xFFFFu);
+    }
+}
+
 struct AttrIn {
     uint32_t cls, set_id;
     uint32_t port, len[5], asn, country;
@@ -3610,6 +3714,14 @@ int launch_ipres(const VerdictArgs &a, void *stream) {
     const uint32_t blocks = std::min<uint32_t>((a.n + 255) / 256, forced ? forced : 8 * std::max(1u, a.attr_blocks));
     if (a.ipres_packed) hipLaunchKernelGGL(ipres_kernel<true>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, a);
     else hipLaunchKernelGGL(ipres_kernel<false>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, a);
+    return (int)hipGetLastError();
+}
+
+// GeoIP records: ipres_kernel's geometry (grid-stride; 8 workgroups of 256 per CU)
+int launch_georec(const GeoRecArgs &a, void *stream) {
+    if (a.n == 0) return 0;
+    const uint32_t blocks = std::min<uint32_t>((a.n + 255) / 256, 8 * std::max(1u, a.n_cus));
+    hipLaunchKernelGGL(georec_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, a);
     return (int)hipGetLastError();
 }
 

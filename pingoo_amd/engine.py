@@ -24,7 +24,7 @@ from typing import Dict, Iterable, List, Optional, Sequence, Tuple
 import numpy as np
 
 from . import _abi
-from .batch import VERDICT_DTYPE, Request, RequestBatch
+from .batch import GEO_DTYPE, VERDICT_DTYPE, Request, RequestBatch
 
 _LIB = None
 # PWAF_LIB_VARIANT=prof loads libpwaf_prof.so, the -DPWAF_PROFILING build with the timing-experiment switches (tools/ only: results may
@@ -151,6 +151,16 @@ def lib():
     L.pwaf_async_stats.argtypes = [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
     L.pwaf_async_destroy.argtypes = [vp]
     L.pwaf_async_destroy.restype = None
+    # GeoIP answers (engines created with OPT_GEO_ANSWERS)
+    L.pwaf_geoip_lookup.argtypes = [vp, vp, vp, C.c_uint32, C.c_uint32, vp, vp]
+    L.pwaf_evaluate_batch_geo.argtypes = [vp, C.POINTER(_abi.Batch), vp, vp, vp]
+    L.pwaf_evaluate_device_geo.argtypes = [vp, C.POINTER(_abi.Batch), vp, vp, vp, vp, vp, vp]
+    L.pwaf_evaluate_records_geo.argtypes = [vp, vp, C.c_size_t, vp, C.c_uint32, vp, vp, vp]
+    L.pwaf_evaluate_one_geo.argtypes = [vp, C.POINTER(_abi.Request), C.POINTER(_abi.Verdict), C.POINTER(_abi.Geo)]
+    L.pwaf_async_create_geo.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(vp)]
+    L.pwaf_async_poll_geo.argtypes = [vp, C.POINTER(_abi.Completion), C.POINTER(_abi.Geo), C.c_size_t]
+    L.pwaf_async_poll_geo.restype = C.c_size_t
+    L.pwaf_engine_geo_answer_tables.argtypes = [vp, C.POINTER(C.c_uint32)]
     L.pwaf_geoip_from_mmdb.argtypes = [C.c_char_p, C.c_size_t, C.POINTER(C.POINTER(_abi.GeoipEntry)), C.POINTER(C.c_size_t)]
     L.pwaf_geoip_from_file_image.argtypes = [C.c_char_p, C.c_char_p, C.c_size_t, C.POINTER(C.POINTER(_abi.GeoipEntry)), C.POINTER(C.c_size_t)]
     L.pwaf_zstd_decompress.argtypes = [C.c_char_p, C.c_size_t, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]
@@ -418,6 +428,27 @@ class RuleEngine:
             _raise(rc, lib().pwaf_last_error().decode(errors="replace"))
         return dict(zip(_abi.ADDRESS_TABLE_FIELDS, (int(x) for x in out)))
 
+    def geo_answer_tables(self) -> dict:
+        """TEST HOOK (pwaf_engine_geo_answer_tables; OPT_GEO_ANSWERS engines): the shape of the record tables, by the names of
+        _abi.GEO_ANSWER_TABLE_FIELDS."""
+        out = (C.c_uint32 * len(_abi.GEO_ANSWER_TABLE_FIELDS))()
+        rc = lib().pwaf_engine_geo_answer_tables(self._h, out)
+        if rc != 0:
+            _raise(rc, lib().pwaf_last_error().decode(errors="replace"))
+        return dict(zip(_abi.GEO_ANSWER_TABLE_FIELDS, (int(x) for x in out)))
+
+    def lookup_geoip(self, ip16, v6) -> np.ndarray:
+        """GeoipDB::lookup for a batch of addresses (pwaf_geoip_lookup; OPT_GEO_ANSWERS engines): ip16 = n x 16 address bytes (IPv4 in
+        bytes 0..3), v6 = n family flags -> GEO_DTYPE array, the default record {0, "XX"} where the reference finds none."""
+        ip16 = np.ascontiguousarray(ip16, dtype=np.uint8).reshape(-1, 16)
+        v6 = np.ascontiguousarray(v6, dtype=np.uint8).reshape(-1)
+        assert len(ip16) == len(v6)
+        out = np.zeros(len(v6), dtype=GEO_DTYPE)
+        rc = lib().pwaf_geoip_lookup(self._h, ip16.ctypes.data, v6.ctypes.data, len(v6), _abi.MEM_HOST, out.ctypes.data, None)
+        if rc != 0:
+            _raise(rc, lib().pwaf_last_error().decode(errors="replace"))
+        return out
+
     def rule_errors(self, n_rules: int) -> List[int]:
         """Per caller rule: requests (over every batch so far) for which the rule's evaluation ended in an execution error — what the
         reference logs per occurrence (pingoo/rules.rs:41-45). Static errors are creation-time warnings instead."""
@@ -433,46 +464,62 @@ class RuleEngine:
         return {k: getattr(s, k) for k, _ in _abi.Stats._fields_ if k != "reserved"}
 
     # ---- evaluation -------------------------------------------------------------------------------
-    def evaluate_batch(self, batch: RequestBatch, with_counts: bool = False, out: Optional[np.ndarray] = None):
+    def evaluate_batch(self, batch: RequestBatch, with_counts: bool = False, out: Optional[np.ndarray] = None, with_geo: bool = False):
         """Host batch in, numpy VERDICT_DTYPE array out (and the 4 action counters when asked). `out`: a caller-owned result array
-        (e.g. page-locked: PinnedVerdicts(n).array) instead of a fresh one per call."""
+        (e.g. page-locked: PinnedVerdicts(n).array) instead of a fresh one per call. with_geo (OPT_GEO_ANSWERS engines): the GEO_DTYPE
+        array of the requests' GeoIP records is appended to what is returned."""
         if out is None:
             out = np.zeros(batch.n, dtype=VERDICT_DTYPE)
         assert out.dtype == VERDICT_DTYPE and len(out) >= batch.n and out.flags["C_CONTIGUOUS"]
         counts = _abi.Counts()
         st = batch.as_struct(self.header_names)
-        rc = lib().pwaf_evaluate_batch(self._h, C.byref(st), out.ctypes.data, C.addressof(counts))
+        geo = np.zeros(batch.n, dtype=GEO_DTYPE) if with_geo else None
+        if with_geo:
+            rc = lib().pwaf_evaluate_batch_geo(self._h, C.byref(st), out.ctypes.data, C.addressof(counts), geo.ctypes.data)
+        else:
+            rc = lib().pwaf_evaluate_batch(self._h, C.byref(st), out.ctypes.data, C.addressof(counts))
         if rc != 0:
             _raise(rc, lib().pwaf_last_error().decode(errors="replace"))
-        if with_counts:
-            return out, np.array(list(counts.by_action), dtype=np.uint64)
-        return out
+        res = (out, np.array(list(counts.by_action), dtype=np.uint64)) if with_counts else (out,)
+        res += (geo,) if with_geo else ()
+        return res if len(res) > 1 else res[0]
 
-    def evaluate_records(self, buf: np.ndarray, rec_off: np.ndarray, with_counts: bool = False):
+    def evaluate_records(self, buf: np.ndarray, rec_off: np.ndarray, with_counts: bool = False, with_geo: bool = False):
         """Request records (RequestBatch.to_records, include/pwaf.h pwaf_record_head) in, VERDICT_DTYPE array out: verdict i belongs to the
         record at buf[rec_off[i]] (pwaf_evaluate_records). `buf` may be page-locked (pwaf_host_alloc / _register) or not."""
         buf = np.ascontiguousarray(buf, dtype=np.uint8)
         rec_off = np.ascontiguousarray(rec_off, dtype=np.uint32)
         out = np.zeros(len(rec_off), dtype=VERDICT_DTYPE)
         counts = _abi.Counts()
-        rc = lib().pwaf_evaluate_records(self._h, buf.ctypes.data, buf.nbytes, rec_off.ctypes.data, len(rec_off), out.ctypes.data, C.addressof(counts))
+        geo = np.zeros(len(rec_off), dtype=GEO_DTYPE) if with_geo else None
+        if with_geo:  # (OPT_GEO_ANSWERS engines: the records' GeoIP answers, appended to what is returned)
+            rc = lib().pwaf_evaluate_records_geo(self._h, buf.ctypes.data, buf.nbytes, rec_off.ctypes.data, len(rec_off), out.ctypes.data, C.addressof(counts), geo.ctypes.data)
+        else:
+            rc = lib().pwaf_evaluate_records(self._h, buf.ctypes.data, buf.nbytes, rec_off.ctypes.data, len(rec_off), out.ctypes.data, C.addressof(counts))
         if rc != 0:
             _raise(rc, lib().pwaf_last_error().decode(errors="replace"))
-        if with_counts:
-            return out, np.array(list(counts.by_action), dtype=np.uint64)
-        return out
+        res = (out, np.array(list(counts.by_action), dtype=np.uint64)) if with_counts else (out,)
+        res += (geo,) if with_geo else ()
+        return res if len(res) > 1 else res[0]
 
-    def evaluate(self, request: Request) -> Verdict:
-        """RuleEngine::evaluate(Request) -> Action (pwaf_evaluate_one): a batch of one through the same device path."""
+    def evaluate(self, request: Request, with_geo: bool = False):
+        """RuleEngine::evaluate(Request) -> Action (pwaf_evaluate_one): a batch of one through the same device path. with_geo
+        (OPT_GEO_ANSWERS engines): -> (Verdict, (asn, country)) — the reference's (Action, GeoipRecord)."""
         st, _keep = _request_struct(request, self.header_names)
         out = _abi.Verdict()
-        rc = lib().pwaf_evaluate_one(self._h, C.byref(st), C.byref(out))
+        geo = _abi.Geo()
+        if with_geo:
+            rc = lib().pwaf_evaluate_one_geo(self._h, C.byref(st), C.byref(out), C.byref(geo))
+        else:
+            rc = lib().pwaf_evaluate_one(self._h, C.byref(st), C.byref(out))
         if rc != 0:
             _raise(rc, lib().pwaf_last_error().decode(errors="replace"))
-        return verdict_from_record({"action": out.action, "rule_idx": out.rule_idx})
+        v = verdict_from_record({"action": out.action, "rule_idx": out.rule_idx})
+        return (v, (int(geo.asn), bytes(geo.country).decode("latin-1"))) if with_geo else v
 
-    def evaluate_device(self, dbatch: "DeviceBatch", out=None, counts=None, match_idx=None, n_matches=None, stream=None):
-        """Device-resident evaluation on torch's current stream (or `stream`). Tensors stay on the GPU."""
+    def evaluate_device(self, dbatch: "DeviceBatch", out=None, counts=None, match_idx=None, n_matches=None, stream=None, geo=None):
+        """Device-resident evaluation on torch's current stream (or `stream`). Tensors stay on the GPU. geo (OPT_GEO_ANSWERS engines): a
+        device tensor of n x 8 bytes that receives the requests' GeoIP records (pwaf_geo)."""
         import torch
 
         if out is None:
@@ -480,9 +527,13 @@ class RuleEngine:
         if stream is None:
             stream = torch.cuda.current_stream(dbatch.device).cuda_stream
         st = dbatch.as_struct(self.header_names)
-        rc = lib().pwaf_evaluate_device(self._h, C.byref(st), out.data_ptr(), counts.data_ptr() if counts is not None else None,
-                                        match_idx.data_ptr() if match_idx is not None else None, n_matches.data_ptr() if n_matches is not None else None,
-                                        C.c_void_p(stream))
+        args = (self._h, C.byref(st), out.data_ptr(), counts.data_ptr() if counts is not None else None,
+                match_idx.data_ptr() if match_idx is not None else None, n_matches.data_ptr() if n_matches is not None else None)
+        if geo is not None:
+            assert geo.is_contiguous() and geo.numel() * geo.element_size() >= dbatch.n * GEO_DTYPE.itemsize
+            rc = lib().pwaf_evaluate_device_geo(*args, geo.data_ptr(), C.c_void_p(stream))
+        else:
+            rc = lib().pwaf_evaluate_device(*args, C.c_void_p(stream))
         if rc != 0:
             _raise(rc, lib().pwaf_last_error().decode(errors="replace"))
         return out
@@ -748,10 +799,11 @@ class AsyncBatcher:
     status) tuples. Wait for `fileno()` to be readable (select / an event loop), read it (`drain_fd()`), then poll until it returns [].
     Safe from many threads (ctypes drops the GIL)."""
 
-    def __init__(self, engine: "RuleEngine", max_batch: int = 4096, max_delay_us: int = 200, max_in_flight: int = 65536):
+    def __init__(self, engine: "RuleEngine", max_batch: int = 4096, max_delay_us: int = 200, max_in_flight: int = 65536, geo: bool = False):
         self._engine = engine  # keeps the engine alive
+        self._geo = geo  # pwaf_async_create_geo (OPT_GEO_ANSWERS engines): completions carry the request's GeoIP record
         h = C.c_void_p()
-        rc = lib().pwaf_async_create(engine._h, max_batch, max_delay_us, max_in_flight, C.byref(h))
+        rc = (lib().pwaf_async_create_geo if geo else lib().pwaf_async_create)(engine._h, max_batch, max_delay_us, max_in_flight, C.byref(h))
         if rc != 0:
             _raise(rc, lib().pwaf_last_error().decode(errors="replace"))
         self._h = h
@@ -765,8 +817,16 @@ class AsyncBatcher:
             _raise(rc, lib().pwaf_last_error().decode(errors="replace"))
         return True
 
-    def poll(self, cap: int = 4096) -> List[Tuple[int, Verdict, int]]:
+    def poll(self, cap: int = 4096, with_geo: bool = False):
+        """-> [(tag, Verdict, status)]; with_geo (a queue made with geo=True): [(tag, Verdict, status, (asn, country))]"""
         arr = (_abi.Completion * cap)()
+        if with_geo:
+            garr = (_abi.Geo * cap)()
+            k = lib().pwaf_async_poll_geo(self._h, arr, garr, cap)
+            if k == 0 and not self._geo:
+                _raise(_abi.E_UNSUPPORTED, lib().pwaf_last_error().decode(errors="replace"))
+            return [(arr[i].tag, verdict_from_record({"action": arr[i].verdict.action, "rule_idx": arr[i].verdict.rule_idx}), arr[i].status,
+                     (int(garr[i].asn), bytes(garr[i].country).decode("latin-1"))) for i in range(k)]
         k = lib().pwaf_async_poll(self._h, arr, cap)
         return [(arr[i].tag, verdict_from_record({"action": arr[i].verdict.action, "rule_idx": arr[i].verdict.rule_idx}), arr[i].status) for i in range(k)]
 
