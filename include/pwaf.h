@@ -141,6 +141,10 @@ void pwaf_list_free(char **items, size_t n);
 #define PWAF_OPT_GEO_ANSWERS 256u     /* the engine also keeps RECORD tables and answers each request's GeoIP record: pwaf_geoip_lookup,
                                        * pwaf_evaluate_*_geo, pwaf_async_create_geo (see "GeoIP answers" below). Without it those return
                                        * PWAF_E_UNSUPPORTED and nothing about the engine differs: memory, creation time, launches, verdicts */
+#define PWAF_OPT_RULE_HITS 131072u    /* the engine can report EVERY rule that matches a request, not only the deciding one: pwaf_evaluate_batch_hits /
+                                       * pwaf_evaluate_device_hits. A rule whose actions can never take effect (an empty action list: an observe-only
+                                       * rule) is then kept, matched and reported, and never decides a verdict. Not with PWAF_OPT_SPARSE_VERDICT /
+                                       * PWAF_OPT_DENSE_VERDICT (PWAF_E_INVALID_ARG). Without the flag nothing about the engine differs. */
 #define PWAF_OPT_NO_RESIDUAL 64u      /* do not use the per-request residual interpreter (testing / benchmarking the column path alone) */
 #define PWAF_OPT_NO_RESIDUAL_JIT 1024u /* residual rules are INTERPRETED per request (residual_kernel) instead of running as the specialized
                                        * device program compiled by hiprtc when the engine is created (the default): same verdicts */
@@ -484,6 +488,34 @@ size_t pwaf_async_poll_geo(pwaf_async *, pwaf_completion *out, pwaf_geo *geo /* 
  * out[3] = 1 when a summary bitmap stands in front, out[4] = its granularity, out[5] = the table entry a clear summary bit stands for,
  * out[6] = records, out[7] = 0. */
 int pwaf_engine_geo_answer_tables(const pwaf_engine *, uint32_t out[8]);
+
+/* ---- rule hits (ABI 4, additive; engines created with PWAF_OPT_RULE_HITS) ---------------------------
+ * Every rule that matches a request, as a sparse list: one entry per (rule, group of 64 requests) with a non-zero match word. Bit r of
+ * `mask` is set when the request 64 * group + r is not answered by a gate (PWAF_RULE_UA_GATE, PWAF_RULE_CAPTCHA_ENDPOINT: the reference
+ * evaluates no rule for those, http_listener.rs:196-204) and the rule's expression evaluates to Bool(true) or the rule has none —
+ * whatever the rule's actions, PWAF_FLAG_CAPTCHA_VERIFIED and the other rules say. An execution error and a rule refused under
+ * PWAF_OPT_LENIENT are no match. A (rule, group) pair appears at most once; the order of the entries is unspecified (like match_idx).
+ * The list comes out of the verdict kernel: no launch and no pass over the requests is added.
+ *   hits, n_hits   given together or both NULL. *n_hits receives the number of entries the batch produced whatever hits_cap is (below
+ *                  2^32: groups x rules); only the first hits_cap reserved slots are written, nothing at or beyond hits + hits_cap.
+ *                  *n_hits > hits_cap: the list is incomplete — no error, the verdicts are complete: call again with a larger list.
+ *                  hits_cap == 0 is a count-only query.
+ *   rule_hits      (nullable) n_rules counters: the requests of this call that rule k matches, exact even when the list overflowed.
+ * They live where the verdicts live. pwaf_evaluate_batch_hits OVERWRITES n_hits and rule_hits (as it does counts; a batch run again for
+ * its overflow pool is not counted twice); pwaf_evaluate_device_hits ACCUMULATES into them (the caller zeroes, as for counts and
+ * n_matches). With hits, n_hits and rule_hits all NULL each function is exactly its plain counterpart: same launches, same copies. On an
+ * engine without the flag a non-NULL hits or rule_hits returns PWAF_E_UNSUPPORTED and launches nothing.
+ * Out of scope: pwaf_evaluate_records, pwaf_evaluate_one, pwaf_batcher_*, pwaf_async_*, pwaf_node_* and the _geo variants. */
+typedef struct pwaf_rule_hit {
+    uint32_t rule_idx; /* caller's rule index, < n_rules; the gate pseudo rules never appear */
+    uint32_t group;    /* requests 64*group .. 64*group+63 */
+    uint64_t mask;     /* bit r: the rule matches request 64*group + r; never 0 */
+} pwaf_rule_hit;       /* 16 bytes */
+int pwaf_evaluate_batch_hits(pwaf_engine *, const pwaf_batch *in, pwaf_verdict *out, pwaf_counts *counts, pwaf_rule_hit *hits,
+                             uint32_t hits_cap, uint32_t *n_hits, uint64_t *rule_hits /* n_rules, nullable */);
+int pwaf_evaluate_device_hits(pwaf_engine *, const pwaf_batch *in, pwaf_verdict *out, pwaf_counts *counts, uint32_t *match_idx,
+                              uint32_t *n_matches, pwaf_rule_hit *hits, uint32_t hits_cap, uint32_t *n_hits, uint64_t *rule_hits,
+                              void *stream);
 
 /* ---- measurement ------------------------------------------------------------------------- */
 typedef struct pwaf_kernel_time {

@@ -27,6 +27,7 @@ LIST_STRING, LIST_INT, LIST_IP = 0, 1, 2
 OPT_NO_UA_GATE, OPT_NO_CAPTCHA_BYPASS, OPT_NO_PREFILTER, OPT_STRICT, OPT_FILTER_STRIDE2, OPT_LENIENT, OPT_NO_RESIDUAL, OPT_GLOBAL_VERDICT_TABLES, OPT_NO_CONFIRM, OPT_NO_RESIDUAL_JIT = 1, 2, 4, 8, 16, 32, 64, 128, 512, 1024
 OPT_DENSE_VERDICT, OPT_TINY_VERDICT_SLOTS, OPT_NO_DIR_SUMMARY, OPT_SPARSE_VERDICT, OPT_EAGER_CMP, OPT_NO_DENSE_SWITCH = 2048, 4096, 8192, 16384, 32768, 65536
 OPT_GEO_ANSWERS = 256  # the engine also answers each request's GeoIP record (pwaf_geoip_lookup, pwaf_evaluate_*_geo)
+OPT_RULE_HITS = 131072  # the engine can report every rule that matches a request (pwaf_evaluate_*_hits); keeps observe-only rules
 W_PARTIAL = 1
 MEM_HOST, MEM_DEVICE = 0, 1
 FLAG_CAPTCHA_VERIFIED = 1
@@ -158,6 +159,12 @@ class Geo(C.Structure):
     """pwaf_geo: one GeoIP answer (PWAF_OPT_GEO_ANSWERS) — the record the rules saw as client.asn / client.country."""
 
     _fields_ = [("asn", C.c_uint32), ("country", C.c_uint8 * 2), ("reserved", C.c_uint16)]
+
+
+class RuleHit(C.Structure):
+    """pwaf_rule_hit: rule `rule_idx` matches the requests 64 * group + r for every set bit r of mask (PWAF_OPT_RULE_HITS)."""
+
+    _fields_ = [("rule_idx", C.c_uint32), ("group", C.c_uint32), ("mask", C.c_uint64)]
 
 
 class Completion(C.Structure):

@@ -25,6 +25,21 @@ assert GEOIP_DTYPE.itemsize == 24 and VERDICT_DTYPE.itemsize == 8
 # pwaf_geo: one GeoIP answer (engines created with OPT_GEO_ANSWERS)
 GEO_DTYPE = np.dtype([("asn", "<u4"), ("country", "S2"), ("reserved", "<u2")])
 assert GEO_DTYPE.itemsize == 8
+# pwaf_rule_hit (OPT_RULE_HITS): rule `rule_idx` matches the requests 64 * group + r for every set bit r of mask
+RULE_HIT_DTYPE = np.dtype([("rule_idx", "<u4"), ("group", "<u4"), ("mask", "<u8")])
+assert RULE_HIT_DTYPE.itemsize == 16
+
+
+def hits_to_matrix(hits, n: int, n_rules: int) -> np.ndarray:
+    """A rule-hit list (RULE_HIT_DTYPE) -> bool[n_rules, n]: M[k, i] = rule k matches request i. For tests and small batches."""
+    m = np.zeros((n_rules, n), dtype=bool)
+    if len(hits):
+        bits = (hits["mask"][:, None] >> np.arange(64, dtype=np.uint64)[None, :]) & np.uint64(1)
+        k, r = np.nonzero(bits)
+        rule, req = hits["rule_idx"][k].astype(np.int64), hits["group"][k].astype(np.int64) * 64 + r
+        assert (rule < n_rules).all() and (req < n).all(), "a hit names a rule or a request beyond the batch"
+        m[rule, req] = True
+    return m
 
 
 def _b(x) -> bytes:

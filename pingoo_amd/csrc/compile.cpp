@@ -1057,6 +1057,11 @@ int compile_program(const CompileInput &in, std::unique_ptr<Program> &out, pwaf_
         return PWAF_E_INVALID_ARG;
     }
     P.lds_hot_budget = lds_budget;
+    if ((P.flags & PWAF_OPT_RULE_HITS) && (P.flags & (PWAF_OPT_SPARSE_VERDICT | PWAF_OPT_DENSE_VERDICT))) {
+        // (those A-B variants run verdict_kernel, which reports nothing but the deciding rule)
+        set_err(err, PWAF_E_INVALID_ARG, 0xFFFFFFFFu, "PWAF_OPT_RULE_HITS cannot be combined with PWAF_OPT_SPARSE_VERDICT or PWAF_OPT_DENSE_VERDICT: only the entry-list verdict kernel reports rule hits");
+        return PWAF_E_INVALID_ARG;
+    }
     if (max_table_bytes < 1024) {
         set_err(err, PWAF_E_INVALID_ARG, 0xFFFFFFFFu, "max_table_bytes must be at least 1 KiB");
         return PWAF_E_INVALID_ARG;
@@ -1239,7 +1244,9 @@ int compile_program(const CompileInput &in, std::unique_ptr<Program> &out, pwaf_
                 }
             }
         }
-        if (eff_u == PWAF_ACTION_ALLOW && eff_v == PWAF_ACTION_ALLOW) continue;  // no action can ever take effect
+        // no action can ever take effect: the rule decides nothing. PWAF_OPT_RULE_HITS keeps it, with effects {ALLOW, ALLOW} — an observe-only
+        // rule, matched and reported (the verdict kernel's action mask is 0 for it: it never fires)
+        if (eff_u == PWAF_ACTION_ALLOW && eff_v == PWAF_ACTION_ALLOW && !(P.flags & PWAF_OPT_RULE_HITS)) continue;
         if (t_root == 0) continue;                                                 // can never match
         routs.push_back({t_root, (uint32_t)k, eff_u, eff_v});
     }

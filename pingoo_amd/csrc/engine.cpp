@@ -231,6 +231,7 @@ struct Scratch {
     uint32_t arg_next = 0;
     std::vector<DevBuf> stage_field_data, stage_field_off;  // n_fields each
     DevBuf stage_ip, stage_v6, stage_port, stage_flags, stage_asn, stage_country, stage_out, stage_counts;
+    DevBuf stage_hits, stage_hit_counts;  // a host batch's rule hits on their way back (PWAF_OPT_RULE_HITS): the list; {n_hits, pad, rule_hits[n_rules]}
     DevBuf stage_geo;  // the GeoIP answers of a large host batch / a host pwaf_geoip_lookup on their way back (PWAF_OPT_GEO_ANSWERS)
     // A SMALL host batch (the micro-batcher's, pwaf_evaluate_one's) travels as ONE block: every column packed into page-locked memory,
     // one asynchronous copy in, one out (pwaf_evaluate_batch). pin_status: the status words on their way back (never a pageable target:
@@ -264,7 +265,7 @@ struct Scratch {
     }
     void release() {
         for (DevBuf *b : {&status, &ipres, &rec, &res_words, &err_sink, &pool, &verdict_spill, &zero_block, &gate_lists, &attr, &chunk_bits, &cand_cnt, &need, &pairs, &zero_off, &args, &stage_ip, &stage_v6, &stage_port, &stage_flags,
-                          &stage_asn, &stage_country, &stage_out, &stage_counts, &stage_geo})
+                          &stage_asn, &stage_country, &stage_out, &stage_counts, &stage_geo, &stage_hits, &stage_hit_counts})
             b->release();
         for (PinBuf &b : arg_slot) b.release();
         for (hipEvent_t ev : arg_ev)
@@ -676,6 +677,21 @@ void set_georec_args(const pwaf_engine *e, GeoRecArgs &g) {
 int need_geo_answers(const pwaf_engine *e, const char *fn) {
     if (e->geo_answers) return PWAF_OK;
     return fail(PWAF_E_UNSUPPORTED, std::string(fn) + ": the engine was not created with PWAF_OPT_GEO_ANSWERS");
+}
+
+// PWAF_OPT_RULE_HITS: where a call's rule hits go (include/pwaf.h: pwaf_evaluate_*_hits). All null = nothing asked for.
+struct HitOut {
+    pwaf_rule_hit *hits = nullptr;
+    uint32_t cap = 0;
+    uint32_t *n_hits = nullptr;
+    uint64_t *rule_hits = nullptr;
+    bool any() const { return hits || n_hits || rule_hits; }
+};
+int check_hit_args(const pwaf_engine *e, const char *fn, const HitOut &h) {
+    if (!h.any()) return PWAF_OK;
+    if (!(e->prog.p->flags & PWAF_OPT_RULE_HITS)) return fail(PWAF_E_UNSUPPORTED, std::string(fn) + ": the engine was not created with PWAF_OPT_RULE_HITS");
+    if ((h.hits == nullptr) != (h.n_hits == nullptr)) return fail(PWAF_E_INVALID_ARG, std::string(fn) + ": hits and n_hits must be given together");
+    return PWAF_OK;
 }
 
 // Decides which passes are list-driven and uploads what that needs: a pass behind a bigram prefilter walks the filter's candidate
@@ -1761,13 +1777,19 @@ struct BatchRun {
 // BatchRun's destructor: the descriptor slot's event is recorded whichever way the batch leaves (ArgSlotMark).
 int run_pipeline(pwaf_engine *e, Scratch &S, const pwaf_batch &db /* device pointers */, pwaf_verdict *d_out, pwaf_counts *d_counts, uint32_t *d_match_idx,
                  uint32_t *d_n_matches, hipStream_t stream, bool totals_known = false, const std::vector<uint32_t> *col_begin = nullptr, bool sync_status = false,
-                 pwaf_geo *d_geo = nullptr) {
+                 pwaf_geo *d_geo = nullptr, const HitOut *d_hits = nullptr) {
     if (db.n == 0) return PWAF_OK;
     BatchRun b(e, S, db, stream, col_begin);
     b.d_geo = d_geo;
     int rc;
     if ((rc = b.reserve_scratch(sync_status)) || (rc = b.resolve_columns(totals_known))) return rc;
     if ((rc = b.fill_verdict_args(d_out, d_counts, d_match_idx, d_n_matches)) || (rc = b.zero_head_records())) return rc;
+    if (d_hits && d_hits->any()) {  // (the verdict kernel's rule-hit variant: launch_verdict)
+        b.v.hits = d_hits->hits;
+        b.v.hits_cap = d_hits->cap;
+        b.v.n_hits = d_hits->n_hits;
+        b.v.rule_hits = (unsigned long long *)d_hits->rule_hits;
+    }
     b.pick_list_shapes();
     if ((rc = b.attr_at_start()) || (rc = b.launch_plain_scans())) return rc;
     // every descriptor of the batch: built, checked against the launch plan, uploaded once
@@ -1807,16 +1829,20 @@ int device_error(const char *call, hipError_t he) { return fail(PWAF_E_DEVICE, s
 // drained before the call returns: what was enqueued may still read the caller's buffers.
 template <class After>
 int run_with_retry(pwaf_engine *e, Scratch &S, const pwaf_batch &db, pwaf_verdict *d_out, pwaf_counts *d_counts, bool known, const std::vector<uint32_t> *begins, bool counts_zero,
-                   After &&after, pwaf_geo *d_geo = nullptr) {
+                   After &&after, pwaf_geo *d_geo = nullptr, const HitOut *d_hits = nullptr) {
     const hipStream_t s = S.stream;
     int r = S.pin_status.reserve(16);
     volatile uint32_t *const st = (volatile uint32_t *)S.pin_status.p;
     for (int attempt = 0;; attempt++) {
         hipError_t he = hipSuccess;
         if (!r && d_counts && !(counts_zero && attempt == 0) && (he = hipMemsetAsync(d_counts, 0, sizeof *d_counts, s)) != hipSuccess) r = device_error("hipMemsetAsync", he);
+        // the rule hits are overwritten like the counters: zeroed before EVERY attempt, so that a batch run again is not counted twice
+        if (!r && d_hits && d_hits->n_hits && (he = hipMemsetAsync(d_hits->n_hits, 0, 4, s)) != hipSuccess) r = device_error("hipMemsetAsync", he);
+        if (!r && d_hits && d_hits->rule_hits && e->prog.p->n_user_rules && (he = hipMemsetAsync(d_hits->rule_hits, 0, (size_t)e->prog.p->n_user_rules * 8, s)) != hipSuccess)
+            r = device_error("hipMemsetAsync", he);
         if (!r) {
             S.retry = attempt > 0;
-            r = run_pipeline(e, S, db, d_out, d_counts, nullptr, nullptr, s, known, begins, true, d_geo);
+            r = run_pipeline(e, S, db, d_out, d_counts, nullptr, nullptr, s, known, begins, true, d_geo, d_hits);
             S.retry = false;
         }
         if (!r) {
@@ -2522,7 +2548,8 @@ int pwaf_program_confirm_field(const pwaf_program *p, uint32_t group, const uint
 
 }  // extern "C"
 namespace {
-int evaluate_device_impl(pwaf_engine *e, const pwaf_batch *in, pwaf_verdict *out, pwaf_counts *counts, uint32_t *match_idx, uint32_t *n_matches, pwaf_geo *geo, void *stream) {
+int evaluate_device_impl(pwaf_engine *e, const pwaf_batch *in, pwaf_verdict *out, pwaf_counts *counts, uint32_t *match_idx, uint32_t *n_matches, pwaf_geo *geo, void *stream,
+                         const HitOut *hits = nullptr) {
     int rc = validate_batch_header(in);
     if (rc) return rc;
     if (in->memory != PWAF_MEM_DEVICE) return fail(PWAF_E_INVALID_ARG, "pwaf_evaluate_device needs a DEVICE batch");
@@ -2535,17 +2562,28 @@ int evaluate_device_impl(pwaf_engine *e, const pwaf_batch *in, pwaf_verdict *out
     Scratch &S = acquire_context(e, false, (hipStream_t)stream, lock, must_wait);
     if ((rc = S.ensure(false))) return rc;
     if (must_wait) HIP_TRY(hipStreamWaitEvent((hipStream_t)stream, S.done, 0));
-    rc = run_pipeline(e, S, *in, out, counts, match_idx, n_matches, (hipStream_t)stream, false, nullptr, false, geo);
+    rc = run_pipeline(e, S, *in, out, counts, match_idx, n_matches, (hipStream_t)stream, false, nullptr, false, geo, hits);
     const hipError_t he = mark_context_used(S, (hipStream_t)stream, false);
     return he != hipSuccess ? device_error("hipEventRecord", he) : rc;
 }
 
 // `geo` (nullable; PWAF_OPT_GEO_ANSWERS engines only): the GeoIP record of every request, where `out` lives
-int evaluate_batch_impl(pwaf_engine *e, const pwaf_batch *in, pwaf_verdict *out, pwaf_counts *counts, pwaf_geo *geo) {
+// `hits` (nullable; PWAF_OPT_RULE_HITS engines only): the call's rule hits, where `out` lives; overwritten
+int evaluate_batch_impl(pwaf_engine *e, const pwaf_batch *in, pwaf_verdict *out, pwaf_counts *counts, pwaf_geo *geo, const HitOut *hits = nullptr) {
     int rc = validate_batch_header(in);
     if (rc) return rc;
+    if (hits && !hits->any()) hits = nullptr;
+    const size_t rule_hit_bytes = (size_t)e->prog.p->n_user_rules * 8;
     if (in->n == 0) {
         if (counts && in->memory == PWAF_MEM_HOST) memset(counts, 0, sizeof *counts);
+        if (hits && in->memory == PWAF_MEM_HOST) {
+            if (hits->n_hits) *hits->n_hits = 0;
+            if (hits->rule_hits) memset(hits->rule_hits, 0, rule_hit_bytes);
+        } else if (hits) {
+            HIP_TRY(hipSetDevice(e->device));
+            if (hits->n_hits) HIP_TRY(hipMemset(hits->n_hits, 0, 4));
+            if (hits->rule_hits && rule_hit_bytes) HIP_TRY(hipMemset(hits->rule_hits, 0, rule_hit_bytes));
+        }
         return PWAF_OK;
     }
     HIP_TRY(hipSetDevice(e->device));
@@ -2556,7 +2594,36 @@ int evaluate_batch_impl(pwaf_engine *e, const pwaf_batch *in, pwaf_verdict *out,
     if ((rc = S.ensure(true))) return rc;
     hipStream_t s = S.stream;
     if (must_wait) HIP_TRY(hipStreamWaitEvent(s, S.done, 0));
-    if (in->memory == PWAF_MEM_DEVICE) return run_with_retry(e, S, *in, out, counts, false, nullptr, false, [] { return PWAF_OK; }, geo);
+    if (in->memory == PWAF_MEM_DEVICE) return run_with_retry(e, S, *in, out, counts, false, nullptr, false, [] { return PWAF_OK; }, geo, hits);
+    // a HOST batch's rule hits: produced into staging buffers of the context ({n_hits, pad, rule_hits[]}; the list), fetched once the batch is
+    // done and the number of entries is known — only the entries the batch wrote travel, the rest of the caller's list is left alone
+    HitOut dh;
+    if (hits) {
+        if ((rc = S.stage_hit_counts.reserve(8 + rule_hit_bytes)) || (rc = S.stage_hits.reserve(std::max<size_t>(16, (size_t)hits->cap * sizeof(pwaf_rule_hit))))) return rc;
+        if (hits->n_hits) {
+            dh.hits = (pwaf_rule_hit *)S.stage_hits.p;
+            dh.cap = hits->cap;
+            dh.n_hits = (uint32_t *)S.stage_hit_counts.p;
+        }
+        if (hits->rule_hits) dh.rule_hits = (uint64_t *)((char *)S.stage_hit_counts.p + 8);
+    }
+    const HitOut *const d_hits = hits ? &dh : nullptr;
+    auto fetch_hits = [&](int code) -> int {
+        if (code || !hits) return code;
+        std::vector<uint64_t> back(1 + rule_hit_bytes / 8);
+        HIP_TRY(hipMemcpyAsync(back.data(), S.stage_hit_counts.p, back.size() * 8, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        if (hits->rule_hits && rule_hit_bytes) memcpy(hits->rule_hits, back.data() + 1, rule_hit_bytes);
+        if (hits->n_hits) {
+            const uint32_t total = (uint32_t)back[0], got = std::min(total, hits->cap);
+            *hits->n_hits = total;
+            if (got) {
+                HIP_TRY(hipMemcpyAsync(hits->hits, S.stage_hits.p, (size_t)got * sizeof(pwaf_rule_hit), hipMemcpyDeviceToHost, s));
+                HIP_TRY(hipStreamSynchronize(s));
+            }
+        }
+        return PWAF_OK;
+    };
     // HOST batch: stage, validate what a device cannot report (while the copies are in flight, when the caller's memory is page-locked:
     // pwaf_host_alloc / pwaf_host_register), run, copy back
     const uint32_t n = in->n;
@@ -2648,8 +2715,8 @@ int evaluate_batch_impl(pwaf_engine *e, const pwaf_batch *in, pwaf_verdict *out,
         rc = run_with_retry(e, S, dv.db, d_out, d_counts, true, &col_begin, true, [&]() -> int {
             HIP_TRY(hipMemcpyAsync(S.pin_out.p, d_counts, back, hipMemcpyDeviceToHost, s));
             return PWAF_OK;
-        }, geo ? (pwaf_geo *)((char *)S.packed.p + at_geo) : nullptr);
-        if (rc) return rc;
+        }, geo ? (pwaf_geo *)((char *)S.packed.p + at_geo) : nullptr, d_hits);
+        if ((rc = fetch_hits(rc))) return rc;
         if (geo) memcpy(geo, (const char *)S.pin_out.p + (at_geo - at_counts), (size_t)n * sizeof(pwaf_geo));
         memcpy(out, (const char *)S.pin_out.p + (at_out - at_counts), (size_t)n * sizeof(pwaf_verdict));
         if (counts) memcpy(counts, S.pin_out.p, sizeof(pwaf_counts));
@@ -2690,12 +2757,12 @@ int evaluate_batch_impl(pwaf_engine *e, const pwaf_batch *in, pwaf_verdict *out,
     if ((rc = S.stage_counts.reserve(sizeof(pwaf_counts)))) return bail(rc);
     if (geo && (rc = S.stage_geo.reserve((size_t)n * sizeof(pwaf_geo)))) return bail(rc);
     if ((rc = validate())) return bail(rc);
-    return run_with_retry(e, S, dv.db, (pwaf_verdict *)S.stage_out.p, (pwaf_counts *)S.stage_counts.p, true, &col_begin, false, [&]() -> int {
+    return fetch_hits(run_with_retry(e, S, dv.db, (pwaf_verdict *)S.stage_out.p, (pwaf_counts *)S.stage_counts.p, true, &col_begin, false, [&]() -> int {
         HIP_TRY(hipMemcpyAsync(out, S.stage_out.p, (size_t)n * sizeof(pwaf_verdict), hipMemcpyDeviceToHost, s));
         if (counts) HIP_TRY(hipMemcpyAsync(counts, S.stage_counts.p, sizeof(pwaf_counts), hipMemcpyDeviceToHost, s));
         if (geo) HIP_TRY(hipMemcpyAsync(geo, S.stage_geo.p, (size_t)n * sizeof(pwaf_geo), hipMemcpyDeviceToHost, s));
         return PWAF_OK;
-    }, geo ? (pwaf_geo *)S.stage_geo.p : nullptr);
+    }, geo ? (pwaf_geo *)S.stage_geo.p : nullptr, d_hits));
 }
 }  // namespace
 
@@ -2714,6 +2781,23 @@ int pwaf_evaluate_device_geo(pwaf_engine *e, const pwaf_batch *in, pwaf_verdict 
 int pwaf_evaluate_batch(pwaf_engine *e, const pwaf_batch *in, pwaf_verdict *out, pwaf_counts *counts) {
     if (!e || !out) return fail(PWAF_E_INVALID_ARG, "NULL argument");
     return evaluate_batch_impl(e, in, out, counts, nullptr);
+}
+// The plain entry points with the rule-hit outputs (PWAF_OPT_RULE_HITS; include/pwaf.h). All of them NULL: exactly the plain call.
+int pwaf_evaluate_batch_hits(pwaf_engine *e, const pwaf_batch *in, pwaf_verdict *out, pwaf_counts *counts, pwaf_rule_hit *hits, uint32_t hits_cap, uint32_t *n_hits,
+                             uint64_t *rule_hits) {
+    if (!e || !out) return fail(PWAF_E_INVALID_ARG, "NULL argument");
+    HitOut h;
+    h.hits = hits; h.cap = hits ? hits_cap : 0u; h.n_hits = n_hits; h.rule_hits = rule_hits;
+    if (int rc = check_hit_args(e, "pwaf_evaluate_batch_hits", h)) return rc;
+    return evaluate_batch_impl(e, in, out, counts, nullptr, &h);
+}
+int pwaf_evaluate_device_hits(pwaf_engine *e, const pwaf_batch *in, pwaf_verdict *out, pwaf_counts *counts, uint32_t *match_idx, uint32_t *n_matches, pwaf_rule_hit *hits,
+                              uint32_t hits_cap, uint32_t *n_hits, uint64_t *rule_hits, void *stream) {
+    if (!e || !out) return fail(PWAF_E_INVALID_ARG, "NULL argument");
+    HitOut h;
+    h.hits = hits; h.cap = hits ? hits_cap : 0u; h.n_hits = n_hits; h.rule_hits = rule_hits;
+    if (int rc = check_hit_args(e, "pwaf_evaluate_device_hits", h)) return rc;
+    return evaluate_device_impl(e, in, out, counts, match_idx, n_matches, nullptr, stream, &h);
 }
 int pwaf_evaluate_batch_geo(pwaf_engine *e, const pwaf_batch *in, pwaf_verdict *out, pwaf_counts *counts, pwaf_geo *geo) {
     if (!e || !out) return fail(PWAF_E_INVALID_ARG, "NULL argument");

@@ -453,6 +453,13 @@ struct VerdictArgs {
     unsigned long long *counts;  // 4, accumulated (nullable)
     uint32_t *match_idx;         // nullable
     uint32_t *n_matches;         // nullable
+    // PWAF_OPT_RULE_HITS (verdict2_kernel<.., HITS = true>; all nullable, launch_verdict picks the HITS variant when one is set): every
+    // (rule, group) whose match word is non-zero. n_hits counts ALL entries, only slots below hits_cap are written; rule_hits[k] += the
+    // popcount of rule k's words. Both accumulate.
+    pwaf_rule_hit *hits;
+    uint32_t hits_cap;
+    uint32_t *n_hits;
+    unsigned long long *rule_hits;  // [the caller's n_rules]
 };
 
 // Launchers (hipStream_t passed as void*). Return hipError_t as int.

@@ -2657,8 +2657,15 @@ __device__ __forceinline__ void park96(uint32_t &c, uint32_t &lo, uint32_t &hi, 
 }
 #pragma clang diagnostic pop
 
-template <bool LT, int BR>
-__global__ __launch_bounds__(768, BR == 1 ? 6 : 1) void verdict2_kernel(VerdictArgs a) {
+// HITS (PWAF_OPT_RULE_HITS, only when a hit output was asked for): every candidate's match word is reported, not only the first firing one.
+// The candidate loop then runs to the end of the list, a lane keeps acc_or beside fire, and per chunk of 64 candidates the non-zero words
+// of caller rules are queued for a.hits (the wave's queue leaves up to 64 entries at a time: one atomic on n_hits per flush). Requests answered by a gate are
+// masked out: the two gate pseudo rules are device rules 0 and 1 (compile.cpp prepends them), the candidate list ascends, so they stand
+// in the FIRST chunk and a gated request is decided (both gates always take effect) before that chunk's words are appended.
+// (HITS, up to 64 passes: 5 waves per SIMD. The plain kernel fills its 80 registers at 6; the queue's three more put one into scratch there.
+// A CU then holds ONE 12-wave workgroup at a time; the persistent grid is unchanged, its workgroups take turns.)
+template <bool LT, int BR, bool HITS>
+__global__ __launch_bounds__(768, BR == 1 ? (HITS ? 5 : 6) : 1) void verdict2_kernel(VerdictArgs a) {
     extern __shared__ __align__(16) unsigned char lds[];
     const uint32_t tid = threadIdx.x, wave = wave_index(), lane = tid & 63, n_waves = blockDim.x >> 6;
 #ifdef PWAF_PROFILING
@@ -2706,6 +2713,27 @@ __global__ __launch_bounds__(768, BR == 1 ? 6 : 1) void verdict2_kernel(VerdictA
     const unsigned long long mybit = 1ull << lane;
     const unsigned long long lt_mask = mybit - 1;
     unsigned long long cnt_block = 0, cnt_captcha = 0, cnt_bypass = 0, cnt_allow = 0;
+    // (HITS) the wave's entries wait in three registers, lane k = entry k, and leave up to 64 at a time: ONE atomic on n_hits and one coalesced
+    // store per flush. (One returning atomic per wave and chunk of candidates was measured at 1.5 ms of a 1.78 ms kernel for 10M requests x
+    // 1024 rules: ~7 entries per group, a few hundred thousand same-address atomics that the L2 performs one after the other.) An entry is
+    // {rule | k << 16, mask}: its group is the k-th of this wave counted from q_g0, the group of the queue's first entry.
+    uint32_t q_rk = 0, q_lo = 0, q_hi = 0, q_n = 0, q_g0 = 0, q_k = 0;
+    const uint32_t q_stride = gridDim.x * n_waves;
+    auto q_flush = [&]() {
+        if (q_n == 0) return;
+        uint32_t slot0 = 0;
+        if (lane == 0) slot0 = atomicAdd(a.n_hits, q_n);
+        slot0 = __builtin_amdgcn_readfirstlane(slot0);
+        const uint32_t at = slot0 + lane;
+        if (lane < q_n && at < a.hits_cap) {  // (never at or beyond hits + hits_cap, whatever the counter held)
+            pwaf_rule_hit h;
+            h.rule_idx = q_rk & 0xFFFFu;
+            h.group = q_g0 + (q_rk >> 16) * q_stride;
+            h.mask = ((unsigned long long)q_hi << 32) | q_lo;
+            a.hits[at] = h;
+        }
+        q_n = 0;
+    };
     const uint32_t h_always = lane < rulew ? a.always_rules[lane] : 0u;
     const bool true_triggers = a.trig_off[1] != a.trig_off[0];  // rules whose chosen positive literal is the constant TRUE (`expression: None`)
 
@@ -3015,8 +3043,10 @@ __global__ __launch_bounds__(768, BR == 1 ? 6 : 1) void verdict2_kernel(VerdictA
         uint32_t n_exact = 0;
         bool undecided = valid;
         uint32_t my_action = PWAF_ACTION_ALLOW, my_rule = PWAF_RULE_NONE;
-        for (uint32_t base = 0; base < n_cand && pending != 0 && !(dbg_skip & 32u); base += 64) {
+        unsigned long long gated = 0;  // (HITS) requests answered by a gate pseudo rule: known after the first chunk
+        for (uint32_t base = 0; base < n_cand && (HITS || pending != 0) && !(dbg_skip & 32u); base += 64) {
             unsigned long long fire = 0, eff_mask = 0;
+            unsigned long long match = 0;  // (HITS) the rule's match word whatever its actions
             uint32_t lit_off = 0, lit_cnt = 0;
             bool lazy_seen = false;
             if (base + lane < n_cand) {
@@ -3059,11 +3089,13 @@ __global__ __launch_bounds__(768, BR == 1 ? 6 : 1) void verdict2_kernel(VerdictA
                 }
                 eff_mask = (eff_u ? ~verified_mask : 0ull) | (eff_v ? verified_mask : 0ull);
                 fire = acc_or & eff_mask;
+                if (HITS) match = acc_or & valid_mask;
             }
             // Rules with lazy comparison atoms whose OTHER literals hold for somebody (rare): the rule again, exactly, one request per lane —
             // an eager literal's bit from its column word, a lazy one from the request's own value (fetched with the group's inputs)
-            if (dbg_skip & 512u) n_exact += (uint32_t)__builtin_popcountll(__ballot(lazy_seen && fire != 0));
-            for (unsigned long long need = (dbg_skip & 1024u) ? 0ull : __ballot(lazy_seen && fire != 0); need != 0; need &= need - 1) {
+            // (HITS: also for a rule whose match word is non-zero while no action of its takes effect for those requests)
+            if (dbg_skip & 512u) n_exact += (uint32_t)__builtin_popcountll(__ballot(lazy_seen && (HITS ? match : fire) != 0));
+            for (unsigned long long need = (dbg_skip & 1024u) ? 0ull : __ballot(lazy_seen && (HITS ? match : fire) != 0); need != 0; need &= need - 1) {
                 const int j = __builtin_ctzll(need);
                 const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)lit_off, j), cn = (uint32_t)__builtin_amdgcn_readlane((int)lit_cnt, j);
                 const unsigned long long em = ((unsigned long long)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(eff_mask >> 32), j) << 32) |
@@ -3092,11 +3124,19 @@ __global__ __launch_bounds__(768, BR == 1 ? 6 : 1) void verdict2_kernel(VerdictA
                         r_and = true;
                     }
                 }
-                const unsigned long long exact = __ballot(r_or && valid) & em;
-                uint32_t f_lo = (uint32_t)fire, f_hi = (uint32_t)(fire >> 32);
-                park64(f_lo, f_hi, exact, (uint32_t)j);
-                fire = ((unsigned long long)f_hi << 32) | f_lo;
+                const unsigned long long exact_all = __ballot(r_or && valid);
+                if (HITS) {  // the match word is the exact result WITHOUT the action mask (fire follows from it below)
+                    uint32_t m_lo = (uint32_t)match, m_hi = (uint32_t)(match >> 32);
+                    park64(m_lo, m_hi, exact_all, (uint32_t)j);
+                    match = ((unsigned long long)m_hi << 32) | m_lo;
+                } else {
+                    uint32_t f_lo = (uint32_t)fire, f_hi = (uint32_t)(fire >> 32);
+                    park64(f_lo, f_hi, exact_all & em, (uint32_t)j);
+                    fire = ((unsigned long long)f_hi << 32) | f_lo;
+                }
             }
+            // (HITS: one word less to keep through the loop above; the same value on every valid request, and `pending` holds no other)
+            if (HITS) fire = match & eff_mask;
             unsigned long long firing = __ballot(fire != 0);
             uint32_t first = kNone;
             while (firing != 0 && pending != 0) {
@@ -3124,6 +3164,34 @@ __global__ __launch_bounds__(768, BR == 1 ? 6 : 1) void verdict2_kernel(VerdictA
                     my_rule = dr.public_idx;
                 }
                 my_action = (verified_mask & mybit) ? eff_v : eff_u;
+            }
+            if (HITS) {
+                if (base == 0) gated = __ballot(valid && !undecided && my_rule >= 0xFFFFFFF0u);
+                // (a gate pseudo rule's own word is a subset of `gated`: nothing of it is left, so every non-zero word is a caller rule's)
+                const unsigned long long word = match & ~gated;
+                unsigned long long has = __ballot(word != 0);
+                if (has != 0) {
+                    uint32_t pub = 0;  // the caller's index of this lane's rule (< 65520: engine.cpp)
+                    if (word != 0) {
+                        const uint32_t c = cand[base + lane];
+                        pub = LT ? (uint32_t)l_pub[c] : a.rules[c].public_idx;
+                        if (a.rule_hits != nullptr) atomicAdd(&a.rule_hits[pub], (unsigned long long)__builtin_popcountll(word));
+                    }
+                    if (a.n_hits != nullptr) {
+                        if (q_n + (uint32_t)__builtin_popcountll(has) > 64u) q_flush();
+                        if (q_n == 0) {
+                            q_g0 = g;
+                            q_k = 0;
+                        }
+                        for (; has != 0; has &= has - 1) {  // one entry per lane with a word, into lane q_n of the queue registers
+                            const int j = __builtin_ctzll(has);
+                            const unsigned long long wj = ((unsigned long long)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(word >> 32), j) << 32) |
+                                                          (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)word, j);
+                            park96(q_rk, q_lo, q_hi, (uint32_t)__builtin_amdgcn_readlane((int)pub, j) | (q_k << 16), wj, q_n);
+                            q_n++;
+                        }
+                    }
+                }
             }
         }
         if (dbg_skip & 512u) my_rule = n_exact;  // profiling aid: rules evaluated exactly for their lazy comparison atoms
@@ -3163,8 +3231,10 @@ __global__ __launch_bounds__(768, BR == 1 ? 6 : 1) void verdict2_kernel(VerdictA
             if (lane == 0) slot[0] = 1;
         }
         __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+        if (HITS && q_n != 0 && ++q_k == 0x10000u) q_flush();  // (an entry's group index relative to the queue's first has 16 bits)
         cur = nxt;
     }
+    if (HITS && a.n_hits != nullptr) q_flush();
     __syncthreads();
     unsigned long long *tally = reinterpret_cast<unsigned long long *>(lds);
     if (lane == 0) {
@@ -3841,9 +3911,14 @@ int launch_verdict(const VerdictArgs &a, void *stream) {
                                  {reinterpret_cast<const void *>(verdict_kernel<true, kBRmax, false>), reinterpret_cast<const void *>(verdict_kernel<true, 1, false>)}},
                                 {{reinterpret_cast<const void *>(verdict_kernel<false, kBRmax, true>), reinterpret_cast<const void *>(verdict_kernel<false, 1, true>)},
                                  {reinterpret_cast<const void *>(verdict_kernel<true, kBRmax, true>), reinterpret_cast<const void *>(verdict_kernel<true, 1, true>)}}};
-    const void *fns2[2][2] = {{reinterpret_cast<const void *>(verdict2_kernel<false, kBRmax>), reinterpret_cast<const void *>(verdict2_kernel<false, 1>)},
-                              {reinterpret_cast<const void *>(verdict2_kernel<true, kBRmax>), reinterpret_cast<const void *>(verdict2_kernel<true, 1>)}};
-    const void *fn = sh.sparse == 2 ? fns2[sh.lds_tables ? 1 : 0][variant] : fns[sh.sparse ? 1 : 0][sh.lds_tables ? 1 : 0][variant];
+    const void *fns2[2][2][2] = {{{reinterpret_cast<const void *>(verdict2_kernel<false, kBRmax, false>), reinterpret_cast<const void *>(verdict2_kernel<false, 1, false>)},
+                                  {reinterpret_cast<const void *>(verdict2_kernel<true, kBRmax, false>), reinterpret_cast<const void *>(verdict2_kernel<true, 1, false>)}},
+                                 {{reinterpret_cast<const void *>(verdict2_kernel<false, kBRmax, true>), reinterpret_cast<const void *>(verdict2_kernel<false, 1, true>)},
+                                  {reinterpret_cast<const void *>(verdict2_kernel<true, kBRmax, true>), reinterpret_cast<const void *>(verdict2_kernel<true, 1, true>)}}};
+    // the rule-hit variants only when a hit output was asked for (PWAF_OPT_RULE_HITS engines; the entry-list kernel only: engine_create)
+    const bool want_hits = a.n_hits != nullptr || a.rule_hits != nullptr;
+    if (want_hits && (sh.sparse != 2 || (a.hits == nullptr && a.n_hits != nullptr && a.hits_cap != 0))) return (int)hipErrorInvalidValue;
+    const void *fn = sh.sparse == 2 ? fns2[want_hits ? 1 : 0][sh.lds_tables ? 1 : 0][variant] : fns[sh.sparse ? 1 : 0][sh.lds_tables ? 1 : 0][variant];
     uint32_t blocks = (a.n_groups + sh.waves - 1) / sh.waves;
 #ifdef PWAF_PROFILING
     static const uint32_t forced_cap = getenv("PWAF_VERDICT_BLOCKS") ? (uint32_t)atoi(getenv("PWAF_VERDICT_BLOCKS")) : 0u;
@@ -3874,8 +3949,10 @@ int configure_kernels(int device) {
                          reinterpret_cast<const void *>(verdict_kernel<true, 1, false>), reinterpret_cast<const void *>(verdict_kernel<false, 1, false>),
                          reinterpret_cast<const void *>(verdict_kernel<true, (kMaxPasses + 1 + 63) / 64, true>), reinterpret_cast<const void *>(verdict_kernel<false, (kMaxPasses + 1 + 63) / 64, true>),
                          reinterpret_cast<const void *>(verdict_kernel<true, 1, true>), reinterpret_cast<const void *>(verdict_kernel<false, 1, true>),
-                         reinterpret_cast<const void *>(verdict2_kernel<true, (kMaxPasses + 1 + 63) / 64>), reinterpret_cast<const void *>(verdict2_kernel<false, (kMaxPasses + 1 + 63) / 64>),
-                         reinterpret_cast<const void *>(verdict2_kernel<true, 1>), reinterpret_cast<const void *>(verdict2_kernel<false, 1>),
+                         reinterpret_cast<const void *>(verdict2_kernel<true, (kMaxPasses + 1 + 63) / 64, false>), reinterpret_cast<const void *>(verdict2_kernel<false, (kMaxPasses + 1 + 63) / 64, false>),
+                         reinterpret_cast<const void *>(verdict2_kernel<true, 1, false>), reinterpret_cast<const void *>(verdict2_kernel<false, 1, false>),
+                         reinterpret_cast<const void *>(verdict2_kernel<true, (kMaxPasses + 1 + 63) / 64, true>), reinterpret_cast<const void *>(verdict2_kernel<false, (kMaxPasses + 1 + 63) / 64, true>),
+                         reinterpret_cast<const void *>(verdict2_kernel<true, 1, true>), reinterpret_cast<const void *>(verdict2_kernel<false, 1, true>),
                          reinterpret_cast<const void *>(filter_kernel<true>), reinterpret_cast<const void *>(filter_kernel<false>),
                          lscan_fn(false), lscan_fn(true)};
     for (const void *fn : fns) {

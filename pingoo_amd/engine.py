@@ -24,7 +24,7 @@ from typing import Dict, Iterable, List, Optional, Sequence, Tuple
 import numpy as np
 
 from . import _abi
-from .batch import GEO_DTYPE, VERDICT_DTYPE, Request, RequestBatch
+from .batch import GEO_DTYPE, RULE_HIT_DTYPE, VERDICT_DTYPE, Request, RequestBatch
 
 _LIB = None
 # PWAF_LIB_VARIANT=prof loads libpwaf_prof.so, the -DPWAF_PROFILING build with the timing-experiment switches (tools/ only: results may
@@ -155,6 +155,8 @@ def lib():
     L.pwaf_geoip_lookup.argtypes = [vp, vp, vp, C.c_uint32, C.c_uint32, vp, vp]
     L.pwaf_evaluate_batch_geo.argtypes = [vp, C.POINTER(_abi.Batch), vp, vp, vp]
     L.pwaf_evaluate_device_geo.argtypes = [vp, C.POINTER(_abi.Batch), vp, vp, vp, vp, vp, vp]
+    L.pwaf_evaluate_batch_hits.argtypes = [vp, C.POINTER(_abi.Batch), vp, vp, vp, C.c_uint32, vp, vp]
+    L.pwaf_evaluate_device_hits.argtypes = [vp, C.POINTER(_abi.Batch), vp, vp, vp, vp, vp, C.c_uint32, vp, vp, vp]
     L.pwaf_evaluate_records_geo.argtypes = [vp, vp, C.c_size_t, vp, C.c_uint32, vp, vp, vp]
     L.pwaf_evaluate_one_geo.argtypes = [vp, C.POINTER(_abi.Request), C.POINTER(_abi.Verdict), C.POINTER(_abi.Geo)]
     L.pwaf_async_create_geo.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(vp)]
@@ -484,6 +486,40 @@ class RuleEngine:
         res += (geo,) if with_geo else ()
         return res if len(res) > 1 else res[0]
 
+    def evaluate_batch_hits_into(self, batch: RequestBatch, hits: Optional[np.ndarray], cap: int = 0, with_rule_hits: bool = True):
+        """pwaf_evaluate_batch_hits as it is (OPT_RULE_HITS engines): `hits` = a caller-owned RULE_HIT_DTYPE array of which at most `cap`
+        entries are written (None: no list) -> (verdicts, counts, n_hits or None, rule_hits or None). n_hits > cap: the list is incomplete."""
+        out = np.zeros(batch.n, dtype=VERDICT_DTYPE)
+        counts = _abi.Counts()
+        n_hits = C.c_uint32(0)
+        if hits is not None:
+            assert hits.dtype == RULE_HIT_DTYPE and hits.flags["C_CONTIGUOUS"] and len(hits) >= cap
+        rule_hits = np.zeros(max(1, len(self.rules)), dtype=np.uint64) if with_rule_hits else None
+        st = batch.as_struct(self.header_names)
+        rc = lib().pwaf_evaluate_batch_hits(self._h, C.byref(st), out.ctypes.data, C.addressof(counts), None if hits is None else max(hits.ctypes.data, 1), cap,
+                                            None if hits is None else C.addressof(n_hits), None if rule_hits is None else rule_hits.ctypes.data)
+        if rc != 0:
+            _raise(rc, lib().pwaf_last_error().decode(errors="replace"))
+        return (out, np.array(list(counts.by_action), dtype=np.uint64), None if hits is None else int(n_hits.value),
+                None if rule_hits is None else rule_hits[:len(self.rules)])
+
+    def evaluate_batch_hits(self, batch: RequestBatch, with_counts: bool = False, cap: Optional[int] = None):
+        """Every rule that matches, not only the deciding one (OPT_RULE_HITS engines): -> (verdicts, hits, rule_hits[, counts]). hits = the
+        RULE_HIT_DTYPE list, one entry per (rule, group of 64 requests) with a non-zero match word, in no particular order
+        (batch.hits_to_matrix turns it into bool[n_rules, n]); rule_hits[k] = the requests rule k matches. Gated requests match nothing.
+        cap: entries to make room for at first; a list that did not fit is fetched again, once, with the size the engine reported."""
+        if cap is None:
+            cap = max(1024, 8 * ((batch.n + 63) // 64))
+        for _ in range(2):
+            hits = np.zeros(max(1, cap), dtype=RULE_HIT_DTYPE)
+            out, counts, n_hits, rule_hits = self.evaluate_batch_hits_into(batch, hits, cap)
+            if n_hits <= cap:
+                break
+            cap = n_hits
+        assert n_hits <= cap
+        res = (out, hits[:n_hits], rule_hits)
+        return res + (counts,) if with_counts else res
+
     def evaluate_records(self, buf: np.ndarray, rec_off: np.ndarray, with_counts: bool = False, with_geo: bool = False):
         """Request records (RequestBatch.to_records, include/pwaf.h pwaf_record_head) in, VERDICT_DTYPE array out: verdict i belongs to the
         record at buf[rec_off[i]] (pwaf_evaluate_records). `buf` may be page-locked (pwaf_host_alloc / _register) or not."""
@@ -517,9 +553,12 @@ class RuleEngine:
         v = verdict_from_record({"action": out.action, "rule_idx": out.rule_idx})
         return (v, (int(geo.asn), bytes(geo.country).decode("latin-1"))) if with_geo else v
 
-    def evaluate_device(self, dbatch: "DeviceBatch", out=None, counts=None, match_idx=None, n_matches=None, stream=None, geo=None):
+    def evaluate_device(self, dbatch: "DeviceBatch", out=None, counts=None, match_idx=None, n_matches=None, stream=None, geo=None, hits=None, n_hits=None,
+                        rule_hits=None, hits_cap=None):
         """Device-resident evaluation on torch's current stream (or `stream`). Tensors stay on the GPU. geo (OPT_GEO_ANSWERS engines): a
-        device tensor of n x 8 bytes that receives the requests' GeoIP records (pwaf_geo)."""
+        device tensor of n x 8 bytes that receives the requests' GeoIP records (pwaf_geo). hits / n_hits / rule_hits (OPT_RULE_HITS engines;
+        not together with geo): device tensors for the rule-hit list (16 bytes per entry, RULE_HIT_DTYPE; hits_cap entries, default: all
+        the tensor holds), its 32-bit entry counter and the n_rules 64-bit per-rule counters — the counters ACCUMULATE: zero them first."""
         import torch
 
         if out is None:
@@ -529,7 +568,16 @@ class RuleEngine:
         st = dbatch.as_struct(self.header_names)
         args = (self._h, C.byref(st), out.data_ptr(), counts.data_ptr() if counts is not None else None,
                 match_idx.data_ptr() if match_idx is not None else None, n_matches.data_ptr() if n_matches is not None else None)
-        if geo is not None:
+        if hits is not None or n_hits is not None or rule_hits is not None:
+            assert geo is None, "the _geo and _hits entry points are separate calls"
+            room = 0 if hits is None else hits.numel() * hits.element_size() // RULE_HIT_DTYPE.itemsize
+            cap = room if hits_cap is None else int(hits_cap)
+            assert hits is None or (hits.is_contiguous() and cap <= room)
+            assert rule_hits is None or (rule_hits.is_contiguous() and rule_hits.numel() * rule_hits.element_size() >= 8 * len(self.rules))
+            # (a list of no entries still needs a non-NULL pointer beside n_hits: a count-only query)
+            rc = lib().pwaf_evaluate_device_hits(*args, None if hits is None else max(hits.data_ptr(), 1), cap, None if n_hits is None else n_hits.data_ptr(),
+                                                 None if rule_hits is None else rule_hits.data_ptr(), C.c_void_p(stream))
+        elif geo is not None:
             assert geo.is_contiguous() and geo.numel() * geo.element_size() >= dbatch.n * GEO_DTYPE.itemsize
             rc = lib().pwaf_evaluate_device_geo(*args, geo.data_ptr(), C.c_void_p(stream))
         else:
