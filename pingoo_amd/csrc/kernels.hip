@@ -2784,6 +2784,11 @@ __global__ __launch_bounds__(768, BR == 1 ? (HITS ? 5 : 6) : 1) void verdict2_ke
         const uint32_t i = g * 64 + lane;
         const bool valid = g < a.n_groups && i < a.n;
         unsigned long long nzp[kBitRegs];
+        // The visited words (the youngest loads in flight: request_bits of the previous turn) are waited for HERE, once. Every use below
+        // sits under a wave-uniform condition, where the compiler waits for ALL outstanding loads again — after the first slot that
+        // means for the record load just issued: one exposed round trip per prefetch slot.
+#pragma unroll
+        for (int r = 0; r < kBitRegs; r++) asm volatile("" ::"v"(bt.w[r]));
 #pragma unroll
         for (int r = 0; r < kBitRegs; r++) nzp[r] = (uint32_t)r * 64 < a.n_passes ? __ballot(bt.w[r] != 0) : 0ull;
 #pragma unroll
@@ -3255,9 +3260,9 @@ __global__ __launch_bounds__(768, BR == 1 ? (HITS ? 5 : 6) : 1) void verdict2_ke
 // attributes: everything about a request that is NOT a string scan — GeoIP record, ip-list membership, country / integer-set
 // membership, length / port / asn comparisons — reduced per 64-request group to a list of (column, 64-request mask) pairs
 // -------------------------------------------------------------------------------------------------
-// The lookups are chains of dependent gathers (DIR-24 / trie levels, membership rows); the kernel needs no LDS and does not depend on
-// the scans, so it runs BESIDE them on the engine's side stream at the lowest wave priority. One wave = one 64-request group; the
-// verdict kernel only copies the group's pairs into its column file.
+// The lookups are chains of dependent gathers (DIR-24 / trie levels, membership rows); the kernel keeps only its small constant tables
+// in LDS (see the last point below) and does not depend on the scans, so it runs BESIDE them on the engine's side stream at the lowest
+// wave priority. One wave = one 64-request group; the verdict kernel only copies the group's pairs into its column file.
 //
 // What keeps it short (round 2: it had become the longest kernel, 2.8 GB fetched for 0.38 GB of input):
 //   * everything that is a function of the GeoIP record — country-table bits, asn-set bits and the asn comparisons — is folded at
@@ -3266,7 +3271,12 @@ __global__ __launch_bounds__(768, BR == 1 ? (HITS ? 5 : 6) : 1) void verdict2_ke
 //   * IPv4: ONE gather into a 2^24 x 4-byte table (DIR-24-8, 64 MiB) yields class | membership-set id << 16; prefixes longer than
 //     /24 and oversized ids escape to an 8-byte side table and continue in the 8-bit trie nodes;
 //   * a group's inputs are requested TWO groups ahead and its DIR-24 / root entries ONE group ahead, so the long-latency loads of the
-//     next groups are in flight while the current group's rows are transposed (few waves per CU: nothing else hides them).
+//     next groups are in flight while the current group's rows are transposed (few waves per CU: nothing else hides them);
+//   * the constant tables the group loop reads AFTER it has issued that prefetch — the (source word, bit) -> column table, the
+//     comparison atoms and short literals beyond the 64 held in registers — are staged once per workgroup in LDS. Read from global
+//     memory (the stores to the pair list may alias them, so the compiler cannot hoist the loads) each read was followed by a wait for
+//     ALL outstanding loads — they return in order — which drained the prefetch once per group: one exposed L2 round trip per present
+//     source word on top of it. LDS reads are counted apart from the vector-memory loads, so the prefetch stays in flight.
 static constexpr uint32_t DIR_ESCAPE = 0x80000000u;
 
 // ipres_kernel (round 3): the address lookups of the attribute path as a kernel of their own — one lane per request, ~20 registers,
@@ -3522,14 +3532,22 @@ struct AttrIn {
 // 0.227, nothing.)
 // SMALL: the rule set's membership rows fit 4 ip-set words, 2 country words and one word each of port sets, asn sets and asn
 // comparisons (a 1k-rule set with 124 CIDR lists does): 9 row registers instead of 36.
+// Atoms beyond the 64 that live in registers, staged in LDS for the group loop (the chunks beyond these are re-read from global memory
+// per group: a rule set with more than 256 eager comparison atoms or 128 short literals).
+static constexpr uint32_t kAttrCmpStaged = 192, kAttrShortStaged = 64;
 template <bool PACKED, bool SMALL>
 __global__ __launch_bounds__(256) void attr_kernel(VerdictArgs a) {
     constexpr uint32_t SW = SMALL ? 4 : kSetWordsMax, CW = SMALL ? 2 : kCcWordsMax, IW = SMALL ? 1 : kIntWordsMax, QW = SMALL ? 1 : kAcmpWordsMax;
+    // LDS (one array): the rows of bit_col this instantiation can meet, in the order of the transposes below (slot -> source word:
+    // SW ip-set words, CW country words, IW port-set words, IW asn-set words, QW asn-comparison words), then the staged comparison
+    // atoms {col, c} and the staged short literals {col, len_exact, lit_lo, lit_hi}. 1.1 KiB + 2.5 KiB (SMALL), 4.5 KiB + 2.5 KiB.
+    constexpr uint32_t kSlotCc = SW, kSlotPort = SW + CW, kSlotAsn = SW + CW + IW, kSlotAcmp = SW + CW + 2 * IW, kSlots = SW + CW + 2 * IW + QW;
+    constexpr uint32_t kLdsCmp = kSlots * 32, kLdsShort = kLdsCmp + 2 * kAttrCmpStaged, kLdsWords = kLdsShort + 4 * kAttrShortStaged;
+    __shared__ uint32_t tab[kLdsWords];
 #ifdef PWAF_PROFILING
     if (a.debug_skip & 0x80000000u) __builtin_amdgcn_s_setprio(3);  // timing experiment
 #endif
     const uint32_t lane = threadIdx.x & 63, wave = wave_index();
-    const unsigned long long lt_mask = (1ull << lane) - 1;
     const bool from_row = a.asn == nullptr;  // asn / country come from the engine's own GeoIP record (or its default)
 #ifdef PWAF_PROFILING
     // timing experiments (wrong results): which part of the kernel costs what
@@ -3544,7 +3562,14 @@ __global__ __launch_bounds__(256) void attr_kernel(VerdictArgs a) {
         h_c = a.cmp[lane].c;
     }
     const uint32_t g_stride = gridDim.x * 4;
-    // stage A: the fixed-width inputs of a group (unconditional loads, clamped indices: no branch, so no wait is forced)
+    // stage A: the fixed-width inputs of a group. Every load is UNCONDITIONAL: a column the rule set does not read (or the batch does not
+    // carry) is replaced by element 0 of a column that always exists — one cached line for the whole wave, its value discarded. A load
+    // under a wave-uniform condition becomes a branch around it, and the compiler waits for ALL outstanding loads where the branches
+    // join: one exposed round trip per length column, in the middle of the prefetch.
+    const uint32_t *const asn_col = from_row ? a.off[0] : a.asn;
+    const uint16_t *const country_col = from_row ? a.port : a.country;
+    const uint32_t *const short_col = a.n_short ? a.short_off : a.off[0];
+    const uint8_t *const short_bytes = a.n_short ? a.short_data : reinterpret_cast<const uint8_t *>(a.off[0]);
     auto load_in = [&](const uint32_t g, AttrIn &in) {
         const uint32_t i0 = g * 64 + lane;
         const uint32_t i = (g < a.n_groups && i0 < a.n) ? i0 : 0u;
@@ -3559,17 +3584,23 @@ __global__ __launch_bounds__(256) void attr_kernel(VerdictArgs a) {
         }
         in.port = a.port[i];
 #pragma unroll
-        for (int f = 0; f < 5; f++) in.len[f] = ((a.cmp_vars >> f) & 1u) ? a.off[f][i + 1] - a.off[f][i] : 0u;  // (wave-uniform: only the lengths some comparison atom reads)
-        in.asn = from_row ? 0u : a.asn[i];
-        in.country = from_row ? 0u : (uint32_t)a.country[i];
-        in.sstart = a.n_short ? a.short_off[i] : 0u;
-        in.slen = a.n_short ? a.short_off[i + 1] - in.sstart : 0u;
+        for (int f = 0; f < 5; f++) {  // (wave-uniform: only the lengths some comparison atom reads)
+            const bool used = (a.cmp_vars >> f) & 1u;
+            const uint32_t j = used ? i : 0u;
+            const uint32_t d = a.off[f][j + 1] - a.off[f][j];
+            in.len[f] = used ? d : 0u;
+        }
+        const uint32_t ja = from_row ? 0u : i, js = a.n_short ? i : 0u;
+        const uint32_t v_asn = asn_col[ja], v_country = country_col[ja], s0 = short_col[js], s1 = short_col[js + 1];
+        in.asn = from_row ? 0u : v_asn;
+        in.country = from_row ? 0u : v_country;
+        in.sstart = a.n_short ? s0 : 0u;
+        in.slen = a.n_short ? s1 - s0 : 0u;
     };
     // stage B: the short-literal field's first 8 bytes (arenas carry 16 readable slack bytes)
     auto load_short = [&](const AttrIn &in, uint32_t &s_lo, uint32_t &s_hi) {
         typedef uint2 __attribute__((aligned(1))) uint2_u;
-        uint2 sv = make_uint2(0u, 0u);
-        if (a.n_short) sv = *reinterpret_cast<const uint2_u *>(a.short_data + in.sstart);
+        const uint2 sv = *reinterpret_cast<const uint2_u *>(short_bytes + in.sstart);  // (no short literals: the first 8 bytes of a column that exists, unused)
         s_lo = sv.x;
         s_hi = sv.y;
     };
@@ -3582,6 +3613,24 @@ __global__ __launch_bounds__(256) void attr_kernel(VerdictArgs a) {
     // group-invariant: the first 64 short-literal atoms, one per lane
     ShortAtom h_short{0, 0, 0, 0};
     if (lane < a.n_short) h_short = a.short_atoms[lane];
+    // the LDS tables, once per workgroup (behind the first groups' input loads, so that all of them share one round trip)
+    for (uint32_t t = threadIdx.x; t < kSlots * 32; t += 256) {
+        const uint32_t s = t >> 5;
+        const uint32_t src = s < kSlotCc ? kSrcSet + s : s < kSlotPort ? kSrcCc + (s - kSlotCc) : s < kSlotAsn ? kSrcPort + (s - kSlotPort) : s < kSlotAcmp ? kSrcAsn + (s - kSlotAsn) : kSrcAcmp + (s - kSlotAcmp);
+        tab[t] = a.bit_col[src * 32 + (t & 31u)];
+    }
+    for (uint32_t t = threadIdx.x; t < kAttrCmpStaged && 64 + t < a.n_cmp; t += 256) {
+        tab[kLdsCmp + 2 * t] = a.cmp[64 + t].col;
+        tab[kLdsCmp + 2 * t + 1] = a.cmp[64 + t].c;
+    }
+    for (uint32_t t = threadIdx.x; t < kAttrShortStaged && 64 + t < a.n_short; t += 256) {
+        const ShortAtom s = a.short_atoms[64 + t];
+        tab[kLdsShort + 4 * t] = s.col;
+        tab[kLdsShort + 4 * t + 1] = s.len_exact;
+        tab[kLdsShort + 4 * t + 2] = s.lit_lo;
+        tab[kLdsShort + 4 * t + 3] = s.lit_hi;
+    }
+    __syncthreads();
 
     for (uint32_t g = g0; g < a.n_groups; g += g_stride) {
         const uint32_t i = g * 64 + lane;
@@ -3592,7 +3641,7 @@ __global__ __launch_bounds__(256) void attr_kernel(VerdictArgs a) {
         // lane-private (column, mask) -> the group's pair list, in lane order
         auto emit_pairs = [&](const bool has, const uint32_t c, const uint32_t lo, const uint32_t hi) {
             const unsigned long long em = __ballot(has);
-            if (has) pairs[n_pairs + (uint32_t)__builtin_popcountll(em & lt_mask)] = make_uint4(c, 0u, lo, hi);
+            if (has) pairs[n_pairs + __builtin_amdgcn_mbcnt_hi((uint32_t)(em >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)em, 0u))] = make_uint4(c, 0u, lo, hi);  // (emitting lanes below this one)
             n_pairs += (uint32_t)__builtin_popcountll(em);
         };
         const uint32_t port = cur.port;
@@ -3644,10 +3693,21 @@ __global__ __launch_bounds__(256) void attr_kernel(VerdictArgs a) {
         load_in(g + 2 * g_stride, nn);
         uint32_t n_slo, n_shi;
         load_short(nxt, n_slo, n_shi);
+        // The rows are waited for HERE, once, with the prefetch behind them still in flight. Left to the first use inside each transpose,
+        // the wait is placed where paths with and without a pair store join, and is counted for the path without: behind every
+        // store it then also waits for one more load of the prefetch.
+#pragma unroll
+        for (uint32_t q = 0; q < SW; q++) asm volatile("" : "+v"(rs[q]));
+#pragma unroll
+        for (uint32_t q = 0; q < CW; q++) asm volatile("" : "+v"(rc[q]));
+#pragma unroll
+        for (uint32_t q = 0; q < IW; q++) asm volatile("" : "+v"(rp[q]), "+v"(ra[q]));
+#pragma unroll
+        for (uint32_t q = 0; q < QW; q++) asm volatile("" : "+v"(rq[q]));
 
         // ---- 3. transposes: one ballot per bit that ANY of the 64 requests has set (wave-wide OR first, so absent bits cost
         //         nothing); lane b keeps bit b's request mask and owns that atom's pair ----
-        auto transpose = [&](const uint32_t w, const uint32_t src_word) {
+        auto transpose = [&](const uint32_t w, const uint32_t slot) {
             const uint32_t orw0 = wave_or(w);
             if (orw0 == 0) return;
             // (the mask is PARKED in lane b with v_writelane: two vector instructions per bit — a compare of the lane id and two
@@ -3659,20 +3719,20 @@ __global__ __launch_bounds__(256) void attr_kernel(VerdictArgs a) {
                 park64(mine_lo, mine_hi, m, b);
             }
             const bool owner = lane < 32 && ((orw0 >> lane) & 1u);
-            const uint32_t c = owner ? a.bit_col[src_word * 32 + lane] : 0u;  // (source word, bit) -> column, 0 = no such atom
+            const uint32_t c = owner ? tab[slot * 32 + (lane & 31u)] : 0u;  // (source word, bit) -> column, 0 = no such atom (LDS: no wait on the prefetch)
             emit_pairs(c != 0, c, mine_lo, mine_hi);
         };
         if (!skip_transpose) {
 #pragma unroll
-            for (uint32_t q = 0; q < SW; q++) if (q < a.set_words) transpose(rs[q], kSrcSet + q);  // (uniform conditions)
+            for (uint32_t q = 0; q < SW; q++) if (q < a.set_words) transpose(rs[q], q);  // (uniform conditions)
 #pragma unroll
-            for (uint32_t q = 0; q < CW; q++) if (q < a.cc_words) transpose(rc[q], kSrcCc + q);
+            for (uint32_t q = 0; q < CW; q++) if (q < a.cc_words) transpose(rc[q], kSlotCc + q);
 #pragma unroll
-            for (uint32_t q = 0; q < IW; q++) if (q < a.iu_words[0]) transpose(rp[q], kSrcPort + q);
+            for (uint32_t q = 0; q < IW; q++) if (q < a.iu_words[0]) transpose(rp[q], kSlotPort + q);
 #pragma unroll
-            for (uint32_t q = 0; q < IW; q++) if (q < a.iu_words[1]) transpose(ra[q], kSrcAsn + q);
+            for (uint32_t q = 0; q < IW; q++) if (q < a.iu_words[1]) transpose(ra[q], kSlotAsn + q);
 #pragma unroll
-            for (uint32_t q = 0; q < QW; q++) if (q < a.acmp_words) transpose(rq[q], kSrcAcmp + q);
+            for (uint32_t q = 0; q < QW; q++) if (q < a.acmp_words) transpose(rq[q], kSlotAcmp + q);
         }
 
         // Comparison atoms (lengths, port, asn against constants): the engine has reduced them to `v == c` / `v <= c` on 32-bit
@@ -3680,11 +3740,17 @@ __global__ __launch_bounds__(256) void attr_kernel(VerdictArgs a) {
         // vector compare and a ballot parked in the atom's lane. (asn comparisons of engine-resolved records are class-row bits.)
         for (uint32_t base = 0; base < a.n_cmp && !skip_cmp; base += 64) {
             uint32_t m_col = h_col, m_c = h_c;
-            if (base != 0) {  // more than 64 comparison atoms: the later chunks are re-read per group
+            if (base != 0) {  // more than 64 comparison atoms: the later chunks come from LDS (beyond the staged ones: re-read per group)
                 m_col = m_c = 0;
                 if (base + lane < a.n_cmp) {
-                    m_col = a.cmp[base + lane].col;
-                    m_c = a.cmp[base + lane].c;
+                    if (base < 64 + kAttrCmpStaged) {  // (uniform)
+                        m_col = tab[kLdsCmp + 2 * (base - 64 + lane)];
+                        m_c = tab[kLdsCmp + 2 * (base - 64 + lane) + 1];
+                    } else {
+                        m_col = a.cmp[base + lane].col;
+                        m_c = a.cmp[base + lane].c;
+                        asm volatile("" : "+v"(m_col), "+v"(m_c));  // (the wait for this load belongs HERE, not where the branches join)
+                    }
                 }
             }
             const uint32_t my_code = base + lane < a.n_cmp ? (m_col >> 24) & 0x7Fu : 0xFFu;
@@ -3721,7 +3787,15 @@ __global__ __launch_bounds__(256) void attr_kernel(VerdictArgs a) {
             ShortAtom m = h_short;
             if (base != 0) {
                 m = ShortAtom{0, 0, 0, 0};
-                if (base + lane < a.n_short) m = a.short_atoms[base + lane];
+                if (base + lane < a.n_short) {
+                    const uint32_t *s = tab + kLdsShort + 4 * (base - 64 + lane);
+                    if (base < 64 + kAttrShortStaged) {  // (uniform)
+                        m = ShortAtom{s[0], s[1], s[2], s[3]};
+                    } else {
+                        m = a.short_atoms[base + lane];
+                        asm volatile("" : "+v"(m.col), "+v"(m.len_exact), "+v"(m.lit_lo), "+v"(m.lit_hi));  // (as above)
+                    }
+                }
             }
             const uint32_t cnt = min(64u, a.n_short - base);
             uint32_t acc_lo = 0, acc_hi = 0;
