@@ -1176,16 +1176,18 @@ struct BatchRun {
         return PWAF_OK;
     }
 
-    // A pass with heads writes records outside its candidate list too: zeroed here, read densely. (A confirm tier MERGES hits into zeroed
-    // records: resolve_kernel zeroes the records of the requests that have a flagged chunk — the only ones a hit can land in.) Passes are
-    // laid out so that the filtered ones are neighbours: runs of passes to zero take ONE memset each.
+    // A pass with heads has records outside its candidate list too, read densely: filter_kernel stores the record of EVERY request of such
+    // a pass, zero included (it visits each request's start once anyway; until then a memset of n x 4 bytes per pass stood in front of
+    // every batch's descriptor upload: 7.6 us for 10M requests). (A confirm tier MERGES hits into zeroed records: resolve_kernel zeroes
+    // the records of the requests that have a flagged chunk — the only ones a hit can land in.) What is left for the host is the pass
+    // the launch has no wave for — an arena without a slab of its own (every field of the batch empty) — and, in profiling builds, the
+    // "no heads" timing switch, which stores no record at all. Called once the arena sizes are known.
     int zero_head_records() {
-        for (size_t k = 0; k < e->groups.size();) {
-            size_t k1 = k;
-            while (k1 < e->groups.size() && e->groups[k1].filtered && !e->groups[k1].filter.heads.empty()) k1++;
-            if (k1 == k) { k++; continue; }
-            HIP_TRY(hipMemsetAsync((uint32_t *)S.rec.p + k * (size_t)n, 0, (k1 - k) * (size_t)n * 4, stream));
-            k = k1;
+        for (size_t k = 0; k < e->groups.size(); k++) {
+            const DevGroup &d = e->groups[k];
+            if (!d.filtered || d.filter.heads.empty()) continue;
+            if (slab_count(col_bytes[d.field], slab0_of(d.field)) != 0 && !(sw.filter_debug_skip & 4u)) continue;
+            HIP_TRY(hipMemsetAsync((uint32_t *)S.rec.p + k * (size_t)n, 0, (size_t)n * 4, stream));
         }
         return PWAF_OK;
     }
@@ -1783,7 +1785,7 @@ int run_pipeline(pwaf_engine *e, Scratch &S, const pwaf_batch &db /* device poin
     b.d_geo = d_geo;
     int rc;
     if ((rc = b.reserve_scratch(sync_status)) || (rc = b.resolve_columns(totals_known))) return rc;
-    if ((rc = b.fill_verdict_args(d_out, d_counts, d_match_idx, d_n_matches)) || (rc = b.zero_head_records())) return rc;
+    if ((rc = b.fill_verdict_args(d_out, d_counts, d_match_idx, d_n_matches))) return rc;
     if (d_hits && d_hits->any()) {  // (the verdict kernel's rule-hit variant: launch_verdict)
         b.v.hits = d_hits->hits;
         b.v.hits_cap = d_hits->cap;
@@ -1793,7 +1795,7 @@ int run_pipeline(pwaf_engine *e, Scratch &S, const pwaf_batch &db /* device poin
     b.pick_list_shapes();
     if ((rc = b.attr_at_start()) || (rc = b.launch_plain_scans())) return rc;
     // every descriptor of the batch: built, checked against the launch plan, uploaded once
-    if ((rc = b.learn_arena_sizes()) || (rc = b.build_filter_args())) return rc;
+    if ((rc = b.learn_arena_sizes()) || (rc = b.zero_head_records()) || (rc = b.build_filter_args())) return rc;
     b.build_confirm_args();
     b.build_list_args();
     b.build_column_pointers();

@@ -198,7 +198,7 @@ int launch_confirm(const ConfirmArgs *host, uint32_t count, const ConfirmArgs *d
 // and a window that straddles a request boundary can only ADD a candidate.
 //   filter_kernel   per 16-byte chunk a hit bit, written as the pass's dense chunk bitmap (a row's ballot is its 64-bit word: no
 //                   lists, no atomics). Heads (anchored literals) are compared at request starts, which the wave finds by walking
-//                   the offsets column alongside the bytes.
+//                   the offsets column alongside the bytes; the record of EVERY request of a pass with heads is stored, zero included.
 //   resolve_kernel  flagged chunks -> requests (rank queries over the slab's bitmap), one bit per request in `bitmap`.
 //   bitcount_kernel / compact_kernel   bitmap -> dense ascending request list + its length for the confirming lscan_kernel.
 static constexpr uint32_t kStreamSlab = 128 * 1024;   // bytes per wave
@@ -220,7 +220,7 @@ struct FilterArgs {
     uint32_t head_m[2][4];    // byte masks of the literal's length
     uint32_t head_len[2];     // length | exact << 8
     uint32_t head_code[2];    // hit-record bits of the head's atom
-    uint32_t *rec;            // n hit records of the pass, zeroed by the host: written only where a head holds
+    uint32_t *rec;            // n hit records of the pass. A pass with heads: every one of them written by filter_kernel (zero where no head holds; an arena without a slab: zeroed by the host)
     uint32_t *chunk_bits;     // the pass's chunk bitmap: bit c = the 16-byte chunk c of the streamed slabs holds a position that completed a window (kStreamSlab / 512 words per slab)
     uint32_t *sub_count;      // [slabs]: flagged chunks of the slab
     uint32_t *bitmap;         // [(n + 31) / 32], zeroed by the host: candidate requests
@@ -238,7 +238,7 @@ struct FilterArgs {
     const uint32_t *dense_flag;
     uint32_t dense_thresh;
     uint32_t first_block;     // first workgroup of this pass in the fused filter launch
-    uint32_t debug;           // -DPWAF_PROFILING timing experiments only (wrong results): 1 = no table lookups, 2 = no loads after a slab's first iteration
+    uint32_t debug;           // -DPWAF_PROFILING timing experiments only (wrong results): 1 = no table lookups, 2 = no loads after a slab's first iteration, 4 = no heads (the host clears the records)
 };
 // The descriptors of all passes of a launch live in DEVICE memory (a 4096-rule set over 64 header fields has ~70 filtered passes:
 // 15 KB of descriptors, kernel arguments hold 8). The host builds the descriptors of EVERY launch of a batch before the first one, writes

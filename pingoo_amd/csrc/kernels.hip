@@ -1474,8 +1474,7 @@ __device__ __forceinline__ void filter_rows(const FilterArgs &a, const uint32_t 
                     const bool in = s < lim;
                     const uint32_t cnt = (uint32_t)__builtin_popcountll(__ballot(in));
                     if (in) {
-                        const uint32_t hrec = head_record(*reinterpret_cast<const PWAF_GLOBAL u32x4_u *>(gdata + s), a.off[idx + 1] - s);
-                        if (hrec) a.rec[idx] = hrec;
+                        a.rec[idx] = head_record(*reinterpret_cast<const PWAF_GLOBAL u32x4_u *>(gdata + s), a.off[idx + 1] - s);
                     }
                     rq += cnt;
                     if (cnt < 64) break;
@@ -1538,16 +1537,20 @@ __device__ __forceinline__ void filter_rows(const FilterArgs &a, const uint32_t 
         if (lane < 4) my_bits[(b - base0) / kRow + lane] = lane == 0 ? hm[0] : lane == 1 ? hm[1] : lane == 2 ? hm[2] : hm[3];
         n_hit += (uint32_t)(__builtin_popcountll(hm[0]) + __builtin_popcountll(hm[1]) + __builtin_popcountll(hm[2]) + __builtin_popcountll(hm[3]));
 
-        if (heads) {
+        if (heads) {  // the record of EVERY request of the iteration, zero included: nothing clears these records in front of the batch
 #pragma unroll
-            for (uint32_t q = 0; q < 2; q++) {
-                if (hlen[q] != 0xFFFFFFFFu) {
-                    const uint32_t hrec = head_record(hw[q], hlen[q]);
-                    if (hrec) a.rec[rq_here + 64u * q + lane] = hrec;
-                }
-            }
+            for (uint32_t q = 0; q < 2; q++)
+                if (hlen[q] != 0xFFFFFFFFu) a.rec[rq_here + 64u * q + lane] = head_record(hw[q], hlen[q]);
         }
     }
+    // The requests no iteration enumerates start AT off[n]: empty fields at the arena's end. The wave of the arena's last slab writes
+    // their (zero) records. (An arena without a slab — every field empty — has no wave: the host clears that pass, engine.cpp.)
+#ifdef PWAF_PROFILING
+    if (heads && !(a.debug & 4u) && slab_end == total)
+#else
+    if (heads && slab_end == total)
+#endif
+        for (uint32_t idx = rq + lane; idx < a.n; idx += 64) a.rec[idx] = 0u;
     // (the arena's last slab: the words of the iterations it does not have read as "no chunk flagged")
     for (uint32_t wd = (slab_end - base0 + kStreamIter - 1) / kStreamIter * 4 + lane; wd < kStreamSlab / kRow; wd += 64) my_bits[wd] = 0;
     if (lane == 0) {
@@ -1956,7 +1959,7 @@ __global__ __launch_bounds__(256) void resolve_kernel(FilterTable B) {
                 continue;
             }
             if (pair_base + k < a.pair_cap) a.pairs[pair_base + k] = make_uint2(l, chunk);
-            if (a.n_heads == 0) {  // the requests with a byte in the chunk (their records are merged into by confirm_kernel: see below)
+            if (a.n_heads == 0) {  // the requests with a byte in the chunk (their records are merged into by confirm_kernel: see below; a pass with heads: all written by filter_kernel)
                 uint32_t r = l, steps = 0;
                 for (; r < a.n && steps < 48u; r++, steps++) {
                     const uint32_t s = a.off[r];
@@ -1988,7 +1991,7 @@ __global__ __launch_bounds__(256) void resolve_kernel(FilterTable B) {
             // A request with a flagged chunk among its own gets its hit record ZEROED here (confirm_kernel merges hits into it; the verdict
             // kernel only reads records whose valid bit a hit or a walk set — which implies a flagged chunk): one store per such request
             // instead of a memset of the pass's every record (69 passes x 4 MB per batch of the 4096-rule set). A pass with filter
-            // heads keeps the host's memset: its records are written outside the flagged requests too.
+            // heads needs neither: filter_kernel has stored the record of its every request, zero where no head holds, before this launch.
             if (a.n_heads == 0 && live && e > s) {
                 const uint32_t g_lo = s >> 4, g_hi = (e - 1u) >> 4;
                 if (g_hi >= c_first + lo_c && g_lo < c_first + hi_c) {
