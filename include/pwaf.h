@@ -575,6 +575,13 @@ int pwaf_program_confirm_field(const pwaf_program *, uint32_t group, const uint8
  * 2^out[3] /24s), out[4] = the table entry a clear summary bit stands for, out[5] = 1 when (class, set) travel packed in one word,
  * out[6] = GeoIP classes, out[7] = membership sets. The reference has no counterpart (pingoo/geoip.rs, lists.rs scan per request). */
 int pwaf_engine_address_tables(const pwaf_engine *, uint32_t out[8]);
+/* TEST HOOK (needs an engine; reads host-side fields only): the coarse bitmap that the address lookups read from on-chip memory
+ * before the summary bitmap (one bit per 2^shift /24s, set = some /24 of the block differs from the common entry). out[0] = 1 when
+ * the level is present, out[1] = its shift, out[2] = its size in bytes, out[3] = blocks set, out[4] = blocks set in the summary
+ * bitmap (0 without one), out[5], out[6] = threads per workgroup and workgroups per CU of the lookup kernel's launch; out[8..11] =
+ * present / shift / bytes / blocks set for the record table of a PWAF_OPT_GEO_ANSWERS engine (all 0: that table has no such level);
+ * the rest 0. The reference has no counterpart. */
+int pwaf_engine_coarse_tables(const pwaf_engine *, uint32_t out[16]);
 int pwaf_program_stats(const pwaf_program *, pwaf_stats *out);
 
 /* ---- host-side field derivation (what the reference does before building RequestData) ------ */

@@ -36,6 +36,9 @@ FIELD_NAMES = ("host", "url", "path", "method", "user_agent")
 ARENA_PAD = 16
 # pwaf_engine_address_tables (test hook): the meaning of out[0..7]
 ADDRESS_TABLE_FIELDS = ("escapes", "n_vals", "has_summary", "shift", "common", "packed", "classes", "sets")
+# pwaf_engine_coarse_tables (test hook): the meaning of out[0..15]
+COARSE_TABLE_FIELDS = ("present", "shift", "bytes", "blocks_set", "summary_blocks_set", "threads", "wg_per_cu", "zero7",
+                       "rec_present", "rec_shift", "rec_bytes", "rec_blocks_set", "zero12", "zero13", "zero14", "zero15")
 # pwaf_engine_geo_answer_tables (test hook): the meaning of out[0..7]
 GEO_ANSWER_TABLE_FIELDS = ("has_table", "escapes", "n_vals", "has_summary", "shift", "common", "records", "zero")
 

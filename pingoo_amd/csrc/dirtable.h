@@ -17,6 +17,15 @@
 // of /24s answers most lookups from a bitmap small enough to stay in every XCD's L2. Granularity: /20 ... /24 blocks,
 // whichever minimises (fraction of the space that still needs the table) + (bitmap bytes / 8 MiB); no summary when more
 // than half of the blocks need the table anyway, or when the caller asks for none (PWAF_OPT_NO_DIR_SUMMARY).
+//
+// The coarse bitmap in front of the summary (kernels.h: VerdictArgs::dir_coarse). The summary lookup is still one scattered global
+// load per request — one lane address through the texture addresser and one L1 -> L2 line for one bit — and that NUMBER is what
+// bounds the kernel (above). A bitmap over larger blocks fits in LDS, where a gather costs neither: one bit per block of
+// 2^coarse_shift /24s, 1 = some /24 of the block differs from `common` (= the OR of the block's summary bits), staged once per
+// workgroup by ipres_kernel<.., COARSE>. A clear bit ends the lookup without a global load; a set bit continues with the summary
+// exactly as before, so the answers are the same by construction. Built only in front of a summary, with the summary's own rule
+// (at most half of the coarse blocks set), at the smallest shift whose bitmap fits the LDS budget of the kernel's launch shape
+// (64 KiB: /19 blocks, shift 5; 32 KiB: /18, shift 6); budget 0 = none.
 #pragma once
 #include <cstddef>
 #include <cstdint>
@@ -34,13 +43,25 @@ struct Compressed {
     std::vector<uint32_t> vals;     // entries of the second and further runs of a group (never empty: uploads need a byte)
     std::vector<uint32_t> summary;  // one bit per block of 2^shift /24s: 1 = look the table up; empty = no summary
     uint32_t shift = 0, common = 0;  // (meaningful with a summary only: 0 otherwise, as the lookup kernel expects)
+    std::vector<uint32_t> coarse;   // one bit per block of 2^coarse_shift /24s: 1 = look the summary up; empty = no coarse level
+    uint32_t coarse_shift = 0;
 };
 
-inline void compress(const uint32_t *d24, bool no_summary, Compressed &out) {
+static constexpr size_t kCoarseBudget = 64 * 1024;  // bytes of LDS the default launch shape of ipres_kernel gives the coarse bitmap
+static constexpr uint32_t kMaxCoarseShift = 12;     // (4096 /24s per bit, a 512-byte bitmap: coarser than any table could use)
+
+inline uint64_t popcount_words(const std::vector<uint32_t> &w) {
+    uint64_t n = 0;
+    for (uint32_t x : w) n += (uint64_t)__builtin_popcount(x);
+    return n;
+}
+
+inline void compress(const uint32_t *d24, bool no_summary, Compressed &out, size_t coarse_budget = kCoarseBudget) {
     out.chunks.assign((size_t)65536 * kChunkWords, 0);
     out.vals.clear();
     out.summary.clear();
-    out.shift = out.common = 0;
+    out.coarse.clear();
+    out.shift = out.common = out.coarse_shift = 0;
     for (uint32_t x = 0; x < 65536; x++) {
         const uint32_t *en = &d24[(size_t)x << 8];
         for (uint32_t w = 0; w < 8; w++) {
@@ -90,6 +111,27 @@ inline void compress(const uint32_t *d24, bool no_summary, Compressed &out) {
         out.summary.swap(best_bits);
         out.shift = best_shift;
         out.common = common;
+    }
+    if (out.summary.empty()) return;
+    // the coarse level: the smallest shift above the summary's whose bitmap fits the budget; a coarse bit is the OR of its summary bits
+    for (uint32_t cs = out.shift + 1; cs <= kMaxCoarseShift; cs++) {
+        const size_t n_blk = kEntries >> cs;
+        if (n_blk / 8 > coarse_budget) continue;
+        const uint32_t per = 1u << (cs - out.shift);  // summary bits per coarse bit: 2 ... 4096, all inside one or a run of whole words
+        std::vector<uint32_t> bits(n_blk / 32, 0);
+        uint64_t set = 0;
+        for (size_t b = 0; b < n_blk; b++) {
+            bool any = false;
+            if (per >= 32) {
+                for (size_t w = b * (per / 32); w < (b + 1) * (per / 32) && !any; w++) any = out.summary[w] != 0;
+            } else {
+                const size_t first = b * per;
+                any = ((out.summary[first >> 5] >> (first & 31)) & ((1u << per) - 1u)) != 0;
+            }
+            if (any) { bits[b >> 5] |= 1u << (b & 31); set++; }
+        }
+        if (set * 2 <= n_blk) { out.coarse.swap(bits); out.coarse_shift = cs; }
+        break;
     }
 }
 

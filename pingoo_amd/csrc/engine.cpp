@@ -316,6 +316,8 @@ struct pwaf_engine {
     DevBuf residual_blob, geo_rec_root4, geo_rec_root6, geo_rec_nodes;  // residual rules: the program image; the GeoIP trie with RECORD leaves (client.asn / country values)
     DevBuf pass_base, colmask, dir24 /* build-time only: released once compressed */, dir_chunks, dir_vals, dir_summary;
     uint32_t dir_sum_shift = 0, dir_common = 0;  // (VerdictArgs::dir_summary)
+    DevBuf dir_coarse;                           // (VerdictArgs::dir_coarse)
+    uint32_t dir_coarse_shift = 0, dir_coarse_bytes = 0, dir_coarse_set = 0, dir_summary_set = 0;  // (.._set: bits set, pwaf_engine_coarse_tables)
     uint32_t dir_n_esc = 0, dir_n_vals = 0;      // (pwaf_engine_address_tables)
     // PWAF_OPT_GEO_ANSWERS: the RECORD of every request (georec_kernel). The record-leaf trie and the records are geo_rec_* / geo_recs
     // above (shared with the residual rules); the IPv4 table of record ids is the engine's own (csrc/georec.h)
@@ -652,6 +654,9 @@ void set_trie_args(const pwaf_engine *e, VerdictArgs &v) {
     v.dir_summary = (const uint32_t *)e->dir_summary.p;
     v.dir_sum_shift = e->dir_sum_shift;
     v.dir_common = e->dir_common;
+    v.dir_coarse = (const uint32_t *)e->dir_coarse.p;
+    v.dir_coarse_shift = e->dir_coarse_shift;
+    v.dir_coarse_bytes = e->dir_coarse_bytes;
     v.class_rows = (const uint32_t *)e->class_rows.p;
     v.class_words = e->class_words;
     v.acmp_words = e->acmp_words;
@@ -2363,7 +2368,7 @@ int pwaf_engine_create(const pwaf_rule_desc *rules, size_t n_rules, const pwaf_l
             std::vector<uint32_t> d24;
             e->georec_n_esc = georec::flatten(P.geo_trie.root4.data(), P.geo_trie.nodes.data(), d24);
             dirtable::Compressed ct;
-            dirtable::compress(d24.data(), (P.flags & PWAF_OPT_NO_DIR_SUMMARY) != 0, ct);
+            dirtable::compress(d24.data(), (P.flags & PWAF_OPT_NO_DIR_SUMMARY) != 0, ct, 0);  // (georec_kernel has no coarse level)
             if ((rc = upload(e->georec_chunks, ct.chunks)) || (rc = upload(e->georec_vals, ct.vals))) return dev_fail(rc);
             if (!ct.summary.empty()) {
                 if ((rc = upload(e->georec_summary, ct.summary))) return dev_fail(rc);
@@ -2394,12 +2399,19 @@ int pwaf_engine_create(const pwaf_rule_desc *rules, size_t n_rules, const pwaf_l
             if (hipMemcpy(d24.data(), e->dir24.p, d24.size() * 4, hipMemcpyDeviceToHost) != hipSuccess) { fail(PWAF_E_DEVICE, "DIR-24 download failed"); return dev_fail(PWAF_E_DEVICE); }
             static_assert(dirtable::kChunkWords == kDirChunkWords, "dirtable.h and kernels.h disagree on the record layout");
             dirtable::Compressed ct;
-            dirtable::compress(d24.data(), (P.flags & PWAF_OPT_NO_DIR_SUMMARY) != 0, ct);
+            dirtable::compress(d24.data(), (P.flags & PWAF_OPT_NO_DIR_SUMMARY) != 0, ct, ipres_shape().coarse_bytes);
             if ((rc = upload(e->dir_chunks, ct.chunks)) || (rc = upload(e->dir_vals, ct.vals))) return dev_fail(rc);
             if (!ct.summary.empty()) {
                 if ((rc = upload(e->dir_summary, ct.summary))) return dev_fail(rc);
                 e->dir_sum_shift = ct.shift;
                 e->dir_common = ct.common;
+                e->dir_summary_set = (uint32_t)dirtable::popcount_words(ct.summary);
+            }
+            if (!ct.coarse.empty()) {  // (only in front of a summary)
+                if ((rc = upload(e->dir_coarse, ct.coarse))) return dev_fail(rc);
+                e->dir_coarse_shift = ct.coarse_shift;
+                e->dir_coarse_bytes = (uint32_t)(ct.coarse.size() * 4);
+                e->dir_coarse_set = (uint32_t)dirtable::popcount_words(ct.coarse);
             }
             e->dir_n_esc = n_esc;
             e->dir_n_vals = (uint32_t)ct.vals.size();
@@ -2415,7 +2427,7 @@ void pwaf_engine_destroy(pwaf_engine *e) {
     if (!e) return;
     for (auto &g : e->groups) { for (DevBuf *b : {&g.tab, &g.classmap, &g.special, &g.list_off, &g.list, &g.ftable, &g.c_head, &g.c_entries, &g.c_bytes, &g.c_classes}) b->release(); g.fl.release(); g.rt.release(); }
     for (DevBuf *b : {&e->num_atoms, &e->lazy_atoms, &e->bit_atoms, &e->trig_off, &e->trig_rules, &e->always_rules, &e->iu_vals[0], &e->iu_vals[1], &e->iu_masks[0], &e->iu_masks[1], &e->country_luts, &e->rules, &e->lits,
-                      &e->set_masks, &e->ip_root4, &e->ip_root6, &e->ip_nodes, &e->geo_root4, &e->geo_root6, &e->geo_nodes, &e->geo_recs, &e->residual_blob, &e->residual_errors, &e->geo_rec_root4, &e->geo_rec_root6, &e->geo_rec_nodes, &e->pass_base, &e->colmask, &e->dir24, &e->dir_chunks, &e->dir_vals, &e->dir_summary, &e->class_rows,
+                      &e->set_masks, &e->ip_root4, &e->ip_root6, &e->ip_nodes, &e->geo_root4, &e->geo_root6, &e->geo_nodes, &e->geo_recs, &e->residual_blob, &e->residual_errors, &e->geo_rec_root4, &e->geo_rec_root6, &e->geo_rec_nodes, &e->pass_base, &e->colmask, &e->dir24, &e->dir_chunks, &e->dir_vals, &e->dir_summary, &e->dir_coarse, &e->class_rows,
                       &e->dir_esc, &e->leaf_root, &e->geo_leaf_root, &e->pass_table, &e->georec_chunks, &e->georec_vals, &e->georec_summary})
         b->release();
     if (e->residual_jit.module) {  // (a module belongs to the device it was loaded on)
@@ -2448,6 +2460,20 @@ int pwaf_engine_address_tables(const pwaf_engine *e, uint32_t out[8]) {
     out[5] = v.ipres_packed;
     out[6] = e->n_classes;
     out[7] = P.set_words ? (uint32_t)(P.set_masks.size() / P.set_words) : 1u;
+    return PWAF_OK;
+}
+int pwaf_engine_coarse_tables(const pwaf_engine *e, uint32_t out[16]) {
+    if (!e || !out) return fail(PWAF_E_INVALID_ARG, "pwaf_engine_coarse_tables: NULL argument");
+    const IpresShape sh = ipres_shape();
+    for (int i = 0; i < 16; i++) out[i] = 0;
+    out[0] = e->dir_coarse.p ? 1u : 0u;
+    out[1] = e->dir_coarse_shift;
+    out[2] = e->dir_coarse_bytes;
+    out[3] = e->dir_coarse_set;
+    out[4] = e->dir_summary_set;
+    out[5] = e->dir_coarse.p ? sh.threads : 256u;
+    out[6] = e->dir_coarse.p ? sh.wg_per_cu : 8u;
+    // out[8..11]: the record table (georec_kernel) has no coarse level
     return PWAF_OK;
 }
 int pwaf_engine_geo_answer_tables(const pwaf_engine *e, uint32_t out[8]) {

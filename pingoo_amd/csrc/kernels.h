@@ -434,6 +434,11 @@ struct VerdictArgs {
     // lines over the fabric per batch). Null: no summary (most blocks differ: the bit would cost a load and save nothing).
     const uint32_t *dir_summary;
     uint32_t dir_sum_shift, dir_common;
+    // COARSE bitmap in front of the summary (csrc/dirtable.h): one bit per block of 2^dir_coarse_shift /24s, the OR of the block's
+    // summary bits, small enough (dir_coarse_bytes, a multiple of 16, at most ipres_shape().coarse_bytes) for every workgroup of
+    // ipres_kernel<.., COARSE> to stage in LDS: a clear bit ends the lookup at dir_common without a global load. Null: none.
+    const uint32_t *dir_coarse;
+    uint32_t dir_coarse_shift, dir_coarse_bytes;
     const uint2 *dir_esc;         // {geo trie entry, ip-list trie entry} of the escaped /24s
     const uint32_t *class_rows;   // per GeoIP class: country-table words, asn-set words, asn-comparison words (class 0 = all zero)
     uint32_t class_words;
@@ -480,6 +485,12 @@ uint32_t list_hot_bytes(const ListShape &shape);
 int launch_scan_gated(const ListScanArgs *host, uint32_t count, const ListScanArgs *dev, uint32_t *plan, const ListShape &shape, void *stream);
 int launch_verdict(const VerdictArgs &a, void *stream);
 int launch_ipres(const VerdictArgs &a, void *stream);  // address lookups -> a.ipres; then, on the same stream:
+// Launch shape of ipres_kernel<.., COARSE>: threads per workgroup, LDS bytes for the coarse bitmap (the budget dirtable::compress
+// gets; 0 = no coarse level, the 256-thread kernel without LDS), workgroups per CU
+struct IpresShape {
+    uint32_t threads, coarse_bytes, wg_per_cu;
+};
+IpresShape ipres_shape();
 int launch_attr(const VerdictArgs &a, void *stream);
 int launch_dir24(const VerdictArgs &a, void *out /* 2^24 x u32, or null: count only */, void *esc, void *esc_count, void *stream);
 // georec_kernel (PWAF_OPT_GEO_ANSWERS): the GeoIP RECORD of every request, 8 bytes each ({asn, country, 0} = pwaf_geo = GeoRec) — what

@@ -3289,13 +3289,19 @@ static constexpr uint32_t DIR_ESCAPE = 0x80000000u;
 // kernel of the step. Here 32 waves per CU overlap those waits, and an IPv4 address behind the DIR-24 table costs ONE gather (round 2
 // also fetched both 16-bit root entries for every lane and threw them away). Output: the GeoIP CLASS and the ip-list membership SET
 // of every request, packed into one word (class | set << 16) when both fit 16 bits (else two words).
-template <bool PACKED>
-__global__ __launch_bounds__(256) void ipres_kernel(VerdictArgs a) {
+//
+// COARSE (csrc/dirtable.h; launch shape: ipres_shape()): the workgroup stages the coarse bitmap — one bit per block of
+// 2^dir_coarse_shift /24s, at most 64 KiB — in LDS, and an IPv4 lane reads its block's bit there before anything else. Clear = the
+// answer is dir_common and the lane issues no global load at all: an LDS gather takes neither a texture-addresser slot nor an
+// L1 -> L2 request, which are what bound this kernel. Set = the lookup goes on as without the level. 8 waves per SIMD as before.
+template <bool PACKED, bool COARSE>
+__global__ __launch_bounds__(COARSE ? 1024 : 256, COARSE ? 8 : 1) void ipres_kernel(VerdictArgs a) {
     // A lookup is a chain of dependent accesses (address bytes -> first level -> run bitmap -> value; IPv6: root -> trie nodes), each an
     // L2 / Infinity-Cache round trip: with one request per lane at a time the kernel was latency-bound even at 32 waves per CU (0.24 ms
     // for 10M requests, 19 chains per lane one after the other). Every lane now walks U = 4 requests in lockstep: each phase issues
     // the loads of all four before any is used.
     constexpr uint32_t U = 4;
+    extern __shared__ uint4 ipres_lds[];  // COARSE: the coarse bitmap (dir_coarse_bytes)
     const bool from_row = a.asn == nullptr;
 #ifdef PWAF_PROFILING
     // timing experiments (wrong results): bit 16 = no table lookups for IPv4, bit 17 = no trie walks for IPv6
@@ -3305,19 +3311,47 @@ __global__ __launch_bounds__(256) void ipres_kernel(VerdictArgs a) {
     const bool dir = a.dir_chunks != nullptr;
     constexpr bool skip_v6 = false, skip_v4 = false;
 #endif
-    const uint32_t T = gridDim.x * 256u;
-    for (uint32_t i0 = blockIdx.x * 256u + threadIdx.x; i0 < a.n; i0 += T * U) {
+    const uint32_t T = gridDim.x * blockDim.x;
+    uint32_t i0 = blockIdx.x * blockDim.x + threadIdx.x;
+    uint4 raw[U];
+    uint32_t v6b[U];
+    // the addresses and families of the lane's four requests (a dead slot re-reads the lane's first request)
+    auto load_inputs = [&](uint32_t base) {
+#pragma unroll
+        for (uint32_t u = 0; u < U; u++) {
+            const uint32_t j = base + u * T < a.n ? base + u * T : base;
+            raw[u] = *reinterpret_cast<const uint4 *>(a.ip + (size_t)j * 16);
+            v6b[u] = a.ip_is_v6[j];
+        }
+    };
+    bool loaded = false;
+    if (COARSE) {
+        // Staged BEHIND the first sweep's address loads, so that both share one round trip (loads return in order: the wait for the
+        // bitmap's words covers the addresses): 16-byte loads, four in flight per lane — the whole bitmap in one trip at 64 KiB / 1024
+        // or 32 KiB / 512 threads. A lane without a request (the last workgroup) stages with the others and loads request 0.
+        load_inputs(i0 < a.n ? i0 : 0u);
+        loaded = true;
+        const uint4 *src = reinterpret_cast<const uint4 *>(a.dir_coarse);
+        const uint32_t n16 = a.dir_coarse_bytes >> 4;
+        for (uint32_t j = threadIdx.x; j < n16; j += 4u * blockDim.x) {
+            uint4 w[4];
+#pragma unroll
+            for (uint32_t q = 0; q < 4; q++) w[q] = src[min(j + q * blockDim.x, n16 - 1u)];
+#pragma unroll
+            for (uint32_t q = 0; q < 4; q++)
+                if (j + q * blockDim.x < n16) ipres_lds[j + q * blockDim.x] = w[q];
+        }
+        __syncthreads();
+    }
+    for (; i0 < a.n; i0 += T * U) {
         uint32_t idx[U], ipw[U][4], eg[U], ei[U], k[U];
         bool live[U], v6[U], geo_walk[U], chunked[U];
-        uint4 raw[U];
-        uint32_t v6b[U];
+        if (!loaded) load_inputs(i0);
+        loaded = false;
 #pragma unroll
         for (uint32_t u = 0; u < U; u++) {
             idx[u] = i0 + u * T;
             live[u] = idx[u] < a.n;
-            const uint32_t j = live[u] ? idx[u] : i0;
-            raw[u] = *reinterpret_cast<const uint4 *>(a.ip + (size_t)j * 16);
-            v6b[u] = a.ip_is_v6[j];
         }
         uint32_t first[U], top16[U];
 #pragma unroll
@@ -3346,12 +3380,20 @@ __global__ __launch_bounds__(256) void ipres_kernel(VerdictArgs a) {
                 if (a.n_ip_lists) ei[u] = (v6[u] ? a.ip_root6 : a.ip_root4)[top16[u]];
             }
         }
-        // phase 1b: the summary bit of the address's block of /24s (L2-resident bitmap): 0 = the table's most common entry, no gather
+        // phase 1b: the coarse bit of the address's block of /24s (LDS), then for the lanes it leaves the summary bit (L2-resident
+        // bitmap): 0 = the table's most common entry, no gather
         uint32_t look[U];
 #pragma unroll
         for (uint32_t u = 0; u < U; u++) {
             look[u] = chunked[u] ? 1u : 0u;
-            if (chunked[u] && a.dir_summary != nullptr) {
+            if (COARSE && chunked[u]) {
+                const uint32_t blk = ((top16[u] << 8) | ip_byte(ipw[u], 2)) >> a.dir_coarse_shift;
+                look[u] = (reinterpret_cast<const uint32_t *>(ipres_lds)[blk >> 5] >> (blk & 31u)) & 1u;
+            }
+        }
+#pragma unroll
+        for (uint32_t u = 0; u < U; u++) {
+            if (look[u] && a.dir_summary != nullptr) {
                 const uint32_t blk = ((top16[u] << 8) | ip_byte(ipw[u], 2)) >> a.dir_sum_shift;
                 look[u] = (a.dir_summary[blk >> 5] >> (blk & 31u)) & 1u;
             }
@@ -3850,7 +3892,24 @@ int launch_dir24(const VerdictArgs &a, void *out, void *esc, void *esc_count, vo
     return (int)hipGetLastError();
 }
 
-// address lookups: one lane per request at full occupancy (grid-stride; 8 workgroups of 256 per CU)
+// Launch shape of the COARSE instantiation. The bitmap is staged per workgroup and held for the whole (persistent) launch, so the shape
+// trades how many lookups end in LDS against the waves and the LDS left on a CU for the kernels of the main stream (DESIGN.md §6.1:
+// the three shapes measured in the step). 1: two 1024-thread workgroups per CU, 64 KiB each (/19 blocks); 2: four 512-thread
+// workgroups, 32 KiB each (/18); 3: one 1024-thread workgroup, 64 KiB; 0: no coarse level.
+#ifndef PWAF_IPRES_SHAPE
+#define PWAF_IPRES_SHAPE 1
+#endif
+IpresShape ipres_shape() {
+    static const IpresShape shapes[4] = {{256, 0, 8}, {1024, 64 * 1024, 2}, {512, 32 * 1024, 4}, {1024, 64 * 1024, 1}};
+#ifdef PWAF_PROFILING
+    static const uint32_t pick = getenv("PWAF_IPRES_SHAPE") ? (uint32_t)atoi(getenv("PWAF_IPRES_SHAPE")) & 3u : (uint32_t)PWAF_IPRES_SHAPE;
+#else
+    const uint32_t pick = PWAF_IPRES_SHAPE;
+#endif
+    return shapes[pick];
+}
+
+// address lookups: one lane per request at full occupancy (grid-stride; 8 workgroups of 256 per CU, or ipres_shape() with a coarse bitmap)
 int launch_ipres(const VerdictArgs &a, void *stream) {
     if (a.n == 0) return 0;
 #ifdef PWAF_PROFILING
@@ -3858,9 +3917,18 @@ int launch_ipres(const VerdictArgs &a, void *stream) {
 #else
     const uint32_t forced = 0;
 #endif
+    if (a.dir_coarse != nullptr) {
+        const IpresShape sh = ipres_shape();
+        // (the kernel indexes the bitmap by the address alone: its size must be the one the shift implies)
+        if (a.dir_coarse_shift > 17u || a.dir_coarse_bytes != (1u << 21) >> a.dir_coarse_shift || a.dir_coarse_bytes > sh.coarse_bytes) return (int)hipErrorInvalidValue;
+        const uint32_t blocks = std::min<uint32_t>((a.n + sh.threads - 1) / sh.threads, forced ? forced : sh.wg_per_cu * std::max(1u, a.attr_blocks));
+        if (a.ipres_packed) hipLaunchKernelGGL((ipres_kernel<true, true>), dim3(blocks), dim3(sh.threads), a.dir_coarse_bytes, (hipStream_t)stream, a);
+        else hipLaunchKernelGGL((ipres_kernel<false, true>), dim3(blocks), dim3(sh.threads), a.dir_coarse_bytes, (hipStream_t)stream, a);
+        return (int)hipGetLastError();
+    }
     const uint32_t blocks = std::min<uint32_t>((a.n + 255) / 256, forced ? forced : 8 * std::max(1u, a.attr_blocks));
-    if (a.ipres_packed) hipLaunchKernelGGL(ipres_kernel<true>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, a);
-    else hipLaunchKernelGGL(ipres_kernel<false>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, a);
+    if (a.ipres_packed) hipLaunchKernelGGL((ipres_kernel<true, false>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, a);
+    else hipLaunchKernelGGL((ipres_kernel<false, false>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, a);
     return (int)hipGetLastError();
 }
 

@@ -163,6 +163,7 @@ def lib():
     L.pwaf_async_poll_geo.argtypes = [vp, C.POINTER(_abi.Completion), C.POINTER(_abi.Geo), C.c_size_t]
     L.pwaf_async_poll_geo.restype = C.c_size_t
     L.pwaf_engine_geo_answer_tables.argtypes = [vp, C.POINTER(C.c_uint32)]
+    L.pwaf_engine_coarse_tables.argtypes = [vp, C.POINTER(C.c_uint32)]
     L.pwaf_geoip_from_mmdb.argtypes = [C.c_char_p, C.c_size_t, C.POINTER(C.POINTER(_abi.GeoipEntry)), C.POINTER(C.c_size_t)]
     L.pwaf_geoip_from_file_image.argtypes = [C.c_char_p, C.c_char_p, C.c_size_t, C.POINTER(C.POINTER(_abi.GeoipEntry)), C.POINTER(C.c_size_t)]
     L.pwaf_zstd_decompress.argtypes = [C.c_char_p, C.c_size_t, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]
@@ -429,6 +430,15 @@ class RuleEngine:
         if rc != 0:
             _raise(rc, lib().pwaf_last_error().decode(errors="replace"))
         return dict(zip(_abi.ADDRESS_TABLE_FIELDS, (int(x) for x in out)))
+
+    def coarse_tables(self) -> dict:
+        """TEST HOOK (pwaf_engine_coarse_tables): the coarse bitmap in front of the summary — present, shift, bytes, blocks set, the
+        summary's blocks set, the lookup kernel's launch shape — by the names of _abi.COARSE_TABLE_FIELDS."""
+        out = (C.c_uint32 * len(_abi.COARSE_TABLE_FIELDS))()
+        rc = lib().pwaf_engine_coarse_tables(self._h, out)
+        if rc != 0:
+            _raise(rc, lib().pwaf_last_error().decode(errors="replace"))
+        return dict(zip(_abi.COARSE_TABLE_FIELDS, (int(x) for x in out)))
 
     def geo_answer_tables(self) -> dict:
         """TEST HOOK (pwaf_engine_geo_answer_tables; OPT_GEO_ANSWERS engines): the shape of the record tables, by the names of
