@@ -517,6 +517,48 @@ int pwaf_evaluate_device_hits(pwaf_engine *, const pwaf_batch *in, pwaf_verdict 
                               uint32_t *n_matches, pwaf_rule_hit *hits, uint32_t hits_cap, uint32_t *n_hits, uint64_t *rule_hits,
                               void *stream);
 
+/* ---- routes (ABI 4, additive; engines created with pwaf_engine_create_routed) -------------------------
+ * After its rule loop the reference hands a request to the first service whose `route:` expression is true or that has none
+ * (http_listener.rs:266-270, services/http_proxy_service.rs:84-95). A route is written in the rules' language over the rules' context; an
+ * execution error and a result that is not a Bool are no match. An engine may be created with an ORDERED list of routes beside its rules;
+ * they are compiled with the rules (shared predicates are evaluated once, a route's host or path literal joins the scan pass the rules'
+ * patterns over that field already run) and answered by the verdict kernel: no launch and no pass over the requests is added.
+ *   route[i] = the index of the first route whose expression is Bool(true) for request i (expression NULL: every request), or
+ *              PWAF_ROUTE_NONE when there is none (the reference answers 404 then).
+ * route[i] is answered for EVERY request, whatever its verdict: gates A and B, Block / Captcha actions, PWAF_FLAG_CAPTCHA_VERIFIED and the
+ * PWAF_OPT_NO_*_GATE flags do not enter it. The reference routes only what it lets through, so the host reads route[i] when out[i].action
+ * lets the request through (PWAF_ACTION_ALLOW) and ignores it otherwise.
+ * Creation: header names (http_request.headers["x"]) are collected over the rules and then the routes, before anything is compiled. In
+ * pwaf_compile_error.rule_index, pwaf_program_rule_status and pwaf_engine_rule_errors route k stands at index n_rules + k (the routes'
+ * entries follow the rules'; a message about a route begins "route #k"). A route neither compiler can take fails creation
+ * (PWAF_E_UNSUPPORTED); under PWAF_OPT_LENIENT it never matches and creation returns PWAF_W_PARTIAL. A route outside the column compiler's
+ * subset runs as a residual program like any rule. Rules plus routes share the limit of 65519 device rules. Routes beside
+ * PWAF_OPT_SPARSE_VERDICT / PWAF_OPT_DENSE_VERDICT are refused (PWAF_E_INVALID_ARG): only the entry-list verdict kernel answers them.
+ * With n_routes == 0 the two functions ARE pwaf_program_compile / pwaf_engine_create: same program, same dump, same engine.
+ * Evaluation: `route` (n entries) lives where `out` lives. route == NULL: each function is exactly its plain counterpart — same launches,
+ * same copies — and so are the plain entry points on an engine with routes. A non-NULL route on an engine created without routes returns
+ * PWAF_E_UNSUPPORTED and launches nothing. A batch the synchronous entry points run again for its overflow pool answers its routes again.
+ * Out of scope: pwaf_evaluate_records, pwaf_batcher_*, pwaf_async_*, pwaf_node_* and the _geo / _hits variants (an engine may have routes
+ * and those flags together: one call answers one of the reports). */
+#define PWAF_ROUTE_NONE 0xFFFFFFFFu
+typedef struct pwaf_route_desc {
+    const char *name;       /* NUL-terminated, for diagnostics (nullable) */
+    const char *expression; /* NUL-terminated; NULL = matches every request */
+    uint64_t reserved;      /* 0 */
+} pwaf_route_desc;          /* 24 bytes */
+int pwaf_program_compile_routed(const pwaf_rule_desc *rules, size_t n_rules, const pwaf_route_desc *routes, size_t n_routes,
+                                const pwaf_list_desc *lists, size_t n_lists, const pwaf_geoip_table *geoip, const pwaf_options *opts,
+                                pwaf_program **out, pwaf_compile_error *err);
+int pwaf_engine_create_routed(const pwaf_rule_desc *rules, size_t n_rules, const pwaf_route_desc *routes, size_t n_routes,
+                              const pwaf_list_desc *lists, size_t n_lists, const pwaf_geoip_table *geoip, const pwaf_options *opts,
+                              pwaf_engine **out, pwaf_compile_error *err);
+uint32_t pwaf_engine_route_count(const pwaf_engine *);   /* the routes the engine was created with (0: none; also for NULL) */
+uint32_t pwaf_program_route_count(const pwaf_program *);
+int pwaf_evaluate_batch_routes(pwaf_engine *, const pwaf_batch *in, pwaf_verdict *out, pwaf_counts *counts, uint32_t *route /* n, nullable */);
+int pwaf_evaluate_device_routes(pwaf_engine *, const pwaf_batch *in, pwaf_verdict *out, pwaf_counts *counts, uint32_t *match_idx,
+                                uint32_t *n_matches, uint32_t *route /* n, device memory, nullable */, void *stream);
+int pwaf_evaluate_one_route(pwaf_engine *, const pwaf_request *req, pwaf_verdict *out, uint32_t *route /* nullable */);
+
 /* ---- measurement ------------------------------------------------------------------------- */
 typedef struct pwaf_kernel_time {
     char name[48];
@@ -545,7 +587,8 @@ int pwaf_engine_stats(const pwaf_engine *, pwaf_stats *out);
  * the context's schema being fixed — are reported ONCE at creation (pwaf_program_warning: "can never match"). What remains are
  * run-time errors of rules on the per-request interpreter (checked arithmetic: overflow, division by zero; an index computed from a
  * request value): counted on the device. counts[i] = requests, over every batch this engine has evaluated, for which caller rule i
- * ended in an execution error. Waits for the device. */
+ * ended in an execution error. Waits for the device. (An engine with routes: n_rules + n_routes counters may be asked for, the routes'
+ * following the rules'; asking for n_rules gives the rules' alone.) */
 int pwaf_engine_rule_errors(pwaf_engine *, uint64_t *counts, size_t n_rules);
 /* How the engine evaluates the rules outside the column compiler's subset (the reference: Program::execute on every request,
  * pingoo/rules.rs:37-51): 0 = the rule set has none, 1 = interpreted per request on the device (residual_kernel),

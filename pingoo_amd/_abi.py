@@ -31,6 +31,7 @@ OPT_RULE_HITS = 131072  # the engine can report every rule that matches a reques
 W_PARTIAL = 1
 MEM_HOST, MEM_DEVICE = 0, 1
 FLAG_CAPTCHA_VERIFIED = 1
+ROUTE_NONE = 0xFFFFFFFF  # PWAF_ROUTE_NONE: no route matches the request (pwaf_evaluate_*_routes)
 N_FIELDS = 5
 FIELD_NAMES = ("host", "url", "path", "method", "user_agent")
 ARENA_PAD = 16
@@ -51,6 +52,12 @@ class RuleDesc(C.Structure):
         ("n_actions", C.c_uint32),
         ("reserved", C.c_uint32),
     ]
+
+
+class RouteDesc(C.Structure):
+    """pwaf_route_desc: one route of an engine created with routes (expression None = matches every request)."""
+
+    _fields_ = [("name", C.c_char_p), ("expression", C.c_char_p), ("reserved", C.c_uint64)]
 
 
 class ListDesc(C.Structure):
@@ -211,6 +218,17 @@ def marshal_rules(rules, m):
         arr[i].n_actions = len(actions)
     m.keep.append(arr)
     return arr, len(rules)
+
+
+def marshal_routes(routes, m):
+    """routes: iterable of (name, expression-or-None) -> (RouteDesc array, n)."""
+    routes = list(routes)
+    arr = (RouteDesc * max(1, len(routes)))()
+    for i, (name, expr) in enumerate(routes):
+        arr[i].name = name.encode() if isinstance(name, str) else name
+        arr[i].expression = None if expr is None else (expr.encode() if isinstance(expr, str) else expr)
+    m.keep.append(arr)
+    return arr, len(routes)
 
 
 def marshal_lists(lists, m):

@@ -1062,6 +1062,10 @@ int compile_program(const CompileInput &in, std::unique_ptr<Program> &out, pwaf_
         set_err(err, PWAF_E_INVALID_ARG, 0xFFFFFFFFu, "PWAF_OPT_RULE_HITS cannot be combined with PWAF_OPT_SPARSE_VERDICT or PWAF_OPT_DENSE_VERDICT: only the entry-list verdict kernel reports rule hits");
         return PWAF_E_INVALID_ARG;
     }
+    if (in.n_routes && (P.flags & (PWAF_OPT_SPARSE_VERDICT | PWAF_OPT_DENSE_VERDICT))) {
+        set_err(err, PWAF_E_INVALID_ARG, 0xFFFFFFFFu, "routes cannot be combined with PWAF_OPT_SPARSE_VERDICT or PWAF_OPT_DENSE_VERDICT: only the entry-list verdict kernel answers routes");
+        return PWAF_E_INVALID_ARG;
+    }
     if (max_table_bytes < 1024) {
         set_err(err, PWAF_E_INVALID_ARG, 0xFFFFFFFFu, "max_table_bytes must be at least 1 KiB");
         return PWAF_E_INVALID_ARG;
@@ -1123,8 +1127,15 @@ int compile_program(const CompileInput &in, std::unique_ptr<Program> &out, pwaf_
         int t_root;
         uint32_t public_idx;
         uint8_t eff_unverified, eff_verified;
+        uint32_t src;  // index among the caller's rules followed by its routes (what rule_status, the error counters and a compile error name); 0xFFFFFFFF: a gate
     };
     std::vector<RuleOut> routs;
+    // The caller's routes are compiled as further rules behind its rules (source index n_rules + k): same language, same context, same
+    // atoms. They decide no verdict (effects {ALLOW, ALLOW}); the verdict kernel's ROUTES variant picks each request's first one.
+    const size_t n_src = in.n_rules + in.n_routes;
+    auto is_route = [&](size_t k) { return k >= in.n_rules; };
+    auto src_expr = [&](size_t k) { return is_route(k) ? in.routes[k - in.n_rules].expression : in.rules[k].expression; };
+    auto src_label = [&](size_t k) { return (is_route(k) ? "route #" : "rule #") + std::to_string(is_route(k) ? k - in.n_rules : k); };
 
     // ---- pseudo rules: gates A and B (http_listener.rs:196-204) ----
     if (!(P.flags & PWAF_OPT_NO_UA_GATE)) {
@@ -1132,23 +1143,24 @@ int compile_program(const CompileInput &in, std::unique_ptr<Program> &out, pwaf_
         ua.k = SVal::LEN;
         ua.field = PWAF_FIELD_USER_AGENT;
         TF empty = rc.int_cmp_atom(ua, OP_EQ, 0), big = rc.int_cmp_atom(ua, OP_GE, 256);
-        routs.push_back({dag.Or(empty.t, big.t), PWAF_RULE_UA_GATE, PWAF_ACTION_BLOCK, PWAF_ACTION_BLOCK});
+        routs.push_back({dag.Or(empty.t, big.t), PWAF_RULE_UA_GATE, PWAF_ACTION_BLOCK, PWAF_ACTION_BLOCK, 0xFFFFFFFFu});
     }
     if (!(P.flags & PWAF_OPT_NO_CAPTCHA_BYPASS)) {
         SVal path;
         path.k = SVal::FIELD;
         path.field = PWAF_FIELD_PATH;
         TF t = rc.string_atom(path, RuleCompiler::anchored(rx_literal("/__pingoo/captcha"), true, false));
-        routs.push_back({t.t, PWAF_RULE_CAPTCHA_ENDPOINT, PWAF_ACTION_BYPASS, PWAF_ACTION_BYPASS});
+        routs.push_back({t.t, PWAF_RULE_CAPTCHA_ENDPOINT, PWAF_ACTION_BYPASS, PWAF_ACTION_BYPASS, 0xFFFFFFFFu});
     }
 
     // ---- user rules ----
     P.n_user_rules = (uint32_t)in.n_rules;
-    P.rule_status.assign(in.n_rules, {PWAF_OK, std::string()});
+    P.n_routes = (uint32_t)in.n_routes;
+    P.rule_status.assign(n_src, {PWAF_OK, std::string()});  // the rules', then the routes'
     const bool strict = !(P.flags & PWAF_OPT_LENIENT);
     auto unsupported_rule = [&](size_t k, const std::string &why) {
         P.rule_status[k] = {PWAF_E_UNSUPPORTED, why};
-        P.warnings.push_back("rule #" + std::to_string(k) + " is NOT evaluated (it never matches): " + why);
+        P.warnings.push_back(src_label(k) + " is NOT evaluated (it never matches): " + why);
     };
     // A rule the column compiler cannot take is lowered WHOLE to a stack program for the residual interpreter (residual.h): it
     // becomes ONE atom whose column residual_kernel fills per request. Only what that compiler refuses as well stays unsupported.
@@ -1159,7 +1171,7 @@ int compile_program(const CompileInput &in, std::unique_ptr<Program> &out, pwaf_
         rl.name = l.name; rl.type = l.type; rl.strs = l.strs; rl.ints = l.ints; rl.nets = l.nets;
         rlists.push_back(std::move(rl));
     }
-    std::vector<Syntax> syntaxes(in.n_rules);
+    std::vector<Syntax> syntaxes(n_src);
     // EXTENSION: the headers map holds the names the WHOLE rule set mentions with a literal key. They are collected
     // before any rule is compiled — the oracle's rule and order (collect_header_names) — so that the set is CLOSED when a rule needs the
     // map as a value (a computed key into http_request / http_request.headers, length() of the headers map: residual.cpp). A syntax
@@ -1167,11 +1179,11 @@ int compile_program(const CompileInput &in, std::unique_ptr<Program> &out, pwaf_
     bool headers_closed = true;
     {
         std::vector<std::string> names;
-        for (size_t k = 0; k < in.n_rules; k++) {
-            if (!in.rules[k].expression) continue;
+        for (size_t k = 0; k < n_src; k++) {  // over the rules, then the routes
+            if (!src_expr(k)) continue;
             Syntax syn;
             std::string perr;
-            if (!parse_expression(in.rules[k].expression, syn, perr)) { headers_closed = false; break; }
+            if (!parse_expression(src_expr(k), syn, perr)) { headers_closed = false; break; }
             collect_header_names(syn, names);
         }
         if (names.size() > kMaxHeaders) headers_closed = false;  // (the rule that mentions one name too many is refused below, as before)
@@ -1189,12 +1201,21 @@ int compile_program(const CompileInput &in, std::unique_ptr<Program> &out, pwaf_
         a.kind = ATOM_RESIDUAL;
         a.ref = (uint32_t)idx;
         a.key = "R" + std::to_string(idx);
-        P.warnings.push_back("rule #" + std::to_string(k) + " has no column form and is lowered to a residual program (compiled for the device when an engine is created, else run by the per-request residual interpreter): " + col_why);
+        P.warnings.push_back(src_label(k) + " has no column form and is lowered to a residual program (compiled for the device when an engine is created, else run by the per-request residual interpreter): " + col_why);
         return rc.intern_atom(std::move(a));
     };
-    for (size_t k = 0; k < in.n_rules; k++) {
-        const pwaf_rule_desc &rd = in.rules[k];
-        std::string rname = rd.name ? rd.name : ("#" + std::to_string(k));
+    for (size_t k = 0; k < n_src; k++) {
+        const bool route = is_route(k);
+        pwaf_rule_desc rd{};  // (a route: no actions)
+        if (route) {
+            rd.name = in.routes[k - in.n_rules].name;
+            rd.expression = in.routes[k - in.n_rules].expression;
+        } else {
+            rd = in.rules[k];
+        }
+        // (a message about a route begins "route #k")
+        std::string rname = route ? "#" + std::to_string(k - in.n_rules) + (rd.name ? std::string(" (") + rd.name + ")" : std::string()) : rd.name ? rd.name : ("#" + std::to_string(k));
+        const std::string what = route ? "route " : "rule ";
         uint8_t eff_u = PWAF_ACTION_ALLOW, eff_v = PWAF_ACTION_ALLOW;
         for (uint32_t a = 0; a < rd.n_actions; a++) {
             uint8_t act = rd.actions[a];
@@ -1211,14 +1232,14 @@ int compile_program(const CompileInput &in, std::unique_ptr<Program> &out, pwaf_
             Syntax &syn = syntaxes[k];
             std::string perr;
             if (!parse_expression(rd.expression, syn, perr)) {
-                set_err(err, PWAF_E_SYNTAX, (uint32_t)k, "error parsing rules: Expression is not valid: " + perr + " (rule " + rname + ")");
+                set_err(err, PWAF_E_SYNTAX, (uint32_t)k, route ? "route " + rname + ": Expression is not valid: " + perr : "error parsing rules: Expression is not valid: " + perr + " (rule " + rname + ")");
                 return PWAF_E_SYNTAX;
             }
             rc.syn = &syn;
             try {
                 SVal v = rc.lower(syn.root);
                 if (v.k == SVal::ERR) {
-                    P.warnings.push_back("rule " + rname + ": expression always fails at run time (" + v.emsg + "): the rule can never match");
+                    P.warnings.push_back(what + rname + ": expression always fails at run time (" + v.emsg + "): the rule can never match");
                     t_root = 0;
                 } else if (v.k == SVal::BOOLX) {
                     t_root = v.tf.t;
@@ -1226,7 +1247,7 @@ int compile_program(const CompileInput &in, std::unique_ptr<Program> &out, pwaf_
                     t_root = v.c.b ? 1 : 0;
                 } else {
                     // a non-Bool result never equals Bool(true) (pingoo/rules.rs:47)
-                    P.warnings.push_back("rule " + rname + ": expression does not evaluate to a Bool: the rule can never match");
+                    P.warnings.push_back(what + rname + ": expression does not evaluate to a Bool: the rule can never match");
                     t_root = 0;
                 }
             } catch (Unsupported &u) {
@@ -1236,19 +1257,20 @@ int compile_program(const CompileInput &in, std::unique_ptr<Program> &out, pwaf_
                     t_root = dag.atom(ra);
                 } else {
                     if (strict) {
-                        set_err(err, PWAF_E_UNSUPPORTED, (uint32_t)k, "rule " + rname + ": " + why);
+                        set_err(err, PWAF_E_UNSUPPORTED, (uint32_t)k, what + rname + ": " + why);
                         return PWAF_E_UNSUPPORTED;
                     }
-                    unsupported_rule(k, "rule " + rname + ": " + why);
+                    unsupported_rule(k, what + rname + ": " + why);
                     t_root = 0;
                 }
             }
         }
         // no action can ever take effect: the rule decides nothing. PWAF_OPT_RULE_HITS keeps it, with effects {ALLOW, ALLOW} — an observe-only
         // rule, matched and reported (the verdict kernel's action mask is 0 for it: it never fires)
-        if (eff_u == PWAF_ACTION_ALLOW && eff_v == PWAF_ACTION_ALLOW && !(P.flags & PWAF_OPT_RULE_HITS)) continue;
+        // (a route is kept as well: it decides no verdict, and the verdict kernel's ROUTES variant reads its match word)
+        if (eff_u == PWAF_ACTION_ALLOW && eff_v == PWAF_ACTION_ALLOW && !(P.flags & PWAF_OPT_RULE_HITS) && !route) continue;
         if (t_root == 0) continue;                                                 // can never match
-        routs.push_back({t_root, (uint32_t)k, eff_u, eff_v});
+        routs.push_back({t_root, (uint32_t)(route ? k - in.n_rules : k), eff_u, eff_v, (uint32_t)k});
     }
 
     // ---- DNF per rule (over source atom indices) ----
@@ -1258,7 +1280,7 @@ int compile_program(const CompileInput &in, std::unique_ptr<Program> &out, pwaf_
         try {
             rule_terms.push_back(dnf.conv(r.t_root, false));
         } catch (Unsupported &u) {
-            uint32_t idx = r.public_idx < in.n_rules ? r.public_idx : 0xFFFFFFFFu;
+            uint32_t idx = r.src;
             std::string why = u.msg;
             const int ra = idx != 0xFFFFFFFFu ? try_residual(idx, u.msg, why) : -1;
             if (ra >= 0) {
@@ -1266,10 +1288,10 @@ int compile_program(const CompileInput &in, std::unique_ptr<Program> &out, pwaf_
                 continue;
             }
             if (strict || idx == 0xFFFFFFFFu) {
-                set_err(err, PWAF_E_UNSUPPORTED, idx, "rule #" + std::to_string(r.public_idx) + ": " + why);
+                set_err(err, PWAF_E_UNSUPPORTED, idx, (idx == 0xFFFFFFFFu ? "rule #" + std::to_string(r.public_idx) : src_label(idx)) + ": " + why);
                 return PWAF_E_UNSUPPORTED;
             }
-            unsupported_rule(idx, why);
+            unsupported_rule(idx, (is_route(idx) ? src_label(idx) + ": " : std::string()) + why);  // (a message about a route begins "route #k")
             rule_terms.push_back({});  // no term: never matches
         }
     }
@@ -1401,8 +1423,8 @@ int compile_program(const CompileInput &in, std::unique_ptr<Program> &out, pwaf_
                     for (auto &ba : bad_atoms)
                         if ((l >> 1) == ba.first) why = &ba.second;
             if (!why) continue;
-            const uint32_t idx = routs[k].public_idx < in.n_rules ? routs[k].public_idx : 0xFFFFFFFFu;
-            std::string why2 = *why;
+            const uint32_t idx = routs[k].src;
+            std::string why2 = (idx != 0xFFFFFFFFu && is_route(idx) ? src_label(idx) + ": " : std::string()) + *why;
             const int ra = idx != 0xFFFFFFFFu ? try_residual(idx, *why, why2) : -1;
             if (ra >= 0) {  // (the interpreter walks a DFA of the pattern alone, within a budget of its own)
                 rule_terms[k] = {Term{(uint32_t)ra << 1}};
@@ -1521,7 +1543,10 @@ int compile_program(const CompileInput &in, std::unique_ptr<Program> &out, pwaf_
         }
 
     // ---- rules -> literal lists over device columns ----
+    P.route_base = 0xFFFFFFFFu;
     for (size_t k = 0; k < routs.size(); k++) {
+        const bool route = routs[k].src != 0xFFFFFFFFu && is_route(routs[k].src);
+        if (route && P.route_base == 0xFFFFFFFFu) P.route_base = (uint32_t)P.rules.size();  // (the routes stand behind every rule)
         DevRule dr{};
         dr.lit_off = (uint32_t)P.lits.size();
         dr.public_idx = routs[k].public_idx;
@@ -1543,6 +1568,8 @@ int compile_program(const CompileInput &in, std::unique_ptr<Program> &out, pwaf_
         if (dr.lit_cnt == 0) continue;  // constant false after simplification
         P.rules.push_back(dr);
     }
+    if (P.route_base == 0xFFFFFFFFu) P.route_base = (uint32_t)P.rules.size();  // no route, or none that can match: an empty range
+    P.n_dev_routes = (uint32_t)P.rules.size() - P.route_base;
 
     // ---- ip lists -> membership-set trie ----
     P.n_ip_lists = (uint32_t)n_ip_lists;
@@ -1703,6 +1730,12 @@ std::vector<uint8_t> dump_program(const Program &p) {
         const uint32_t rs[2] = {p.n_residual, p.residual_base};
         w.section("RSDL", 2, rs, sizeof rs);
         w.section("RVMB", p.n_residual, p.residual_blob.data(), p.residual_blob.size());  // the residual interpreter's program image (residual.h)
+    }
+    if (p.n_routes) {
+        // the route range: device rules [route_base, route_base + n_dev_routes) are the caller's routes that can match, in route order;
+        // their public_idx is the route's index. (Only a routed program has the section: without routes the dump is what it was.)
+        const uint32_t rt[4] = {p.route_base, p.n_dev_routes, p.n_routes, p.n_user_rules};
+        w.section("ROUT", 4, rt, sizeof rt);
     }
     return w.buf;
 }

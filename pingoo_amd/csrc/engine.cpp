@@ -231,6 +231,7 @@ struct Scratch {
     uint32_t arg_next = 0;
     std::vector<DevBuf> stage_field_data, stage_field_off;  // n_fields each
     DevBuf stage_ip, stage_v6, stage_port, stage_flags, stage_asn, stage_country, stage_out, stage_counts;
+    DevBuf stage_route;  // a large host batch's routes on their way back (pwaf_evaluate_batch_routes)
     DevBuf stage_hits, stage_hit_counts;  // a host batch's rule hits on their way back (PWAF_OPT_RULE_HITS): the list; {n_hits, pad, rule_hits[n_rules]}
     DevBuf stage_geo;  // the GeoIP answers of a large host batch / a host pwaf_geoip_lookup on their way back (PWAF_OPT_GEO_ANSWERS)
     // A SMALL host batch (the micro-batcher's, pwaf_evaluate_one's) travels as ONE block: every column packed into page-locked memory,
@@ -265,7 +266,7 @@ struct Scratch {
     }
     void release() {
         for (DevBuf *b : {&status, &ipres, &rec, &res_words, &err_sink, &pool, &verdict_spill, &zero_block, &gate_lists, &attr, &chunk_bits, &cand_cnt, &need, &pairs, &zero_off, &args, &stage_ip, &stage_v6, &stage_port, &stage_flags,
-                          &stage_asn, &stage_country, &stage_out, &stage_counts, &stage_geo, &stage_hits, &stage_hit_counts})
+                          &stage_asn, &stage_country, &stage_out, &stage_counts, &stage_geo, &stage_hits, &stage_hit_counts, &stage_route})
             b->release();
         for (PinBuf &b : arg_slot) b.release();
         for (hipEvent_t ev : arg_ev)
@@ -313,6 +314,7 @@ struct pwaf_engine {
     DevBuf residual_errors;  // per residual rule: requests whose evaluation ended in an execution error (accumulated; pwaf_engine_rule_errors)
     std::string residual_note;  // why the residual rules are interpreted although specialization was asked for (pwaf_engine_residual_fallback)
     JitKernel residual_jit;  // the specialized residual program (residual_jit.cpp + rtc.cpp); function == nullptr: the rules are interpreted
+    DevBuf rules_unrouted;  // engines with routes and PWAF_OPT_RULE_HITS: `rules` with the routes' literal lists emptied (a hit report names rules only)
     DevBuf residual_blob, geo_rec_root4, geo_rec_root6, geo_rec_nodes;  // residual rules: the program image; the GeoIP trie with RECORD leaves (client.asn / country values)
     DevBuf pass_base, colmask, dir24 /* build-time only: released once compressed */, dir_chunks, dir_vals, dir_summary;
     uint32_t dir_sum_shift = 0, dir_common = 0;  // (VerdictArgs::dir_summary)
@@ -684,15 +686,22 @@ int need_geo_answers(const pwaf_engine *e, const char *fn) {
     return fail(PWAF_E_UNSUPPORTED, std::string(fn) + ": the engine was not created with PWAF_OPT_GEO_ANSWERS");
 }
 
-// PWAF_OPT_RULE_HITS: where a call's rule hits go (include/pwaf.h: pwaf_evaluate_*_hits). All null = nothing asked for.
-struct HitOut {
+// The opt-in report of a call beside its verdicts, where `out` lives: the rule hits (PWAF_OPT_RULE_HITS; include/pwaf.h: pwaf_evaluate_*_hits)
+// OR the routes (engines with routes: pwaf_evaluate_*_routes) — one call answers one of them. All null = nothing asked for.
+struct ReportOut {
     pwaf_rule_hit *hits = nullptr;
     uint32_t cap = 0;
     uint32_t *n_hits = nullptr;
     uint64_t *rule_hits = nullptr;
-    bool any() const { return hits || n_hits || rule_hits; }
+    uint32_t *route = nullptr;  // (engines with routes: pwaf_evaluate_*_routes; never together with the three above)
+    bool hit_any() const { return hits || n_hits || rule_hits; }
+    bool any() const { return hit_any() || route; }
 };
-int check_hit_args(const pwaf_engine *e, const char *fn, const HitOut &h) {
+int need_routes(const pwaf_engine *e, const char *fn) {
+    if (e->prog.p->n_routes) return PWAF_OK;
+    return fail(PWAF_E_UNSUPPORTED, std::string(fn) + ": the engine was created without routes (pwaf_engine_create_routed)");
+}
+int check_hit_args(const pwaf_engine *e, const char *fn, const ReportOut &h) {
     if (!h.any()) return PWAF_OK;
     if (!(e->prog.p->flags & PWAF_OPT_RULE_HITS)) return fail(PWAF_E_UNSUPPORTED, std::string(fn) + ": the engine was not created with PWAF_OPT_RULE_HITS");
     if ((h.hits == nullptr) != (h.n_hits == nullptr)) return fail(PWAF_E_INVALID_ARG, std::string(fn) + ": hits and n_hits must be given together");
@@ -1784,18 +1793,21 @@ struct BatchRun {
 // BatchRun's destructor: the descriptor slot's event is recorded whichever way the batch leaves (ArgSlotMark).
 int run_pipeline(pwaf_engine *e, Scratch &S, const pwaf_batch &db /* device pointers */, pwaf_verdict *d_out, pwaf_counts *d_counts, uint32_t *d_match_idx,
                  uint32_t *d_n_matches, hipStream_t stream, bool totals_known = false, const std::vector<uint32_t> *col_begin = nullptr, bool sync_status = false,
-                 pwaf_geo *d_geo = nullptr, const HitOut *d_hits = nullptr) {
+                 pwaf_geo *d_geo = nullptr, const ReportOut *d_rep = nullptr) {
     if (db.n == 0) return PWAF_OK;
     BatchRun b(e, S, db, stream, col_begin);
     b.d_geo = d_geo;
     int rc;
     if ((rc = b.reserve_scratch(sync_status)) || (rc = b.resolve_columns(totals_known))) return rc;
     if ((rc = b.fill_verdict_args(d_out, d_counts, d_match_idx, d_n_matches))) return rc;
-    if (d_hits && d_hits->any()) {  // (the verdict kernel's rule-hit variant: launch_verdict)
-        b.v.hits = d_hits->hits;
-        b.v.hits_cap = d_hits->cap;
-        b.v.n_hits = d_hits->n_hits;
-        b.v.rule_hits = (unsigned long long *)d_hits->rule_hits;
+    if (d_rep && d_rep->any()) {  // (the verdict kernel's rule-hit variant, or its route variant: launch_verdict)
+        b.v.hits = d_rep->hits;
+        b.v.hits_cap = d_rep->cap;
+        b.v.n_hits = d_rep->n_hits;
+        b.v.rule_hits = (unsigned long long *)d_rep->rule_hits;
+        b.v.route = d_rep->route;
+        b.v.route_base = e->prog.p->route_base;
+        if (d_rep->hit_any() && e->rules_unrouted.p) b.v.rules = (const DevRule *)e->rules_unrouted.p;
     }
     b.pick_list_shapes();
     if ((rc = b.attr_at_start()) || (rc = b.launch_plain_scans())) return rc;
@@ -1836,7 +1848,7 @@ int device_error(const char *call, hipError_t he) { return fail(PWAF_E_DEVICE, s
 // drained before the call returns: what was enqueued may still read the caller's buffers.
 template <class After>
 int run_with_retry(pwaf_engine *e, Scratch &S, const pwaf_batch &db, pwaf_verdict *d_out, pwaf_counts *d_counts, bool known, const std::vector<uint32_t> *begins, bool counts_zero,
-                   After &&after, pwaf_geo *d_geo = nullptr, const HitOut *d_hits = nullptr) {
+                   After &&after, pwaf_geo *d_geo = nullptr, const ReportOut *d_rep = nullptr) {
     const hipStream_t s = S.stream;
     int r = S.pin_status.reserve(16);
     volatile uint32_t *const st = (volatile uint32_t *)S.pin_status.p;
@@ -1844,12 +1856,12 @@ int run_with_retry(pwaf_engine *e, Scratch &S, const pwaf_batch &db, pwaf_verdic
         hipError_t he = hipSuccess;
         if (!r && d_counts && !(counts_zero && attempt == 0) && (he = hipMemsetAsync(d_counts, 0, sizeof *d_counts, s)) != hipSuccess) r = device_error("hipMemsetAsync", he);
         // the rule hits are overwritten like the counters: zeroed before EVERY attempt, so that a batch run again is not counted twice
-        if (!r && d_hits && d_hits->n_hits && (he = hipMemsetAsync(d_hits->n_hits, 0, 4, s)) != hipSuccess) r = device_error("hipMemsetAsync", he);
-        if (!r && d_hits && d_hits->rule_hits && e->prog.p->n_user_rules && (he = hipMemsetAsync(d_hits->rule_hits, 0, (size_t)e->prog.p->n_user_rules * 8, s)) != hipSuccess)
+        if (!r && d_rep && d_rep->n_hits && (he = hipMemsetAsync(d_rep->n_hits, 0, 4, s)) != hipSuccess) r = device_error("hipMemsetAsync", he);
+        if (!r && d_rep && d_rep->rule_hits && e->prog.p->n_user_rules && (he = hipMemsetAsync(d_rep->rule_hits, 0, (size_t)e->prog.p->n_user_rules * 8, s)) != hipSuccess)
             r = device_error("hipMemsetAsync", he);
         if (!r) {
             S.retry = attempt > 0;
-            r = run_pipeline(e, S, db, d_out, d_counts, nullptr, nullptr, s, known, begins, true, d_geo, d_hits);
+            r = run_pipeline(e, S, db, d_out, d_counts, nullptr, nullptr, s, known, begins, true, d_geo, d_rep);
             S.retry = false;
         }
         if (!r) {
@@ -1938,11 +1950,16 @@ int pwaf_validate_expression(const char *expression, char *errbuf, size_t errbuf
 
 int pwaf_program_compile(const pwaf_rule_desc *rules, size_t n_rules, const pwaf_list_desc *lists, size_t n_lists, const pwaf_geoip_table *geoip,
                          const pwaf_options *opts, pwaf_program **out, pwaf_compile_error *err) {
-    if (!out || (n_rules && !rules) || (n_lists && !lists)) return fail(PWAF_E_INVALID_ARG, "NULL argument");
+    return pwaf_program_compile_routed(rules, n_rules, nullptr, 0, lists, n_lists, geoip, opts, out, err);
+}
+// With an ordered list of routes beside the rules (include/pwaf.h: routes). n_routes == 0: nothing differs.
+int pwaf_program_compile_routed(const pwaf_rule_desc *rules, size_t n_rules, const pwaf_route_desc *routes, size_t n_routes, const pwaf_list_desc *lists, size_t n_lists,
+                                const pwaf_geoip_table *geoip, const pwaf_options *opts, pwaf_program **out, pwaf_compile_error *err) {
+    if (!out || (n_rules && !rules) || (n_routes && !routes) || (n_lists && !lists)) return fail(PWAF_E_INVALID_ARG, "NULL argument");
     pwaf_options o;
     int rc = check_opts(opts, o);
     if (rc) return rc;
-    CompileInput in{rules, n_rules, lists, n_lists, geoip, o};
+    CompileInput in{rules, n_rules, routes, n_routes, lists, n_lists, geoip, o};
     pwaf_compile_error ce{};
     ce.rule_index = 0xFFFFFFFFu;
     std::unique_ptr<Program> p;
@@ -1990,11 +2007,18 @@ int pwaf_program_stats(const pwaf_program *p, pwaf_stats *out) {
     return PWAF_OK;
 }
 
+uint32_t pwaf_program_route_count(const pwaf_program *p) { return p && p->p ? p->p->n_routes : 0u; }
+uint32_t pwaf_engine_route_count(const pwaf_engine *e) { return e && e->prog.p ? e->prog.p->n_routes : 0u; }
+
 int pwaf_engine_create(const pwaf_rule_desc *rules, size_t n_rules, const pwaf_list_desc *lists, size_t n_lists, const pwaf_geoip_table *geoip,
                        const pwaf_options *opts, pwaf_engine **out, pwaf_compile_error *err) {
+    return pwaf_engine_create_routed(rules, n_rules, nullptr, 0, lists, n_lists, geoip, opts, out, err);
+}
+int pwaf_engine_create_routed(const pwaf_rule_desc *rules, size_t n_rules, const pwaf_route_desc *routes, size_t n_routes, const pwaf_list_desc *lists, size_t n_lists,
+                              const pwaf_geoip_table *geoip, const pwaf_options *opts, pwaf_engine **out, pwaf_compile_error *err) {
     if (!out) return fail(PWAF_E_INVALID_ARG, "NULL argument");
     pwaf_program *pp = nullptr;
-    int rc = pwaf_program_compile(rules, n_rules, lists, n_lists, geoip, opts, &pp, err);
+    int rc = pwaf_program_compile_routed(rules, n_rules, routes, n_routes, lists, n_lists, geoip, opts, &pp, err);
     if (rc < 0) return rc;
     const int partial = rc;  // PWAF_W_PARTIAL or PWAF_OK
     std::unique_ptr<pwaf_engine> e(new pwaf_engine());
@@ -2179,7 +2203,11 @@ int pwaf_engine_create(const pwaf_rule_desc *rules, size_t n_rules, const pwaf_l
         // column to be non-zero. Per term pick the positive literal least likely to be set (scan < membership < comparison <
         // TRUE) and file the rule under that column; terms made of negations only make the rule an unconditional candidate.
         // (rule indices travel as 16-bit values inside the verdict kernel; 0xFFF0.. is kept for the pseudo rules of the two gates)
-        if (P.rules.size() > 65519 || n_rules > 65519) { fail(PWAF_E_UNSUPPORTED, "more than 65519 rules"); return dev_fail(PWAF_E_UNSUPPORTED); }
+        // (the caller's routes are device rules too: rules and routes share the limit)
+        if (P.rules.size() > 65519 || n_rules + n_routes > 65519) {
+            fail(PWAF_E_UNSUPPORTED, n_routes ? "more than 65519 rules and routes" : "more than 65519 rules");
+            return dev_fail(PWAF_E_UNSUPPORTED);
+        }
         // lower = rarer: scan atoms by how specific their pattern is (shortest possible match), then memberships, then
         // comparisons (often true for most requests), then the constant TRUE column
         std::vector<uint32_t> rank(P.n_cols, 100);
@@ -2286,6 +2314,13 @@ int pwaf_engine_create(const pwaf_rule_desc *rules, size_t n_rules, const pwaf_l
         UP(country_luts, masks)
     }
     UP(rules, P.rules)
+    if (P.n_dev_routes && (P.flags & PWAF_OPT_RULE_HITS)) {
+        // The HITS variant of the verdict kernel reports every candidate's match word under its public index; a route's is its ROUTE index.
+        // A hit call therefore runs over a copy of the rule table in which the routes have no literal: their word is 0, nothing is reported.
+        std::vector<DevRule> unrouted = P.rules;
+        for (size_t k = P.route_base; k < unrouted.size(); k++) unrouted[k].lit_cnt = 0;
+        UP(rules_unrouted, unrouted)
+    }
     UP(set_masks, P.set_masks)
     UP(ip_root4, P.ipset_trie.root4)
     UP(ip_root6, P.ipset_trie.root6)
@@ -2426,7 +2461,7 @@ int pwaf_engine_create(const pwaf_rule_desc *rules, size_t n_rules, const pwaf_l
 void pwaf_engine_destroy(pwaf_engine *e) {
     if (!e) return;
     for (auto &g : e->groups) { for (DevBuf *b : {&g.tab, &g.classmap, &g.special, &g.list_off, &g.list, &g.ftable, &g.c_head, &g.c_entries, &g.c_bytes, &g.c_classes}) b->release(); g.fl.release(); g.rt.release(); }
-    for (DevBuf *b : {&e->num_atoms, &e->lazy_atoms, &e->bit_atoms, &e->trig_off, &e->trig_rules, &e->always_rules, &e->iu_vals[0], &e->iu_vals[1], &e->iu_masks[0], &e->iu_masks[1], &e->country_luts, &e->rules, &e->lits,
+    for (DevBuf *b : {&e->num_atoms, &e->lazy_atoms, &e->bit_atoms, &e->trig_off, &e->trig_rules, &e->always_rules, &e->iu_vals[0], &e->iu_vals[1], &e->iu_masks[0], &e->iu_masks[1], &e->country_luts, &e->rules, &e->rules_unrouted, &e->lits,
                       &e->set_masks, &e->ip_root4, &e->ip_root6, &e->ip_nodes, &e->geo_root4, &e->geo_root6, &e->geo_nodes, &e->geo_recs, &e->residual_blob, &e->residual_errors, &e->geo_rec_root4, &e->geo_rec_root6, &e->geo_rec_nodes, &e->pass_base, &e->colmask, &e->dir24, &e->dir_chunks, &e->dir_vals, &e->dir_summary, &e->dir_coarse, &e->class_rows,
                       &e->dir_esc, &e->leaf_root, &e->geo_leaf_root, &e->pass_table, &e->georec_chunks, &e->georec_vals, &e->georec_summary})
         b->release();
@@ -2577,7 +2612,7 @@ int pwaf_program_confirm_field(const pwaf_program *p, uint32_t group, const uint
 }  // extern "C"
 namespace {
 int evaluate_device_impl(pwaf_engine *e, const pwaf_batch *in, pwaf_verdict *out, pwaf_counts *counts, uint32_t *match_idx, uint32_t *n_matches, pwaf_geo *geo, void *stream,
-                         const HitOut *hits = nullptr) {
+                         const ReportOut *rep = nullptr) {
     int rc = validate_batch_header(in);
     if (rc) return rc;
     if (in->memory != PWAF_MEM_DEVICE) return fail(PWAF_E_INVALID_ARG, "pwaf_evaluate_device needs a DEVICE batch");
@@ -2590,27 +2625,30 @@ int evaluate_device_impl(pwaf_engine *e, const pwaf_batch *in, pwaf_verdict *out
     Scratch &S = acquire_context(e, false, (hipStream_t)stream, lock, must_wait);
     if ((rc = S.ensure(false))) return rc;
     if (must_wait) HIP_TRY(hipStreamWaitEvent((hipStream_t)stream, S.done, 0));
-    rc = run_pipeline(e, S, *in, out, counts, match_idx, n_matches, (hipStream_t)stream, false, nullptr, false, geo, hits);
+    rc = run_pipeline(e, S, *in, out, counts, match_idx, n_matches, (hipStream_t)stream, false, nullptr, false, geo, rep);
     const hipError_t he = mark_context_used(S, (hipStream_t)stream, false);
     return he != hipSuccess ? device_error("hipEventRecord", he) : rc;
 }
 
 // `geo` (nullable; PWAF_OPT_GEO_ANSWERS engines only): the GeoIP record of every request, where `out` lives
-// `hits` (nullable; PWAF_OPT_RULE_HITS engines only): the call's rule hits, where `out` lives; overwritten
-int evaluate_batch_impl(pwaf_engine *e, const pwaf_batch *in, pwaf_verdict *out, pwaf_counts *counts, pwaf_geo *geo, const HitOut *hits = nullptr) {
+// `rep` (nullable): the call's report — rule hits (PWAF_OPT_RULE_HITS engines; overwritten) or routes (engines with routes) — where `out` lives
+int evaluate_batch_impl(pwaf_engine *e, const pwaf_batch *in, pwaf_verdict *out, pwaf_counts *counts, pwaf_geo *geo, const ReportOut *rep = nullptr) {
     int rc = validate_batch_header(in);
     if (rc) return rc;
-    if (hits && !hits->any()) hits = nullptr;
+    if (rep && !rep->any()) rep = nullptr;
+    uint32_t *const route = rep ? rep->route : nullptr;  // (nullable; engines with routes only) every request's route, where `out` lives
+    const bool want_hits = rep && rep->hit_any();
     const size_t rule_hit_bytes = (size_t)e->prog.p->n_user_rules * 8;
     if (in->n == 0) {
         if (counts && in->memory == PWAF_MEM_HOST) memset(counts, 0, sizeof *counts);
-        if (hits && in->memory == PWAF_MEM_HOST) {
-            if (hits->n_hits) *hits->n_hits = 0;
-            if (hits->rule_hits) memset(hits->rule_hits, 0, rule_hit_bytes);
-        } else if (hits) {
+        if (!want_hits) return PWAF_OK;
+        if (in->memory == PWAF_MEM_HOST) {
+            if (rep->n_hits) *rep->n_hits = 0;
+            if (rep->rule_hits) memset(rep->rule_hits, 0, rule_hit_bytes);
+        } else {
             HIP_TRY(hipSetDevice(e->device));
-            if (hits->n_hits) HIP_TRY(hipMemset(hits->n_hits, 0, 4));
-            if (hits->rule_hits && rule_hit_bytes) HIP_TRY(hipMemset(hits->rule_hits, 0, rule_hit_bytes));
+            if (rep->n_hits) HIP_TRY(hipMemset(rep->n_hits, 0, 4));
+            if (rep->rule_hits && rule_hit_bytes) HIP_TRY(hipMemset(rep->rule_hits, 0, rule_hit_bytes));
         }
         return PWAF_OK;
     }
@@ -2622,31 +2660,31 @@ int evaluate_batch_impl(pwaf_engine *e, const pwaf_batch *in, pwaf_verdict *out,
     if ((rc = S.ensure(true))) return rc;
     hipStream_t s = S.stream;
     if (must_wait) HIP_TRY(hipStreamWaitEvent(s, S.done, 0));
-    if (in->memory == PWAF_MEM_DEVICE) return run_with_retry(e, S, *in, out, counts, false, nullptr, false, [] { return PWAF_OK; }, geo, hits);
+    if (in->memory == PWAF_MEM_DEVICE) return run_with_retry(e, S, *in, out, counts, false, nullptr, false, [] { return PWAF_OK; }, geo, rep);
     // a HOST batch's rule hits: produced into staging buffers of the context ({n_hits, pad, rule_hits[]}; the list), fetched once the batch is
     // done and the number of entries is known — only the entries the batch wrote travel, the rest of the caller's list is left alone
-    HitOut dh;
-    if (hits) {
-        if ((rc = S.stage_hit_counts.reserve(8 + rule_hit_bytes)) || (rc = S.stage_hits.reserve(std::max<size_t>(16, (size_t)hits->cap * sizeof(pwaf_rule_hit))))) return rc;
-        if (hits->n_hits) {
+    ReportOut dh;
+    if (want_hits) {
+        if ((rc = S.stage_hit_counts.reserve(8 + rule_hit_bytes)) || (rc = S.stage_hits.reserve(std::max<size_t>(16, (size_t)rep->cap * sizeof(pwaf_rule_hit))))) return rc;
+        if (rep->n_hits) {
             dh.hits = (pwaf_rule_hit *)S.stage_hits.p;
-            dh.cap = hits->cap;
+            dh.cap = rep->cap;
             dh.n_hits = (uint32_t *)S.stage_hit_counts.p;
         }
-        if (hits->rule_hits) dh.rule_hits = (uint64_t *)((char *)S.stage_hit_counts.p + 8);
+        if (rep->rule_hits) dh.rule_hits = (uint64_t *)((char *)S.stage_hit_counts.p + 8);
     }
-    const HitOut *const d_hits = hits ? &dh : nullptr;
+    const ReportOut *const d_rep = rep ? &dh : nullptr;
     auto fetch_hits = [&](int code) -> int {
-        if (code || !hits) return code;
+        if (code || !want_hits) return code;
         std::vector<uint64_t> back(1 + rule_hit_bytes / 8);
         HIP_TRY(hipMemcpyAsync(back.data(), S.stage_hit_counts.p, back.size() * 8, hipMemcpyDeviceToHost, s));
         HIP_TRY(hipStreamSynchronize(s));
-        if (hits->rule_hits && rule_hit_bytes) memcpy(hits->rule_hits, back.data() + 1, rule_hit_bytes);
-        if (hits->n_hits) {
-            const uint32_t total = (uint32_t)back[0], got = std::min(total, hits->cap);
-            *hits->n_hits = total;
+        if (rep->rule_hits && rule_hit_bytes) memcpy(rep->rule_hits, back.data() + 1, rule_hit_bytes);
+        if (rep->n_hits) {
+            const uint32_t total = (uint32_t)back[0], got = std::min(total, rep->cap);
+            *rep->n_hits = total;
             if (got) {
-                HIP_TRY(hipMemcpyAsync(hits->hits, S.stage_hits.p, (size_t)got * sizeof(pwaf_rule_hit), hipMemcpyDeviceToHost, s));
+                HIP_TRY(hipMemcpyAsync(rep->hits, S.stage_hits.p, (size_t)got * sizeof(pwaf_rule_hit), hipMemcpyDeviceToHost, s));
                 HIP_TRY(hipStreamSynchronize(s));
             }
         }
@@ -2711,6 +2749,7 @@ int evaluate_batch_impl(pwaf_engine *e, const pwaf_batch *in, pwaf_verdict *out,
     const size_t in_bytes = pk.size();
     const size_t at_out = pk.take((size_t)n * sizeof(pwaf_verdict));
     const size_t at_geo = geo ? pk.take((size_t)n * sizeof(pwaf_geo)) : 0;  // (returns with the verdicts)
+    const size_t at_route = route ? pk.take((size_t)n * 4) : 0;             // (the same)
     const size_t need = pk.size();
     if (packable && need <= kPackMax && !switches().no_packed_staging) {
         if ((rc = validate())) return rc;
@@ -2740,12 +2779,14 @@ int evaluate_batch_impl(pwaf_engine *e, const pwaf_batch *in, pwaf_verdict *out,
         pwaf_verdict *const d_out = (pwaf_verdict *)((char *)S.packed.p + at_out);
         pwaf_counts *const d_counts = (pwaf_counts *)((char *)S.packed.p + at_counts);
         const size_t back = need - at_counts;
+        if (route) dh.route = (uint32_t *)((char *)S.packed.p + at_route);
         rc = run_with_retry(e, S, dv.db, d_out, d_counts, true, &col_begin, true, [&]() -> int {
             HIP_TRY(hipMemcpyAsync(S.pin_out.p, d_counts, back, hipMemcpyDeviceToHost, s));
             return PWAF_OK;
-        }, geo ? (pwaf_geo *)((char *)S.packed.p + at_geo) : nullptr, d_hits);
+        }, geo ? (pwaf_geo *)((char *)S.packed.p + at_geo) : nullptr, d_rep);
         if ((rc = fetch_hits(rc))) return rc;
         if (geo) memcpy(geo, (const char *)S.pin_out.p + (at_geo - at_counts), (size_t)n * sizeof(pwaf_geo));
+        if (route) memcpy(route, (const char *)S.pin_out.p + (at_route - at_counts), (size_t)n * 4);
         memcpy(out, (const char *)S.pin_out.p + (at_out - at_counts), (size_t)n * sizeof(pwaf_verdict));
         if (counts) memcpy(counts, S.pin_out.p, sizeof(pwaf_counts));
         return PWAF_OK;
@@ -2784,13 +2825,18 @@ int evaluate_batch_impl(pwaf_engine *e, const pwaf_batch *in, pwaf_verdict *out,
     if ((rc = S.stage_out.reserve((size_t)n * sizeof(pwaf_verdict)))) return bail(rc);
     if ((rc = S.stage_counts.reserve(sizeof(pwaf_counts)))) return bail(rc);
     if (geo && (rc = S.stage_geo.reserve((size_t)n * sizeof(pwaf_geo)))) return bail(rc);
+    if (route) {
+        if ((rc = S.stage_route.reserve((size_t)n * 4))) return bail(rc);
+        dh.route = (uint32_t *)S.stage_route.p;
+    }
     if ((rc = validate())) return bail(rc);
     return fetch_hits(run_with_retry(e, S, dv.db, (pwaf_verdict *)S.stage_out.p, (pwaf_counts *)S.stage_counts.p, true, &col_begin, false, [&]() -> int {
         HIP_TRY(hipMemcpyAsync(out, S.stage_out.p, (size_t)n * sizeof(pwaf_verdict), hipMemcpyDeviceToHost, s));
         if (counts) HIP_TRY(hipMemcpyAsync(counts, S.stage_counts.p, sizeof(pwaf_counts), hipMemcpyDeviceToHost, s));
         if (geo) HIP_TRY(hipMemcpyAsync(geo, S.stage_geo.p, (size_t)n * sizeof(pwaf_geo), hipMemcpyDeviceToHost, s));
+        if (route) HIP_TRY(hipMemcpyAsync(route, S.stage_route.p, (size_t)n * 4, hipMemcpyDeviceToHost, s));
         return PWAF_OK;
-    }, geo ? (pwaf_geo *)S.stage_geo.p : nullptr, d_hits));
+    }, geo ? (pwaf_geo *)S.stage_geo.p : nullptr, d_rep));
 }
 }  // namespace
 
@@ -2814,7 +2860,7 @@ int pwaf_evaluate_batch(pwaf_engine *e, const pwaf_batch *in, pwaf_verdict *out,
 int pwaf_evaluate_batch_hits(pwaf_engine *e, const pwaf_batch *in, pwaf_verdict *out, pwaf_counts *counts, pwaf_rule_hit *hits, uint32_t hits_cap, uint32_t *n_hits,
                              uint64_t *rule_hits) {
     if (!e || !out) return fail(PWAF_E_INVALID_ARG, "NULL argument");
-    HitOut h;
+    ReportOut h;
     h.hits = hits; h.cap = hits ? hits_cap : 0u; h.n_hits = n_hits; h.rule_hits = rule_hits;
     if (int rc = check_hit_args(e, "pwaf_evaluate_batch_hits", h)) return rc;
     return evaluate_batch_impl(e, in, out, counts, nullptr, &h);
@@ -2822,9 +2868,27 @@ int pwaf_evaluate_batch_hits(pwaf_engine *e, const pwaf_batch *in, pwaf_verdict 
 int pwaf_evaluate_device_hits(pwaf_engine *e, const pwaf_batch *in, pwaf_verdict *out, pwaf_counts *counts, uint32_t *match_idx, uint32_t *n_matches, pwaf_rule_hit *hits,
                               uint32_t hits_cap, uint32_t *n_hits, uint64_t *rule_hits, void *stream) {
     if (!e || !out) return fail(PWAF_E_INVALID_ARG, "NULL argument");
-    HitOut h;
+    ReportOut h;
     h.hits = hits; h.cap = hits ? hits_cap : 0u; h.n_hits = n_hits; h.rule_hits = rule_hits;
     if (int rc = check_hit_args(e, "pwaf_evaluate_device_hits", h)) return rc;
+    return evaluate_device_impl(e, in, out, counts, match_idx, n_matches, nullptr, stream, &h);
+}
+// The plain entry points with the route output (engines created with routes; include/pwaf.h). route == NULL: exactly the plain call.
+int pwaf_evaluate_batch_routes(pwaf_engine *e, const pwaf_batch *in, pwaf_verdict *out, pwaf_counts *counts, uint32_t *route) {
+    if (!e || !out) return fail(PWAF_E_INVALID_ARG, "NULL argument");
+    if (!route) return evaluate_batch_impl(e, in, out, counts, nullptr);
+    if (int rc = need_routes(e, "pwaf_evaluate_batch_routes")) return rc;
+    ReportOut h;
+    h.route = route;
+    return evaluate_batch_impl(e, in, out, counts, nullptr, &h);
+}
+int pwaf_evaluate_device_routes(pwaf_engine *e, const pwaf_batch *in, pwaf_verdict *out, pwaf_counts *counts, uint32_t *match_idx, uint32_t *n_matches, uint32_t *route,
+                                void *stream) {
+    if (!e || !out) return fail(PWAF_E_INVALID_ARG, "NULL argument");
+    if (!route) return evaluate_device_impl(e, in, out, counts, match_idx, n_matches, nullptr, stream);
+    if (int rc = need_routes(e, "pwaf_evaluate_device_routes")) return rc;
+    ReportOut h;
+    h.route = route;
     return evaluate_device_impl(e, in, out, counts, match_idx, n_matches, nullptr, stream, &h);
 }
 int pwaf_evaluate_batch_geo(pwaf_engine *e, const pwaf_batch *in, pwaf_verdict *out, pwaf_counts *counts, pwaf_geo *geo) {
@@ -3315,7 +3379,7 @@ int pwaf_engine_device_status(pwaf_engine *e) {
 
 }  // extern "C"
 namespace {
-int evaluate_one_impl(pwaf_engine *e, const pwaf_request *r, pwaf_verdict *out, pwaf_geo *geo) {
+int evaluate_one_impl(pwaf_engine *e, const pwaf_request *r, pwaf_verdict *out, pwaf_geo *geo, uint32_t *route = nullptr) {
     if (r->n_headers && !r->headers) return fail(PWAF_E_INVALID_ARG, "n_headers without a headers array");
     const uint32_t n_hdr = e->n_fields - PWAF_N_FIELDS;  // header columns the rule set reads
     const uint32_t n_cols = PWAF_N_FIELDS + n_hdr;
@@ -3363,7 +3427,10 @@ int evaluate_one_impl(pwaf_engine *e, const pwaf_request *r, pwaf_verdict *out, 
         b.asn = &asn;
         b.country = &country;
     }
-    return evaluate_batch_impl(e, &b, out, nullptr, geo);
+    if (!route) return evaluate_batch_impl(e, &b, out, nullptr, geo);
+    ReportOut h;
+    h.route = route;
+    return evaluate_batch_impl(e, &b, out, nullptr, geo, &h);
 }
 }  // namespace
 
@@ -3372,6 +3439,12 @@ extern "C" {
 int pwaf_evaluate_one(pwaf_engine *e, const pwaf_request *r, pwaf_verdict *out) {
     if (!e || !r || !out) return fail(PWAF_E_INVALID_ARG, "NULL argument");
     return evaluate_one_impl(e, r, out, nullptr);
+}
+int pwaf_evaluate_one_route(pwaf_engine *e, const pwaf_request *r, pwaf_verdict *out, uint32_t *route) {
+    if (!e || !r || !out) return fail(PWAF_E_INVALID_ARG, "NULL argument");
+    if (route)
+        if (int rc = need_routes(e, "pwaf_evaluate_one_route")) return rc;
+    return evaluate_one_impl(e, r, out, nullptr, route);
 }
 int pwaf_evaluate_one_geo(pwaf_engine *e, const pwaf_request *r, pwaf_verdict *out, pwaf_geo *geo) {
     if (!e || !r || !out) return fail(PWAF_E_INVALID_ARG, "NULL argument");

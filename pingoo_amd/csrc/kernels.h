@@ -465,6 +465,11 @@ struct VerdictArgs {
     uint32_t hits_cap;
     uint32_t *n_hits;
     unsigned long long *rule_hits;  // [the caller's n_rules]
+    // routes (verdict2_kernel<.., ROUTES = true>; launch_verdict picks the variant when `route` is set, never together with the hit outputs):
+    // route[i] = the index of request i's first matching route, PWAF_ROUTE_NONE when there is none. Device rules [route_base, n_rules) are
+    // the routes (Program::route_base).
+    uint32_t *route;  // [n], nullable
+    uint32_t route_base;
 };
 
 // Launchers (hipStream_t passed as void*). Return hipError_t as int.

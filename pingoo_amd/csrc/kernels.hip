@@ -2667,8 +2667,14 @@ __device__ __forceinline__ void park96(uint32_t &c, uint32_t &lo, uint32_t &hi, 
 // in the FIRST chunk and a gated request is decided (both gates always take effect) before that chunk's words are appended.
 // (HITS, up to 64 passes: 5 waves per SIMD. The plain kernel fills its 80 registers at 6; the queue's three more put one into scratch there.
 // A CU then holds ONE 12-wave workgroup at a time; the persistent grid is unchanged, its workgroups take turns.)
-template <bool LT, int BR, bool HITS>
+// ROUTES (an engine created with routes, only when a route output was asked for; never with HITS): the caller's routes are the device rules
+// [a.route_base, a.n_rules), behind every rule, with effects {ALLOW, ALLOW}: they never fire. A lane that holds one keeps its match word
+// where a rule's lane keeps `fire`; the candidate list ascends, so a chunk's route lanes are its upper lanes (one wave-uniform mask). A second
+// ordered pick over those lanes, against `rpending`, gives each request its first route, whatever its verdict: the loop runs until both
+// the verdicts and the routes of the group are known.
+template <bool LT, int BR, bool HITS, bool ROUTES>
 __global__ __launch_bounds__(768, BR == 1 ? (HITS ? 5 : 6) : 1) void verdict2_kernel(VerdictArgs a) {
+    static_assert(!(HITS && ROUTES), "one call answers one of the reports");
     extern __shared__ __align__(16) unsigned char lds[];
     const uint32_t tid = threadIdx.x, wave = wave_index(), lane = tid & 63, n_waves = blockDim.x >> 6;
 #ifdef PWAF_PROFILING
@@ -3052,13 +3058,17 @@ __global__ __launch_bounds__(768, BR == 1 ? (HITS ? 5 : 6) : 1) void verdict2_ke
         bool undecided = valid;
         uint32_t my_action = PWAF_ACTION_ALLOW, my_rule = PWAF_RULE_NONE;
         unsigned long long gated = 0;  // (HITS) requests answered by a gate pseudo rule: known after the first chunk
-        for (uint32_t base = 0; base < n_cand && (HITS || pending != 0) && !(dbg_skip & 32u); base += 64) {
+        unsigned long long rpending = ROUTES ? valid_mask : 0ull;  // (ROUTES) requests whose route is not known yet
+        uint32_t my_route = PWAF_ROUTE_NONE;
+        for (uint32_t base = 0; base < n_cand && (HITS || pending != 0 || (ROUTES && rpending != 0)) && !(dbg_skip & 32u); base += 64) {
             unsigned long long fire = 0, eff_mask = 0;
             unsigned long long match = 0;  // (HITS) the rule's match word whatever its actions
             uint32_t lit_off = 0, lit_cnt = 0;
             bool lazy_seen = false;
+            bool is_route = false;
             if (base + lane < n_cand) {
                 const uint32_t my_cand = cand[base + lane];
+                if (ROUTES) is_route = my_cand >= a.route_base;
                 uint32_t eff_u, eff_v;
                 if (LT) {
                     const uint2 hdr = l_rules[my_cand];
@@ -3096,6 +3106,8 @@ __global__ __launch_bounds__(768, BR == 1 ? (HITS ? 5 : 6) : 1) void verdict2_ke
                     }
                 }
                 eff_mask = (eff_u ? ~verified_mask : 0ull) | (eff_v ? verified_mask : 0ull);
+                // (ROUTES: a route's lane keeps its match word in `fire` — its own eff_mask is 0 — through the exact evaluation below)
+                if (ROUTES && is_route) eff_mask = valid_mask;
                 fire = acc_or & eff_mask;
                 if (HITS) match = acc_or & valid_mask;
             }
@@ -3146,6 +3158,12 @@ __global__ __launch_bounds__(768, BR == 1 ? (HITS ? 5 : 6) : 1) void verdict2_ke
             // (HITS: one word less to keep through the loop above; the same value on every valid request, and `pending` holds no other)
             if (HITS) fire = match & eff_mask;
             unsigned long long firing = __ballot(fire != 0);
+            unsigned long long rfiring = 0;
+            if (ROUTES) {  // the route lanes' words are picked apart from the rules': they decide no verdict
+                const unsigned long long rlanes = __ballot(is_route);
+                rfiring = firing & rlanes;
+                firing &= ~rlanes;
+            }
             uint32_t first = kNone;
             while (firing != 0 && pending != 0) {
                 const int j = __builtin_ctzll(firing);
@@ -3172,6 +3190,22 @@ __global__ __launch_bounds__(768, BR == 1 ? (HITS ? 5 : 6) : 1) void verdict2_ke
                     my_rule = dr.public_idx;
                 }
                 my_action = (verified_mask & mybit) ? eff_v : eff_u;
+            }
+            if (ROUTES) {
+                // the second ordered pick: the first route lane whose word holds the request (a request leaves rpending once)
+                uint32_t rfirst = kNone;
+                while (rfiring != 0 && rpending != 0) {
+                    const int j = __builtin_ctzll(rfiring);
+                    rfiring &= rfiring - 1;
+                    const unsigned long long rj = (((unsigned long long)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(fire >> 32), j) << 32) |
+                                                   (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)fire, j)) & rpending;
+                    if (rj & mybit) rfirst = (uint32_t)j;
+                    rpending &= ~rj;
+                }
+                if (rfirst != kNone) {
+                    const uint32_t jc = cand[base + rfirst];
+                    my_route = LT ? (uint32_t)l_pub[jc] : a.rules[jc].public_idx;
+                }
             }
             if (HITS) {
                 if (base == 0) gated = __ballot(valid && !undecided && my_rule >= 0xFFFFFFF0u);
@@ -3211,6 +3245,7 @@ __global__ __launch_bounds__(768, BR == 1 ? (HITS ? 5 : 6) : 1) void verdict2_ke
             v.x = my_action;
             v.y = my_rule;
             *reinterpret_cast<uint2 *>(&a.out[i]) = v;
+            if (ROUTES) a.route[i] = my_route;  // (one coalesced 4-byte store per lane; PWAF_ROUTE_NONE where no route matched)
         }
         const unsigned long long m_block = __ballot(valid && my_action == PWAF_ACTION_BLOCK);
         const unsigned long long m_captcha = __ballot(valid && my_action == PWAF_ACTION_CAPTCHA);
@@ -4056,14 +4091,19 @@ int launch_verdict(const VerdictArgs &a, void *stream) {
                                  {reinterpret_cast<const void *>(verdict_kernel<true, kBRmax, false>), reinterpret_cast<const void *>(verdict_kernel<true, 1, false>)}},
                                 {{reinterpret_cast<const void *>(verdict_kernel<false, kBRmax, true>), reinterpret_cast<const void *>(verdict_kernel<false, 1, true>)},
                                  {reinterpret_cast<const void *>(verdict_kernel<true, kBRmax, true>), reinterpret_cast<const void *>(verdict_kernel<true, 1, true>)}}};
-    const void *fns2[2][2][2] = {{{reinterpret_cast<const void *>(verdict2_kernel<false, kBRmax, false>), reinterpret_cast<const void *>(verdict2_kernel<false, 1, false>)},
-                                  {reinterpret_cast<const void *>(verdict2_kernel<true, kBRmax, false>), reinterpret_cast<const void *>(verdict2_kernel<true, 1, false>)}},
-                                 {{reinterpret_cast<const void *>(verdict2_kernel<false, kBRmax, true>), reinterpret_cast<const void *>(verdict2_kernel<false, 1, true>)},
-                                  {reinterpret_cast<const void *>(verdict2_kernel<true, kBRmax, true>), reinterpret_cast<const void *>(verdict2_kernel<true, 1, true>)}}};
+    const void *fns2[3][2][2] = {{{reinterpret_cast<const void *>(verdict2_kernel<false, kBRmax, false, false>), reinterpret_cast<const void *>(verdict2_kernel<false, 1, false, false>)},
+                                  {reinterpret_cast<const void *>(verdict2_kernel<true, kBRmax, false, false>), reinterpret_cast<const void *>(verdict2_kernel<true, 1, false, false>)}},
+                                 {{reinterpret_cast<const void *>(verdict2_kernel<false, kBRmax, true, false>), reinterpret_cast<const void *>(verdict2_kernel<false, 1, true, false>)},
+                                  {reinterpret_cast<const void *>(verdict2_kernel<true, kBRmax, true, false>), reinterpret_cast<const void *>(verdict2_kernel<true, 1, true, false>)}},
+                                 {{reinterpret_cast<const void *>(verdict2_kernel<false, kBRmax, false, true>), reinterpret_cast<const void *>(verdict2_kernel<false, 1, false, true>)},
+                                  {reinterpret_cast<const void *>(verdict2_kernel<true, kBRmax, false, true>), reinterpret_cast<const void *>(verdict2_kernel<true, 1, false, true>)}}};
     // the rule-hit variants only when a hit output was asked for (PWAF_OPT_RULE_HITS engines; the entry-list kernel only: engine_create)
     const bool want_hits = a.n_hits != nullptr || a.rule_hits != nullptr;
     if (want_hits && (sh.sparse != 2 || (a.hits == nullptr && a.n_hits != nullptr && a.hits_cap != 0))) return (int)hipErrorInvalidValue;
-    const void *fn = sh.sparse == 2 ? fns2[want_hits ? 1 : 0][sh.lds_tables ? 1 : 0][variant] : fns[sh.sparse ? 1 : 0][sh.lds_tables ? 1 : 0][variant];
+    // the route variants only when a route output was asked for (engines created with routes; the entry-list kernel only; one report per call)
+    const bool want_routes = a.route != nullptr;
+    if (want_routes && (sh.sparse != 2 || want_hits || a.route_base > a.n_rules)) return (int)hipErrorInvalidValue;
+    const void *fn = sh.sparse == 2 ? fns2[want_routes ? 2 : want_hits ? 1 : 0][sh.lds_tables ? 1 : 0][variant] : fns[sh.sparse ? 1 : 0][sh.lds_tables ? 1 : 0][variant];
     uint32_t blocks = (a.n_groups + sh.waves - 1) / sh.waves;
 #ifdef PWAF_PROFILING
     static const uint32_t forced_cap = getenv("PWAF_VERDICT_BLOCKS") ? (uint32_t)atoi(getenv("PWAF_VERDICT_BLOCKS")) : 0u;
@@ -4094,10 +4134,12 @@ int configure_kernels(int device) {
                          reinterpret_cast<const void *>(verdict_kernel<true, 1, false>), reinterpret_cast<const void *>(verdict_kernel<false, 1, false>),
                          reinterpret_cast<const void *>(verdict_kernel<true, (kMaxPasses + 1 + 63) / 64, true>), reinterpret_cast<const void *>(verdict_kernel<false, (kMaxPasses + 1 + 63) / 64, true>),
                          reinterpret_cast<const void *>(verdict_kernel<true, 1, true>), reinterpret_cast<const void *>(verdict_kernel<false, 1, true>),
-                         reinterpret_cast<const void *>(verdict2_kernel<true, (kMaxPasses + 1 + 63) / 64, false>), reinterpret_cast<const void *>(verdict2_kernel<false, (kMaxPasses + 1 + 63) / 64, false>),
-                         reinterpret_cast<const void *>(verdict2_kernel<true, 1, false>), reinterpret_cast<const void *>(verdict2_kernel<false, 1, false>),
-                         reinterpret_cast<const void *>(verdict2_kernel<true, (kMaxPasses + 1 + 63) / 64, true>), reinterpret_cast<const void *>(verdict2_kernel<false, (kMaxPasses + 1 + 63) / 64, true>),
-                         reinterpret_cast<const void *>(verdict2_kernel<true, 1, true>), reinterpret_cast<const void *>(verdict2_kernel<false, 1, true>),
+                         reinterpret_cast<const void *>(verdict2_kernel<true, (kMaxPasses + 1 + 63) / 64, false, false>), reinterpret_cast<const void *>(verdict2_kernel<false, (kMaxPasses + 1 + 63) / 64, false, false>),
+                         reinterpret_cast<const void *>(verdict2_kernel<true, 1, false, false>), reinterpret_cast<const void *>(verdict2_kernel<false, 1, false, false>),
+                         reinterpret_cast<const void *>(verdict2_kernel<true, (kMaxPasses + 1 + 63) / 64, true, false>), reinterpret_cast<const void *>(verdict2_kernel<false, (kMaxPasses + 1 + 63) / 64, true, false>),
+                         reinterpret_cast<const void *>(verdict2_kernel<true, 1, true, false>), reinterpret_cast<const void *>(verdict2_kernel<false, 1, true, false>),
+                         reinterpret_cast<const void *>(verdict2_kernel<true, (kMaxPasses + 1 + 63) / 64, false, true>), reinterpret_cast<const void *>(verdict2_kernel<false, (kMaxPasses + 1 + 63) / 64, false, true>),
+                         reinterpret_cast<const void *>(verdict2_kernel<true, 1, false, true>), reinterpret_cast<const void *>(verdict2_kernel<false, 1, false, true>),
                          reinterpret_cast<const void *>(filter_kernel<true>), reinterpret_cast<const void *>(filter_kernel<false>),
                          lscan_fn(false), lscan_fn(true)};
     for (const void *fn : fns) {

@@ -308,6 +308,9 @@ struct Program {
     std::vector<DevRule> rules;               // pseudo rules first, then the caller's rules with an effect
     std::vector<uint32_t> lits;
     uint32_t n_user_rules = 0;
+    // routes (pwaf_program_compile_routed): the caller's routes are device rules [route_base, route_base + n_dev_routes) BEHIND every
+    // rule, effects {ALLOW, ALLOW}, public_idx = the route's index. n_routes = what the caller gave (some may be dropped: never matching)
+    uint32_t n_routes = 0, route_base = 0, n_dev_routes = 0;
 
     // ip lists -> membership sets
     uint32_t n_ip_lists = 0;
@@ -326,6 +329,8 @@ struct Program {
 struct CompileInput {
     const pwaf_rule_desc *rules;
     size_t n_rules;
+    const pwaf_route_desc *routes;  // may be null when n_routes == 0
+    size_t n_routes;
     const pwaf_list_desc *lists;
     size_t n_lists;
     const pwaf_geoip_table *geoip;

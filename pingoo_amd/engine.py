@@ -157,6 +157,16 @@ def lib():
     L.pwaf_evaluate_device_geo.argtypes = [vp, C.POINTER(_abi.Batch), vp, vp, vp, vp, vp, vp]
     L.pwaf_evaluate_batch_hits.argtypes = [vp, C.POINTER(_abi.Batch), vp, vp, vp, C.c_uint32, vp, vp]
     L.pwaf_evaluate_device_hits.argtypes = [vp, C.POINTER(_abi.Batch), vp, vp, vp, vp, vp, C.c_uint32, vp, vp, vp]
+    # routes (engines created with routes beside their rules)
+    routed_args = create_args[:2] + [C.POINTER(_abi.RouteDesc), C.c_size_t] + create_args[2:]
+    L.pwaf_program_compile_routed.argtypes = routed_args + [C.POINTER(vp), C.POINTER(_abi.CompileError)]
+    L.pwaf_engine_create_routed.argtypes = routed_args + [C.POINTER(vp), C.POINTER(_abi.CompileError)]
+    for fn_name in ("pwaf_engine_route_count", "pwaf_program_route_count"):
+        getattr(L, fn_name).argtypes = [vp]
+        getattr(L, fn_name).restype = C.c_uint32
+    L.pwaf_evaluate_batch_routes.argtypes = [vp, C.POINTER(_abi.Batch), vp, vp, vp]
+    L.pwaf_evaluate_device_routes.argtypes = [vp, C.POINTER(_abi.Batch), vp, vp, vp, vp, vp, vp]
+    L.pwaf_evaluate_one_route.argtypes = [vp, C.POINTER(_abi.Request), C.POINTER(_abi.Verdict), C.POINTER(C.c_uint32)]
     L.pwaf_evaluate_records_geo.argtypes = [vp, vp, C.c_size_t, vp, C.c_uint32, vp, vp, vp]
     L.pwaf_evaluate_one_geo.argtypes = [vp, C.POINTER(_abi.Request), C.POINTER(_abi.Verdict), C.POINTER(_abi.Geo)]
     L.pwaf_async_create_geo.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(vp)]
@@ -283,7 +293,8 @@ def _norm_rules(rules) -> List[Tuple[str, Optional[str], List[int]]]:
 class CompiledProgram:
     """Host-side compilation only (no GPU): stats, warnings and the table dump used by the tests."""
 
-    def __init__(self, rules, lists: Optional[Dict[str, Tuple[int, Sequence[str]]]] = None, geoip: Optional[np.ndarray] = None, **opts):
+    def __init__(self, rules, lists: Optional[Dict[str, Tuple[int, Sequence[str]]]] = None, geoip: Optional[np.ndarray] = None, routes=None, **opts):
+        """routes: ordered [(name, expression | None)] compiled beside the rules (pwaf_program_compile_routed); None: pwaf_program_compile."""
         L = lib()
         m = _abi.Marshalled()
         r, nr = _abi.marshal_rules(_norm_rules(rules), m)
@@ -292,7 +303,11 @@ class CompiledProgram:
         o = _options(**opts)
         h = C.c_void_p()
         err = _abi.CompileError()
-        rc = L.pwaf_program_compile(r, nr, l, nl, g, C.byref(o), C.byref(h), C.byref(err))
+        if routes is None:
+            rc = L.pwaf_program_compile(r, nr, l, nl, g, C.byref(o), C.byref(h), C.byref(err))
+        else:
+            rt, nrt = _abi.marshal_routes(routes, m)
+            rc = L.pwaf_program_compile_routed(r, nr, rt, nrt, l, nl, g, C.byref(o), C.byref(h), C.byref(err))
         if rc < 0:
             _raise(rc, err.message.decode(errors="replace"), None if err.rule_index == 0xFFFFFFFF else err.rule_index)
         self.partial = rc == _abi.W_PARTIAL  # PWAF_OPT_LENIENT: some rule is not evaluated (rule_status / warnings say which)
@@ -372,7 +387,9 @@ class CompiledProgram:
     def stats(self) -> dict:
         s = _abi.Stats()
         lib().pwaf_program_stats(self._h, C.byref(s))
-        return {k: getattr(s, k) for k, _ in _abi.Stats._fields_ if k != "reserved"}
+        res = {k: getattr(s, k) for k, _ in _abi.Stats._fields_ if k != "reserved"}
+        res["n_routes"] = int(lib().pwaf_program_route_count(self._h))  # (pwaf_stats has no room: a getter of its own)
+        return res
 
 
 class RuleEngine:
@@ -381,19 +398,26 @@ class RuleEngine:
     rules: ordered [Rule | (name, expression|None, [actions])]
     lists: {name: (LIST_STRING|LIST_INT|LIST_IP, [csv column-0 strings])}
     geoip: GEOIP_DTYPE array (see pingoo_amd.batch.geoip_entries) or None
+    routes: ordered [(name, expression|None)] — the services' `route:` expressions; the engine then also answers each request's first
+            matching route in the same pass (evaluate_batch_routes, evaluate_routed, evaluate_device(route=...)). None: no routes.
     """
 
-    def __init__(self, rules, lists: Optional[Dict[str, Tuple[int, Sequence[str]]]] = None, geoip: Optional[np.ndarray] = None, **opts):
+    def __init__(self, rules, lists: Optional[Dict[str, Tuple[int, Sequence[str]]]] = None, geoip: Optional[np.ndarray] = None, routes=None, **opts):
         L = lib()
         m = _abi.Marshalled()
         self.rules = _norm_rules(rules)
+        self.routes = [(n, x) for n, x in routes] if routes is not None else []
         r, nr = _abi.marshal_rules(self.rules, m)
         l, nl = _abi.marshal_lists(lists, m)
         g = _abi.marshal_geoip(geoip, m)
         o = _options(**opts)
         h = C.c_void_p()
         err = _abi.CompileError()
-        rc = L.pwaf_engine_create(r, nr, l, nl, g, C.byref(o), C.byref(h), C.byref(err))
+        if routes is None:
+            rc = L.pwaf_engine_create(r, nr, l, nl, g, C.byref(o), C.byref(h), C.byref(err))
+        else:
+            rt, nrt = _abi.marshal_routes(self.routes, m)
+            rc = L.pwaf_engine_create_routed(r, nr, rt, nrt, l, nl, g, C.byref(o), C.byref(h), C.byref(err))
         if rc < 0:
             _raise(rc, err.message.decode(errors="replace"), None if err.rule_index == 0xFFFFFFFF else err.rule_index)
         self.partial = rc == _abi.W_PARTIAL  # PWAF_OPT_LENIENT: some rule is not evaluated (program.rule_status / warnings say which)
@@ -496,6 +520,30 @@ class RuleEngine:
         res += (geo,) if with_geo else ()
         return res if len(res) > 1 else res[0]
 
+    def evaluate_batch_routes(self, batch: RequestBatch, with_counts: bool = False):
+        """Verdicts and service routes in one pass (engines created with routes=; pwaf_evaluate_batch_routes) -> (verdicts, routes[, counts]).
+        routes: int32, the index of the first route whose expression is true for the request, -1 where none is (ServiceRouter's
+        convention). It is answered for every request whatever its verdict; the reference routes only what it lets through."""
+        out = np.zeros(batch.n, dtype=VERDICT_DTYPE)
+        route = np.full(max(1, batch.n), _abi.ROUTE_NONE, dtype=np.uint32)
+        counts = _abi.Counts()
+        st = batch.as_struct(self.header_names)
+        rc = lib().pwaf_evaluate_batch_routes(self._h, C.byref(st), out.ctypes.data, C.addressof(counts), route.ctypes.data)
+        if rc != 0:
+            _raise(rc, lib().pwaf_last_error().decode(errors="replace"))
+        res = (out, route[:batch.n].view(np.int32))
+        return res + (np.array(list(counts.by_action), dtype=np.uint64),) if with_counts else res
+
+    def evaluate_routed(self, request: Request) -> Tuple[Verdict, int]:
+        """One request -> (Verdict, route index or -1) (pwaf_evaluate_one_route; engines created with routes=)."""
+        st, _keep = _request_struct(request, self.header_names)
+        out = _abi.Verdict()
+        route = C.c_uint32(_abi.ROUTE_NONE)
+        rc = lib().pwaf_evaluate_one_route(self._h, C.byref(st), C.byref(out), C.byref(route))
+        if rc != 0:
+            _raise(rc, lib().pwaf_last_error().decode(errors="replace"))
+        return verdict_from_record({"action": out.action, "rule_idx": out.rule_idx}), (-1 if route.value == _abi.ROUTE_NONE else int(route.value))
+
     def evaluate_batch_hits_into(self, batch: RequestBatch, hits: Optional[np.ndarray], cap: int = 0, with_rule_hits: bool = True):
         """pwaf_evaluate_batch_hits as it is (OPT_RULE_HITS engines): `hits` = a caller-owned RULE_HIT_DTYPE array of which at most `cap`
         entries are written (None: no list) -> (verdicts, counts, n_hits or None, rule_hits or None). n_hits > cap: the list is incomplete."""
@@ -564,11 +612,13 @@ class RuleEngine:
         return (v, (int(geo.asn), bytes(geo.country).decode("latin-1"))) if with_geo else v
 
     def evaluate_device(self, dbatch: "DeviceBatch", out=None, counts=None, match_idx=None, n_matches=None, stream=None, geo=None, hits=None, n_hits=None,
-                        rule_hits=None, hits_cap=None):
+                        rule_hits=None, hits_cap=None, route=None):
         """Device-resident evaluation on torch's current stream (or `stream`). Tensors stay on the GPU. geo (OPT_GEO_ANSWERS engines): a
         device tensor of n x 8 bytes that receives the requests' GeoIP records (pwaf_geo). hits / n_hits / rule_hits (OPT_RULE_HITS engines;
         not together with geo): device tensors for the rule-hit list (16 bytes per entry, RULE_HIT_DTYPE; hits_cap entries, default: all
-        the tensor holds), its 32-bit entry counter and the n_rules 64-bit per-rule counters — the counters ACCUMULATE: zero them first."""
+        the tensor holds), its 32-bit entry counter and the n_rules 64-bit per-rule counters — the counters ACCUMULATE: zero them first.
+        route (engines created with routes=; not together with geo or the hit outputs): a device tensor of n 32-bit words that receives
+        each request's first matching route (as int32: -1 where none matches)."""
         import torch
 
         if out is None:
@@ -578,7 +628,11 @@ class RuleEngine:
         st = dbatch.as_struct(self.header_names)
         args = (self._h, C.byref(st), out.data_ptr(), counts.data_ptr() if counts is not None else None,
                 match_idx.data_ptr() if match_idx is not None else None, n_matches.data_ptr() if n_matches is not None else None)
-        if hits is not None or n_hits is not None or rule_hits is not None:
+        if route is not None:
+            assert geo is None and hits is None and n_hits is None and rule_hits is None, "the _routes, _geo and _hits entry points are separate calls"
+            assert route.is_contiguous() and route.numel() * route.element_size() >= 4 * dbatch.n
+            rc = lib().pwaf_evaluate_device_routes(*args, route.data_ptr(), C.c_void_p(stream))
+        elif hits is not None or n_hits is not None or rule_hits is not None:
             assert geo is None, "the _geo and _hits entry points are separate calls"
             room = 0 if hits is None else hits.numel() * hits.element_size() // RULE_HIT_DTYPE.itemsize
             cap = room if hits_cap is None else int(hits_cap)
@@ -729,7 +783,10 @@ class ServiceRouter:
     first one whose `route:` expression is true — or has none (http_listener.rs:266-271, http_proxy_service.rs:84-95: same language,
     same context, error / non-bool = no match). That is first-match-wins over one expression per service, i.e. a rule set whose rule
     k 'blocks' with rule index k: no new device code, just an engine without the two request gates.
-    `route_batch` -> int32 array: index of the selected service, -1 = none (the reference answers 404)."""
+    `route_batch` -> int32 array: index of the selected service, -1 = none (the reference answers 404).
+    For route-only callers. A host that wants the verdict AND the service creates ONE engine with both —
+    RuleEngine(rules, lists, geoip, routes=[...]).evaluate_batch_routes(batch) -> (verdicts, routes) — which answers the same routes in
+    the verdict's own pass: no second pipeline, no second set of tables."""
 
     def __init__(self, routes: Sequence[Tuple[str, Optional[str]]], lists=None, geoip=None, **opts):
         rules = [(name, expr, [_abi.RULE_ACTION_BLOCK]) for name, expr in routes]
