@@ -232,7 +232,7 @@ public:
     // or not: conservative.)
     std::set<std::string> fcmp_keys;
     std::vector<int> fcmp_fields;
-    // (mirrors of the device tables' widths: kernels.h kMaxHeaderLens, engine.cpp's 128 asn comparisons / 256 country tables / 128 integer
+    // (mirrors of the device tables' widths: program.h kMaxHeaderLens, tableplan.cpp's 128 asn comparisons / 256 country tables / 128 integer
     // sets per client variable — the class-row and membership-row words of attr_kernel)
     static constexpr uint32_t kDevMaxHeaderLens = 8, kDevMaxAsnCmp = 128, kDevMaxCountryLuts = 256, kDevMaxIntSets = 128;
     std::vector<int> hlen_fields_seen;
@@ -292,7 +292,7 @@ public:
             a.c = c;
             a.key = std::string(v.k == SVal::LEN ? "L" : "I") + std::to_string(v.field) + "o" + std::to_string((int)op) + ":" + std::to_string(c);
             if (!atom_index.count(a.key)) {
-                // Device-table limits that used to fail engine creation AS A WHOLE (engine.cpp checks them again): a rule that would
+                // Device-table limits that used to fail engine creation AS A WHOLE (tableplan.cpp checks them again): a rule that would
                 // exceed one is lowered to a residual program instead — the caller catches Unsupported. Counted over every atom made.
                 if (v.k == SVal::LEN && v.field >= PWAF_N_FIELDS) {
                     if (std::find(hlen_fields_seen.begin(), hlen_fields_seen.end(), v.field) == hlen_fields_seen.end()) {

@@ -26,6 +26,7 @@
 #include "lscan_split.h"
 #include "program.h"
 #include "records.h"
+#include "tableplan.h"
 
 using namespace pwaf;
 
@@ -287,27 +288,19 @@ struct Scratch {
 };
 static constexpr size_t kContexts = 3;
 
-struct pwaf_engine {
+struct pwaf_engine : PlanShape {  // (PlanShape: the widths and counts of the planned tables, tableplan.h)
     pwaf_program prog;
     int device = 0;
     std::vector<std::unique_ptr<Scratch>> ctx;  // kContexts
     size_t next_ctx = 0;
     std::vector<DevGroup> groups;
     DevBuf num_atoms, bit_atoms /* (source word, bit) -> column */, trig_off, trig_rules, always_rules, country_luts /* transposed: [676][cc_words] */, rules, lits, set_masks;
-    uint32_t cmp_vars = 0;  // (VerdictArgs::cmp_vars)
-    uint32_t cc_words = 1, n_cmp_atoms = 0, n_bit_atoms = 0, n_trig = 0, n_lazy = 0;
     DevBuf lazy_atoms;  // (VerdictArgs::lazy)
-    std::vector<uint32_t> lazy_vars;  // (VerdictArgs::lazy_var)
     uint32_t n_short = 0;  // short-literal atoms (kernels.h: ShortAtom) of the one field handled that way
     int short_field = -1;
     DevBuf short_atoms;
-    uint32_t class_words = 1, acmp_words = 0, geo_default = 0, n_classes = 1;
     DevBuf class_rows, dir_esc, leaf_root, geo_leaf_root;
-    std::vector<uint32_t> host_cc_masks, host_iu_masks1;  // kept for building the per-record rows
-    std::vector<std::pair<uint32_t, uint32_t>> host_acmp;  // (operator 0: ==, 1: <=; constant) of the client.asn comparisons
-    std::vector<int64_t> host_iu_vals1;
     DevBuf iu_vals[2], iu_masks[2];
-    uint32_t iu_n[2] = {0, 0}, iu_words[2] = {1, 1};
     DevBuf ip_root4, ip_root6, ip_nodes, geo_root4, geo_root6, geo_nodes, geo_recs;
     std::mutex mu;  // guards the context ring and table rebuilds (pwaf_engine_tune)
     std::mutex prof_mu;  // while profiling is on, calls enqueue one at a time: the event / timing tables below are per engine
@@ -334,7 +327,6 @@ struct pwaf_engine {
     uint32_t n_gap = 0;                 // gated gap passes (list slots [0, kGapLists), one factor-mask bit each)
     std::vector<uint32_t> lscan_launches[2];  // per list-scan phase: the descriptors of each launch_scan_gated call (lscan_split.h)
     DevBuf pass_table;                  // PassInfo per pass
-    std::vector<uint32_t> hlen_fields;  // header columns whose length some rule compares (comparison variable 7 + k)
     uint32_t n_fields = PWAF_N_FIELDS;  // 5 + header columns
     // profiling
     int profiling = 0;  // 0 off, 1 every kernel, 2 only the launches that stream request bytes (pwaf_engine_set_profiling)
@@ -355,14 +347,6 @@ int check_opts(const pwaf_options *o, pwaf_options &out) {
     if (o->struct_size != sizeof(pwaf_options)) return fail(PWAF_E_INVALID_ARG, "pwaf_options.struct_size mismatch");
     out = *o;
     return PWAF_OK;
-}
-
-// which verdict kernel (kernels.h: verdict_shape's mode): the entry list unless an A/B flag asks for an earlier column file
-uint32_t verdict_mode(uint32_t flags) {
-    const bool tiny = (flags & PWAF_OPT_TINY_VERDICT_SLOTS) != 0;
-    if (flags & PWAF_OPT_DENSE_VERDICT) return 0u;
-    if (flags & PWAF_OPT_SPARSE_VERDICT) return tiny ? 2u : 1u;
-    return tiny ? 4u : 3u;
 }
 
 void put_err(pwaf_compile_error *dst, const pwaf_compile_error &src) {
@@ -2010,6 +1994,56 @@ int pwaf_program_stats(const pwaf_program *p, pwaf_stats *out) {
 uint32_t pwaf_program_route_count(const pwaf_program *p) { return p && p->p ? p->p->n_routes : 0u; }
 uint32_t pwaf_engine_route_count(const pwaf_engine *e) { return e && e->prog.p ? e->prog.p->n_routes : 0u; }
 
+namespace {
+
+// The tables of a plan (tableplan.h) and of the program itself on their way to the device; the engine keeps the plan's shape.
+int upload_tables(pwaf_engine *e, const TablePlan &t) {
+    const Program &P = *e->prog.p;
+    int rc = PWAF_OK;
+    const auto up = [&](DevBuf &buf, const auto &vec) { if (!rc) rc = upload(buf, vec); };
+    static_cast<PlanShape &>(*e) = t;
+    for (int var = 0; var < 2; var++) {
+        up(e->iu_vals[var], t.iu_vals[var]);
+        up(e->iu_masks[var], t.iu_masks[var]);
+    }
+    up(e->bit_atoms, t.bit_col);
+    up(e->num_atoms, t.cmp_atoms);
+    up(e->lazy_atoms, t.lazy_atoms);
+    up(e->lits, t.lits);
+    up(e->trig_off, t.trig_off);
+    up(e->trig_rules, t.trig_rules);
+    up(e->always_rules, t.always);
+    up(e->country_luts, t.cc_masks);
+    up(e->rules, P.rules);
+    if (!t.rules_unrouted.empty()) up(e->rules_unrouted, t.rules_unrouted);
+    up(e->set_masks, P.set_masks);
+    up(e->ip_root4, P.ipset_trie.root4);
+    up(e->ip_root6, P.ipset_trie.root6);
+    up(e->ip_nodes, P.ipset_trie.nodes);
+    up(e->class_rows, t.class_rows);
+    up(e->geo_root4, t.geo_root4);
+    up(e->geo_root6, t.geo_root6);
+    up(e->geo_nodes, t.geo_nodes);
+    // the root of a family without prefixes: every address reads class 0 (ip lists) / the default record's class (GeoIP: tableplan.cpp)
+    up(e->leaf_root, std::vector<uint32_t>(65536, TRIE_LEAF));
+    up(e->geo_leaf_root, std::vector<uint32_t>(65536, TRIE_LEAF | t.geo_default));
+    if (P.n_residual) {
+        up(e->residual_blob, P.residual_blob);
+        up(e->residual_errors, std::vector<unsigned long long>(P.n_residual, 0ull));
+        if (P.has_geo && P.residual_needs_geo) {
+            // client.asn / client.country VALUES (the class trie above only keeps which predicates hold): the trie with record leaves
+            const std::vector<uint32_t> leaf0(65536, TRIE_LEAF);  // record 0 = the default {0, "XX"}
+            up(e->geo_rec_root4, P.geo_trie.root4.empty() ? leaf0 : P.geo_trie.root4);
+            up(e->geo_rec_root6, P.geo_trie.root6.empty() ? leaf0 : P.geo_trie.root6);
+            up(e->geo_rec_nodes, P.geo_trie.nodes);
+            up(e->geo_recs, P.geo_recs);
+        }
+    }
+    return rc;
+}
+
+}  // namespace
+
 int pwaf_engine_create(const pwaf_rule_desc *rules, size_t n_rules, const pwaf_list_desc *lists, size_t n_lists, const pwaf_geoip_table *geoip,
                        const pwaf_options *opts, pwaf_engine **out, pwaf_compile_error *err) {
     return pwaf_engine_create_routed(rules, n_rules, nullptr, 0, lists, n_lists, geoip, opts, out, err);
@@ -2084,309 +2118,14 @@ int pwaf_engine_create_routed(const pwaf_rule_desc *rules, size_t n_rules, const
         if (!ok) e->residual_note = "residual rules are interpreted per request, not specialized: " + why;  // (the ENGINE's: this device, this hiprtc — not the program's)
     }
     if ((rc = assign_lists(e.get()))) return dev_fail(rc);
-#define UP(buf, vec)                                     \
-    if ((rc = upload(e->buf, vec))) return dev_fail(rc);
-    {
-        // integer-set atoms: merge all sets tested against one variable into a sorted union with membership rows, so the
-        // device does one binary search per request and variable instead of one per predicate
-        std::vector<NumAtomDev> atoms = P.num_atoms;
-        for (int var = 0; var < 2; var++) {
-            std::map<int64_t, std::vector<uint32_t>> member;
-            uint32_t n_sets = 0;
-            for (auto &d : atoms) {
-                if (d.kind != ATOM_INTSET || d.var != var) continue;
-                for (uint32_t k = d.ref; k < d.ref2; k++) member[P.int_pool[k]].push_back(n_sets);
-                d.ref = n_sets++;  // from now on: bit index in the variable's membership row
-            }
-            if (n_sets > 128) { fail(PWAF_E_UNSUPPORTED, "more than 128 integer-set predicates on one client variable"); return dev_fail(PWAF_E_UNSUPPORTED); }
-            e->iu_words[var] = std::max(1u, (n_sets + 31) / 32);
-            e->iu_n[var] = (uint32_t)member.size();
-            std::vector<int64_t> vals;
-            std::vector<uint32_t> masks(e->iu_words[var], 0);  // row 0: the value is in no set
-            for (auto &kv : member) {
-                vals.push_back(kv.first);
-                std::vector<uint32_t> row(e->iu_words[var], 0);
-                for (uint32_t b : kv.second) row[b >> 5] |= 1u << (b & 31);
-                masks.insert(masks.end(), row.begin(), row.end());
-            }
-            if (var == 1) { e->host_iu_vals1 = vals; e->host_iu_masks1 = masks; }
-            UP(iu_vals[var], vals)
-            UP(iu_masks[var], masks)
-        }
-        // split: membership atoms become register bit tests (source word, bit); the rest are comparisons
-        std::vector<NumAtomDev> cmp_src;
-        std::vector<uint32_t> bit_atoms;
-        if (P.n_cols >= (1u << 20)) { fail(PWAF_E_UNSUPPORTED, "more than 2^20 predicate columns"); return dev_fail(PWAF_E_UNSUPPORTED); }
-        if (P.set_words > kSetWordsMax) { fail(PWAF_E_UNSUPPORTED, "more than 512 ip lists"); return dev_fail(PWAF_E_UNSUPPORTED); }
-        if (P.country_luts.size() > 256) { fail(PWAF_E_UNSUPPORTED, "more than 256 distinct client.country predicates"); return dev_fail(PWAF_E_UNSUPPORTED); }
-        for (auto &d : atoms) {
-            uint32_t src;
-            if (d.kind == ATOM_IPSET) src = d.ref >> 5;
-            else if (d.kind == ATOM_COUNTRY) src = kSrcCc + (d.ref >> 5);
-            else if (d.kind == ATOM_INTSET) src = (d.var == 0 ? kSrcPort : kSrcAsn) + (d.ref >> 5);
-            else {
-                cmp_src.push_back(d);
-                continue;
-            }
-            bit_atoms.push_back(d.col | ((d.ref & 31u) << 20) | (src << 25));
-        }
-        e->n_bit_atoms = (uint32_t)bit_atoms.size();
-        // (source word, bit) -> column
-        std::vector<uint32_t> bit_col(kSrcWords * 32, 0);
-        for (uint32_t d : bit_atoms) bit_col[(d >> 25) * 32 + ((d >> 20) & 31u)] = d & 0xFFFFFu;
-        // Comparison atoms in the canonical form the kernel evaluates: variable (0-4 field lengths, 5 remote_port, 6 asn) against
-        // a 32-bit constant with == or <=. Lengths, ports and ASNs are unsigned 32-bit, so constants outside [0, 2^32) fold to
-        // "never" (the atom is dropped: its column stays zero) or "always" (<= 0xFFFFFFFF); `v < c` becomes `v <= c - 1`.
-        struct Canon { uint32_t vi, op, col, c; };
-        std::vector<Canon> canon;
-        for (const NumAtomDev &d : cmp_src) {
-            uint32_t vi;
-            if (d.kind == ATOM_LEN && d.var >= PWAF_N_FIELDS) {
-                // length of a header column: comparison variable 7 + k for the k-th such column
-                size_t slot = std::find(e->hlen_fields.begin(), e->hlen_fields.end(), (uint32_t)d.var) - e->hlen_fields.begin();
-                if (slot == e->hlen_fields.size()) e->hlen_fields.push_back(d.var);
-                if (slot >= kMaxHeaderLens) { fail(PWAF_E_UNSUPPORTED, "length() of more than 8 distinct headers is compared"); return dev_fail(PWAF_E_UNSUPPORTED); }
-                vi = 7u + (uint32_t)slot;
-            } else {
-                vi = d.kind == ATOM_LEN ? d.var : 5u + d.var;
-                if (vi > 6) { fail(PWAF_E_UNSUPPORTED, "comparison atom on an unknown variable"); return dev_fail(PWAF_E_UNSUPPORTED); }
-            }
-            int64_t c = d.c;
-            uint32_t op;  // 0: ==, 1: <=
-            if (d.op == OP_EQ) {
-                if (c < 0 || c > 0xFFFFFFFFll) continue;
-                op = 0;
-            } else {
-                if (d.op == OP_LT) {
-                    if (c <= 0) continue;  // v < c with c <= 0: never
-                    c -= 1;
-                }
-                if (c < 0) continue;
-                if (c > 0xFFFFFFFFll) c = 0xFFFFFFFFll;
-                op = 1;
-            }
-            canon.push_back({vi, op, d.col, (uint32_t)c});
-        }
-        std::stable_sort(canon.begin(), canon.end(), [](const Canon &x, const Canon &y) { return x.vi != y.vi ? x.vi < y.vi : x.op < y.op; });
-        if (canon.size() > 65535) { fail(PWAF_E_UNSUPPORTED, "more than 65535 comparison predicates"); return dev_fail(PWAF_E_UNSUPPORTED); }
-        // POLARITY (round 6). `user_agent.length() >= 256` reaches here as NOT(length <= 255), `path.length() > 20` as NOT(length <= 20): atoms that
-        // hold for nearly every request and only ever appear negated — a (column, mask) pair per group for nothing, and gate A's term
-        // [NOT(length <= 255)] has no positive literal at all: the gate was a candidate rule in EVERY group. An atom whose literals are mostly
-        // negations is evaluated COMPLEMENTED on the device (flag 0x80 of its code: `v > c`, `v != c`) and every literal of it toggles its
-        // negation in the device copy of the literals: same truth table, rare columns, and gate A becomes a triggered rule. (client.asn
-        // comparisons keep their polarity: an engine-resolved record answers them through class-row bits computed below.)
-        std::vector<uint8_t> flipped(P.n_cols, 0);
-        if (verdict_mode(P.flags) >= 3u && !(P.flags & PWAF_OPT_EAGER_CMP)) {
-            std::vector<uint32_t> n_pos(P.n_cols, 0), n_neg(P.n_cols, 0);
-            for (const uint32_t lit : P.lits) ((lit & LIT_NEG) ? n_neg : n_pos)[lit & LIT_ATOM_MASK]++;
-            for (const Canon &cn : canon)
-                if (cn.vi != 6u && n_neg[cn.col] > n_pos[cn.col]) flipped[cn.col] = 1;
-        }
-        std::vector<uint32_t> L = P.lits;  // the literals as the device evaluates them
-        for (uint32_t &lit : L)
-            if (flipped[lit & LIT_ATOM_MASK]) lit ^= LIT_NEG;
-        std::vector<CmpAtomDev> cmp_atoms;
-        for (const Canon &cn : canon) {
-            cmp_atoms.push_back({cn.col | (((2 * cn.vi + cn.op) | (flipped[cn.col] ? 0x80u : 0u)) << 24), cn.c});
-            if (cn.vi == 6) {
-                // client.asn against a constant is a function of the GeoIP record: bit j of the class row's comparison words
-                // (source words 24..27) when the engine resolves the record itself
-                const uint32_t j = (uint32_t)e->host_acmp.size();
-                if (j >= 128) { fail(PWAF_E_UNSUPPORTED, "more than 128 distinct client.asn comparisons"); return dev_fail(PWAF_E_UNSUPPORTED); }
-                bit_col[(kSrcAcmp + j / 32) * 32 + (j & 31)] = cn.col;
-                e->host_acmp.push_back({cn.op, cn.c});
-            }
-        }
-        e->acmp_words = ((uint32_t)e->host_acmp.size() + 31) / 32;
-        UP(bit_atoms, bit_col)
-        // Trigger lists: a rule can match only if one of its DNF terms is true; a term with a positive literal needs that
-        // column to be non-zero. Per term pick the positive literal least likely to be set (scan < membership < comparison <
-        // TRUE) and file the rule under that column; terms made of negations only make the rule an unconditional candidate.
-        // (rule indices travel as 16-bit values inside the verdict kernel; 0xFFF0.. is kept for the pseudo rules of the two gates)
-        // (the caller's routes are device rules too: rules and routes share the limit)
-        if (P.rules.size() > 65519 || n_rules + n_routes > 65519) {
-            fail(PWAF_E_UNSUPPORTED, n_routes ? "more than 65519 rules and routes" : "more than 65519 rules");
-            return dev_fail(PWAF_E_UNSUPPORTED);
-        }
-        // lower = rarer: scan atoms by how specific their pattern is (shortest possible match), then memberships, then
-        // comparisons (often true for most requests), then the constant TRUE column
-        std::vector<uint32_t> rank(P.n_cols, 100);
-        for (auto &at : P.atoms)
-            if (at.kind == ATOM_SCAN && at.id < P.n_cols) rank[at.id] = 64 - std::min<uint32_t>(at.min_len, 64);
-        rank[0] = 300;
-        for (auto &d : cmp_src) rank[d.col] = 200;
-        for (uint32_t d : bit_atoms) rank[d & 0xFFFFFu] = 60;
-        std::vector<std::vector<uint16_t>> by_col(P.n_cols);
-        std::vector<uint32_t> always((P.rules.size() + 31) / 32 + 1, 0);
-        std::vector<uint8_t> in_untriggered_term(P.n_cols, 0);  // the column stands in a term made of negations only: its rule is a candidate in EVERY group
-        for (size_t r = 0; r < P.rules.size(); r++) {
-            const DevRule &dr = P.rules[r];
-            int best = -1;
-            bool term_open = false;
-            uint32_t term_first = dr.lit_off;
-            for (uint32_t k = dr.lit_off; k < dr.lit_off + dr.lit_cnt; k++) {
-                const uint32_t lit = L[k];
-                if (!term_open) { best = -1; term_open = true; term_first = k; }
-                if (!(lit & LIT_NEG)) {
-                    const int c = (int)(lit & LIT_ATOM_MASK);
-                    if (best < 0 || rank[c] < rank[best]) best = c;
-                }
-                if (lit & LIT_TERM_END) {
-                    if (best < 0) {
-                        always[r >> 5] |= 1u << (r & 31);
-                        for (uint32_t q = term_first; q <= k; q++) in_untriggered_term[L[q] & LIT_ATOM_MASK] = 1;
-                    } else if (by_col[best].empty() || by_col[best].back() != (uint16_t)r) by_col[best].push_back((uint16_t)r);
-                    term_open = false;
-                }
-            }
-        }
-        std::vector<uint32_t> trig_off(1, 0);
-        std::vector<uint16_t> trig_rules;
-        for (uint32_t c = 0; c < P.n_cols; c++) {
-            trig_rules.insert(trig_rules.end(), by_col[c].begin(), by_col[c].end());
-            trig_off.push_back((uint32_t)trig_rules.size());
-        }
-        e->n_trig = (uint32_t)trig_rules.size();
-        // LAZY comparison atoms (round 6; program.h: LIT_LAZY). `path.length() > 20`, `remote_port >= 1024` hold for somebody in nearly every
-        // group of 64 requests, yet almost all of them only ever stand beside a rarer literal (`lit && path.length() > K`): the attribute kernel
-        // spent a third of its time evaluating them for every group, and the verdict kernel filed a pair for each. An atom that is NO rule's
-        // trigger (and stands in no term of negations only) is only needed once such a rule is a candidate whose other literals hold for somebody: the verdict kernel then compares the
-        // 64 requests' values itself. (client.asn comparisons stay eager: engine-resolved records answer them through class-row bits.)
-        std::vector<CmpAtomDev> lazy_atoms;
-        std::vector<uint32_t> lazy_of(P.n_cols, 0xFFFFFFFFu);
-        if (verdict_mode(P.flags) >= 3u && !(P.flags & PWAF_OPT_EAGER_CMP)) {
-            // (up to two variables: the verdict kernel keeps a group's raw values of the lazy variables in two registers)
-            std::vector<CmpAtomDev> eager;
-            for (const CmpAtomDev &ca : cmp_atoms) {
-                const uint32_t col = ca.col & 0xFFFFFFu, code = ca.col >> 24, vi = (code & 0x7Fu) / 2u;
-                // (an atom of a term without a trigger — `user_agent.length() >= 256` is NOT(length <= 255): gate A — would be evaluated lazily in every group)
-                bool lazy = vi != 6u && by_col[col].empty() && !in_untriggered_term[col] && ca.c <= 0xFFFFu;  // (the constant travels inside the literal word)
-                uint32_t slot = 0;
-                if (lazy) {
-                    slot = (uint32_t)(std::find(e->lazy_vars.begin(), e->lazy_vars.end(), vi) - e->lazy_vars.begin());
-                    if (slot == e->lazy_vars.size()) {
-                        if (slot < 2) e->lazy_vars.push_back(vi);
-                        else lazy = false;
-                    }
-                }
-                if (lazy) {
-                    lazy_of[col] = ca.c | ((code & 1u) << 16) | (slot << 17) | ((code & 0x80u) ? 1u << 18 : 0u);
-                    lazy_atoms.push_back({((2u * slot + (code & 1u)) | (code & 0x80u)) << 24, ca.c});  // (kept for pwaf_engine_stats-style introspection: the kernel reads the literal word)
-                } else {
-                    eager.push_back(ca);
-                }
-            }
-            cmp_atoms.swap(eager);
-        }
-        e->n_cmp_atoms = (uint32_t)cmp_atoms.size();
-        e->cmp_vars = 0;
-        for (const CmpAtomDev &ca : cmp_atoms) e->cmp_vars |= 1u << std::min(31u, ((ca.col >> 24) & 0x7Fu) / 2u);
-        e->n_lazy = (uint32_t)lazy_atoms.size();
-        if (lazy_atoms.empty()) lazy_atoms.push_back({0, 0});
-        UP(num_atoms, cmp_atoms)
-        UP(lazy_atoms, lazy_atoms)
-        {
-            std::vector<uint32_t> dev_lits = L;
-            for (uint32_t &lit : dev_lits) {
-                const uint32_t j = lazy_of[lit & LIT_ATOM_MASK];
-                if (j != 0xFFFFFFFFu) lit = (lit & (LIT_NEG | LIT_TERM_END)) | LIT_LAZY | j;
-            }
-            UP(lits, dev_lits)
-        }
-        UP(trig_off, trig_off)
-        UP(trig_rules, trig_rules)
-        UP(always_rules, always)
-        if (verdict_shape(P.n_cols, (uint32_t)P.rules.size(), e->n_trig, (uint32_t)P.lits.size(), (P.flags & PWAF_OPT_GLOBAL_VERDICT_TABLES) != 0,
-                          (int)verdict_mode(P.flags), (uint32_t)P.groups.size() + 2u).waves == 0 || P.n_cols >= 65536u) {
-            fail(PWAF_E_UNSUPPORTED, "too many distinct predicates for one LDS column file (160 KiB)");
-            return dev_fail(PWAF_E_UNSUPPORTED);
-        }
+    TablePlan plan;
+    if ((rc = plan_tables(P, n_rules, n_routes, plan))) return dev_fail(rc);
+    if (verdict_shape(P.n_cols, (uint32_t)P.rules.size(), plan.n_trig, (uint32_t)P.lits.size(), (P.flags & PWAF_OPT_GLOBAL_VERDICT_TABLES) != 0,
+                      (int)verdict_mode(P.flags), (uint32_t)P.groups.size() + 2u).waves == 0 || P.n_cols >= 65536u) {
+        fail(PWAF_E_UNSUPPORTED, "too many distinct predicates for one LDS column file (160 KiB)");
+        return dev_fail(PWAF_E_UNSUPPORTED);
     }
-    {
-        // transpose the per-predicate 676-bit country tables into per-country membership words (one gather per request)
-        const uint32_t n_luts = (uint32_t)P.country_luts.size();
-        e->cc_words = std::max(1u, (n_luts + 31) / 32);
-        std::vector<uint32_t> masks((size_t)676 * e->cc_words, 0);
-        for (uint32_t t = 0; t < n_luts; t++)
-            for (uint32_t c = 0; c < 676; c++)
-                if (P.country_luts[t][c]) masks[(size_t)c * e->cc_words + (t >> 5)] |= 1u << (t & 31);
-        e->host_cc_masks = masks;
-        UP(country_luts, masks)
-    }
-    UP(rules, P.rules)
-    if (P.n_dev_routes && (P.flags & PWAF_OPT_RULE_HITS)) {
-        // The HITS variant of the verdict kernel reports every candidate's match word under its public index; a route's is its ROUTE index.
-        // A hit call therefore runs over a copy of the rule table in which the routes have no literal: their word is 0, nothing is reported.
-        std::vector<DevRule> unrouted = P.rules;
-        for (size_t k = P.route_base; k < unrouted.size(); k++) unrouted[k].lit_cnt = 0;
-        UP(rules_unrouted, unrouted)
-    }
-    UP(set_masks, P.set_masks)
-    UP(ip_root4, P.ipset_trie.root4)
-    UP(ip_root6, P.ipset_trie.root6)
-    UP(ip_nodes, P.ipset_trie.nodes)
-    {
-        // GeoIP classes: everything that depends on the record — country-table bits, asn-set bits, asn comparisons — as one row per
-        // record; records with equal rows share a CLASS (a few hundred for a real rule set), class 0 is the all-zero row. The
-        // device trie's leaves carry class ids, so a request gathers one small cache-resident row instead of a per-record one.
-        e->class_words = std::max(1u, e->cc_words + e->iu_words[1] + e->acmp_words);
-        std::map<std::vector<uint32_t>, uint32_t> class_of;
-        std::vector<uint32_t> rows(e->class_words, 0);  // class 0
-        class_of.emplace(rows, 0u);
-        std::vector<uint32_t> rec_class(P.geo_recs.size(), 0);
-        for (size_t r = 0; r < P.geo_recs.size(); r++) {
-            std::vector<uint32_t> row(e->class_words, 0);
-            const uint32_t c0 = (P.geo_recs[r].country & 0xFFu) - 'A', c1 = (P.geo_recs[r].country >> 8) - 'A';
-            const uint32_t cidx = (c0 < 26u && c1 < 26u) ? c0 * 26u + c1 : 23u * 26u + 23u;
-            for (uint32_t w = 0; w < e->cc_words; w++) row[w] = e->host_cc_masks[(size_t)cidx * e->cc_words + w];
-            const uint32_t asn = P.geo_recs[r].asn;
-            auto it = std::lower_bound(e->host_iu_vals1.begin(), e->host_iu_vals1.end(), (int64_t)asn);
-            const size_t mrow = (it != e->host_iu_vals1.end() && *it == (int64_t)asn) ? (size_t)(it - e->host_iu_vals1.begin()) + 1 : 0;
-            for (uint32_t w = 0; w < e->iu_words[1]; w++) row[e->cc_words + w] = e->host_iu_masks1[mrow * e->iu_words[1] + w];
-            for (size_t j = 0; j < e->host_acmp.size(); j++)
-                if (e->host_acmp[j].first == 0 ? asn == e->host_acmp[j].second : asn <= e->host_acmp[j].second)
-                    row[e->cc_words + e->iu_words[1] + j / 32] |= 1u << (j & 31);
-            auto ins = class_of.emplace(row, (uint32_t)class_of.size());
-            if (ins.second) rows.insert(rows.end(), row.begin(), row.end());
-            rec_class[r] = ins.first->second;
-        }
-        e->n_classes = (uint32_t)class_of.size();
-        e->geo_default = rec_class[0];
-        UP(class_rows, rows)
-        auto remap = [&](const std::vector<uint32_t> &src) {
-            std::vector<uint32_t> out(src);
-            for (auto &x : out)
-                if (x & TRIE_LEAF) x = TRIE_LEAF | rec_class[x & ~TRIE_LEAF];
-            return out;
-        };
-        const std::vector<uint32_t> r4 = remap(P.geo_trie.root4), r6 = remap(P.geo_trie.root6), nd = remap(P.geo_trie.nodes);
-        UP(geo_root4, r4)
-        UP(geo_root6, r6)
-        UP(geo_nodes, nd)
-        const std::vector<uint32_t> leaf(65536, TRIE_LEAF);
-        UP(leaf_root, leaf)
-        // (a GeoIP family without prefixes: every address reads the DEFAULT record's class — not class 0: `["XX"].contains(client.country)` or
-        // `client.asn < N` hold for the default record. Round 6: an IPv6 client against a table of IPv4 prefixes read class 0 and such a rule
-        // failed open; found by tests/test_gpu_paths.py: test_lazy_comparison_atoms_agree_with_eager_ones_and_the_oracle)
-        const std::vector<uint32_t> geo_leaf(65536, TRIE_LEAF | e->geo_default);
-        UP(geo_leaf_root, geo_leaf)
-    }
-    if (P.n_residual) {
-        UP(residual_blob, P.residual_blob)
-        {
-            const std::vector<unsigned long long> zero(P.n_residual, 0ull);
-            UP(residual_errors, zero)
-        }
-        if (P.has_geo && P.residual_needs_geo) {
-            // client.asn / client.country VALUES (the class trie above only keeps which predicates hold): the trie with record leaves
-            const std::vector<uint32_t> leaf0(65536, TRIE_LEAF);  // record 0 = the default {0, "XX"}
-            UP(geo_rec_root4, (P.geo_trie.root4.empty() ? leaf0 : P.geo_trie.root4))
-            UP(geo_rec_root6, (P.geo_trie.root6.empty() ? leaf0 : P.geo_trie.root6))
-            UP(geo_rec_nodes, P.geo_trie.nodes)
-            UP(geo_recs, P.geo_recs)
-        }
-    }
-#undef UP
+    if ((rc = upload_tables(e.get(), plan))) return dev_fail(rc);
     if (P.flags & PWAF_OPT_GEO_ANSWERS) {
         // GeoIP answers: the trie with RECORD leaves and the records (shared with the residual rules: uploaded once), and for IPv4 a table
         // of record ids over the trie's first 24 bits, compressed like the class table (csrc/georec.h, csrc/dirtable.h)

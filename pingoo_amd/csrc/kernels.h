@@ -11,7 +11,6 @@ namespace pwaf {
 static constexpr int kMaxPasses = 250;  // (= program.h kMaxGroups)
 static constexpr int kVerdictPre = 12;  // hit records per request the verdict kernel requests one group ahead
 static constexpr uint32_t kGapLists = 32;     // gated gap passes own list slots [0, 32) (one bit each in the factor masks); filtered passes follow
-static constexpr uint32_t kMaxHeaderLens = 8; // header columns whose LENGTH rules compare
 static constexpr uint32_t kDirChunkWords = 32; // one 128-byte line per /16 of the compressed DIR-24 table (VerdictArgs::dir_chunks)
 
 // Hit record of one (scan pass, request): what the request's field matched in that pass's DFA.
@@ -262,10 +261,6 @@ int launch_compact(const FilterArgs *host, uint32_t count, const FilterArgs *dev
 // devices of one process each need it).
 int configure_kernels(int device);
 
-// Source words of the membership atoms of one request (bit_col maps (source word, bit) -> column): ip-list sets, country tables,
-// port sets, asn sets, asn comparisons.
-static constexpr uint32_t kSrcSet = 0, kSetWordsMax = 16, kSrcCc = 16, kCcWordsMax = 8, kSrcPort = 24, kSrcAsn = 28, kIntWordsMax = 4, kSrcAcmp = 32, kAcmpWordsMax = 4,
-                          kSrcWords = 36;
 struct PassInfo {
     uint32_t base;       // first device column of the pass
     uint32_t kind_slot;  // kind << 24 | slot
@@ -341,9 +336,6 @@ int launch_residual_jit(const JitKernel &k, const ResidualJitArgs &a, uint32_t n
 struct ColPtrChunk {
     const void *p[2 * (PWAF_N_FIELDS + kMaxHeaders)];
     uint32_t count;
-};
-struct CmpAtomDev {
-    uint32_t col, c;
 };
 // A string atom that is an anchored literal of at most 8 bytes (`method == "POST"`, `method.starts_with("P")`) on a field whose
 // pass consists of such atoms only: evaluated by the attribute kernel from the field's first 8 bytes instead of a DFA pass over

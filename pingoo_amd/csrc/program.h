@@ -263,16 +263,27 @@ struct DevRule {
 static constexpr uint32_t LIT_NEG = 1u << 30;       // negated atom
 static constexpr uint32_t LIT_TERM_END = 1u << 31;  // last literal of its conjunction
 static constexpr uint32_t LIT_ATOM_MASK = (1u << 24) - 1;
-// DEVICE copy of the literals only (engine.cpp; never in Program::lits): a LAZY comparison atom — `length / port op constant` that is no rule's
+// DEVICE copy of the literals only (tableplan.cpp; never in Program::lits): a LAZY comparison atom — `length / port op constant` that is no rule's
 // trigger — is not evaluated per group by the attribute kernel; its literal carries an index into VerdictArgs::lazy instead of a column and the
 // verdict kernel evaluates it for the few rules whose other literals already hold for somebody (kernels.hip: verdict2_kernel)
 static constexpr uint32_t LIT_LAZY = 1u << 29;  // then bits [15:0] = the constant (<= 65534... any 16-bit value), bit 16 = operator (0: ==, 1: <=), bit 17 = slot of the variable (VerdictArgs::lazy_var), bit 18 = the atom is evaluated complemented (!=, >)
+static constexpr uint32_t LIT_LAZY_CONST_MASK = 0xFFFFu, LIT_LAZY_OP = 1u << 16, LIT_LAZY_SLOT = 1u << 17, LIT_LAZY_COMPLEMENT = 1u << 18;  // the fields of such a word
 
 struct NumAtomDev {  // numeric atom descriptor consumed by the verdict kernel
     uint32_t col;    // device column
     uint8_t kind, var, op, pad;
     uint32_t ref, ref2;  // INTSET: [begin,end) into int_pool; IPSET: list bit; COUNTRY: lut index
     int64_t c;
+};
+
+// ---- layouts of the attribute tables: planned on the host (tableplan.cpp), read by attr_kernel / the verdict kernels ----
+// Source words of the membership atoms of one request (bit_col maps (source word, bit) -> column): ip-list sets, country tables,
+// port sets, asn sets, asn comparisons.
+static constexpr uint32_t kSrcSet = 0, kSetWordsMax = 16, kSrcCc = 16, kCcWordsMax = 8, kSrcPort = 24, kSrcAsn = 28, kIntWordsMax = 4, kSrcAcmp = 32, kAcmpWordsMax = 4,
+                          kSrcWords = 36;
+static constexpr uint32_t kMaxHeaderLens = 8;  // header columns whose LENGTH rules compare
+struct CmpAtomDev {  // a comparison atom: col = device column | code << 24 (tableplan.h: cmp_code), c = the constant
+    uint32_t col, c;
 };
 
 static constexpr uint32_t kMaxHeaders = 120;   // header columns (field ids 5 .. 5 + kMaxHeaders - 1)

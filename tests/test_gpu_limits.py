@@ -224,3 +224,27 @@ def test_lazy_constants_across_0xffff():
 
 def rstr(rng):
     return H.rstr(rng, 1, 8, "abcxyz/")
+
+
+def test_a_refusal_of_the_table_planner_reaches_the_caller():
+    """Creation only (no batch): a refusal of csrc/tableplan.cpp comes back as PWAF_E_UNSUPPORTED without a rule index, its text in the
+    compile error and in pwaf_last_error, and the device is left usable. 513 ip lists are the planner refusal a rule set reaches; 129
+    integer sets on one variable are not one — the rule compiler counts that width too and runs the 129th rule as a residual program
+    (tests/test_tableplan_cpu.py: test_attribute_row_widths_at_and_past_the_limit) — so that rule set must still create."""
+    from pingoo_amd.engine import UnsupportedExpression, lib
+
+    rules = [("r", 'lists["l0"].contains(client.ip) || client.ip in lists.l512', [H.B])]
+    lists = {f"l{k}": (_abi.LIST_IP, [f"10.{k >> 8}.{k & 255}.0/24"]) for k in range(513)}
+    with pytest.raises(UnsupportedExpression) as ei:
+        RuleEngine(rules, lists, None)
+    assert ei.value.code == _abi.E_UNSUPPORTED and ei.value.rule_index is None  # (err.rule_index == 0xFFFFFFFF)
+    assert ei.value.message == "more than 512 ip lists" and lib().pwaf_last_error() == b"more than 512 ip lists"
+    sets = [(f"r{k}", f"[{k + 2}, {70000 + k}].contains(client.remote_port)", [H.B]) for k in range(129)]
+    eng = RuleEngine(sets, {}, None, flags=_abi.OPT_NO_RESIDUAL_JIT)
+    try:
+        assert eng.residual_mode == 1  # (one rule runs in the residual interpreter)
+    finally:
+        eng.close()
+    lists.pop("l512")
+    rules = [("r", 'lists["l0"].contains(client.ip) || client.ip in lists.l511', [H.B])]
+    RuleEngine(rules, lists, None).close()  # 512 lists, the widest membership set, on the same device
