@@ -611,6 +611,14 @@ long pwaf_program_residual_compile(const pwaf_program *, const char *arch, char 
  * no prefilter. The reference has no counterpart: it evaluates every predicate on every request (pingoo/rules.rs:37-51). */
 int pwaf_program_confirm_field(const pwaf_program *, uint32_t group, const uint8_t *bytes, size_t len, uint32_t arena_offset,
                                uint16_t *atoms, size_t cap, size_t *n_atoms, int *flagged, int *walk);
+/* TEST HOOK (CPU, no device): the shape of the confirm tier of scan pass `group`, so that a test can assert that the path it was
+ * written for exists. out[0] = entries, out[1] = bytes of the value / mask / class-position pool, out[2] = class words (8 per byte
+ * class), out[3] = 1 when entries * 3 + bytes / 4 + class words fit the LDS pool of confirm_kernel (the kernel's own test: the
+ * comparison tables are then read from on-chip memory, otherwise from global memory), out[4] = the longest factor in bytes, out[5] =
+ * the highest class position of any entry (0 without classes), out[6] = the largest entry count of one bin, out[7] = 1 when the
+ * table has a walk entry (a factor of a non-literal predicate). PWAF_E_INVALID_ARG when the pass has no confirm tier. The reference
+ * has no counterpart. */
+int pwaf_program_confirm_shape(const pwaf_program *, uint32_t group, uint32_t out[8]);
 /* TEST HOOK (needs an engine, i.e. a device; reads host-side fields only): what the IPv4 lookup structures of this engine look like,
  * so that a test can assert that the path it was written for exists. out[0] = escaped /24s of the DIR-24 table (a prefix longer
  * than /24, or a class >= 65536 / membership set >= 32768), out[1] = entries of the run table behind the 16-byte records (0: the

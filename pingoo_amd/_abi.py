@@ -37,6 +37,8 @@ FIELD_NAMES = ("host", "url", "path", "method", "user_agent")
 ARENA_PAD = 16
 # pwaf_engine_address_tables (test hook): the meaning of out[0..7]
 ADDRESS_TABLE_FIELDS = ("escapes", "n_vals", "has_summary", "shift", "common", "packed", "classes", "sets")
+# pwaf_program_confirm_shape (test hook): the meaning of out[0..7]
+CONFIRM_SHAPE_FIELDS = ("entries", "bytes", "class_words", "in_lds", "longest", "top_class_pos", "widest_bin", "has_walk")
 # pwaf_engine_coarse_tables (test hook): the meaning of out[0..15]
 COARSE_TABLE_FIELDS = ("present", "shift", "bytes", "blocks_set", "summary_blocks_set", "threads", "wg_per_cu", "zero7",
                        "rec_present", "rec_shift", "rec_bytes", "rec_blocks_set", "zero12", "zero13", "zero14", "zero15")

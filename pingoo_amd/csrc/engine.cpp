@@ -1601,7 +1601,7 @@ struct BatchRun {
         c.c_bytes = (const uint8_t *)d.c_bytes.p;
         c.c_classes = (const uint32_t *)d.c_classes.p;
         c.n_entries = (uint32_t)d.filter.confirm.entries.size();
-        c.n_bytes = (uint32_t)d.filter.confirm.bytes.size() & ~3u;
+        c.n_bytes = confirm_table_bytes(d.filter.confirm.bytes.size());
         c.n_class_words = (uint32_t)d.filter.confirm.classes.size();
         c.rec = f.rec;
         c.valid_bits = f.bitmap;
@@ -2345,6 +2345,33 @@ int pwaf_program_confirm_field(const pwaf_program *p, uint32_t group, const uint
     for (size_t k = 0; k < *n_atoms; k++) atoms[k] = lits[k];
     *flagged = fl ? 1 : 0;
     *walk = wk ? 1 : 0;
+    return PWAF_OK;
+}
+
+int pwaf_program_confirm_shape(const pwaf_program *p, uint32_t group, uint32_t out[8]) {
+    if (!p || !p->p || group >= p->p->groups.size() || !out) return fail(PWAF_E_INVALID_ARG, "pwaf_program_confirm_shape: bad argument");
+    const GroupFilter &f = p->p->groups[group].filter;
+    if (!f.enabled || !f.confirm.enabled) return fail(PWAF_E_INVALID_ARG, "the pass has no confirm tier");
+    const ConfirmTable &t = f.confirm;
+    // the sizes as the engine hands them to confirm_kernel (ConfirmArgs: n_entries, n_bytes, n_class_words) and the kernel's own test (kernels.h)
+    const uint32_t n_entries = (uint32_t)t.entries.size(), n_bytes = confirm_table_bytes(t.bytes.size()), n_class_words = (uint32_t)t.classes.size();
+    const bool in_lds = confirm_tables_fit(n_entries, n_bytes, n_class_words);
+    uint32_t longest = 0, top_class = 0, widest = 0, walk = 0;
+    for (const ConfirmEntry &e : t.entries) {
+        longest = std::max<uint32_t>(longest, e.len);
+        if (e.atom == kConfirmWalk) walk = 1;
+        const size_t cls = (size_t)e.bytes_off + 2u * ((e.len + 3u) & ~3u);  // behind the value and the mask: n_cls x {position, class id}
+        for (uint32_t k = 0; k < e.n_cls && cls + 2u * k < t.bytes.size(); k++) top_class = std::max<uint32_t>(top_class, t.bytes[cls + 2u * k]);
+    }
+    for (const uint32_t hd : t.head) widest = std::max(widest, hd >> 20);
+    out[0] = n_entries;
+    out[1] = n_bytes;
+    out[2] = n_class_words;
+    out[3] = in_lds ? 1u : 0u;
+    out[4] = longest;
+    out[5] = top_class;
+    out[6] = widest;
+    out[7] = walk;
     return PWAF_OK;
 }
 

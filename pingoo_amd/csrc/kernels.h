@@ -181,6 +181,13 @@ struct ConfirmArgs {
 };
 static constexpr uint32_t kConfirmThreads = 1024;
 static constexpr uint32_t kConfirmPoolBytes = 40 * 1024;  // LDS for a pass's entries + bytes + classes, next to the two 16 KiB tables: two 1024-thread workgroups per CU
+// ConfirmArgs::n_bytes of a value / mask / class pool of `pool_bytes` bytes (whole words: the pool is copied to LDS word by word)
+constexpr uint32_t confirm_table_bytes(const size_t pool_bytes) { return (uint32_t)pool_bytes & ~3u; }
+// does a pass's comparison tables fit confirm_kernel's LDS pool? (ConfirmArgs::n_entries, n_bytes, n_class_words; an entry is three
+// words.) The ONE test: confirm_kernel decides with it where it compares from, pwaf_program_confirm_shape reports it.
+constexpr bool confirm_tables_fit(const uint32_t n_entries, const uint32_t n_bytes, const uint32_t n_class_words) {
+    return (uint64_t)n_entries * 3u + n_bytes / 4u + n_class_words <= kConfirmPoolBytes / 4;
+}
 struct ConfirmTableDev {
     const ConfirmArgs *c;  // device
     uint32_t count;

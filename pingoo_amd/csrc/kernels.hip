@@ -1068,7 +1068,7 @@ __global__ __launch_bounds__(kConfirmThreads, 8) void confirm_kernel(ConfirmTabl
         }
         // the comparison tables: LDS when they fit (generic pointers: the same comparison code reads either copy)
         const uint32_t e_words = a.n_entries * 3u, b_words = a.n_bytes / 4u, c_words = a.n_class_words;
-        const bool in_lds = (uint64_t)e_words + b_words + c_words <= kConfirmPoolBytes / 4;
+        const bool in_lds = confirm_tables_fit(a.n_entries, a.n_bytes, a.n_class_words);
         const ConfirmEntry *t_entries = a.c_entries;
         const uint8_t *t_bytes = a.c_bytes;
         const uint32_t *t_classes = a.c_classes;

@@ -87,6 +87,7 @@ def lib():
     L.pwaf_program_stats.argtypes = [vp, C.POINTER(_abi.Stats)]
     L.pwaf_program_rule_status.argtypes = [vp, C.c_uint32, C.c_char_p, C.c_size_t]
     L.pwaf_program_confirm_field.argtypes = [vp, C.c_uint32, C.c_char_p, C.c_size_t, C.c_uint32, C.POINTER(C.c_uint16), C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_int), C.POINTER(C.c_int)]
+    L.pwaf_program_confirm_shape.argtypes = [vp, C.c_uint32, C.POINTER(C.c_uint32)]
     L.pwaf_engine_rule_errors.argtypes = [vp, C.POINTER(C.c_uint64), C.c_size_t]
     L.pwaf_engine_residual_mode.argtypes = [vp]
     L.pwaf_engine_address_tables.argtypes = [vp, C.POINTER(C.c_uint32)]
@@ -346,6 +347,16 @@ class CompiledProgram:
         if rc != 0:
             _raise(rc, lib().pwaf_last_error().decode(errors="replace"))
         return sorted(set(atoms[k] for k in range(n.value))), bool(fl.value), bool(wk.value)
+
+    def confirm_shape(self, group: int) -> dict:
+        """TEST HOOK (pwaf_program_confirm_shape): the shape of pass `group`'s confirm tier, by the names of _abi.CONFIRM_SHAPE_FIELDS —
+        entries, pool bytes, class words, in_lds (confirm_kernel compares from its LDS copy), longest factor, highest class position,
+        largest bin, has_walk. Raises for a pass without a confirm tier."""
+        out = (C.c_uint32 * len(_abi.CONFIRM_SHAPE_FIELDS))()
+        rc = lib().pwaf_program_confirm_shape(self._h, group, out)
+        if rc != 0:
+            _raise(rc, lib().pwaf_last_error().decode(errors="replace"))
+        return dict(zip(_abi.CONFIRM_SHAPE_FIELDS, (int(x) for x in out)))
 
     def residual_source(self, kind: int = 1) -> str:
         """Inspection hook: the specialized form of the residual rules (csrc/residual_jit.cpp). kind 0 = the rule functions alone,

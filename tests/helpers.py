@@ -1,13 +1,16 @@
 """Shared test helpers: golden-vector loading, a random expression / request fuzzer, verdict comparison."""
 from __future__ import annotations
 
+import ctypes as C
 import json
 import os
 import random
 
 import numpy as np
 
+from oracle import pyoracle
 from pingoo_amd import Request, RequestBatch, _abi
+from pingoo_amd.batch import hits_to_matrix
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 B, CAP = _abi.RULE_ACTION_BLOCK, _abi.RULE_ACTION_CAPTCHA
@@ -531,3 +534,32 @@ def pinned_requests(rng: random.Random, ps: PinnedSet, n: int, hit: float = 0.3,
                             ip=f"{rng.randint(1, 3)}.{rng.randint(0, 3)}.0.{rng.randint(0, 255)}", remote_port=rng.randint(0, 65535),
                             captcha_verified=rng.random() < 0.3))
     return reqs
+
+
+# ---------------------------------------------------------------------------------------------------------
+# the hit matrix of PWAF_OPT_RULE_HITS against the oracle's own
+# ---------------------------------------------------------------------------------------------------------
+def oracle_matrix(oracle, batch, only=None):
+    """-> (M, the oracle's verdicts): M[k, i] = rule k evaluates to Bool(true) for request i (or has no expression), cleared where the
+    request's verdict is a gate's. `only`: the requests (columns) to fill; the others stay False."""
+    st = batch.as_struct(oracle.header_names)
+    fn, h, ref = pyoracle.lib().pwaf_oracle_execute_rule, oracle._h, C.byref(st)
+    m = np.zeros((oracle.n_rules, batch.n), dtype=bool)
+    cols = range(batch.n) if only is None else list(only)
+    for k in range(oracle.n_rules):
+        for i in cols:
+            m[k, i] = fn(h, k, ref, i) == 1
+    want = oracle.evaluate(batch)
+    m[:, np.isin(want["rule_idx"], (_abi.RULE_UA_GATE, _abi.RULE_CAPTCHA_ENDPOINT))] = False
+    return m, want
+
+
+def assert_hits(label, hits, rule_hits, m):
+    n_rules, n = m.shape
+    assert (hits["mask"] != 0).all(), f"{label}: an entry with an empty mask"
+    pairs = hits["rule_idx"].astype(np.uint64) << np.uint64(32) | hits["group"].astype(np.uint64)
+    assert len(np.unique(pairs)) == len(hits), f"{label}: a (rule, group) pair appears twice"
+    got = hits_to_matrix(hits, n, n_rules)
+    bad = np.argwhere(got != m)
+    assert len(bad) == 0, f"{label}: {len(bad)} of {m.size} (rule, request) bits differ; first: rule {bad[0][0]}, request {bad[0][1]}: got {got[tuple(bad[0])]}"
+    assert rule_hits.tolist() == m.sum(axis=1).tolist(), f"{label}: rule_hits"

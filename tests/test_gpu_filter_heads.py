@@ -11,10 +11,11 @@ pass is observed by itself, fillers included."""
 import numpy as np
 import pytest
 
+import confirm_cases
 import helpers as H
 import table_walker
 from oracle import pyoracle
-from pingoo_amd import Request, RequestBatch, _abi
+from pingoo_amd import _abi
 from pingoo_amd.engine import CompiledProgram, NodeEngine, RuleEngine
 
 pytestmark = pytest.mark.gpu
@@ -94,34 +95,13 @@ def probes(lit, exact):
     return [lit + tail, lit[:-1] + alt + tail, lit[:-1], lit] + ([lit + "x"] if exact else [])
 
 
-class Arena:
+class Arena(confirm_cases.Arena):
     """A batch in which the values of ONE field are placed at chosen bytes of its arena (a request's value begins where its predecessor's
-    ends). Fillers carry the paths of the field's heads in turn, so their records count too."""
+    ends: confirm_cases.Arena). Fillers carry the paths of the field's heads in turn, so their records count too."""
 
     def __init__(self, heads, field):
-        self.field, self.reqs, self.cur, self.turn = field, [], 0, 0
-        self.ks = [k for k, (f, _, _) in enumerate(heads) if f == field]
+        super().__init__(field, [k for k, (f, _, _) in enumerate(heads) if f == field])
         self.heads = heads
-
-    def add(self, value, k=None):
-        if k is None:
-            k, self.turn = self.ks[self.turn % len(self.ks)], self.turn + 1
-        other = {"url": "/i", "user_agent": "ua"}
-        other[self.field] = value
-        self.reqs.append(Request(host="h", path=f"/h{k}", **other))
-        self.cur += len(value)
-
-    def pad_to(self, pos, piece=200):
-        """fillers of 16 bytes or more each (one start per chunk) up to arena byte pos"""
-        assert pos >= self.cur and (pos == self.cur or pos - self.cur >= 16), (pos, self.cur)
-        while self.cur < pos:
-            k = pos - self.cur
-            self.add("filler-" + "q" * ((k if k < piece + 16 else piece) - 7))
-
-    def at(self, start, step, lo=16):
-        """the first byte == start (mod step) that leaves room for a filler"""
-        p = (self.cur + lo - start + step - 1) // step * step + start
-        return p
 
     def place_all(self, start, step, piece=200, skip=lambda p: False):
         """every probe of every head of the field, each at the next byte == start (mod step)"""
@@ -132,9 +112,6 @@ class Arena:
                     p += step
                 self.pad_to(p, piece)
                 self.add(v, k)
-
-    def batch(self):
-        return RequestBatch.from_requests(self.reqs)
 
 
 @pytest.mark.parametrize("field", ["user_agent", "url"])

@@ -23,29 +23,7 @@ GATES = (_abi.RULE_UA_GATE, _abi.RULE_CAPTCHA_ENDPOINT)
 NO_GATES = _abi.OPT_NO_UA_GATE | _abi.OPT_NO_CAPTCHA_BYPASS
 
 
-def oracle_matrix(oracle, batch):
-    """-> (M, the oracle's verdicts): M[k, i] = rule k evaluates to Bool(true) for request i (or has no expression), cleared where the
-    request's verdict is a gate's"""
-    st = batch.as_struct(oracle.header_names)
-    fn, h, ref = pyoracle.lib().pwaf_oracle_execute_rule, oracle._h, C.byref(st)
-    m = np.zeros((oracle.n_rules, batch.n), dtype=bool)
-    for k in range(oracle.n_rules):
-        for i in range(batch.n):
-            m[k, i] = fn(h, k, ref, i) == 1
-    want = oracle.evaluate(batch)
-    m[:, np.isin(want["rule_idx"], GATES)] = False
-    return m, want
-
-
-def assert_hits(label, hits, rule_hits, m):
-    n_rules, n = m.shape
-    assert (hits["mask"] != 0).all(), f"{label}: an entry with an empty mask"
-    pairs = hits["rule_idx"].astype(np.uint64) << np.uint64(32) | hits["group"].astype(np.uint64)
-    assert len(np.unique(pairs)) == len(hits), f"{label}: a (rule, group) pair appears twice"
-    got = hits_to_matrix(hits, n, n_rules)
-    bad = np.argwhere(got != m)
-    assert len(bad) == 0, f"{label}: {len(bad)} of {m.size} (rule, request) bits differ; first: rule {bad[0][0]}, request {bad[0][1]}: got {got[tuple(bad[0])]}"
-    assert rule_hits.tolist() == m.sum(axis=1).tolist(), f"{label}: rule_hits"
+oracle_matrix, assert_hits = H.oracle_matrix, H.assert_hits  # (shared with the confirm edge suite: helpers.py)
 
 
 def check(label, eng, batch, m, want):
