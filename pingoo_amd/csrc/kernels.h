@@ -10,7 +10,6 @@ namespace pwaf {
 
 static constexpr int kMaxPasses = 250;  // (= program.h kMaxGroups)
 static constexpr int kVerdictPre = 12;  // hit records per request the verdict kernel requests one group ahead
-static constexpr uint32_t kGapLists = 32;     // gated gap passes own list slots [0, 32) (one bit each in the factor masks); filtered passes follow
 static constexpr uint32_t kDirChunkWords = 32; // one 128-byte line per /16 of the compressed DIR-24 table (VerdictArgs::dir_chunks)
 
 // Hit record of one (scan pass, request): what the request's field matched in that pass's DFA.
@@ -34,11 +33,7 @@ struct PoolEntry {
 //                   c >= special_base -> index c - special_base into `special`: the target row is cold.
 // emit_base = n_plain * stride, special_base = (n_hot + 1) * stride (just past the sentinel row). A lane whose current row is
 // cold parks on the sentinel row, whose cells are all 0xFFFF, so the same single compare (c >= emit_base) routes it to the
-// careful path that reads the real row from the L2-resident table.
-struct SpecialCell {
-    uint32_t next_off;  // byte offset of the target row in the full table
-    uint32_t emit;      // 1 + emit-list id, 0 = none
-};
+// careful path that reads the real row from the L2-resident table. (SpecialCell: program.h)
 struct ScanArgs {
     const uint8_t *data;      // field arena
     const uint32_t *off;      // n + 1 offsets
@@ -268,10 +263,7 @@ int launch_compact(const FilterArgs *host, uint32_t count, const FilterArgs *dev
 // devices of one process each need it).
 int configure_kernels(int device);
 
-struct PassInfo {
-    uint32_t base;       // first device column of the pass
-    uint32_t kind_slot;  // kind << 24 | slot
-};
+// (PassInfo, the verdict kernel's pass table: program.h)
 // Field-against-field atoms (program.h: ATOM_FCMP): one lane per request compares the two strings (or their lengths); the results
 // are written as the hit record of one more pass whose local atom k is atoms[k].
 struct FcmpArgs {
@@ -343,14 +335,6 @@ int launch_residual_jit(const JitKernel &k, const ResidualJitArgs &a, uint32_t n
 struct ColPtrChunk {
     const void *p[2 * (PWAF_N_FIELDS + kMaxHeaders)];
     uint32_t count;
-};
-// A string atom that is an anchored literal of at most 8 bytes (`method == "POST"`, `method.starts_with("P")`) on a field whose
-// pass consists of such atoms only: evaluated by the attribute kernel from the field's first 8 bytes instead of a DFA pass over
-// every request (the pass then does not exist on the device: no walk, no hit records for the verdict kernel to read).
-struct ShortAtom {
-    uint32_t col;        // device column
-    uint32_t len_exact;  // literal length | exact << 8 (exact: the field IS the literal; else it starts with it)
-    uint32_t lit_lo, lit_hi;
 };
 struct VerdictArgs {
     uint32_t n, n_groups;

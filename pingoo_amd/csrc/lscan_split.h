@@ -4,8 +4,8 @@
 // (the passes behind a prefilter and the identity passes) holds up to two descriptors per pass — a confirm pass's dense alternative and
 // its R-tier walk — so 250 passes can need 500. A phase with more is split into consecutive launches on the batch's stream, each with a
 // plan region of its own (2 * count + 1 words: work-item prefix sums and total, then the entries per item of every descriptor). A pass's
-// descriptors never straddle two launches. assign_lists (engine.cpp) computes the launches when the lists are assigned — at creation
-// and after pwaf_engine_tune — and run_pipeline follows them. Compiled by engine.cpp and by tests/lscan_split_host.cpp (g++: the CPU
+// descriptors never straddle two launches. plan_passes (scanplan.cpp) computes the launches when the passes get their roles — at creation
+// and after pwaf_engine_tune — and run_pipeline follows them. Compiled by scanplan.cpp, engine.cpp and tests/lscan_split_host.cpp (g++: the CPU
 // suite checks the split).
 #pragma once
 #include <stddef.h>

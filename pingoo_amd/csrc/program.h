@@ -286,6 +286,28 @@ struct CmpAtomDev {  // a comparison atom: col = device column | code << 24 (tab
     uint32_t col, c;
 };
 
+// ---- records of the scan-side tables: planned on the host (scanplan.cpp), read by the scan / attribute / verdict kernels (kernels.h) ----
+static constexpr uint32_t kGapLists = 32;     // gated gap passes own list slots [0, 32) (one bit each in the factor masks); filtered passes follow
+// an entry of a scan table's `special` array (kernels.h: the cell encoding): one per cold row
+struct SpecialCell {
+    uint32_t next_off;  // byte offset of the target row in the full table
+    uint32_t emit;      // 1 + emit-list id, 0 = none
+};
+// the verdict kernel's pass table: kind 0 dense records, 1 valid where the filtered pass's candidate bitmap `slot` says, 2 where the gap
+// pass's visited bitmap `slot` says, 3 no records at all
+struct PassInfo {
+    uint32_t base;       // first device column of the pass
+    uint32_t kind_slot;  // kind << 24 | slot
+};
+// A string atom that is an anchored literal of at most 8 bytes (`method == "POST"`, `method.starts_with("P")`) on a field whose
+// pass consists of such atoms only: evaluated by the attribute kernel from the field's first 8 bytes instead of a DFA pass over
+// every request (the pass then does not exist on the device: no walk, no hit records for the verdict kernel to read).
+struct ShortAtom {
+    uint32_t col;        // device column
+    uint32_t len_exact;  // literal length | exact << 8 (exact: the field IS the literal; else it starts with it)
+    uint32_t lit_lo, lit_hi;
+};
+
 static constexpr uint32_t kMaxHeaders = 120;   // header columns (field ids 5 .. 5 + kMaxHeaders - 1)
 static constexpr uint32_t kMaxGroups = 250;    // scan passes per program
 

@@ -12,7 +12,6 @@ hands on), and with hand-made programs (harness --synthetic) for the planner's o
 import json
 import os
 import random
-import struct
 import subprocess
 
 import numpy as np
@@ -20,21 +19,18 @@ import pytest
 
 import helpers as H
 from pingoo_amd import _abi, geoip_entries
+from plan_harness import COMPILER_UNITS, U32, tool as plan_tool, write_case
 from table_walker import (ATOM_COUNTRY, ATOM_INT, ATOM_INTSET, ATOM_IPSET, ATOM_LEN, GREC_DTYPE, LIT_ATOM_MASK, LIT_NEG, LIT_TERM_END, NUMA_DTYPE, OP_EQ, OP_GE, OP_GT, OP_LE, OP_LT,
                           OP_NE, RULE_DTYPE, TRIE_LEAF, parse_dump)
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
-BUILD = os.path.join(HERE, "_build")
-CSRC = os.path.join(ROOT, "pingoo_amd", "csrc")
-UNITS = ["frontend.cpp", "pattern.cpp", "dfa.cpp", "iptrie.cpp", "filter.cpp", "residual.cpp", "compile.cpp", "tableplan.cpp"]
+UNITS = COMPILER_UNITS + ["tableplan.cpp"]
 SRC = os.path.join(HERE, "tableplan_host.cpp")
 
 LIT_LAZY, LAZY_CONST, LAZY_OP, LAZY_SLOT, LAZY_COMPLEMENT = 1 << 29, 0xFFFF, 1 << 16, 1 << 17, 1 << 18  # (program.h)
 SRC_CC, SRC_PORT, SRC_ASN, SRC_ACMP, SRC_WORDS = 16, 24, 28, 32, 36  # (program.h: source words of the membership atoms)
 N_FIELDS = 5
 B = _abi.RULE_ACTION_BLOCK
-U32 = 0xFFFFFFFF
 NO_LAZY_FLAGS = [_abi.OPT_EAGER_CMP, _abi.OPT_SPARSE_VERDICT, _abi.OPT_DENSE_VERDICT, _abi.OPT_SPARSE_VERDICT | _abi.OPT_TINY_VERDICT_SLOTS]
 
 
@@ -42,48 +38,7 @@ NO_LAZY_FLAGS = [_abi.OPT_EAGER_CMP, _abi.OPT_SPARSE_VERDICT, _abi.OPT_DENSE_VER
 # the harness
 # ---------------------------------------------------------------------------------------------------------
 def tool(name="tableplan_host", *extra):
-    """builds on demand (one object per unit, in parallel), again when a source or header is newer"""
-    os.makedirs(BUILD, exist_ok=True)
-    out = os.path.join(BUILD, name)
-    deps = [SRC, os.path.join(ROOT, "include", "pwaf.h")] + [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".cpp", ".h", ".inc"))]
-    if os.path.exists(out) and all(os.path.getmtime(d) <= os.path.getmtime(out) for d in deps):
-        return out
-    objdir = os.path.join(BUILD, name + "_obj")
-    os.makedirs(objdir, exist_ok=True)
-    flags = ["-std=c++17", "-O1", "-Wall", "-Wextra", "-Wno-unused-parameter", "-Wno-unknown-pragmas", "-I", os.path.join(ROOT, "include"), *extra]
-    jobs = []
-    for src in [os.path.join(CSRC, u) for u in UNITS] + [SRC]:
-        obj = os.path.join(objdir, os.path.basename(src) + ".o")
-        jobs.append((obj, subprocess.Popen(["g++", *flags, "-c", src, "-o", obj], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)))
-    for obj, p in jobs:
-        text, _ = p.communicate()
-        assert p.returncode == 0, text[-4000:]
-    subprocess.run(["g++", *extra, *[obj for obj, _ in jobs], "-o", out], check=True)
-    return out
-
-
-def pack_str(s):
-    if s is None:
-        return struct.pack("<I", U32)
-    b = s.encode("utf-8", "surrogateescape") if isinstance(s, str) else bytes(s)
-    return struct.pack("<I", len(b)) + b
-
-
-def write_case(path, rules, routes=None, lists=None, geo=None, flags=0):
-    """rules [(name, expression | None, [actions])], routes [(name, expression | None)], lists {name: (type, [items])}, geo: GEOIP_DTYPE array"""
-    routes, lists = routes or [], lists or {}
-    n_geo = 0 if geo is None else len(geo)
-    out = [b"PWAFCAS1", struct.pack("<5I", flags, len(rules), len(routes), len(lists), n_geo)]
-    for name, expr, acts in rules:
-        out += [pack_str(name), pack_str(expr), struct.pack("<I", len(acts)), bytes(acts)]
-    for name, expr in routes:
-        out += [pack_str(name), pack_str(expr)]
-    for name, (typ, items) in lists.items():
-        out += [pack_str(name), struct.pack("<II", typ, len(items))] + [pack_str(i) for i in items]
-    if n_geo:
-        out.append(np.ascontiguousarray(geo).tobytes())
-    with open(path, "wb") as f:
-        f.write(b"".join(out))
+    return plan_tool(name, SRC, UNITS, *extra)
 
 
 def run_cases(tmp_path, cases, exe=None):
