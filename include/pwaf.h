@@ -619,6 +619,31 @@ int pwaf_program_confirm_field(const pwaf_program *, uint32_t group, const uint8
  * table has a walk entry (a factor of a non-literal predicate). PWAF_E_INVALID_ARG when the pass has no confirm tier. The reference
  * has no counterpart. */
 int pwaf_program_confirm_shape(const pwaf_program *, uint32_t group, uint32_t out[8]);
+/* TEST HOOK (CPU, no device): the flat table of scan pass `group` for the list-driven walks (lscan_kernel), exactly as an engine created
+ * from this program uploads it — after pwaf_program_tune (pwaf_engine_tune, for pwaf_engine_program's handle) the table rebuilt for the
+ * sample, whose states are renumbered by visits. tier 0 = the table of the pass's every atom, 1 = of its non-literal atoms (the R tier:
+ * what the candidates of a confirm tier walk). The image is the dump's magic and sections of pwaf_program_dump's format, count = group:
+ * "FSHP" u32 {n_states, n_classes, scalar_mode, ill_class, n_full, n_delta, LDS bytes the layout was built for}, "FFLT" u16 cells
+ * (n_states rows of n_classes + 3: transitions, then the EMIT, STAY and END cell), "FDLT" u64 delta records (states n_full ..: base row
+ * | class 1 << 16 | class 2 << 24 | cell 1 << 32 | cell 2 << 48), "FCLS" the class image, "FEMO" / "FEML" and "FENO" / "FENL" the emit
+ * and end lists by state. Returns the image's size and copies at most cap bytes; 0 (and pwaf_last_error) for a bad argument or a pass
+ * without that tier. The reference has no counterpart. */
+size_t pwaf_program_flat_image(const pwaf_program *, uint32_t group, uint32_t tier, uint8_t *buf, size_t cap);
+/* TEST HOOK (CPU, no device): the list-scan descriptors of every batch of an engine created from this program (with the program's
+ * flags), in launch order, planned by the functions the engine plans its launches with (csrc/scanplan.h: plan_list_scans) over the
+ * tables built as the engine builds them; profiling-build switches and the state of an engine are not consulted, and the answer is
+ * built on the first call and kept in the program: like pwaf_program_dump, neither hook may run beside another call on the same
+ * program (or, for pwaf_engine_program's handle, beside pwaf_engine_tune). PWAF_LIST_SCAN_WORDS words per descriptor: [0]
+ * phase (0: the passes behind a prefilter and the identity passes, 1: the gap passes), [1] pass, [2] tier walked (0 full, 1 R), [3]
+ * threads and [4] LDS bytes for hot rows of the launch's workgroups, [5] n_hot rows and [6] n_delta records staged, [7] behind_filter,
+ * [8] merge_rec, [9] dense_mode, [10] the pass whose list it shares through need masks (0xFFFFFFFF: its own list) and [11] its need
+ * bit, [12] the launch's index within the phase and [13] its descriptor count (the k of its `lscan_x<k>` timing entry), [14]
+ * workgroups per CU, [15] 0. Writes at most cap descriptors; *n_descs = how many there are. The reference has no counterpart. */
+#define PWAF_LIST_SCAN_WORDS 16
+int pwaf_program_list_scans(const pwaf_program *, uint32_t *out, size_t cap, size_t *n_descs);
+/* TEST HOOK (needs an engine; reads a host-side field): the compute units the engine sizes its persistent grids with (the list scan's
+ * waves = this x workgroups per CU x threads / 64); 0 for NULL. */
+uint32_t pwaf_engine_compute_units(const pwaf_engine *);
 /* TEST HOOK (needs an engine, i.e. a device; reads host-side fields only): what the IPv4 lookup structures of this engine look like,
  * so that a test can assert that the path it was written for exists. out[0] = escaped /24s of the DIR-24 table (a prefix longer
  * than /24, or a class >= 65536 / membership set >= 32768), out[1] = entries of the run table behind the 16-byte records (0: the

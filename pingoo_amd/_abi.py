@@ -39,6 +39,11 @@ ARENA_PAD = 16
 ADDRESS_TABLE_FIELDS = ("escapes", "n_vals", "has_summary", "shift", "common", "packed", "classes", "sets")
 # pwaf_program_confirm_shape (test hook): the meaning of out[0..7]
 CONFIRM_SHAPE_FIELDS = ("entries", "bytes", "class_words", "in_lds", "longest", "top_class_pos", "widest_bin", "has_walk")
+# pwaf_program_list_scans (test hook): the meaning of a descriptor's PWAF_LIST_SCAN_WORDS words (share_owner 0xFFFFFFFF: none)
+LIST_SCAN_FIELDS = ("phase", "pass", "tier", "threads", "hot_bytes", "n_hot", "n_delta", "behind_filter", "merge_rec", "dense_mode", "share_owner", "need_bit",
+                    "launch", "launch_count", "wg_per_cu", "zero15")
+# pwaf_program_flat_image (test hook): the words of its "FSHP" section
+FLAT_SHAPE_FIELDS = ("n_states", "n_classes", "scalar_mode", "ill_class", "n_full", "n_delta", "lds_bytes")
 # pwaf_engine_coarse_tables (test hook): the meaning of out[0..15]
 COARSE_TABLE_FIELDS = ("present", "shift", "bytes", "blocks_set", "summary_blocks_set", "threads", "wg_per_cu", "zero7",
                        "rec_present", "rec_shift", "rec_bytes", "rec_blocks_set", "zero12", "zero13", "zero14", "zero15")

@@ -34,6 +34,19 @@ using namespace pwaf;
 struct pwaf_program {
     std::unique_ptr<Program> p;
     std::vector<uint8_t> dump;  // lazily built
+    // what the list-scan hooks answer from (pwaf_program_flat_image, pwaf_program_list_scans): the profile of the latest tuning sample
+    // (null: never tuned), the mean field lengths the samples so far left, and the plan built from them on the first call
+    std::unique_ptr<TuneOut> tuned;
+    std::vector<double> mean_len;
+    std::unique_ptr<ProgramScans> scans;
+    void keep_tuning(const TuneOut &T) {
+        tuned.reset(new TuneOut(T));
+        mean_len.resize(std::max(mean_len.size(), T.mean_len.size()), 0.0);
+        for (size_t f = 0; f < T.mean_len.size(); f++)
+            if (T.mean_len[f] > 0) mean_len[f] = T.mean_len[f];
+        scans.reset();
+        dump.clear();
+    }
 };
 
 namespace {
@@ -305,6 +318,7 @@ struct pwaf_engine : PlanShape, PassShape {  // (the widths and counts of the pl
     DevBuf georec_chunks, georec_vals, georec_summary;
     uint32_t georec_shift = 0, georec_common = 0, georec_n_esc = 0, georec_n_vals = 0;
     std::vector<double> mean_len;  // per field, from the tuning sample (0 = unknown)
+    ListPlan list_plan;  // the list-scan descriptors of every batch and the launch shapes (scanplan.h; assign_lists)
     DevBuf pass_table;                  // PassInfo per pass
     uint32_t n_fields = PWAF_N_FIELDS;  // 5 + header columns
     // profiling
@@ -560,7 +574,7 @@ struct BatchRun {
     VerdictArgs v{};
     bool ipres_launched = false, attr_launched = false;
     pwaf_geo *d_geo = nullptr;  // PWAF_OPT_GEO_ANSWERS: where the batch's GeoIP records go (null: none asked for, nothing launched)
-    ListShape lshapes[2];  // (the shape is per PHASE: the filtered passes' candidate lists are long, the gap passes' short)
+    const ListShape *lshapes = nullptr;  // (the shape is per PHASE: the filtered passes' candidate lists are long, the gap passes' short — scanplan.h: pick_list_shapes)
     // the descriptors of every launch of the batch (prefilter, resolve, confirm tier, list scans, residual kernel): built on the host,
     // uploaded ONCE
     std::vector<uint32_t> filter_index;  // a filtered pass's index among the filtered passes (its candidate / valid bitmap)
@@ -578,6 +592,7 @@ struct BatchRun {
 
     BatchRun(pwaf_engine *e_, Scratch &S_, const pwaf_batch &db_, hipStream_t stream_, const std::vector<uint32_t> *col_begin_)
         : e(e_), S(S_), P(*e_->prog.p), db(db_), stream(stream_), col_begin(col_begin_), sw(switches()), prof(e_, stream_), arg_slot{S_, stream_} {
+        lshapes = e->list_plan.shapes;
         n = db.n;
         n_groups = (n + 63) / 64;
         residual_pass = (uint32_t)e->groups.size() + (P.fcmp.empty() ? 0u : 1u);
@@ -774,21 +789,6 @@ struct BatchRun {
             HIP_TRY(hipMemsetAsync((uint32_t *)S.rec.p + k * (size_t)n, 0, (size_t)n * 4, stream));
         }
         return PWAF_OK;
-    }
-
-    void pick_list_shapes() {
-        uint32_t variant[2] = {2, 0};  // long candidate lists: 1024 threads over 144 KiB of hot rows (measured: benign 0.169 -> 0.143 ms, adversarial 4.43 -> 3.87 ms); short gap lists: 3 x 48 KiB
-        // With a confirm tier on every filtered pass the phase-0 lists are short walk lists: the small workgroup shape (512 threads,
-        // 48 KiB) starts on whatever wave slots the attribute kernels leave free — the 1024-thread / 144 KiB shape had to wait for a whole
-        // free CU (measured: 0.04 ms alone, 0.17 ms beside the side stream).
-        bool all_confirm = e->n_filtered != 0;
-        for (const DevGroup &d : e->groups) all_confirm = all_confirm && (!d.filtered || d.confirm);
-        if (all_confirm) variant[0] = 0;
-        if (sw.list_shape >= 0) {  // PWAF_LIST_SHAPE, timing experiments (same results): phase 0 | phase 1 << 4
-            variant[0] = (uint32_t)sw.list_shape & 15u;
-            variant[1] = (uint32_t)sw.list_shape >> 4;
-        }
-        for (int phase = 0; phase < 2; phase++) lshapes[phase] = list_shape(variant[phase]);
     }
 
     // ---- launching ----
@@ -1212,7 +1212,9 @@ struct BatchRun {
         }
     }
 
-    ListScanArgs list_args(size_t gi, const ListShape &lshape, bool full_table = false) const {
+    // One descriptor of the plan (scanplan.h: plan_list_scans decided what it walks and what it stages) with this batch's pointers
+    ListScanArgs list_args(const ListDesc &pl) const {
+        const size_t gi = pl.pass;
         const DevGroup &d = e->groups[gi];
         ListScanArgs a{};
         const DevGroup &src = d.share_owner >= 0 ? e->groups[(size_t)d.share_owner] : d;  // whose list this pass walks
@@ -1221,9 +1223,9 @@ struct BatchRun {
             a.n_list = (const uint32_t *)S.ctrl.p + 2 + src.gate;
         }
         if (d.visit_slot >= 0) a.visited = (uint32_t *)S.visit_bits.p + (size_t)d.visit_slot * bit_words;
-        if (d.share_owner >= 0) {
+        if (pl.share_owner >= 0) {
             a.need_in = (const uint32_t *)S.need.p + (size_t)src.need_slot * n;
-            a.need_bit = (uint32_t)d.gate;
+            a.need_bit = pl.need_bit;
         }
         if (feeds_gates(gi)) {
             set_gate_feed(a, d);
@@ -1232,26 +1234,20 @@ struct BatchRun {
                 a.shared_bits = d.shared_bits;
             }
         }
-        if (d.confirm) a.merge_rec = 1;  // the R-tier walk of a pass with a confirm tier: its list is confirm_kernel's walk list, the walk starts from the record it merged
-        a.behind_filter = d.filtered ? 1u : 0u;
+        a.merge_rec = pl.merge_rec ? 1u : 0u;
+        a.behind_filter = pl.behind_filter ? 1u : 0u;
         a.data = cols[d.field].data;
         a.off = cols[d.field].offsets;
         a.n = n;
-        const FlatDev &F = (d.confirm && d.rt.n_states && !full_table) ? d.rt : d.fl;  // (a confirmed candidate walks the DFA of the pass's non-literal atoms)
+        const FlatDev &F = pl.rtier ? d.rt : d.fl;
         a.flat = (const uint16_t *)F.flat.p;
         a.classmap = (const uint8_t *)F.flat_classmap.p;
         a.umap = F.scalar_mode ? (const uint8_t *)F.flat_classmap.p + kUmapAt : nullptr;
         a.ill_class = F.ill_class;
         a.n_classes = F.n_classes;
-        // rows [0, n_full) and the delta records behind them, when this launch's LDS share holds the layout the tables were built for
-        const uint32_t row_bytes = 2u * (F.n_classes + 3u), hb = list_hot_bytes(lshape);
-        if (F.n_delta && (uint64_t)F.n_full * row_bytes + 48u + 8ull * F.n_delta <= hb) {
-            a.n_hot = F.n_full;
-            a.n_delta = F.n_delta;
-            a.delta = (const uint64_t *)F.delta.p;
-        } else {
-            a.n_hot = std::min<uint32_t>(F.n_delta ? F.n_full : F.n_states, (hb - 48u) / row_bytes);  // (states are in visit order: the first rows are the hot ones; 48 bytes stay free for the sentinel cell and lscan_async's dummy record)
-        }
+        a.n_hot = pl.n_hot;
+        a.n_delta = pl.n_delta;
+        if (pl.n_delta) a.delta = (const uint64_t *)F.delta.p;
         a.emit_off = (const uint32_t *)F.emit_off.p;
         a.emit_list = (const uint16_t *)F.emit_list.p;
         a.end_off = (const uint32_t *)F.end_off.p;
@@ -1272,30 +1268,20 @@ struct BatchRun {
         a.dense_thresh = f.dense_thresh;
         a.dense_mode = mode;
     }
-    // list-driven DFA passes: first those behind a prefilter (they may feed the gap passes' lists), then the gap passes
+    // list-driven DFA passes, as planned when the passes got their roles (assign_lists): first those behind a prefilter (they may feed
+    // the gap passes' lists), then the gap passes
     void build_list_args() {
         for (int phase = 0; phase < 2; phase++)
-            for (size_t gi = 0; gi < e->groups.size(); gi++) {
-                const DevGroup &d = e->groups[gi];
-                if (d.identity ? phase != 0 : (d.gate < 0 || d.filtered != (phase == 0))) continue;
-                const FilterArgs *const dense = phase == 0 && d.confirm ? dense_of(gi) : nullptr;
-                const FilterArgs *const owner_dense = d.share_owner >= 0 ? dense_of((size_t)d.share_owner) : nullptr;
-                if (dense) {
-                    // the pass's dense alternative: EVERY request through the full table (the whole-pass walk of PWAF_OPT_NO_CONFIRM, over the
-                    // identity list), records and valid bits written for all; gets work only when the device set the pass's flag
-                    ListScanArgs a = list_args(gi, lshapes[phase], /*full_table=*/true);
+            for (const ListDesc &pl : e->list_plan.descs[phase]) {
+                ListScanArgs a = list_args(pl);
+                const size_t of = pl.dense_mode == 3 ? (size_t)pl.share_owner : (size_t)pl.pass;  // (3: a gap pass riding the owner's list through need masks)
+                if (pl.dense_mode == 1) {
+                    // the pass's dense alternative: EVERY request through the full table, records and valid bits written for all
                     a.req_list = nullptr;
                     a.n_list = nullptr;
-                    a.merge_rec = 0;
-                    a.visited = (uint32_t *)S.cand_bits.p + (size_t)filter_index[gi] * bit_words;
-                    set_dense(a, *dense, 1);
-                    la[phase].push_back(a);
+                    a.visited = (uint32_t *)S.cand_bits.p + (size_t)filter_index[pl.pass] * bit_words;
                 }
-                if (d.confirm && !d.confirm_walk) continue;  // every atom of the pass is a literal the confirm tier decided: nothing to walk
-                if (sw.skip_identity && d.identity) continue;
-                ListScanArgs a = list_args(gi, lshapes[phase]);
-                if (dense) set_dense(a, *dense, 2);  // the R-tier walk over the confirm tier's walk list: idle when the pass is walked whole
-                else if (owner_dense) set_dense(a, *owner_dense, 3);  // a gap pass riding the owner's list through need masks
+                if (pl.dense_mode) set_dense(a, *dense_of(of), pl.dense_mode);
                 la[phase].push_back(a);
             }
     }
@@ -1379,7 +1365,6 @@ int run_pipeline(pwaf_engine *e, Scratch &S, const pwaf_batch &db /* device poin
         b.v.route_base = e->prog.p->route_base;
         if (d_rep->hit_any() && e->rules_unrouted.p) b.v.rules = (const DevRule *)e->rules_unrouted.p;
     }
-    b.pick_list_shapes();
     if ((rc = b.attr_at_start()) || (rc = b.launch_plain_scans())) return rc;
     // every descriptor of the batch: built, checked against the launch plan, uploaded once
     if ((rc = b.learn_arena_sizes()) || (rc = b.zero_head_records()) || (rc = b.build_filter_args())) return rc;
@@ -1630,7 +1615,6 @@ int upload_tables(pwaf_engine *e, const TablePlan &t) {
 
 // The scan tables of pass k (scanplan.h) on their way to the device: the streaming table, the flat table of the list scans and — a pass
 // with an R tier — the flat table of its non-literal atoms. T: the profile of a tuning sample (null at creation).
-uint32_t flat_lds_bytes(bool wide) { return list_hot_bytes(list_shape(wide ? 2u : 0u)); }
 int upload_flat(FlatDev &d, const FlatImage &m) {
     int rc = PWAF_OK;
     const auto up = [&](DevBuf &buf, const auto &vec, size_t pad = 0) { if (!rc) rc = upload(buf, vec, pad); };
@@ -1655,11 +1639,11 @@ int upload_group(pwaf_engine *e, size_t k, const TuneOut *T) {
     if ((rc = upload(d.tab, m.tab, 16)) || (rc = upload(d.classmap, m.classmap)) || (rc = upload(d.special, m.special)) || (rc = upload(d.list_off, m.list_off)) ||
         (rc = upload(d.list, m.list)))
         return rc;
-    FlatImage fm;
-    build_flat_group(g, flat_lds_bytes(d.filter.enabled && g.filter_cols.empty()), fm, T ? &T->visits[k] : nullptr);
+    FlatImage fm, rm;
+    const uint32_t lds[2] = {flat_lds_bytes(false), flat_lds_bytes(true)};
+    build_flat_images(g, d.filter, lds, T, k, fm, rm);
     if ((rc = upload_flat(d.fl, fm)) || !g.rtier) return rc;
-    build_flat_group(*g.rtier, flat_lds_bytes(true), fm, T && !T->rvisits[k].empty() ? &T->rvisits[k] : nullptr);
-    return upload_flat(d.rt, fm);
+    return upload_flat(d.rt, rm);
 }
 
 // Gives every pass its role (scanplan.h: plan_passes) and uploads what the roles need. Called at creation and again when
@@ -1671,6 +1655,12 @@ int assign_lists(pwaf_engine *e) {
     PassPlan plan;
     plan_passes(P, filters, e->mean_len, e->residual_jit.function != nullptr, switches().skip_identity, plan);
     static_cast<PassShape &>(*e) = plan;
+    std::vector<FlatShape> full, rtier;
+    for (const DevGroup &d : e->groups) {
+        full.push_back(d.fl);
+        rtier.push_back(d.rt);
+    }
+    plan_list_scans(plan.roles, full, rtier, !(P.flags & PWAF_OPT_NO_DENSE_SWITCH), switches().skip_identity, switches().list_shape, e->list_plan);
     int rc = PWAF_OK;
     const auto up = [&](DevBuf &buf, const auto &vec) { if (!rc) rc = upload(buf, vec); };
     for (size_t k = 0; k < e->groups.size(); k++) {
@@ -2012,6 +2002,77 @@ int pwaf_program_confirm_shape(const pwaf_program *p, uint32_t group, uint32_t o
     out[5] = top_class;
     out[6] = widest;
     out[7] = walk;
+    return PWAF_OK;
+}
+
+}  // extern "C"
+namespace {
+// the plan the list-scan hooks answer from: built on the first call, again after pwaf_program_tune / pwaf_engine_tune
+const ProgramScans &scans_of(const pwaf_program *p) {
+    auto *mp = const_cast<pwaf_program *>(p);
+    if (!mp->scans) {
+        mp->mean_len.resize(std::max<size_t>(mp->mean_len.size(), PWAF_N_FIELDS + p->p->header_names.size()), 0.0);
+        mp->scans.reset(new ProgramScans());
+        plan_program_scans(*p->p, mp->tuned.get(), mp->mean_len, *mp->scans);
+    }
+    return *mp->scans;
+}
+template <class T>
+void put_section(std::vector<uint8_t> &buf, const char tag[4], uint32_t count, const std::vector<T> &v) {
+    const uint64_t len = v.size() * sizeof(T);
+    const auto raw = [&](const void *q, size_t n) { buf.insert(buf.end(), (const uint8_t *)q, (const uint8_t *)q + n); };
+    raw(tag, 4);
+    raw(&count, 4);
+    raw(&len, 8);
+    if (len) raw(v.data(), (size_t)len);
+    while (buf.size() % 8) buf.push_back(0);
+}
+}  // namespace
+extern "C" {
+
+size_t pwaf_program_flat_image(const pwaf_program *p, uint32_t group, uint32_t tier, uint8_t *buf, size_t cap) {
+    if (!p || !p->p || group >= p->p->groups.size() || tier > 1) { fail(PWAF_E_INVALID_ARG, "pwaf_program_flat_image: bad argument"); return 0; }
+    const ProgramScans &sc = scans_of(p);
+    const FlatImage &m = tier ? sc.rtier[group] : sc.full[group];
+    if (!m.n_states) { fail(PWAF_E_INVALID_ARG, "the pass has no R tier"); return 0; }
+    std::vector<uint8_t> out{'P', 'W', 'A', 'F', 'P', 'R', 'G', '1'};
+    put_section(out, "FSHP", group, std::vector<uint32_t>{m.n_states, m.n_classes, m.scalar_mode, m.ill_class, m.n_full, m.n_delta, tier ? sc.rtier_lds[group] : sc.full_lds[group]});
+    put_section(out, "FFLT", group, m.flat);
+    put_section(out, "FDLT", group, m.delta);
+    put_section(out, "FCLS", group, m.classmap);
+    put_section(out, "FEMO", group, m.emit_off);
+    put_section(out, "FEML", group, m.emit_list);
+    put_section(out, "FENO", group, m.end_off);
+    put_section(out, "FENL", group, m.end_list);
+    if (buf && cap) memcpy(buf, out.data(), std::min(cap, out.size()));
+    return out.size();
+}
+
+uint32_t pwaf_engine_compute_units(const pwaf_engine *e) { return e ? e->n_cus : 0u; }
+
+int pwaf_program_list_scans(const pwaf_program *p, uint32_t *out, size_t cap, size_t *n_descs) {
+    if (!p || !p->p || !n_descs || (!out && cap)) return fail(PWAF_E_INVALID_ARG, "pwaf_program_list_scans: bad argument");
+    const ProgramScans &sc = scans_of(p);
+    size_t at = 0;
+    for (int phase = 0; phase < 2; phase++) {
+        const std::vector<ListDesc> &descs = sc.lists.descs[phase];
+        const std::vector<uint32_t> &launches = sc.passes.lscan_launches[phase];
+        size_t planned = 0;
+        for (const uint32_t c : launches) planned += c;
+        if (planned != descs.size()) return fail(PWAF_E_UNSUPPORTED, "list-scan launch plan does not match the descriptors");  // (run_pipeline's own check)
+        size_t launch = 0, first = 0;
+        for (size_t k = 0; k < descs.size(); k++, at++) {
+            while (k >= first + launches[launch]) first += launches[launch++];
+            if (at >= cap) continue;
+            const ListDesc &d = descs[k];
+            const ListShape &sh = sc.lists.shapes[phase];
+            const uint32_t w[PWAF_LIST_SCAN_WORDS] = {d.phase, d.pass, d.rtier ? 1u : 0u, sh.threads, list_hot_bytes(sh), d.n_hot, d.n_delta, d.behind_filter ? 1u : 0u,
+                                                      d.merge_rec ? 1u : 0u, d.dense_mode, d.share_owner >= 0 ? (uint32_t)d.share_owner : 0xFFFFFFFFu, d.need_bit, (uint32_t)launch,
+                                                      launches[launch], sh.wg_per_cu, 0u};
+            memcpy(out + at * PWAF_LIST_SCAN_WORDS, w, sizeof w);
+        }
+    }
+    *n_descs = at;
     return PWAF_OK;
 }
 
@@ -2503,7 +2564,7 @@ int pwaf_program_tune(pwaf_program *p, const pwaf_batch *sample) {
     for (const DfaGroup &g : p->p->groups) T.filters.push_back(g.filter);
     if ((rc = tune_host(*p->p, sample, T))) return rc;
     for (size_t k = 0; k < p->p->groups.size(); k++) p->p->groups[k].filter = T.filters[k];
-    p->dump.clear();
+    p->keep_tuning(T);
     return PWAF_OK;
 }
 
@@ -2537,6 +2598,8 @@ int pwaf_engine_tune(pwaf_engine *e, const pwaf_batch *sample) {
         if ((rc = upload_group(e, k, &T))) return rc;
     if ((rc = assign_lists(e))) return rc;
     HIP_TRY(hipDeviceSynchronize());
+    for (size_t k = 0; k < P.groups.size(); k++) T.filters[k] = e->groups[k].filter;  // (the filters in use)
+    e->prog.keep_tuning(T);  // (the list-scan hooks of pwaf_engine_program answer for the tuned tables)
     return PWAF_OK;
 }
 

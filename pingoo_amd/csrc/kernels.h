@@ -5,6 +5,7 @@
 #include <vector>
 
 #include "program.h"
+#include "scanplan.h"
 
 namespace pwaf {
 
@@ -70,9 +71,8 @@ struct ScanArgs {
 //   emits (0, 0x8000 | the single local atom, or 1 = a list), cell n_classes + 1 = the state itself (the STAY cell: the "transition"
 //   of a lane past its field's end), cell n_classes + 2 = 1 when the field ending in this state emits; emit / end lists are indexed
 //   by (renumbered) state.
-static constexpr uint32_t kListThreads = 512;
+// (kListThreads, kListHotBytes and the workgroup shapes: scanplan.h, which decides on the host what every launch stages)
 static constexpr uint32_t kListWalks = 1;      // listed requests a lane walks in lockstep (2 was measured: see lscan_kernel)
-static constexpr uint32_t kListHotBytes = 48 * 1024;  // 3 workgroups (24 waves) per CU
 struct ListScanArgs {
     const uint8_t *data;
     const uint32_t *off;
@@ -462,13 +462,7 @@ struct GatedTable {
     uint32_t count;
     uint32_t debug;  // -DPWAF_PROFILING timing experiments only: 1 = never, 2 = always the asynchronous loop for a list (same results)
 };
-// Workgroup shape of the list scan: threads per workgroup, LDS bytes of hot rows per workgroup, workgroups per CU.
-struct ListShape {
-    uint32_t threads, hot_bytes, wg_per_cu;
-};
-ListShape list_shape(uint32_t variant);  // 0 = default
-// LDS bytes for hot rows in a launch of this shape
-uint32_t list_hot_bytes(const ListShape &shape);
+// (ListShape, the workgroup shape of the list scan: scanplan.h)
 // `plan`: count + 1 words of device scratch (the work-item prefix sums, written by lscan_plan_kernel on the same stream)
 int launch_scan_gated(const ListScanArgs *host, uint32_t count, const ListScanArgs *dev, uint32_t *plan, const ListShape &shape, void *stream);
 int launch_verdict(const VerdictArgs &a, void *stream);

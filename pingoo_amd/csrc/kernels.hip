@@ -1271,18 +1271,8 @@ int launch_scan_gated(const ListScanArgs *host, uint32_t count, const ListScanAr
     return (int)(e != hipSuccess ? e : hipGetLastError());
 }
 
-// LDS budget of the list scan: 160 KiB per CU shared by wg_per_cu workgroups. Default 3 x (48 KiB, 512 threads) = 24 waves per CU;
-// PWAF_LIST_SHAPE (profiling builds) tries the others.
-uint32_t list_hot_bytes(const ListShape &shape) { return shape.hot_bytes; }
-
-ListShape list_shape(uint32_t variant) {
-    switch (variant) {
-        case 1: return ListShape{512, 72u * 1024u, 2};     // 16 waves per CU, 1.5x the rows
-        case 2: return ListShape{1024, 144u * 1024u, 1};   // 16 waves per CU, 3x the rows
-        case 3: return ListShape{512, 32u * 1024u, 4};     // 32 waves per CU
-        default: return ListShape{kListThreads, kListHotBytes, 3};
-    }
-}
+// (LDS budget of the list scan — 160 KiB per CU shared by wg_per_cu workgroups, default 3 x (48 KiB, 512 threads) = 24 waves per CU — and
+// the other shapes: list_shape, scanplan.cpp)
 
 // -------------------------------------------------------------------------------------------------
 // bigram prefilter

@@ -586,4 +586,116 @@ int tune_host(const Program &P, const pwaf_batch *sample, TuneOut &T) {
     return PWAF_OK;
 }
 
+// ---- the list scan's launches (scanplan.h) ----
+uint32_t list_hot_bytes(const ListShape &shape) { return shape.hot_bytes; }
+
+// LDS budget of the list scan: 160 KiB per CU shared by wg_per_cu workgroups. Default 3 x (48 KiB, 512 threads) = 24 waves per CU;
+// PWAF_LIST_SHAPE (profiling builds) tries the others.
+ListShape list_shape(uint32_t variant) {
+    switch (variant) {
+        case 1: return ListShape{512, 72u * 1024u, 2};     // 16 waves per CU, 1.5x the rows
+        case 2: return ListShape{1024, 144u * 1024u, 1};   // 16 waves per CU, 3x the rows
+        case 3: return ListShape{512, 32u * 1024u, 4};     // 32 waves per CU
+        default: return ListShape{kListThreads, kListHotBytes, 3};
+    }
+}
+
+bool flat_wide(const DfaGroup &g, const GroupFilter &in_use) { return in_use.enabled && g.filter_cols.empty(); }
+uint32_t flat_lds_bytes(bool wide) { return list_hot_bytes(list_shape(wide ? 2u : 0u)); }
+
+void build_flat_images(const DfaGroup &g, const GroupFilter &in_use, const uint32_t lds[2], const TuneOut *T, size_t k, FlatImage &full, FlatImage &rtier) {
+    build_flat_group(g, lds[flat_wide(g, in_use) ? 1 : 0], full, T ? &T->visits[k] : nullptr);
+    rtier = FlatImage();
+    if (g.rtier) build_flat_group(*g.rtier, lds[1], rtier, T && !T->rvisits[k].empty() ? &T->rvisits[k] : nullptr);
+}
+
+void pick_list_shapes(const std::vector<PassRole> &roles, long forced, ListShape out[2]) {
+    uint32_t variant[2] = {2, 0};  // long candidate lists: 1024 threads over 144 KiB of hot rows (measured: benign 0.169 -> 0.143 ms, adversarial 4.43 -> 3.87 ms); short gap lists: 3 x 48 KiB
+    // With a confirm tier on every filtered pass the phase-0 lists are short walk lists: the small workgroup shape (512 threads,
+    // 48 KiB) starts on whatever wave slots the attribute kernels leave free — the 1024-thread / 144 KiB shape had to wait for a whole
+    // free CU (measured: 0.04 ms alone, 0.17 ms beside the side stream).
+    bool any_filtered = false, all_confirm = true;
+    for (const PassRole &d : roles) {
+        any_filtered = any_filtered || d.filtered;
+        all_confirm = all_confirm && (!d.filtered || d.confirm);
+    }
+    if (any_filtered && all_confirm) variant[0] = 0;
+    if (forced >= 0) {  // PWAF_LIST_SHAPE, timing experiments (same results): phase 0 | phase 1 << 4
+        variant[0] = (uint32_t)forced & 15u;
+        variant[1] = (uint32_t)forced >> 4;
+    }
+    for (int phase = 0; phase < 2; phase++) out[phase] = list_shape(variant[phase]);
+}
+
+ListResident list_resident(const FlatShape &F, const ListShape &shape) {
+    // rows [0, n_full) and the delta records behind them, when this launch's LDS share holds the layout the tables were built for
+    const uint32_t row_bytes = 2u * (F.n_classes + 3u), hb = list_hot_bytes(shape);
+    if (F.n_delta && (uint64_t)F.n_full * row_bytes + 48u + 8ull * F.n_delta <= hb) return ListResident{F.n_full, F.n_delta};
+    // (states are in visit order: the first rows are the hot ones; 48 bytes stay free for the sentinel cell and lscan_async's dummy record)
+    return ListResident{std::min<uint32_t>(F.n_delta ? F.n_full : F.n_states, (hb - 48u) / row_bytes), 0u};
+}
+
+// list-driven DFA passes: first those behind a prefilter (they may feed the gap passes' lists), then the gap passes
+void plan_list_scans(const std::vector<PassRole> &roles, const std::vector<FlatShape> &full, const std::vector<FlatShape> &rtier, bool dense_switch, bool skip_identity,
+                     long forced_shape, ListPlan &out) {
+    pick_list_shapes(roles, forced_shape, out.shapes);
+    const auto has_dense = [&](size_t k) { return dense_switch && roles[k].filtered && roles[k].confirm; };  // (the pass's FilterArgs carry a dense flag)
+    for (int phase = 0; phase < 2; phase++) {
+        out.descs[phase].clear();
+        for (size_t k = 0; k < roles.size(); k++) {
+            const PassRole &d = roles[k];
+            if (d.identity ? phase != 0 : (d.gate < 0 || d.filtered != (phase == 0))) continue;
+            const bool dense = phase == 0 && d.confirm && has_dense(k);
+            const bool owner_dense = d.share_owner >= 0 && has_dense((size_t)d.share_owner);
+            ListDesc a;
+            a.phase = (uint32_t)phase;
+            a.pass = (uint32_t)k;
+            a.behind_filter = d.filtered;
+            if (d.share_owner >= 0) {
+                a.share_owner = d.share_owner;
+                a.need_bit = (uint32_t)d.gate;
+            }
+            if (dense) {
+                // the pass's dense alternative: EVERY request through the full table (the whole-pass walk of PWAF_OPT_NO_CONFIRM, over the
+                // identity list), records and valid bits written for all; gets work only when the device set the pass's flag
+                ListDesc x = a;
+                const ListResident r = list_resident(full[k], out.shapes[phase]);
+                x.n_hot = r.n_hot;
+                x.n_delta = r.n_delta;
+                x.dense_mode = 1;
+                out.descs[phase].push_back(x);
+            }
+            if (d.confirm && !d.confirm_walk) continue;  // every atom of the pass is a literal the confirm tier decided: nothing to walk
+            if (skip_identity && d.identity) continue;
+            a.rtier = d.confirm && rtier[k].n_states != 0;  // (a confirmed candidate walks the DFA of the pass's non-literal atoms)
+            a.merge_rec = d.confirm;  // the R-tier walk of a pass with a confirm tier: its list is confirm_kernel's walk list, the walk starts from the record it merged
+            const ListResident r = list_resident(a.rtier ? rtier[k] : full[k], out.shapes[phase]);
+            a.n_hot = r.n_hot;
+            a.n_delta = r.n_delta;
+            a.dense_mode = dense ? 2u : owner_dense ? 3u : 0u;  // 2: idle when the pass is walked whole; 3: a gap pass riding the owner's list through need masks
+            out.descs[phase].push_back(a);
+        }
+    }
+}
+
+void plan_program_scans(const Program &P, const TuneOut *T, const std::vector<double> &mean_len, ProgramScans &out) {
+    const size_t n = P.groups.size();
+    out = ProgramScans();
+    out.full.resize(n);
+    out.rtier.resize(n);
+    const uint32_t lds[2] = {flat_lds_bytes(false), flat_lds_bytes(true)};
+    std::vector<GroupFilter> filters;
+    std::vector<FlatShape> fs, rs;
+    for (size_t k = 0; k < n; k++) {
+        filters.push_back(T ? T->filters[k] : P.groups[k].filter);
+        build_flat_images(P.groups[k], filters[k], lds, T, k, out.full[k], out.rtier[k]);
+        out.full_lds.push_back(lds[flat_wide(P.groups[k], filters[k]) ? 1 : 0]);
+        out.rtier_lds.push_back(lds[1]);
+        fs.push_back(out.full[k]);
+        rs.push_back(out.rtier[k]);
+    }
+    plan_passes(P, filters, mean_len, false, false, out.passes);
+    plan_list_scans(out.passes.roles, fs, rs, !(P.flags & PWAF_OPT_NO_DENSE_SWITCH), false, -1, out.lists);
+}
+
 }  // namespace pwaf

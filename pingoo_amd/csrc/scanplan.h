@@ -45,7 +45,7 @@ struct FlatImage : FlatShape {
     std::vector<uint32_t> emit_off, end_off;  // lists indexed by (renumbered) state
     std::vector<uint16_t> emit_list, end_list;
 };
-// lds_bytes: what the list scan's workgroup shape leaves for hot rows (kernels.h: list_hot_bytes)
+// lds_bytes: what the list scan's workgroup shape leaves for hot rows (list_hot_bytes below)
 void build_flat_group(const DfaGroup &g, uint32_t lds_bytes, FlatImage &out, const std::vector<uint64_t> *visits = nullptr);
 
 // A table's class lookups on the device: the 256-byte class map of the BYTES, 16 bytes of padding, then — scalar mode — the image of the
@@ -103,5 +103,60 @@ struct TuneOut {
 // program's, so that the table dump shows them — CPU tests interpret tuned tables without a GPU). T.filters comes pre-filled with the
 // filters in use.
 int tune_host(const Program &P, const pwaf_batch *sample, TuneOut &T);
+
+// ---- the list scan's launches: what every descriptor of a batch walks, and with what resident in LDS ----
+// Workgroup shape of the list scan (lscan_kernel): threads per workgroup, LDS bytes of hot rows per workgroup, workgroups per CU.
+static constexpr uint32_t kListThreads = 512;
+static constexpr uint32_t kListHotBytes = 48 * 1024;  // 3 workgroups (24 waves) per CU
+struct ListShape {
+    uint32_t threads, hot_bytes, wg_per_cu;
+};
+ListShape list_shape(uint32_t variant);  // 0 = default
+// LDS bytes for hot rows in a launch of this shape
+uint32_t list_hot_bytes(const ListShape &shape);
+// The LDS budget a pass's flat tables are BUILT for: the wide shape's for the full table of a pass behind a bigram prefilter (in_use: the
+// prefilter in use — the program's, or tune_host's) and for every R tier, the default shape's for the rest.
+bool flat_wide(const DfaGroup &g, const GroupFilter &in_use);
+uint32_t flat_lds_bytes(bool wide);
+// Both flat tables of pass k: of its every atom (full) and — a pass with an R tier — of its non-literal atoms (rtier; n_states 0 when
+// there is none). lds: the budgets {narrow, wide}; T: the profile of a tuning sample (null: none).
+void build_flat_images(const DfaGroup &g, const GroupFilter &in_use, const uint32_t lds[2], const TuneOut *T, size_t k, FlatImage &full, FlatImage &rtier);
+// The shape each phase LAUNCHES with: long candidate lists take 1024 threads over 144 KiB of hot rows, the gap passes' short lists
+// 3 x 48 KiB; with a confirm tier on every filtered pass the phase-0 lists are short walk lists and take the small shape too.
+// forced >= 0: phase 0 | phase 1 << 4 (timing experiments).
+void pick_list_shapes(const std::vector<PassRole> &roles, long forced, ListShape out[2]);
+// What a descriptor stages of a table in a launch of `shape`: rows [0, n_hot) and n_delta delta records behind them when the launch's
+// LDS share holds the layout the table was built for; else no records and as many of the first rows as fit.
+struct ListResident {
+    uint32_t n_hot, n_delta;
+};
+ListResident list_resident(const FlatShape &F, const ListShape &shape);
+// One list-scan descriptor of a batch (kernels.h: ListScanArgs, minus the batch's pointers)
+struct ListDesc {
+    uint32_t phase = 0, pass = 0;
+    bool rtier = false;  // walks the pass's R-tier table (else the full one)
+    uint32_t n_hot = 0, n_delta = 0;
+    bool behind_filter = false, merge_rec = false;
+    uint32_t dense_mode = 0;
+    int share_owner = -1;  // a gap pass riding this pass's list through need masks (bit need_bit)
+    uint32_t need_bit = 0;
+};
+struct ListPlan {
+    ListShape shapes[2];
+    std::vector<ListDesc> descs[2];  // per phase, in launch order: first the passes behind a prefilter (and the identity passes), then the gap passes
+};
+// full / rtier: the shapes of every pass's flat tables; dense_switch: the flag-density switch is on (a pass with a confirm tier also
+// gets its dense alternative). The counts per pass are lsplit::descriptors' (PassShape::lscan_launches cuts them into launches).
+void plan_list_scans(const std::vector<PassRole> &roles, const std::vector<FlatShape> &full, const std::vector<FlatShape> &rtier, bool dense_switch, bool skip_identity,
+                     long forced_shape, ListPlan &out);
+
+// All of the above for a whole program, as an engine created from it (and tuned on T's sample, when given) decides it: no device.
+struct ProgramScans {
+    std::vector<FlatImage> full, rtier;
+    std::vector<uint32_t> full_lds, rtier_lds;  // the budgets the tables were built for
+    PassPlan passes;
+    ListPlan lists;
+};
+void plan_program_scans(const Program &P, const TuneOut *T, const std::vector<double> &mean_len, ProgramScans &out);
 
 }  // namespace pwaf

@@ -88,6 +88,11 @@ def lib():
     L.pwaf_program_rule_status.argtypes = [vp, C.c_uint32, C.c_char_p, C.c_size_t]
     L.pwaf_program_confirm_field.argtypes = [vp, C.c_uint32, C.c_char_p, C.c_size_t, C.c_uint32, C.POINTER(C.c_uint16), C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_int), C.POINTER(C.c_int)]
     L.pwaf_program_confirm_shape.argtypes = [vp, C.c_uint32, C.POINTER(C.c_uint32)]
+    L.pwaf_program_flat_image.argtypes = [vp, C.c_uint32, C.c_uint32, vp, C.c_size_t]
+    L.pwaf_program_flat_image.restype = C.c_size_t
+    L.pwaf_program_list_scans.argtypes = [vp, C.POINTER(C.c_uint32), C.c_size_t, C.POINTER(C.c_size_t)]
+    L.pwaf_engine_compute_units.argtypes = [vp]
+    L.pwaf_engine_compute_units.restype = C.c_uint32
     L.pwaf_engine_rule_errors.argtypes = [vp, C.POINTER(C.c_uint64), C.c_size_t]
     L.pwaf_engine_residual_mode.argtypes = [vp]
     L.pwaf_engine_address_tables.argtypes = [vp, C.POINTER(C.c_uint32)]
@@ -358,6 +363,33 @@ class CompiledProgram:
             _raise(rc, lib().pwaf_last_error().decode(errors="replace"))
         return dict(zip(_abi.CONFIRM_SHAPE_FIELDS, (int(x) for x in out)))
 
+    def flat_image(self, group: int, tier: int = 0) -> bytes:
+        """TEST HOOK (pwaf_program_flat_image): the list scan's flat table of pass `group` exactly as an engine uploads it (tier 0: of every
+        atom, 1: the R tier), as sections of the dump's format — "FSHP" (_abi.FLAT_SHAPE_FIELDS), cells, delta records, class image, emit
+        and end lists. After tune() the table rebuilt for the sample. Raises for a pass without that tier."""
+        n = lib().pwaf_program_flat_image(self._h, group, tier, None, 0)
+        if n == 0:
+            _raise(_abi.E_INVALID_ARG, lib().pwaf_last_error().decode(errors="replace"))
+        buf = C.create_string_buffer(n)
+        lib().pwaf_program_flat_image(self._h, group, tier, buf, n)
+        return buf.raw
+
+    def list_scans(self) -> List[dict]:
+        """TEST HOOK (pwaf_program_list_scans): the list-scan descriptors of every batch of an engine created from this program, in launch
+        order, by the names of _abi.LIST_SCAN_FIELDS (share_owner -1: the pass walks a list of its own)."""
+        W = len(_abi.LIST_SCAN_FIELDS)
+        n = C.c_size_t()
+        rc = lib().pwaf_program_list_scans(self._h, None, 0, C.byref(n))
+        if rc == 0 and n.value:
+            out = (C.c_uint32 * (W * n.value))()
+            rc = lib().pwaf_program_list_scans(self._h, out, n.value, C.byref(n))
+        if rc != 0:
+            _raise(rc, lib().pwaf_last_error().decode(errors="replace"))
+        res = [dict(zip(_abi.LIST_SCAN_FIELDS, (int(x) for x in out[k * W:(k + 1) * W]))) for k in range(n.value)]
+        for d in res:
+            d["share_owner"] = -1 if d["share_owner"] == 0xFFFFFFFF else d["share_owner"]
+        return res
+
     def residual_source(self, kind: int = 1) -> str:
         """Inspection hook: the specialized form of the residual rules (csrc/residual_jit.cpp). kind 0 = the rule functions alone,
         1 = the whole device program as handed to hiprtc at engine creation. "" when the rule set has no residual rules."""
@@ -456,6 +488,10 @@ class RuleEngine:
     @property
     def residual_fallback(self) -> str:
         return (lib().pwaf_engine_residual_fallback(self._h) or b"").decode(errors="replace")
+
+    def compute_units(self) -> int:
+        """TEST HOOK (pwaf_engine_compute_units): the compute units the engine sizes its persistent grids with."""
+        return int(lib().pwaf_engine_compute_units(self._h))
 
     def address_tables(self) -> dict:
         """TEST HOOK (pwaf_engine_address_tables): the shape of this engine's IPv4 lookup structures, by the names of

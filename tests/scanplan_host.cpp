@@ -16,7 +16,8 @@
 // SPEC: "PWAFPAS1", u32 flags, n_cols, n_groups; per group u32 field, atom_base, n_local, filter enabled, confirm tier, ... that walks, heads,
 //   n_filter_cols, the filter columns.
 // OUT: the program dump (pwaf_program_dump's format; --synthetic: its magic alone) followed by more sections of the same format, `count`
-//   = the pass: "S..." the streaming table, "F..." the flat table, "T..." the flat table of the R tier, "U..." what tuning found, then "L..." the pass plan.
+//   = the pass: "S..." the streaming table, "F..." the flat table, "T..." the flat table of the R tier, "U..." what tuning found, then "L..." the pass plan ("LDSC": the list-scan descriptors, 12 words each: phase, pass, tier,
+//   threads, hot bytes, n_hot, n_delta, behind_filter, merge_rec, dense_mode, share owner, need bit).
 #include "plan_case.h"
 
 #include "../pingoo_amd/csrc/scanplan.h"
@@ -138,6 +139,7 @@ static int run_case(const char *case_path, const char *out_path) {
     }
     std::vector<uint8_t> buf = dump_program(P);
     std::vector<GroupFilter> filters;
+    std::vector<FlatShape> flat_shapes[2];  // full, R tier
     for (size_t k = 0; k < P.groups.size(); k++) {
         const DfaGroup &g = P.groups[k];
         filters.push_back(g.filter);
@@ -149,14 +151,12 @@ static int run_case(const char *case_path, const char *out_path) {
             return 0;
         }
         write_scan(buf, m);
-        FlatImage fm;
-        const uint32_t budget = lds[g.filter.enabled && g.filter_cols.empty() ? 1 : 0];
-        build_flat_group(g, budget, fm, has_sample ? &T.visits[k] : nullptr);
-        write_flat(buf, 'F', fm, budget);
-        if (g.rtier) {
-            build_flat_group(*g.rtier, lds[1], fm, has_sample && !T.rvisits[k].empty() ? &T.rvisits[k] : nullptr);
-            write_flat(buf, 'T', fm, lds[1]);
-        }
+        FlatImage fm, rm;
+        build_flat_images(g, g.filter, lds, has_sample ? &T : nullptr, k, fm, rm);
+        write_flat(buf, 'F', fm, lds[flat_wide(g, g.filter) ? 1 : 0]);
+        if (g.rtier) write_flat(buf, 'T', rm, lds[1]);
+        flat_shapes[0].push_back(fm);
+        flat_shapes[1].push_back(rm);
         if (has_sample) {
             gsection(buf, "UVIS", T.visits[k]);
             gsection(buf, "UCFQ", T.class_freq[k]);
@@ -170,6 +170,16 @@ static int run_case(const char *case_path, const char *out_path) {
     PassPlan plan;
     plan_passes(P, filters, mean_len, specialized, skip_identity, plan);
     write_passes(buf, plan);
+    // the list-scan descriptors of a batch (for the default budgets: what the engine launches with)
+    ListPlan lp;
+    plan_list_scans(plan.roles, flat_shapes[0], flat_shapes[1], !(P.flags & PWAF_OPT_NO_DENSE_SWITCH), skip_identity, -1, lp);
+    std::vector<uint32_t> descs;
+    for (int phase = 0; phase < 2; phase++)
+        for (const ListDesc &d : lp.descs[phase])
+            for (uint32_t x : {d.phase, d.pass, (uint32_t)d.rtier, lp.shapes[phase].threads, list_hot_bytes(lp.shapes[phase]), d.n_hot, d.n_delta, (uint32_t)d.behind_filter,
+                               (uint32_t)d.merge_rec, d.dense_mode, (uint32_t)d.share_owner, d.need_bit})
+                descs.push_back(x);
+    gsection(buf, "LDSC", descs);
     if (int wrc = write_file(out_path, buf)) return wrc;
     puts(json_line("ok", 0, 0xFFFFFFFFu, "").c_str());
     return 0;

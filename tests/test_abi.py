@@ -68,6 +68,28 @@ def test_error_paths_do_not_need_a_gpu():
         engine.validate_expression("")
 
 
+def test_the_list_scan_hooks_name_their_words_and_refuse_bad_arguments():
+    """pwaf_program_flat_image / pwaf_program_list_scans (test hooks, no device): the word names of _abi match the header's count, a NULL
+    program or a pass that does not exist is refused, a compiled program answers both"""
+    L = engine.lib()
+    src = open(os.path.join(ROOT, "include", "pwaf.h")).read()
+    assert int(re.search(r"#define PWAF_LIST_SCAN_WORDS (\d+)", src).group(1)) == len(_abi.LIST_SCAN_FIELDS) == 16 and len(_abi.FLAT_SHAPE_FIELDS) == 7
+    n = C.c_size_t(7)
+    assert L.pwaf_engine_compute_units(None) == 0
+    assert L.pwaf_program_flat_image(None, 0, 0, None, 0) == 0 and L.pwaf_program_list_scans(None, None, 0, C.byref(n)) == _abi.E_INVALID_ARG
+    prog = engine.CompiledProgram([("m", 'http_request.method.matches("P[A-Z]{5}$")', [_abi.RULE_ACTION_BLOCK])], {})
+    (d,) = [x for x in prog.list_scans() if not x["behind_filter"]]  # the method's identity pass: the default shape, every row staged
+    assert (d["phase"], d["tier"], d["threads"], d["hot_bytes"], d["behind_filter"], d["dense_mode"], d["share_owner"], d["launch"], d["launch_count"], d["zero15"]) == (0, 0, 512, 48 * 1024, 0, 0, -1, 0, len(prog.list_scans()), 0)
+    img = prog.flat_image(d["pass"], 0)
+    assert img[:8] == b"PWAFPRG1" and img[8:12] == b"FSHP" and d["n_delta"] == 0
+    with pytest.raises(engine.PwafError):
+        prog.flat_image(d["pass"], 1)  # no R tier
+    with pytest.raises(engine.PwafError):
+        prog.flat_image(99, 0)
+    with pytest.raises(engine.PwafError):
+        prog.flat_image(d["pass"], 2)
+
+
 def test_field_derivation_matches_golden_and_oracle(kat):
     d = kat["derive"]
     for raw, want in d["user_agent"]:
