@@ -416,6 +416,45 @@ typedef struct pwaf_record_head {
 int pwaf_evaluate_records(pwaf_engine *, const uint8_t *buf, size_t buf_bytes, const uint32_t *rec_off, uint32_t n, pwaf_verdict *out,
                           pwaf_counts *counts);
 
+/* ---- record export (ABI 4, additive) -------------------------------------------------------------------
+ * The inverse of the above: selected requests of a batch, as records. For a device-resident batch the engine names the requests it did
+ * not allow as an index list (match_idx / n_matches of pwaf_evaluate_device); this call turns such a list into the records of those
+ * requests — a block log, a quarantine file, an offline replay, a second look through another engine — without copying the batch to the
+ * host: evaluate, export, copy out exactly bytes_needed bytes, feed them to anything that takes records. It takes no engine (like
+ * pwaf_host_alloc): everything it needs is in the batch. Verdicts and GeoIP answers are not part of a record: index out[] / geo[] with
+ * the same idx. The reference has no counterpart (it handles one request at a time, http_listener.rs:133-274).
+ * Memory and streams: in->memory says where EVERY pointer lives, the batch's and idx, n_idx, buf, rec_off and stats alike.
+ *   PWAF_MEM_DEVICE  the work is enqueued on `stream` (hipStream_t; NULL = HIP's default stream) of the current device and the call
+ *                    returns at once: one 16-byte memset of *stats and one launch (pack_records_kernel). The kernel reads *n_idx itself,
+ *                    so a call placed right behind pwaf_evaluate_device(..., match_idx, n_matches, stream) on the same stream needs no
+ *                    synchronisation in between. No memory is allocated, nothing is copied. The batch is trusted as
+ *                    pwaf_evaluate_device trusts it (the kernel's 16-byte loads count on PWAF_ARENA_PAD behind every arena, as the
+ *                    evaluation's do), except that the kernel itself guards idx[j] >= n.
+ *   PWAF_MEM_HOST    synchronous, plain C++, no HIP call: works on a machine without a GPU. A selected request whose offsets decrease
+ *                    in some column refuses the whole call with PWAF_E_BATCH (naming the list entry) before anything is written.
+ * Output: n_selected = min(*n_idx, idx_cap) list entries are looked at (idx_cap when n_idx == NULL). For entry j < n_selected, rec_off[j]
+ * is the byte offset in buf of the record of request idx[j], or PWAF_RECORD_NONE when the record did not fit, when idx[j] >= in->n or
+ * when the record would exceed 0xFFFFFFF0 bytes; entries j >= n_selected are not written. Records sit at 16-byte aligned offsets, in
+ * unspecified order, without holes: the written ones occupy a prefix of buf. Nothing is written at or beyond buf + buf_cap. Duplicates in
+ * idx produce one record each. *stats is overwritten, not accumulated into; bytes_needed counts every valid selected record whether or
+ * not it fitted. buf_cap == 0 (buf NULL or not) is a size query. Which records are dropped when buf_cap < bytes_needed is unspecified;
+ * with buf_cap >= bytes_needed none is.
+ * Record content: exactly what pwaf_evaluate_records takes. Values: the five fields, then the batch's n_headers header columns, in that
+ * order; n_values ends after the last non-empty header value (5 when there is none); a header column whose descriptor is NULL reads as
+ * ""; has_geoip = 1 with asn / country iff the batch carries both columns, else those fields are 0; flags, port, ip, ip_is_v6 are
+ * copied; reserved and all padding are 0. Offsets need not begin at 0: a slab of a larger batch is a valid input.
+ * PWAF_E_INVALID_ARG, before anything runs: NULL in, rec_off or stats; NULL idx with idx_cap > 0; a bad struct_size or memory; a NULL
+ * field or numeric column, or NULL headers with n_headers > 0, in a batch with n > 0; n_headers above 120; buf not 16-byte aligned;
+ * buf == NULL with buf_cap != 0; buf_cap > 0xFFFFFFF0 (rec_off is 32 bits wide). */
+#define PWAF_RECORD_NONE 0xFFFFFFFFu
+typedef struct pwaf_export_stats {
+    uint64_t bytes_needed; /* bytes of ALL selected valid records: a buf_cap >= this writes every one */
+    uint32_t n_selected;   /* list entries looked at: min(*n_idx, idx_cap), or idx_cap when n_idx == NULL */
+    uint32_t n_written;    /* records written to buf */
+} pwaf_export_stats;       /* 16 bytes */
+int pwaf_export_records(const pwaf_batch *in, const uint32_t *idx, uint32_t idx_cap, const uint32_t *n_idx /* nullable */, uint8_t *buf,
+                        size_t buf_cap, uint32_t *rec_off /* idx_cap entries */, pwaf_export_stats *stats, void *stream);
+
 /* ---- non-blocking request queue (ABI 4) -------------------------------------------------------------
  * The call shape of an async host (the reference's rule loop runs inside an async hyper closure, http_listener.rs:133-274): submit a
  * request with a tag and go on; collect {tag, verdict, status} completions later. pwaf_async_submit copies the request ONCE, as a record,

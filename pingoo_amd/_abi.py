@@ -32,6 +32,7 @@ W_PARTIAL = 1
 MEM_HOST, MEM_DEVICE = 0, 1
 FLAG_CAPTCHA_VERIFIED = 1
 ROUTE_NONE = 0xFFFFFFFF  # PWAF_ROUTE_NONE: no route matches the request (pwaf_evaluate_*_routes)
+RECORD_NONE = 0xFFFFFFFF  # PWAF_RECORD_NONE: the list entry has no record in the buffer (pwaf_export_records)
 N_FIELDS = 5
 FIELD_NAMES = ("host", "url", "path", "method", "user_agent")
 ARENA_PAD = 16
@@ -170,6 +171,12 @@ class RecordHead(C.Structure):
         ("has_geoip", C.c_uint8),
         ("reserved", C.c_uint8 * 3),
     ]
+
+
+class ExportStats(C.Structure):
+    """pwaf_export_stats: what pwaf_export_records reports — the bytes of every valid selected record, list entries looked at, records written."""
+
+    _fields_ = [("bytes_needed", C.c_uint64), ("n_selected", C.c_uint32), ("n_written", C.c_uint32)]
 
 
 class Geo(C.Structure):

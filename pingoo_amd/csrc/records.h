@@ -1,4 +1,5 @@
-// records.h — the request record of include/pwaf.h (pwaf_record_head + lengths + values): layout, validation, decoding.
+// records.h — the request record of include/pwaf.h (pwaf_record_head + lengths + values): layout, validation, decoding, and (second half)
+// packing: pwaf_export_records.
 //
 // One header, compiled three ways, like confirm.h: by records.hip (unpack_records_kernel decodes records on the device), by engine.cpp
 // (pwaf_evaluate_records validates every record and computes the column offsets on the host before anything is launched) and by
@@ -148,6 +149,126 @@ struct UnpackArgs {
     uint32_t *asn;
 };
 int launch_unpack_records(const UnpackArgs &a, void *stream);
+
+// ---- packing: the inverse (pwaf_export_records). Selected requests of a batch's columns -> records, byte for byte what
+// RequestBatch.to_records builds. The same three compilations: pack_records_kernel (records.hip), the HOST mode of the entry point (a loop
+// over pack_record: export_host below) and tests/records_pack_host.cpp (g++ under the sanitizers).
+static constexpr uint64_t kMaxRecord = 0xFFFFFFF0ull;  // head.size and rec_off are 32 bits wide
+
+// pack_records_kernel's arguments, and export_host's. The column descriptors travel BY VALUE — on the device inside the kernel argument
+// block (kMaxValues x 16 = 2000 bytes of the 4 KiB a launch may carry) — so a call owns no scratch and uploads nothing. Column k < 5 is
+// field k, column 5 + h header h; a descriptor with a NULL pointer reads as "" for every request.
+struct PackArgs {
+    pwaf_strcol col[kMaxValues];
+    uint32_t n, n_cols;  // requests of the batch; columns in use (PWAF_N_FIELDS + n_headers)
+    const uint8_t *ip, *ip_is_v6, *flags;
+    const uint16_t *port, *country;  // country / asn: both or has_geoip = 0
+    const uint32_t *asn;
+    const uint32_t *idx;    // idx_cap entries
+    const uint32_t *n_idx;  // nullable: min(*n_idx, idx_cap) entries are looked at
+    uint32_t idx_cap;
+    uint8_t *buf;
+    uint64_t buf_cap;
+    uint32_t *rec_off;
+    pwaf_export_stats *stats;
+};
+
+PWAF_RECORD_HD uint32_t selected(const PackArgs &a) {
+    if (!a.n_idx) return a.idx_cap;
+    const uint32_t k = *a.n_idx;
+    return k < a.idx_cap ? k : a.idx_cap;
+}
+// length of column k's value of request i (uint32 arithmetic, as every reader of the offsets does; monotone offsets are export_host's check)
+PWAF_RECORD_HD uint32_t col_len(const pwaf_strcol &c, uint32_t i) { return c.data && c.offsets ? c.offsets[i + 1] - c.offsets[i] : 0u; }
+
+// What a request's record looks like, from its column lengths: add() them in column order.
+struct ExportShape {
+    uint32_t n_values = PWAF_N_FIELDS;  // ends after the last non-empty header value
+    uint64_t value_bytes = 0;
+    PWAF_RECORD_HD void add(uint32_t k, uint32_t len) {
+        value_bytes += len;
+        if (len && k >= PWAF_N_FIELDS) n_values = k + 1;
+    }
+    PWAF_RECORD_HD uint64_t size() const { return record_size(n_values, value_bytes); }
+    // a record that cannot be described in 32 bits is not exported (PWAF_RECORD_NONE, not counted)
+    PWAF_RECORD_HD uint32_t size32() const { return size() > kMaxRecord ? 0u : (uint32_t)size(); }
+};
+PWAF_RECORD_HD ExportShape export_shape(const PackArgs &a, uint32_t i) {
+    ExportShape s;
+    for (uint32_t k = 0; k < a.n_cols; k++) s.add(k, col_len(a.col[k], i));
+    return s;
+}
+
+// the head of request i's record (every byte of *h is written: reserved and the GeoIP fields of a batch without GeoIP are 0)
+PWAF_RECORD_HD void fill_head(const PackArgs &a, uint32_t i, uint32_t n_values, uint32_t size, pwaf_record_head *h) {
+    memset(h, 0, kHead);
+    h->size = size;
+    h->n_values = (uint16_t)n_values;
+    h->port = a.port[i];
+    memcpy(h->ip, a.ip + (size_t)i * 16, 16);
+    h->flags = a.flags[i];
+    h->ip_is_v6 = a.ip_is_v6[i];
+    if (a.asn && a.country) {
+        h->has_geoip = 1;
+        h->asn = a.asn[i];
+        memcpy(h->country, &a.country[i], 2);
+    }
+}
+
+// One record, written by one thread: request i with shape s (s.size32() != 0) to dst, s.size() bytes, every one of them written.
+PWAF_RECORD_HD void pack_record(const PackArgs &a, uint32_t i, const ExportShape &s, uint8_t *dst) {
+    const uint32_t size = s.size32(), vo = values_offset(s.n_values);
+    pwaf_record_head h;
+    fill_head(a, i, s.n_values, size, &h);
+    memcpy(dst, &h, kHead);
+    uint8_t *at = dst + vo;
+    for (uint32_t k = 0; k < s.n_values; k++) {
+        const uint32_t len = col_len(a.col[k], i);
+        memcpy(dst + kHead + 4u * k, &len, 4);
+        if (len) memcpy(at, a.col[k].data + a.col[k].offsets[i], len);
+        at += len;
+    }
+    memset(dst + kHead + 4u * s.n_values, 0, vo - (kHead + 4u * s.n_values));
+    memset(at, 0, (size_t)(dst + size - at));
+}
+
+// The HOST mode of pwaf_export_records, after the entry point's argument checks: plain C++, no device. First every selected request of the
+// batch is checked (offsets that decrease: false with *bad = the list entry j, nothing written), then the records are laid out in list
+// order. The rule pack_records_kernel follows too: the byte cursor advances by every valid record, and a record is written iff its whole
+// range lies below buf_cap — so the written ones form a prefix of buf without holes.
+inline bool export_host(const PackArgs &a, uint32_t *bad) {
+    const uint32_t m = selected(a);
+    for (uint32_t j = 0; j < m; j++) {
+        const uint32_t i = a.idx[j];
+        if (i >= a.n) continue;
+        for (uint32_t k = 0; k < a.n_cols; k++)
+            if (a.col[k].data && a.col[k].offsets && a.col[k].offsets[i + 1] < a.col[k].offsets[i]) {
+                *bad = j;
+                return false;
+            }
+    }
+    uint64_t cursor = 0;
+    uint32_t written = 0;
+    for (uint32_t j = 0; j < m; j++) {
+        const uint32_t i = a.idx[j];
+        a.rec_off[j] = PWAF_RECORD_NONE;
+        if (i >= a.n) continue;
+        const ExportShape s = export_shape(a, i);
+        const uint32_t size = s.size32();
+        if (!size) continue;
+        if (cursor + size <= a.buf_cap) {
+            pack_record(a, i, s, a.buf + cursor);
+            a.rec_off[j] = (uint32_t)cursor;
+            written++;
+        }
+        cursor += size;
+    }
+    a.stats->bytes_needed = cursor;
+    a.stats->n_selected = m;
+    a.stats->n_written = written;
+    return true;
+}
+int launch_pack_records(const PackArgs &a, void *stream);
 
 }  // namespace records
 }  // namespace pwaf

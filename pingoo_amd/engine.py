@@ -148,6 +148,7 @@ def lib():
     L.pwaf_batcher_destroy.argtypes = [vp]
     L.pwaf_batcher_destroy.restype = None
     L.pwaf_evaluate_records.argtypes = [vp, vp, C.c_size_t, vp, C.c_uint32, vp, vp]
+    L.pwaf_export_records.argtypes = [C.POINTER(_abi.Batch), vp, C.c_uint32, vp, vp, C.c_size_t, vp, vp, vp]
     L.pwaf_async_create.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(vp)]
     L.pwaf_async_submit.argtypes = [vp, C.POINTER(_abi.Request), C.c_uint64]
     L.pwaf_async_poll.argtypes = [vp, C.POINTER(_abi.Completion), C.c_size_t]
@@ -643,6 +644,10 @@ class RuleEngine:
         res += (geo,) if with_geo else ()
         return res if len(res) > 1 else res[0]
 
+    def export_records(self, batch, idx, n_idx=None, cap=None, stream=None):
+        """export_records (below) with this engine's header columns: the records are what evaluate_records of this engine takes."""
+        return export_records(batch, idx, n_idx=n_idx, cap=cap, stream=stream, header_names=self.header_names)
+
     def evaluate(self, request: Request, with_geo: bool = False):
         """RuleEngine::evaluate(Request) -> Action (pwaf_evaluate_one): a batch of one through the same device path. with_geo
         (OPT_GEO_ANSWERS engines): -> (Verdict, (asn, country)) — the reference's (Action, GeoipRecord)."""
@@ -1117,6 +1122,73 @@ def parse_list_csv(text) -> List[str]:
         return [items[k].decode(errors="surrogateescape") for k in range(n.value)]
     finally:
         lib().pwaf_list_free(items, n.value)
+
+
+def export_stats(stats) -> dict:
+    """The 16 bytes of a pwaf_export_stats (a device tensor once its stream is synchronised, a numpy array or bytes) -> {bytes_needed, n_selected, n_written}."""
+    raw = stats.cpu().numpy().tobytes() if hasattr(stats, "cpu") else bytes(stats)
+    s = _abi.ExportStats.from_buffer_copy(raw[:C.sizeof(_abi.ExportStats)])
+    return {"bytes_needed": int(s.bytes_needed), "n_selected": int(s.n_selected), "n_written": int(s.n_written)}
+
+
+def _aligned_bytes(nbytes: int) -> np.ndarray:
+    """A zeroed uint8 array of nbytes at a 16-byte aligned address."""
+    raw = np.zeros(nbytes + 16, dtype=np.uint8)
+    at = -raw.ctypes.data % 16
+    return raw[at:at + nbytes]
+
+
+def export_records(batch, idx, n_idx=None, cap=None, stream=None, header_names: Optional[Sequence[str]] = None):
+    """The requests of `batch` that the list `idx` names, as request records (pwaf_export_records; include/pwaf.h) -> (buf, rec_off, stats):
+    the record of request idx[j] starts at buf[rec_off[j]], or rec_off[j] == _abi.RECORD_NONE when it has none (it did not fit `cap`
+    bytes, or idx[j] is not a request of the batch). Takes no engine; header_names = the header columns a record carries, in order
+    (default: the batch's own; RuleEngine.export_records passes the engine's, so that its evaluate_records takes the records).
+    RequestBatch: idx (and n_idx: how many entries of idx count, default all) are numpy arrays / ints, the call is synchronous and runs
+    on the CPU; cap=None asks for the size first and exports everything. -> (uint8 array of bytes_needed bytes, uint32 array, dict).
+    DeviceBatch: idx and n_idx (a one-element 32-bit tensor, or None) are device tensors — e.g. evaluate_device's match_idx / n_matches,
+    in which case the call follows the evaluation on `stream` (default: torch's current stream) without a synchronisation in between. The
+    work is enqueued and the call returns: -> (uint8 tensor of cap bytes, int32 tensor, a 16-byte tensor for export_stats()) to be read
+    after the stream is synchronised. cap=None makes room for every request of the batch once, which a list without duplicates cannot
+    exceed (at most 0xFFFFFFF0 bytes)."""
+    names = list(batch.headers) if header_names is None else list(header_names)
+    st = batch.as_struct(names)
+    if isinstance(batch, RequestBatch):
+        idx = np.ascontiguousarray(idx, dtype=np.uint32).reshape(-1)
+        n_ref = None if n_idx is None else np.array([int(np.asarray(n_idx).reshape(-1)[0])], dtype=np.uint32)
+        rec_off = np.full(max(1, len(idx)), _abi.RECORD_NONE, dtype=np.uint32)
+        stats = _abi.ExportStats()
+
+        def call(buf, nbytes):
+            rc = lib().pwaf_export_records(C.byref(st), idx.ctypes.data if len(idx) else None, len(idx), None if n_ref is None else n_ref.ctypes.data,
+                                           None if buf is None else buf.ctypes.data, nbytes, rec_off.ctypes.data, C.addressof(stats), None)
+            if rc != 0:
+                _raise(rc, lib().pwaf_last_error().decode(errors="replace"))
+
+        if cap is None:
+            call(None, 0)
+            cap = int(stats.bytes_needed)
+        buf = _aligned_bytes(int(cap))
+        call(buf, int(cap))
+        res = {"bytes_needed": int(stats.bytes_needed), "n_selected": int(stats.n_selected), "n_written": int(stats.n_written)}
+        return buf[:min(int(cap), res["bytes_needed"])], rec_off[:len(idx)], res
+    import torch
+
+    assert idx.is_contiguous() and idx.element_size() == 4 and (n_idx is None or n_idx.element_size() == 4)
+    n_list = idx.numel()
+    if cap is None:
+        per_record = (C.sizeof(_abi.RecordHead) + 4 * (_abi.N_FIELDS + len(names)) + 15 & ~15) + 15
+        cap = sum(batch.field_bytes) + sum(batch.headers[nm][2] for nm in names if nm in batch.headers) + min(n_list, batch.n) * per_record
+        cap = min(cap + 15 & ~15, 0xFFFFFFF0)
+    if stream is None:
+        stream = torch.cuda.current_stream(batch.device).cuda_stream
+    buf = torch.empty(max(16, int(cap)), dtype=torch.uint8, device=batch.device)
+    rec_off = torch.empty(max(1, n_list), dtype=torch.int32, device=batch.device)
+    stats = torch.empty(16, dtype=torch.uint8, device=batch.device)
+    rc = lib().pwaf_export_records(C.byref(st), idx.data_ptr() if n_list else None, n_list, None if n_idx is None else n_idx.data_ptr(), buf.data_ptr(), int(cap),
+                                   rec_off.data_ptr(), stats.data_ptr(), C.c_void_p(stream))
+    if rc != 0:
+        _raise(rc, lib().pwaf_last_error().decode(errors="replace"))
+    return buf[:int(cap)], rec_off[:n_list], stats
 
 
 def verdict_from_record(v) -> Verdict:
