@@ -455,6 +455,34 @@ typedef struct pwaf_export_stats {
 int pwaf_export_records(const pwaf_batch *in, const uint32_t *idx, uint32_t idx_cap, const uint32_t *n_idx /* nullable */, uint8_t *buf,
                         size_t buf_cap, uint32_t *rec_off /* idx_cap entries */, pwaf_export_stats *stats, void *stream);
 
+/* ---- records in device memory (ABI 4, additive) ----------------------------------------------------------
+ * pwaf_evaluate_records for records that already lie in DEVICE memory — what pwaf_export_records wrote, or a replay file copied to the
+ * device once: the bytes never visit the host. buf, rec_off, n_rec, out, counts, match_idx and n_matches are device pointers on the
+ * engine's device; `stream` is a hipStream_t (NULL = HIP's default stream). buf is 16-byte aligned and carries NO pad: not one byte
+ * outside [buf, buf + buf_bytes) is read, whatever the records say. Request i is the record at buf + rec_off[i] (any order; records may
+ * be shared or skipped). The records evaluated are m = min(*n_rec, n), or n when n_rec is NULL; the device reads *n_rec, so
+ * pwaf_export_stats::n_written of an export enqueued on the same stream is a valid n_rec without a synchronisation in between. out[i]
+ * for i >= m is not written.
+ * Format and validation are exactly pwaf_evaluate_records's, done on the device: a malformed call returns PWAF_E_BATCH with the same
+ * pwaf_last_error() text as the host call gives for the same bytes (the lowest failing index, its offset, the failing check;
+ * PWAF_RECORD_NONE in rec_off is a misaligned offset like any other); nothing behind the validation is launched then, and out, counts,
+ * match_idx and n_matches are untouched.
+ * Synchronisation: the call enqueues the validation and a segmented prefix sum of the lengths (three launches) on `stream` and waits
+ * for the stream ONCE, for one small block (the failure key, m, the common has_geoip, every column's bytes), as pwaf_evaluate_device does
+ * for a batch with field_bytes == 0. It then enqueues unpack_records_kernel and the ordinary pipeline and returns: out is valid once
+ * `stream` has run. counts and n_matches are ACCUMULATED into (zero them first); match_idx needs room for m entries. Overflow-pool
+ * exhaustion is reported by pwaf_engine_device_status, as for pwaf_evaluate_device. m == 0 launches nothing further and returns
+ * PWAF_OK. Re-entrant like pwaf_evaluate_device: the unpacked columns and offsets live in the engine's context, not in caller memory, so
+ * buf and rec_off may be released or rewritten once `stream` has run.
+ * Out of scope: _geo / _hits / _routes variants of this call, and pwaf_node_*. The HOST pwaf_evaluate_records and the async queue keep
+ * their host-side validation. */
+int pwaf_evaluate_records_device(pwaf_engine *, const uint8_t *buf, size_t buf_bytes, const uint32_t *rec_off, uint32_t n,
+                                 const uint32_t *n_rec /* nullable */, pwaf_verdict *out, pwaf_counts *counts /* nullable */,
+                                 uint32_t *match_idx, uint32_t *n_matches /* both or neither */, void *stream);
+/* TEST HOOK (CPU, no device): the shape of that call's scan, so that a test places its sizes on the real boundaries: out[0] = records
+ * per tile of the check and offsets launches, out[1] = tiles one step of the tile-base launch takes, out[2] = out[3] = 0. */
+int pwaf_records_scan_shape(uint32_t out[4]);
+
 /* ---- non-blocking request queue (ABI 4) -------------------------------------------------------------
  * The call shape of an async host (the reference's rule loop runs inside an async hyper closure, http_listener.rs:133-274): submit a
  * request with a tag and go on; collect {tag, verdict, status} completions later. pwaf_async_submit copies the request ONCE, as a record,

@@ -40,6 +40,8 @@ ARENA_PAD = 16
 ADDRESS_TABLE_FIELDS = ("escapes", "n_vals", "has_summary", "shift", "common", "packed", "classes", "sets")
 # pwaf_program_confirm_shape (test hook): the meaning of out[0..7]
 CONFIRM_SHAPE_FIELDS = ("entries", "bytes", "class_words", "in_lds", "longest", "top_class_pos", "widest_bin", "has_walk")
+# pwaf_records_scan_shape (test hook): the meaning of out[0..3] (pwaf_evaluate_records_device's scan: records per tile, tiles per phase-2 step)
+RECORDS_SCAN_SHAPE_FIELDS = ("tile", "step", "zero2", "zero3")
 # pwaf_program_list_scans (test hook): the meaning of a descriptor's PWAF_LIST_SCAN_WORDS words (share_owner 0xFFFFFFFF: none)
 LIST_SCAN_FIELDS = ("phase", "pass", "tier", "threads", "hot_bytes", "n_hot", "n_delta", "behind_filter", "merge_rec", "dense_mode", "share_owner", "need_bit",
                     "launch", "launch_count", "wg_per_cu", "zero15")

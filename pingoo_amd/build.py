@@ -13,7 +13,7 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libpwaf.so")
-SOURCES = ["frontend.cpp", "pattern.cpp", "dfa.cpp", "iptrie.cpp", "filter.cpp", "residual.cpp", "residual_jit.cpp", "rtc.cpp", "compile.cpp", "tableplan.cpp", "scanplan.cpp", "loaders.cpp", "batcher.cpp", "async.cpp", "node.cpp", "engine.cpp", "kernels.hip", "records.hip"]
+SOURCES = ["frontend.cpp", "pattern.cpp", "dfa.cpp", "iptrie.cpp", "filter.cpp", "residual.cpp", "residual_jit.cpp", "rtc.cpp", "compile.cpp", "tableplan.cpp", "scanplan.cpp", "loaders.cpp", "batcher.cpp", "async.cpp", "node.cpp", "engine.cpp", "kernels.hip", "records.hip", "records_scan.hip"]
 HEADERS = ["frontend.h", "program.h", "kernels.h", "residual.h", "confirm.h", "records.h", "lscan_split.h", "dirtable.h", "georec.h", "tableplan.h", "scanplan.h", "unicode_data.inc", os.path.join("..", "..", "include", "pwaf.h")]
 
 

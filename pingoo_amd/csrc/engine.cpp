@@ -2540,6 +2540,104 @@ int evaluate_records_impl(pwaf_engine *e, const uint8_t *buf, size_t buf_bytes, 
     if (counts) memcpy(counts, S.rec_back.p, sizeof(pwaf_counts));
     return PWAF_OK;
 }
+
+// Records that already lie in DEVICE memory. What the host does above — validate every record, turn the lengths into
+// column offsets — runs on the device here (records_scan.hip), on the caller's stream; the host waits for that stream ONCE, for the
+// summary block (failure key, m, has_geoip, the column totals), because the arenas it reserves next and the pipeline's launch plan are
+// sized from the totals. Everything behind the wait is enqueued and the call returns, like pwaf_evaluate_device.
+int evaluate_records_device_impl(pwaf_engine *e, const uint8_t *buf, size_t buf_bytes, const uint32_t *rec_off, uint32_t n, const uint32_t *n_rec, pwaf_verdict *out,
+                                 pwaf_counts *counts, uint32_t *match_idx, uint32_t *n_matches, hipStream_t stream) {
+    namespace R = pwaf::records;
+    if (e->n_fields > R::kMaxValues) return fail(PWAF_E_UNSUPPORTED, "the engine has more columns than a record can carry");
+    if ((match_idx == nullptr) != (n_matches == nullptr)) return fail(PWAF_E_INVALID_ARG, "match_idx and n_matches must be given together");
+    if ((uintptr_t)buf & 15u) return fail(PWAF_E_INVALID_ARG, "pwaf_evaluate_records_device: buf is not 16-byte aligned");
+    if (n == 0) return PWAF_OK;
+    HIP_TRY(hipSetDevice(e->device));
+    std::unique_lock<std::mutex> lock;
+    bool must_wait;
+    Scratch &S = acquire_context(e, false, stream, lock, must_wait);
+    int rc;
+    if ((rc = S.ensure(false))) return rc;
+    if (must_wait) HIP_TRY(hipStreamWaitEvent(stream, S.done, 0));
+    const uint32_t n_cols = e->n_fields;
+    // rec_meta, from n and n_cols alone: [summary] [column places] [tile sums / bases, per column] [column offsets, n + 1 per column]
+    Layout meta;
+    const size_t off_stride = R::offsets_stride(n), tile_stride = ((size_t)R::scan_tiles(n) + 31) & ~(size_t)31;
+    const size_t at_sum = meta.take(sizeof(R::ScanSummary)), at_colat = meta.take((size_t)n_cols * 8), at_tile = meta.take(tile_stride * 8 * n_cols),
+                 at_off = meta.take(off_stride * 4 * n_cols);
+    if (off_stride > 0xFFFFFFFFull) return fail(PWAF_E_UNSUPPORTED, "pwaf_evaluate_records_device: too many records for one call");
+    if ((rc = S.rec_meta.reserve(meta.size())) || (rc = S.rec_pin.reserve(sizeof(R::ScanSummary)))) return rc;
+    uint8_t *const d = (uint8_t *)S.rec_meta.p;
+    R::ScanArgs sa{};
+    sa.buf = buf, sa.buf_bytes = buf_bytes, sa.rec_off = rec_off, sa.n_rec = n_rec, sa.n = n, sa.n_cols = n_cols;
+    sa.off = (uint32_t *)(d + at_off), sa.off_stride = (uint32_t)off_stride;
+    sa.tile = (uint64_t *)(d + at_tile), sa.tile_stride = (uint32_t)tile_stride;
+    sa.col_at = (uint64_t *)(d + at_colat), sa.sum = (R::ScanSummary *)(d + at_sum);
+    const volatile R::ScanSummary *const sum = (const volatile R::ScanSummary *)S.rec_pin.p;
+    // From the first launch on, whatever way the call leaves, the context remembers the stream (its next user waits for what was enqueued).
+    auto body = [&]() -> int {
+        R::UnpackArgs ua{};
+        uint64_t colat[R::kMaxValues], totals[R::kMaxValues];
+        uint32_t m = 0;
+        {
+            KernelTimer prof(e, stream);  // (released before run_pipeline takes its own)
+            HIP_TRY(hipMemsetAsync(&sa.sum->key, 0xFF, 8, stream));  // records::kNoFailure
+            const uint64_t alg[3] = {(uint64_t)n * (4 + R::kHead + 4ull * n_cols), (uint64_t)tile_stride * 16 * n_cols, (uint64_t)off_stride * 8 * n_cols};
+            for (int phase = 1; phase <= 3; phase++) {
+                if ((rc = prof.begin())) return rc;
+                if (R::launch_scan_records(phase, sa, stream)) return fail(PWAF_E_DEVICE, std::string(R::kScanKernelNames[phase - 1]) + " launch failed");
+                if ((rc = prof.end(R::kScanKernelNames[phase - 1], alg[phase - 1]))) return rc;
+            }
+            // the call's one wait: the summary block
+            HIP_TRY(hipMemcpyAsync(S.rec_pin.p, sa.sum, R::summary_bytes(n_cols), hipMemcpyDeviceToHost, stream));
+            HIP_TRY(hipStreamSynchronize(stream));
+            prof.commit();
+            const uint64_t key = sum->key;
+            if (key != R::kNoFailure)
+                return fail(PWAF_E_BATCH, "record " + std::to_string(R::key_index(key)) + " (offset " + std::to_string(sum->bad_off) + "): " + R::check_message(R::key_check(key)));
+            m = sum->m;
+            if (m == 0) return PWAF_OK;
+            const bool geo = sum->has_geoip != 0;
+            for (uint32_t f = 0; f < n_cols; f++) totals[f] = sum->totals[f];
+            // rec_cols, from the totals: [column arenas, each with its PWAF_ARENA_PAD: records::place_columns] [ip] [v6] [port] [flags] [asn] [country]
+            Layout cl;
+            cl.used = (size_t)R::place_columns(totals, n_cols, colat);
+            const size_t c_ip = cl.take((size_t)m * 16), c_v6 = cl.take(m), c_port = cl.take((size_t)m * 2), c_flags = cl.take(m);
+            const size_t c_asn = geo ? cl.take((size_t)m * 4) : 0, c_cc = geo ? cl.take((size_t)m * 2) : 0;
+            if ((rc = S.rec_cols.reserve(cl.size()))) return rc;
+            uint8_t *const dc = (uint8_t *)S.rec_cols.p;
+            ua.rec = buf;
+            ua.rec_off = rec_off;
+            ua.n = m;
+            ua.n_cols = n_cols;
+            ua.arena = dc;
+            ua.col_at = sa.col_at;
+            ua.off = sa.off;
+            ua.off_stride = sa.off_stride;
+            ua.ip = dc + c_ip;
+            ua.ip_is_v6 = dc + c_v6;
+            ua.port = (uint16_t *)(dc + c_port);
+            ua.flags = dc + c_flags;
+            ua.asn = geo ? (uint32_t *)(dc + c_asn) : nullptr;
+            ua.country = geo ? (uint16_t *)(dc + c_cc) : nullptr;
+            prof.last_main = -1;  // (the unpack's time begins at its own event, not in front of the wait)
+            if ((rc = prof.begin())) return rc;
+            if (R::launch_unpack_records(ua, stream)) return fail(PWAF_E_DEVICE, "unpack_records_kernel launch failed");
+            uint64_t bytes = 0;
+            for (uint32_t f = 0; f < n_cols; f++) bytes += totals[f];
+            if ((rc = prof.end("unpack_records_kernel", 2 * bytes + (uint64_t)m * (R::kHead + 4ull * n_cols)))) return rc;
+            prof.commit();
+        }
+        // an ordinary DEVICE batch with every column's size known on the host
+        DeviceBatch dv(m, n_cols);
+        for (uint32_t f = 0; f < n_cols; f++) dv.set_col(f, ua.arena + colat[f], sa.off + (size_t)f * off_stride, (uint32_t)totals[f]);
+        dv.set_fixed(ua.ip, ua.ip_is_v6, ua.port, ua.flags, ua.asn, ua.country);
+        return run_pipeline(e, S, dv.db, out, counts, match_idx, n_matches, stream, true);
+    };
+    rc = body();
+    const hipError_t he = mark_context_used(S, stream, false);
+    return rc ? rc : he != hipSuccess ? device_error("hipEventRecord", he) : PWAF_OK;
+}
 }  // namespace
 
 extern "C" {
@@ -2552,6 +2650,11 @@ int pwaf_evaluate_records_geo(pwaf_engine *e, const uint8_t *buf, size_t buf_byt
     if (!e || (n && (!buf || !rec_off || !out))) return fail(PWAF_E_INVALID_ARG, "NULL argument");
     if (int rc = need_geo_answers(e, "pwaf_evaluate_records_geo")) return rc;
     return evaluate_records_impl(e, buf, buf_bytes, rec_off, n, out, counts, geo);
+}
+int pwaf_evaluate_records_device(pwaf_engine *e, const uint8_t *buf, size_t buf_bytes, const uint32_t *rec_off, uint32_t n, const uint32_t *n_rec, pwaf_verdict *out,
+                                 pwaf_counts *counts, uint32_t *match_idx, uint32_t *n_matches, void *stream) {
+    if (!e || (n && (!buf || !rec_off || !out))) return fail(PWAF_E_INVALID_ARG, "NULL argument");
+    return evaluate_records_device_impl(e, buf, buf_bytes, rec_off, n, n_rec, out, counts, match_idx, n_matches, (hipStream_t)stream);
 }
 
 int pwaf_program_tune(pwaf_program *p, const pwaf_batch *sample) {

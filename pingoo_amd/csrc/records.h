@@ -150,6 +150,95 @@ struct UnpackArgs {
 };
 int launch_unpack_records(const UnpackArgs &a, void *stream);
 
+// ---- validate + column_offsets for records that lie in DEVICE memory (pwaf_evaluate_records_device): reduce-then-scan over tiles of
+// kScanTile records, in three launches (records_scan.hip) that never wait for one another's workgroups:
+//   1 check + lengths   every record through scan_check; its lengths (0 where it fails or does not carry the column) into the offsets
+//                       array, one slot up; per tile and column a 64-bit sum; the lowest failing (index, check) by atomicMin on a key
+//   2 tile bases        per column: the tile sums become exclusive prefixes (kScanStep tiles a step), the last one the column's total; the
+//                       first record at which the column's running total exceeds kMaxColumn joins the key as kColumnTooBig
+//   3 offsets           every tile rescans its lengths from its base, in place; its first workgroup fills the summary and places the columns
+// The per-record and per-column arithmetic below is compiled by the kernels, by engine.cpp and by tests/records_scan_host.cpp (g++ under
+// the sanitizers, the three phases as loops over tiles): what keeps every read inside [buf, buf + buf_bytes) is check_record, as above.
+static constexpr uint32_t kScanTile = 256;  // records per tile: one per lane of a phase-1 workgroup
+static constexpr uint32_t kScanStep = 256;  // tiles one step of phase 2 takes: one per lane
+static constexpr uint64_t kNoFailure = ~0ull;
+
+// the failure key: ordered by (index, check), so that the minimum names what validate()'s loop meets first
+PWAF_RECORD_HD uint64_t fail_key(uint32_t i, int check) { return ((uint64_t)i << 32) | (uint32_t)check; }
+PWAF_RECORD_HD uint32_t key_index(uint64_t key) { return (uint32_t)(key >> 32); }
+PWAF_RECORD_HD int key_check(uint64_t key) { return (int)(uint32_t)key; }
+
+// the records a call looks at: min(*n_rec, n), or n without a count
+PWAF_RECORD_HD uint32_t records_in_call(const uint32_t *n_rec, uint32_t n) {
+    if (!n_rec) return n;
+    const uint32_t k = *n_rec;
+    return k < n ? k : n;
+}
+PWAF_RECORD_HD uint32_t scan_tiles(uint32_t m) { return m / kScanTile + (m % kScanTile ? 1u : 0u); }
+// a column's n + 1 offsets, on a 256-byte grid (evaluate_records_impl's stride)
+PWAF_RECORD_HD size_t offsets_stride(uint32_t n) { return ((size_t)n + 1 + 63) & ~(size_t)63; }
+
+// has_geoip of the call's first record where its head can be read, else a value no record has (the record then fails at index 0, and
+// no kMixedGeo behind it is ever reported)
+PWAF_RECORD_HD uint32_t first_geo(const uint8_t *buf, uint64_t buf_bytes, uint32_t off0) {
+    if ((off0 & 15u) || off0 > buf_bytes || buf_bytes - off0 < kHead) return 0xFFFFFFFFu;
+    return buf[(size_t)off0 + offsetof(pwaf_record_head, has_geoip)];
+}
+// One record of the call, as validate() judges it apart from the column totals: check_record, then has_geoip against the first record's.
+// *n_values = the lengths it carries (0 unless kOk).
+PWAF_RECORD_HD int scan_check(const uint8_t *buf, uint64_t buf_bytes, uint32_t off, uint32_t n_cols, uint32_t geo0, uint32_t *n_values) {
+    *n_values = 0;
+    uint64_t vb = 0;
+    const int c = check_record(buf, buf_bytes, off, n_cols, &vb);
+    if (c != kOk) return c;
+    const uint8_t *r = buf + off;
+    if (r[offsetof(pwaf_record_head, has_geoip)] != geo0) return kMixedGeo;
+    uint16_t nv;
+    memcpy(&nv, r + offsetof(pwaf_record_head, n_values), 2);
+    *n_values = nv;
+    return kOk;
+}
+// the length a record with n_values lengths contributes to column f
+PWAF_RECORD_HD uint32_t scan_len(const uint8_t *rec, uint32_t n_values, uint32_t f) { return f < n_values ? load_len(rec, f) : 0u; }
+// a column's running total, inclusive of a record: validate()'s kColumnTooBig
+PWAF_RECORD_HD bool column_too_big(uint64_t inclusive_total) { return inclusive_total > kMaxColumn; }
+// Where the columns go in the unpacked batch: each total plus PWAF_ARENA_PAD, on the 256-byte grid of engine.cpp's Layout::take.
+// Returns the bytes the columns occupy together (where the fixed columns begin).
+PWAF_RECORD_HD uint64_t place_columns(const uint64_t *totals, uint32_t n_cols, uint64_t *col_at) {
+    uint64_t used = 0;
+    for (uint32_t f = 0; f < n_cols; f++) {
+        col_at[f] = used;
+        used = (used + totals[f] + PWAF_ARENA_PAD + 255u) & ~(uint64_t)255u;
+    }
+    return used;
+}
+
+// What the host reads back, once per call: the failure key (kNoFailure: a valid call), the offset of the record it names, the records
+// evaluated, their common has_geoip, and every column's bytes.
+struct ScanSummary {
+    uint64_t key;
+    uint32_t bad_off, m, has_geoip, reserved;
+    uint64_t totals[kMaxValues];
+};
+PWAF_RECORD_HD size_t summary_bytes(uint32_t n_cols) { return offsetof(ScanSummary, totals) + 8u * (size_t)n_cols; }
+
+// The three launches' arguments. off / col_at are what UnpackArgs then takes; nothing here is the caller's memory but buf, rec_off, n_rec.
+struct ScanArgs {
+    const uint8_t *buf;  // the records: exactly buf_bytes bytes, no pad behind them
+    uint64_t buf_bytes;
+    const uint32_t *rec_off;  // n
+    const uint32_t *n_rec;    // nullable
+    uint32_t n, n_cols;
+    uint32_t *off;  // n_cols x off_stride: slot i + 1 of column f holds record i's length after phase 1, its end offset after phase 3
+    uint32_t off_stride;
+    uint32_t tile_stride;  // >= scan_tiles(n)
+    uint64_t *tile;        // n_cols x tile_stride: tile sums after phase 1, tile bases after phase 2
+    uint64_t *col_at;      // n_cols
+    ScanSummary *sum;      // (key set to kNoFailure in front of phase 1)
+};
+extern const char *const kScanKernelNames[3];
+int launch_scan_records(int phase /* 1 .. 3 */, const ScanArgs &a, void *stream);
+
 // ---- packing: the inverse (pwaf_export_records). Selected requests of a batch's columns -> records, byte for byte what
 // RequestBatch.to_records builds. The same three compilations: pack_records_kernel (records.hip), the HOST mode of the entry point (a loop
 // over pack_record: export_host below) and tests/records_pack_host.cpp (g++ under the sanitizers).

@@ -149,6 +149,8 @@ def lib():
     L.pwaf_batcher_destroy.restype = None
     L.pwaf_evaluate_records.argtypes = [vp, vp, C.c_size_t, vp, C.c_uint32, vp, vp]
     L.pwaf_export_records.argtypes = [C.POINTER(_abi.Batch), vp, C.c_uint32, vp, vp, C.c_size_t, vp, vp, vp]
+    L.pwaf_evaluate_records_device.argtypes = [vp, vp, C.c_size_t, vp, C.c_uint32, vp, vp, vp, vp, vp, vp]
+    L.pwaf_records_scan_shape.argtypes = [C.POINTER(C.c_uint32)]
     L.pwaf_async_create.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(vp)]
     L.pwaf_async_submit.argtypes = [vp, C.POINTER(_abi.Request), C.c_uint64]
     L.pwaf_async_poll.argtypes = [vp, C.POINTER(_abi.Completion), C.c_size_t]
@@ -647,6 +649,31 @@ class RuleEngine:
     def export_records(self, batch, idx, n_idx=None, cap=None, stream=None):
         """export_records (below) with this engine's header columns: the records are what evaluate_records of this engine takes."""
         return export_records(batch, idx, n_idx=n_idx, cap=cap, stream=stream, header_names=self.header_names)
+
+    def evaluate_records_device(self, buf, rec_off, n_rec=None, out=None, counts=None, match_idx=None, n_matches=None, stream=None):
+        """Request records that lie in device memory (pwaf_evaluate_records_device): `buf` a uint8 device tensor of exactly the records'
+        bytes (16-byte aligned, no pad), `rec_off` a 32-bit device tensor — request i is the record at buf[rec_off[i]] —, `n_rec` a
+        one-element 32-bit device tensor or None: min(n_rec, len(rec_off)) records are evaluated (export_records' stats tensor viewed as
+        int32 holds n_written at [3:4]). Validation runs on the device; a malformed call raises PwafError with pwaf_evaluate_records' text
+        and leaves every output untouched. The call waits for the stream once (for the column sizes), enqueues the rest on torch's current
+        stream (or `stream`) and returns `out` ((n, 2) int32; rows past the evaluated records are not written). counts / n_matches
+        ACCUMULATE: zero them first."""
+        import torch
+
+        assert buf.is_contiguous() and buf.element_size() == 1 and rec_off.is_contiguous() and rec_off.element_size() == 4
+        assert n_rec is None or (n_rec.element_size() == 4 and n_rec.numel() >= 1)
+        n = rec_off.numel()
+        if out is None:
+            out = torch.empty((n, 2), dtype=torch.int32, device=buf.device)
+        if stream is None:
+            stream = torch.cuda.current_stream(buf.device).cuda_stream
+        rc = lib().pwaf_evaluate_records_device(self._h, buf.data_ptr() if buf.numel() else None, buf.numel(), rec_off.data_ptr() if n else None, n,
+                                                None if n_rec is None else n_rec.data_ptr(), out.data_ptr(), None if counts is None else counts.data_ptr(),
+                                                None if match_idx is None else match_idx.data_ptr(), None if n_matches is None else n_matches.data_ptr(),
+                                                C.c_void_p(stream))
+        if rc != 0:
+            _raise(rc, lib().pwaf_last_error().decode(errors="replace"))
+        return out
 
     def evaluate(self, request: Request, with_geo: bool = False):
         """RuleEngine::evaluate(Request) -> Action (pwaf_evaluate_one): a batch of one through the same device path. with_geo
@@ -1189,6 +1216,15 @@ def export_records(batch, idx, n_idx=None, cap=None, stream=None, header_names: 
     if rc != 0:
         _raise(rc, lib().pwaf_last_error().decode(errors="replace"))
     return buf[:int(cap)], rec_off[:n_list], stats
+
+
+def records_scan_shape() -> dict:
+    """TEST HOOK (pwaf_records_scan_shape): the shape of evaluate_records_device's scan, by the names of _abi.RECORDS_SCAN_SHAPE_FIELDS."""
+    out = (C.c_uint32 * 4)()
+    rc = lib().pwaf_records_scan_shape(out)
+    if rc != 0:
+        _raise(rc, lib().pwaf_last_error().decode(errors="replace"))
+    return dict(zip(_abi.RECORDS_SCAN_SHAPE_FIELDS, (int(x) for x in out)))
 
 
 def verdict_from_record(v) -> Verdict:
