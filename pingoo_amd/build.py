@@ -13,8 +13,10 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libpwaf.so")
-SOURCES = ["frontend.cpp", "pattern.cpp", "dfa.cpp", "iptrie.cpp", "filter.cpp", "residual.cpp", "residual_jit.cpp", "rtc.cpp", "compile.cpp", "tableplan.cpp", "scanplan.cpp", "loaders.cpp", "batcher.cpp", "async.cpp", "node.cpp", "engine.cpp", "kernels.hip", "records.hip", "records_scan.hip"]
-HEADERS = ["frontend.h", "program.h", "kernels.h", "residual.h", "confirm.h", "records.h", "lscan_split.h", "dirtable.h", "georec.h", "tableplan.h", "scanplan.h", "unicode_data.inc", os.path.join("..", "..", "include", "pwaf.h")]
+SOURCES = ["frontend.cpp", "pattern.cpp", "dfa.cpp", "iptrie.cpp", "filter.cpp", "residual.cpp", "residual_jit.cpp", "rtc.cpp", "compile.cpp", "tableplan.cpp", "scanplan.cpp", "loaders.cpp", "batcher.cpp", "async.cpp", "node.cpp", "program_api.cpp", "engine.cpp", "pipeline.cpp", "evaluate.cpp", "evaluate_records.cpp", "kernels.hip", "records.hip", "records_scan.hip"]
+HEADERS = ["frontend.h", "program.h", "program_handle.h", "engine_impl.h", "staging.h", "kernels.h", "residual.h", "confirm.h", "records.h", "lscan_split.h", "dirtable.h", "georec.h", "tableplan.h", "scanplan.h", "unicode_data.inc", os.path.join("..", "..", "include", "pwaf.h")]
+# host code that calls the HIP runtime (engine_impl.h): compiled as HIP like the kernels; every other .cpp is plain C++
+HIP_HOST_UNITS = ("engine.cpp", "pipeline.cpp", "evaluate.cpp", "evaluate_records.cpp", "rtc.cpp")
 
 
 def hipcc() -> str:
@@ -72,7 +74,7 @@ def build(force: bool = False, verbose: bool = False, variant: str = "") -> str:
         if not force and os.path.exists(obj) and os.path.getmtime(obj) > max(os.path.getmtime(path), *(os.path.getmtime(os.path.join(CSRC, h)) for h in HEADERS)):
             continue
         cmd = [cc, *common, "-c", path, "-o", obj]
-        if src.endswith(".hip") or src in ("engine.cpp", "rtc.cpp"):
+        if src.endswith(".hip") or src in HIP_HOST_UNITS:
             cmd[1:1] = ["-x", "hip", "--offload-arch=gfx950"]
         else:
             # host-only translation units (no HIP headers): plain C++

@@ -21,7 +21,7 @@
 // free list only after pwaf_evaluate_records on it has returned.
 //
 // GeoIP answers. A queue made by pwaf_async_create_geo keeps a pwaf_geo per slot and per completion. The evaluator that fills them
-// (pwaf_evaluate_records_geo) reaches the queue as a function pointer (pwaf::async_create_with, called from engine.cpp): this file refers
+// (pwaf_evaluate_records_geo) reaches the queue as a function pointer (pwaf::async_create_with, called from evaluate_records.cpp): this file refers
 // to no engine symbol beyond pwaf_engine_header_count, pwaf_host_alloc / _free and pwaf_evaluate_records, so the CPU suite links it
 // against a stub engine.
 #include <sys/eventfd.h>

@@ -83,7 +83,7 @@ struct ListScanArgs {
     uint32_t ill_class;
     uint32_t n_classes;
     uint32_t n_hot;            // rows staged in LDS: n_hot * (n_classes + 3) * 2 <= the launch's ListShape::hot_bytes
-    // DELTA records (engine.cpp: build_flat_group): states [n_hot, n_hot + n_delta) live in LDS as 8 bytes each — base row (16 bits), two
+    // DELTA records (scanplan.cpp: build_flat_group): states [n_hot, n_hot + n_delta) live in LDS as 8 bytes each — base row (16 bits), two
     // exception classes (8 bits each), their two cells (16 bits each); every other class reads the base row's cell. Null: none.
     const uint64_t *delta;
     uint32_t n_delta;
@@ -243,7 +243,7 @@ struct FilterArgs {
 };
 // The descriptors of all passes of a launch live in DEVICE memory (a 4096-rule set over 64 header fields has ~70 filtered passes:
 // 15 KB of descriptors, kernel arguments hold 8). The host builds the descriptors of EVERY launch of a batch before the first one, writes
-// them into a page-locked slot and one copy launch on the batch's stream moves the block (engine.cpp: Scratch::args): stream-ordered,
+// them into a page-locked slot and one copy launch on the batch's stream moves the block (engine_impl.h: Scratch::args): stream-ordered,
 // one launch per batch whatever the number of passes.
 int upload_args_block(const void *host_pinned, void *dev, size_t bytes, void *zero /* nullable: a block to clear in the same launch */, size_t zero_bytes, void *stream);
 struct FilterTable {

@@ -17,7 +17,7 @@
 #include "pwaf.h"
 
 namespace pwaf {
-int fail(int code, const std::string &msg);  // engine.cpp: records pwaf_last_error()
+int fail(int code, const std::string &msg);  // program_api.cpp: records pwaf_last_error()
 }
 using pwaf::fail;
 

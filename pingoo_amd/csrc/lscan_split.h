@@ -5,7 +5,7 @@
 // its R-tier walk — so 250 passes can need 500. A phase with more is split into consecutive launches on the batch's stream, each with a
 // plan region of its own (2 * count + 1 words: work-item prefix sums and total, then the entries per item of every descriptor). A pass's
 // descriptors never straddle two launches. plan_passes (scanplan.cpp) computes the launches when the passes get their roles — at creation
-// and after pwaf_engine_tune — and run_pipeline follows them. Compiled by scanplan.cpp, engine.cpp and tests/lscan_split_host.cpp (g++: the CPU
+// and after pwaf_engine_tune — and run_pipeline follows them. Compiled by scanplan.cpp, pipeline.cpp and tests/lscan_split_host.cpp (g++: the CPU
 // suite checks the split).
 #pragma once
 #include <stddef.h>

@@ -21,7 +21,7 @@
 #include "../../include/pwaf.h"
 
 namespace pwaf {
-int fail(int code, const std::string &msg);  // engine.cpp: sets the thread's last-error text
+int fail(int code, const std::string &msg);  // program_api.cpp: sets the thread's last-error text
 }
 
 // One persistent host thread per device (round 3; round 2 spawned std::threads per call): a call posts one job per device and waits

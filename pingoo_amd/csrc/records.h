@@ -1,7 +1,7 @@
 // records.h — the request record of include/pwaf.h (pwaf_record_head + lengths + values): layout, validation, decoding, and (second half)
 // packing: pwaf_export_records.
 //
-// One header, compiled three ways, like confirm.h: by records.hip (unpack_records_kernel decodes records on the device), by engine.cpp
+// One header, compiled three ways, like confirm.h: by records.hip (unpack_records_kernel decodes records on the device), by evaluate_records.cpp
 // (pwaf_evaluate_records validates every record and computes the column offsets on the host before anything is launched) and by
 // tests/records_host.cpp (g++: the CPU suite checks validation and decoding against RequestBatch's own columns). Validation is what
 // guarantees the kernel never reads outside the uploaded buffer: the kernel trusts every head it reads.
@@ -22,7 +22,7 @@ namespace pwaf {
 namespace records {
 
 static constexpr uint32_t kHead = (uint32_t)sizeof(pwaf_record_head);
-// PWAF_N_FIELDS + program.h kMaxHeaders (engine.cpp, which sees both headers, asserts it): sizes the kernel's LDS prefix and async.cpp's
+// PWAF_N_FIELDS + program.h kMaxHeaders (evaluate_records.cpp, which sees both headers, asserts it): sizes the kernel's LDS prefix and async.cpp's
 // per-request arrays; pwaf_evaluate_records and pwaf_async_create also refuse an engine with more columns at run time
 static constexpr uint32_t kMaxValues = PWAF_N_FIELDS + 120;
 static constexpr uint64_t kMaxColumn = 0xFFFFFFF0ull;         // a column's bytes: uint32 offsets, PWAF_ARENA_PAD behind them
@@ -157,7 +157,7 @@ int launch_unpack_records(const UnpackArgs &a, void *stream);
 //   2 tile bases        per column: the tile sums become exclusive prefixes (kScanStep tiles a step), the last one the column's total; the
 //                       first record at which the column's running total exceeds kMaxColumn joins the key as kColumnTooBig
 //   3 offsets           every tile rescans its lengths from its base, in place; its first workgroup fills the summary and places the columns
-// The per-record and per-column arithmetic below is compiled by the kernels, by engine.cpp and by tests/records_scan_host.cpp (g++ under
+// The per-record and per-column arithmetic below is compiled by the kernels, by evaluate_records.cpp and by tests/records_scan_host.cpp (g++ under
 // the sanitizers, the three phases as loops over tiles): what keeps every read inside [buf, buf + buf_bytes) is check_record, as above.
 static constexpr uint32_t kScanTile = 256;  // records per tile: one per lane of a phase-1 workgroup
 static constexpr uint32_t kScanStep = 256;  // tiles one step of phase 2 takes: one per lane
@@ -202,7 +202,7 @@ PWAF_RECORD_HD int scan_check(const uint8_t *buf, uint64_t buf_bytes, uint32_t o
 PWAF_RECORD_HD uint32_t scan_len(const uint8_t *rec, uint32_t n_values, uint32_t f) { return f < n_values ? load_len(rec, f) : 0u; }
 // a column's running total, inclusive of a record: validate()'s kColumnTooBig
 PWAF_RECORD_HD bool column_too_big(uint64_t inclusive_total) { return inclusive_total > kMaxColumn; }
-// Where the columns go in the unpacked batch: each total plus PWAF_ARENA_PAD, on the 256-byte grid of engine.cpp's Layout::take.
+// Where the columns go in the unpacked batch: each total plus PWAF_ARENA_PAD, on the 256-byte grid of staging.h's Layout::take.
 // Returns the bytes the columns occupy together (where the fixed columns begin).
 PWAF_RECORD_HD uint64_t place_columns(const uint64_t *totals, uint32_t n_cols, uint64_t *col_at) {
     uint64_t used = 0;

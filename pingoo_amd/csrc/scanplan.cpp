@@ -11,7 +11,7 @@
 
 namespace pwaf {
 
-int fail(int code, const std::string &msg);  // engine.cpp: records pwaf_last_error()
+int fail(int code, const std::string &msg);  // program_api.cpp: records pwaf_last_error()
 
 std::vector<uint8_t> class_image(const DfaGroup &g, const std::vector<uint32_t> *cpos, uint32_t &ill_class) {
     std::vector<uint8_t> img(kUmapAt, 0);

@@ -8,7 +8,7 @@
 
 namespace pwaf {
 
-int fail(int code, const std::string &msg);  // engine.cpp: records pwaf_last_error()
+int fail(int code, const std::string &msg);  // program_api.cpp: records pwaf_last_error()
 
 namespace {
 

@@ -122,7 +122,7 @@ class PassShape:
         self.slab_first = np.searchsorted(off[1:] + 3 * self.stride, slab_b0, side="right")
         self.owner_rel = self.owner - self.slab_first
         self.reset_steps = np.searchsorted(off[:-1], byte0 + CHUNK, side="left") - self.owner
-        # the flag-density switch (engine.cpp: dense_thresh): above it the pass is walked whole and nothing is confirmed
+        # the flag-density switch (pipeline.cpp: dense_thresh): above it the pass is walked whole and nothing is confirmed
         self.dense_thresh = self.n_slabs * (SLAB // CHUNK) // 2
 
     @property

@@ -20,7 +20,7 @@ using namespace pwaf;
 
 static std::string g_message;
 namespace pwaf {
-int fail(int code, const std::string &msg) {  // (the product's is engine.cpp's)
+int fail(int code, const std::string &msg) {  // (the product's is program_api.cpp's)
     g_message = msg;
     return code;
 }

@@ -18,6 +18,7 @@
 #include <vector>
 
 #include "../pingoo_amd/csrc/records.h"
+#include "../pingoo_amd/csrc/staging.h"
 
 namespace R = pwaf::records;
 
@@ -165,10 +166,9 @@ int main(int argc, char **argv) {
             const size_t stride = (size_t)m + 1;
             std::vector<uint32_t> want(stride * n_cols);
             R::column_offsets(buf.get(), rec_off.get(), m, n_cols, want.data(), stride);
-            size_t used = 0;  // engine.cpp's Layout::take, restated
+            pwaf::Layout cl;  // (the grid the host call places its columns on)
             for (uint32_t f = 0; f < n_cols && same; f++) {
-                same = s.totals[f] == totals[f] && s.col_at[f] == used;
-                used = (used + (size_t)totals[f] + PWAF_ARENA_PAD + 255) & ~(size_t)255;
+                same = s.totals[f] == totals[f] && s.col_at[f] == cl.take((size_t)totals[f] + PWAF_ARENA_PAD);
                 if (m) same = same && !memcmp(s.off.data() + (size_t)f * s.stride, want.data() + (size_t)f * stride, stride * 4);
             }
         }

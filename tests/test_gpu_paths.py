@@ -481,6 +481,84 @@ def test_host_batches_small_and_large_pageable_and_page_locked():
     eng.close()
 
 
+PACK_MAX = 1 << 20  # csrc/staging.h: kPackMax
+
+
+def packed_block(batch, names, geo=False, route=False):
+    """csrc/staging.h: plan_packed, restated from the column sizes -> (bytes of the batch as ONE packed block, whether it travels as one):
+    no column may begin past 0, the columns may not pass PACK_MAX on the way, the whole block may not pass it."""
+    import ctypes as C
+
+    from pingoo_amd.batch import GEO_DTYPE, VERDICT_DTYPE
+
+    def up(b):
+        return (b + 255) & ~255
+    n = batch.n
+    cols = list(batch.offsets) + [batch.headers[h][1] for h in names if h in batch.headers]
+    fits, need = all(int(o[0]) == 0 for o in cols), 0
+    for o in cols:
+        need += up(4 * (n + 1)) + up(int(o[-1]) + _abi.ARENA_PAD)
+        fits = fits and need <= PACK_MAX
+    need += up(16 * n) + up(n) + up(2 * n) + up(n) + (up(4 * n) + up(2 * n) if batch.asn is not None else 0)
+    need += up(C.sizeof(_abi.Counts)) + up(n * VERDICT_DTYPE.itemsize) + (up(n * GEO_DTYPE.itemsize) if geo else 0) + (up(4 * n) if route else 0)
+    return need, fits and need <= PACK_MAX
+
+
+def test_host_batches_on_either_side_of_the_packed_block_s_limit():
+    """pwaf_evaluate_batch, its geo variant and its routes variant on batches of 300 requests whose packed size is PACK_MAX exactly, one
+    256-byte step above it and 4 KiB below it (one header value is padded to get there), and on a slab view (offsets[0] != 0) of the
+    largest: the oracle's verdicts, counters, GeoIP records and routes whichever staging path the size selects. Which path that is follows
+    from the column sizes (packed_block); the geo and route outputs are part of the block, so the exact batch is packed for the plain call
+    and column by column for the other two."""
+    import routed_walker as RW
+
+    rng = random.Random(41)
+    lists, geo = H.fuzz_lists(rng), H.fuzz_geoip(rng)
+    rules = [(f"r{k}", H.rexpr(rng, lists), H.fuzz_actions(rng)) for k in range(10)]
+    rules += [("ha", 'http_request.headers["x-a"].contains("ab") && client.remote_port < 1024', [B]), ("hb", 'http_request.headers["x-b"].ends_with("zM")', [CAP])]
+    routes = [("a", 'http_request.host.starts_with("a")'), ("hdr", 'http_request.headers["x-b"].starts_with("zz")'), ("slash", 'http_request.path.contains("/")')]
+    eng = RuleEngine(rules, lists, geo, routes=routes, flags=_abi.OPT_LENIENT | _abi.OPT_GEO_ANSWERS)
+    assert eng.header_names == ["x-a", "x-b"]
+    seen, _ = H.as_the_engine_sees(rules, eng.program)
+    orc = pyoracle.Oracle(seen, lists, geo)
+    reqs = H.fuzz_requests(rng, 300, with_geo=False)
+    for i, r in enumerate(reqs):
+        r.headers = {"x-a": H.rstr(rng, 0, 6), "x-b": H.rstr(rng, 0, 4, "zM")}
+    reqs[0].host, reqs[0].headers = "a0", {"x-a": "ab", "x-b": "zM"}  # (a slab view from request 1 on begins past 0 in these columns)
+
+    def padded(pad):
+        reqs[150].headers["x-b"] = "z" * pad + "M"
+        return RequestBatch.from_requests(reqs)
+    need0, _ = packed_block(padded(0), eng.header_names)
+    arena0 = int(padded(0).headers["x-b"][1][-1]) + _abi.ARENA_PAD  # (the padded column's part of the block: its arena, rounded up to 256)
+    exact_pad = PACK_MAX - (need0 - ((arena0 + 255) & ~255)) - arena0
+    batches = {"exact": padded(exact_pad), "above": padded(exact_pad + 256), "below": padded(exact_pad - 4096)}
+    assert packed_block(batches["exact"], eng.header_names)[0] == PACK_MAX and packed_block(batches["above"], eng.header_names)[0] == PACK_MAX + 256
+    want = {k: (orc.evaluate(b), RW.oracle_routes(routes, lists, geo, b)) for k, b in batches.items()}
+    batches["slab"] = batches["above"].view(1, 300)
+    want["slab"] = (want["above"][0][1:], want["above"][1][1:])
+    assert any(int(o[0]) != 0 for o in batches["slab"].offsets) and int(batches["slab"].headers["x-b"][1][0]) != 0
+    sides = {}
+    for name, b in batches.items():
+        v, r = want[name]
+        hist = np.bincount(v["action"], minlength=4).tolist()
+        g_want = [orc.geoip_lookup(b.ip[j].tobytes(), bool(b.ip_is_v6[j])) for j in range(b.n)]
+        sides[name] = tuple(packed_block(b, eng.header_names, geo=g, route=t)[1] for g, t in ((False, False), (True, False), (False, True)))
+        got, counts = eng.evaluate_batch(b, with_counts=True)
+        H.assert_verdicts_equal(got, v, b, f"{name}: plain")
+        assert counts.tolist() == hist, name
+        got, counts, g = eng.evaluate_batch(b, with_counts=True, with_geo=True)
+        H.assert_verdicts_equal(got, v, b, f"{name}: geo")
+        assert counts.tolist() == hist and [(int(a), bytes(c)) for a, c in zip(g["asn"], g["country"])] == g_want, name
+        got, rt, counts = eng.evaluate_batch_routes(b, with_counts=True)
+        H.assert_verdicts_equal(got, v, b, f"{name}: routes")
+        assert counts.tolist() == hist and (rt == r).all(), name
+    # (plain, geo, routes) packed?
+    assert sides == {"exact": (True, False, False), "above": (False, False, False), "below": (True, True, True), "slab": (False, False, False)}, sides
+    assert len(set(want["exact"][0]["rule_idx"].tolist())) >= 4 and len(set(want["exact"][1].tolist())) >= 3 and len(set(g_want)) >= 3
+    eng.close()
+
+
 def test_verdict_sparse_column_file_dense_and_spill_agree():
     """The verdict kernel's ENTRY LIST (round 6: verdict2_kernel, the default) against the round-5 sparse column file
     (PWAF_OPT_SPARSE_VERDICT), the round-4 dense file (PWAF_OPT_DENSE_VERDICT) and both with 8 slots per wave

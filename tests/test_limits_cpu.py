@@ -1,6 +1,6 @@
 """The engine's capacity limits on the CPU (no device): rule sets pinned to exact scan-pass counts (helpers.pinned_passes) at the
 250-pass limit and around the 64-pass, 128-pass and 32-gap-pass boundaries, and the split of the list-scan launches
-(csrc/lscan_split.h: at most 256 descriptors per launch_scan_gated call) through the very header engine.cpp plans them with."""
+(csrc/lscan_split.h: at most 256 descriptors per launch_scan_gated call) through the very header pipeline.cpp plans them with."""
 import json
 import os
 import subprocess
