@@ -708,6 +708,17 @@ size_t pwaf_program_flat_image(const pwaf_program *, uint32_t group, uint32_t ti
  * workgroups per CU, [15] 0. Writes at most cap descriptors; *n_descs = how many there are. The reference has no counterpart. */
 #define PWAF_LIST_SCAN_WORDS 16
 int pwaf_program_list_scans(const pwaf_program *, uint32_t *out, size_t cap, size_t *n_descs);
+/* TEST HOOK (CPU, no device): the launch shape of the verdict kernel in every batch of an engine created from this program (with the
+ * program's flags), computed by the function the engine computes it with (csrc/verdictplan.h: verdict_shape) over the tables planned as
+ * the engine plans them and the pass count its batches hand to the kernel. out[0] = the mode (3 entry list, 4 entry list with 8 slots:
+ * PWAF_OPT_TINY_VERDICT_SLOTS; 0 dense, 1 sparse column file, 2 sparse with 8 value slots), out[1] = the capacity per wave (entries of
+ * the entry list, entry 0 = TRUE included — at most 254: a slot byte is 1 + entry index and 255 means spilled; value slots of the
+ * sparse file; 0 for the dense one), out[2] = waves per workgroup (0: pwaf_engine_create refuses the program), out[3] = workgroups per
+ * CU of the persistent grid, out[4] = 1 when the program tables are staged in LDS, out[5] = LDS bytes per workgroup, out[6] = the
+ * pass count the shape was computed for (scan passes + the pseudo passes of field-against-field atoms and residual rules), out[7] =
+ * the bitmap registers of the kernel instantiation that pass count selects (1: up to 64 passes, else 4). Profiling-build switches
+ * are not consulted. The reference has no counterpart. */
+int pwaf_program_verdict_shape(const pwaf_program *, uint32_t out[8]);
 /* TEST HOOK (needs an engine; reads a host-side field): the compute units the engine sizes its persistent grids with (the list scan's
  * waves = this x workgroups per CU x threads / 64); 0 for NULL. */
 uint32_t pwaf_engine_compute_units(const pwaf_engine *);

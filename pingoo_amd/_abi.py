@@ -45,6 +45,8 @@ RECORDS_SCAN_SHAPE_FIELDS = ("tile", "step", "zero2", "zero3")
 # pwaf_program_list_scans (test hook): the meaning of a descriptor's PWAF_LIST_SCAN_WORDS words (share_owner 0xFFFFFFFF: none)
 LIST_SCAN_FIELDS = ("phase", "pass", "tier", "threads", "hot_bytes", "n_hot", "n_delta", "behind_filter", "merge_rec", "dense_mode", "share_owner", "need_bit",
                     "launch", "launch_count", "wg_per_cu", "zero15")
+# pwaf_program_verdict_shape (test hook): the meaning of out[0..7] (capacity: entries / value slots per wave; bit_regs: the BR of the instantiation)
+VERDICT_SHAPE_FIELDS = ("mode", "capacity", "waves", "per_cu", "lds_tables", "lds_bytes", "n_passes", "bit_regs")
 # pwaf_program_flat_image (test hook): the words of its "FSHP" section
 FLAT_SHAPE_FIELDS = ("n_states", "n_classes", "scalar_mode", "ill_class", "n_full", "n_delta", "lds_bytes")
 # pwaf_engine_coarse_tables (test hook): the meaning of out[0..15]

@@ -296,8 +296,8 @@ int pwaf_engine_create_routed(const pwaf_rule_desc *rules, size_t n_rules, const
     if ((rc = assign_lists(e.get()))) return dev_fail(rc);
     TablePlan plan;
     if ((rc = plan_tables(P, n_rules, n_routes, plan))) return dev_fail(rc);
-    if (verdict_shape(P.n_cols, (uint32_t)P.rules.size(), plan.n_trig, (uint32_t)P.lits.size(), (P.flags & PWAF_OPT_GLOBAL_VERDICT_TABLES) != 0,
-                      (int)verdict_mode(P.flags), (uint32_t)P.groups.size() + 2u).waves == 0 || P.n_cols >= 65536u) {
+    if (!verdict_launchable(verdict_shape(P.n_cols, (uint32_t)P.rules.size(), plan.n_trig, (uint32_t)P.lits.size(), (P.flags & PWAF_OPT_GLOBAL_VERDICT_TABLES) != 0,
+                                          (int)verdict_mode(P.flags), verdict_pass_count(P)), P.n_cols)) {
         fail(PWAF_E_UNSUPPORTED, "too many distinct predicates for one LDS column file (160 KiB)");
         return dev_fail(PWAF_E_UNSUPPORTED);
     }

@@ -6,6 +6,7 @@
 
 #include "program.h"
 #include "scanplan.h"
+#include "verdictplan.h"
 
 namespace pwaf {
 
@@ -491,14 +492,6 @@ struct GeoRecArgs {
 };
 int launch_georec(const GeoRecArgs &a, void *stream);
 uint32_t scan_lds_bytes(uint32_t n_hot, uint32_t stride, uint32_t n_gate_atoms);
-struct VerdictShape {
-    uint32_t waves, lds_bytes, lds_tables;
-    uint32_t sparse, v_cap, per_cu;  // sparse: 1 = the sparse column file, 2 = the entry list (verdict2_kernel); (kernels.hip: verdict_kernel<.., SP>): value slots per wave, workgroups per CU
-};
-// force_global (PWAF_OPT_GLOBAL_VERDICT_TABLES): take the variant whose program tables stay in global memory even when they would fit LDS
-// mode: 3 = entry list (default), 4 = entry list with 8 entry slots (PWAF_OPT_TINY_VERDICT_SLOTS: the spill path's test hook); 0 = the dense column file
-// (PWAF_OPT_DENSE_VERDICT), 1 = the sparse column file of round 5 (PWAF_OPT_SPARSE_VERDICT), 2 = that with 8 value slots (both flags)
-VerdictShape verdict_shape(uint32_t n_cols, uint32_t n_rules, uint32_t n_trig, uint32_t n_lits, bool force_global = false, int mode = 3, uint32_t n_passes = 0);
-uint32_t verdict_blocks_sp(const VerdictShape &sh, uint32_t n_cus);
+// VerdictShape, verdict_shape, verdict_blocks_sp: verdictplan.h (host code that g++ compiles too)
 
 }  // namespace pwaf

@@ -2087,44 +2087,8 @@ __global__ __launch_bounds__(256) void compact_kernel(FilterTable B) {
 }
 
 
-__host__ __device__ static inline uint32_t verdict_wave_lds(uint32_t n_cols, uint32_t n_rules) {
-    const uint32_t colw = (n_cols + 31) / 32, rulew = (n_rules + 31) / 32;
-    return ((n_cols * 8 + colw * 4 + rulew * 4 + n_rules * 2) + 15) & ~15u;  // columns, bitmaps, candidates (also: the list of non-zero columns)
-}
-
-// SPARSE column file (verdict_kernel<.., SP = true>): of a rule set's ~1000 - 4500 columns a group of 64 requests dirties a hundred or two,
-// yet the dense file costs 8 bytes per COLUMN and wave — 9 KiB of the 1k-rule set's 11.5 KiB per wave, which is what held the kernel at
-// one workgroup of 11 waves per CU (under 3 waves per SIMD; 57 % of its wave cycles waiting: VERDICT r4). The sparse file keeps, per 32
-// columns, the dirty bits and the number of dirty columns before the word (8 bytes), and one 64-bit value per DIRTY column, at the
-// column's rank among the dirty ones: ~4 KiB per wave whatever the rule set, i.e. two workgroups of 12 waves per CU. A group is marked
-// twice — bits first (the ranks need all of them), values second — and a value read is two dependent LDS reads instead of one. A group
-// with more dirty columns than the value array holds (v_cap) keeps the rest in a per-wave spill array in global memory (same results).
-__host__ __device__ static inline uint32_t verdict_wave_lds_sp(uint32_t n_cols, uint32_t n_rules, uint32_t v_cap) {
-    const uint32_t colw = (n_cols + 31) / 32, rulew = (n_rules + 31) / 32;
-    return ((colw * 8 + v_cap * 8 + rulew * 4 + n_rules * 2) + 15) & ~15u;  // {dirty bits, rank} per 32 columns, values, rule bitmap, candidates
-}
-__host__ __device__ static inline uint32_t verdict_v_cap(uint32_t n_cols, bool tiny) {
-    const uint32_t v = tiny ? 8u : 256u + n_cols / 16u;
-    return v < n_cols ? v : n_cols;
-}
-
-// LDS-resident copies of the small read-mostly program tables (LT = true): trigger lists, rule headers and DNF literals are
-// gathered several times per 64-request group, and each gather from L2 is a ~1 us round trip that the few waves a CU can hold
-// (the column files fill LDS) cannot hide.
-struct VerdictTables {
-    uint32_t bitcol, trig_off, trig_rules, rules, lits, pub, end;  // byte offsets from the start of the table region
-};
-__host__ __device__ static inline VerdictTables verdict_tables(uint32_t n_cols, uint32_t n_rules, uint32_t n_trig, uint32_t n_lits, bool lt) {
-    VerdictTables t;
-    t.bitcol = 0;
-    t.trig_off = 0;
-    t.trig_rules = t.trig_off + (lt ? ((n_cols + 1) * 2 + 3) & ~3u : 0u);
-    t.rules = t.trig_rules + (lt ? (n_trig * 2 + 7) & ~7u : 0u);
-    t.lits = t.rules + (lt ? n_rules * 8 : 0u);
-    t.pub = t.lits + (lt ? n_lits * 4 : 0u);
-    t.end = t.pub + (lt ? (n_rules * 2 + 3) & ~3u : 0u);
-    return t;
-}
+// (the column files' and program tables' LDS layout — verdict_wave_lds, verdict_wave_lds_sp, verdict_v_cap, verdict_wave_lds_el,
+// verdict_tables — and the launch shape computed from it: verdictplan.h)
 
 // BR = 64-pass bitmap registers (1: up to 64 passes, else kMaxPasses)
 template <bool LT, int BR, bool SP>
@@ -2629,11 +2593,7 @@ __global__ __launch_bounds__(SP ? 768 : 1024, (SP && BR == 1) ? 6 : 1) void verd
 // for the life of the wave. A column's word for the DNF step is two dependent LDS reads (slot, value), like the sparse file's.
 // Duplicates: a column belongs to one pass; inside a pass only an overflow chain (a request with more than two atoms) can name a column that
 // another lane's record already named — a pass with such a record appends one column at a time through a lookup of slot[] (rare).
-__host__ __device__ static inline uint32_t verdict_wave_lds_el(uint32_t n_cols, uint32_t n_rules, uint32_t e_cap) {
-    const uint32_t rulew = (n_rules + 31) / 32;
-    // vals | rule bitmap | entry columns (u16) | candidates (u16) | slot bytes
-    return (e_cap * 8 + rulew * 4 + ((e_cap * 2 + 3) & ~3u) + ((n_rules * 2 + 3) & ~3u) + ((n_cols + 7) & ~7u) + 15) & ~15u;
-}
+// (a wave's LDS: verdictplan.h, verdict_wave_lds_el)
 
 // one wave-uniform (column, mask) into lane l of three registers (see park64)
 #pragma clang diagnostic push
@@ -3984,87 +3944,10 @@ int launch_attr(const VerdictArgs &a, void *stream) {
     return (int)hipGetLastError();
 }
 
-// Workgroup shape of the verdict kernel: as many waves as LDS (160 KiB) holds column files for, next to one copy of the program
-// tables; if the tables do not leave room for at least 4 column files they stay in global memory (LT = false).
-static constexpr uint32_t kLdsPerGroup = 160u * 1024u;
-VerdictShape verdict_shape(uint32_t n_cols, uint32_t n_rules, uint32_t n_trig, uint32_t n_lits, bool force_global, int mode, uint32_t n_passes) {
-    VerdictShape s{};
-    const uint32_t t_lds = verdict_tables(n_cols, n_rules, n_trig, n_lits, true).end, t_glb = verdict_tables(n_cols, n_rules, n_trig, n_lits, false).end;
-    if (mode >= 3) {
-        // ENTRY LIST (mode 3; 4 = the test hook with 8 entry slots: every group takes the spill path): as many 12-wave workgroups per CU as
-        // LDS holds, and the largest entry capacity that does not cost a wave (a group of the 1k-rule set appends 50-100 entries)
-        s.sparse = 2;
-        const uint32_t cu_waves = n_passes <= 64 ? 24u : 16u;
-        auto fit = [&](uint32_t cap, uint32_t &bw, uint32_t &bk, uint32_t &lt) {
-            const uint32_t wave = verdict_wave_lds_el(n_cols, n_rules, cap);
-            const bool fits = !force_global && n_trig < 65536 && t_lds + 8 * wave <= kLdsPerGroup;
-            const uint32_t tables = fits ? t_lds : t_glb;
-            bw = 0; bk = 1; lt = fits ? 1u : 0u;
-            for (uint32_t k = 1; k <= 3; k++) {
-                const uint32_t share = kLdsPerGroup / k;
-                if (share <= tables + wave) continue;
-                const uint32_t w = std::min(std::min(12u, cu_waves / k), (share - tables) / wave);
-                if (w * k > bw * bk) { bw = w; bk = k; }
-            }
-        };
-        uint32_t cap = 8, bw = 0, bk = 1, lt = 0;
-        if (mode == 4) fit(cap, bw, bk, lt);
-        else {
-            uint32_t w0, k0, l0;
-            fit(64, w0, k0, l0);  // the occupancy the smallest capacity reaches ...
-            for (uint32_t c : {254u, 224u, 192u, 160u, 128u, 96u, 64u}) {  // ... kept by the largest capacity that still reaches it
-                fit(c, bw, bk, lt);
-                cap = c;
-                if (bw * bk >= w0 * k0) break;
-            }
-        }
-        s.v_cap = cap;
-        s.waves = bw;
-        s.per_cu = bk;
-        s.lds_tables = lt;
-        s.lds_bytes = (lt ? t_lds : t_glb) + bw * verdict_wave_lds_el(n_cols, n_rules, cap);
-        return s;
-    }
-    if (mode != 0) {
-        // SPARSE column file (mode 1; 2 = the test hook with 8 value slots): as many workgroups of 12 waves per CU as LDS holds (two for
-        // the 1k-rule set: 6 waves per SIMD), program tables in LDS when one such workgroup still fits beside them
-        s.sparse = 1;
-        s.v_cap = verdict_v_cap(n_cols, mode == 2);
-        const uint32_t wave = verdict_wave_lds_sp(n_cols, n_rules, s.v_cap);
-        const bool fits = !force_global && n_trig < 65536 && t_lds + 8 * wave <= kLdsPerGroup;
-        s.lds_tables = fits ? 1 : 0;
-        const uint32_t tables = fits ? t_lds : t_glb;
-        // (registers: the variant for up to 64 passes is compiled for 6 waves per SIMD = 24 per CU, the general one takes 124 -> 16 per CU)
-        const uint32_t cu_waves = n_passes <= 64 ? 24u : 16u;
-        uint32_t best_w = 0, best_k = 1;
-        for (uint32_t k = 1; k <= 3; k++) {  // k workgroups per CU
-            const uint32_t share = kLdsPerGroup / k;
-            if (share <= tables + wave) continue;
-            const uint32_t w = std::min(std::min(12u, cu_waves / k), (share - tables) / wave);
-            if (w * k > best_w * best_k) { best_w = w; best_k = k; }
-        }
-        s.waves = best_w;
-        s.per_cu = best_k;
-        s.lds_bytes = tables + s.waves * wave;
-        return s;
-    }
-    const uint32_t wave = verdict_wave_lds(n_cols, n_rules);
-    const bool fits = !force_global && n_trig < 65536 && t_lds + 4 * wave <= kLdsPerGroup;
-    s.lds_tables = fits ? 1 : 0;
-    const uint32_t tables = fits ? t_lds : t_glb;
-    uint32_t w = tables + wave <= kLdsPerGroup ? (kLdsPerGroup - tables) / wave : 0;
-    if (!fits) w = std::min(w, 4u);  // small workgroups: several share a CU
-    s.waves = std::min(w, 16u);
-    s.per_cu = 1;
-    s.lds_bytes = tables + s.waves * wave;
-    return s;
-}
-
-uint32_t verdict_blocks_sp(const VerdictShape &sh, uint32_t n_cus) { return std::max(1u, n_cus) * sh.per_cu; }  // the sparse kernel's persistent grid (sizes the spill array)
-
+// (the workgroup shape of the verdict kernels — verdict_shape, verdict_blocks_sp, kLdsPerGroup: verdictplan.h)
 int launch_verdict(const VerdictArgs &a, void *stream) {
     VerdictShape sh = verdict_shape(a.n_cols, a.n_rules, a.n_trig, a.n_lits, a.force_global_tables != 0, (int)a.sparse_mode, a.n_passes);
-    if (sh.waves == 0 || a.n_cols >= 65536u) return (int)hipErrorInvalidValue;  // (engine_create refuses such programs)
+    if (!verdict_launchable(sh, a.n_cols)) return (int)hipErrorInvalidValue;  // (engine_create refuses such programs)
     if (sh.sparse == 1 && (a.v_cap != sh.v_cap || (sh.v_cap < a.n_cols && a.spill == nullptr))) return (int)hipErrorInvalidValue;
     if (sh.sparse == 2 && (a.v_cap != sh.v_cap || a.spill == nullptr)) return (int)hipErrorInvalidValue;
 #ifdef PWAF_PROFILING
@@ -4072,7 +3955,7 @@ int launch_verdict(const VerdictArgs &a, void *stream) {
     if (cap_waves && cap_waves < sh.waves) sh.waves = cap_waves;
 #endif
     constexpr int kBRmax = (kMaxPasses + 1 + 63) / 64;
-    int variant = a.n_passes <= 64 ? 1 : 0;
+    int variant = verdict_variant(a.n_passes);
 #ifdef PWAF_PROFILING
     static const int forced_variant = getenv("PWAF_VERDICT_VARIANT") ? atoi(getenv("PWAF_VERDICT_VARIANT")) : -1;  // a MORE general variant may be forced (same results)
     if (forced_variant >= 0 && forced_variant < variant) variant = forced_variant;

@@ -81,7 +81,7 @@ struct BatchRun {
         n = db.n;
         n_groups = (n + 63) / 64;
         residual_pass = (uint32_t)e->groups.size() + (P.fcmp.empty() ? 0u : 1u);
-        n_passes = residual_pass + (P.n_residual ? 1u : 0u);  // (+ the pseudo passes of the field-against-field atoms and of the residual rules)
+        n_passes = verdict_pass_count(P);  // (+ the pseudo passes of the field-against-field atoms and of the residual rules)
         // visited bitmaps of the list-driven passes (one bit per request, whole 64-request groups): zeroed per batch — 1/32 of what
         // zeroing the hit records themselves would write. They share ONE zeroed block with the control words and the confirm tier's walk bitmaps.
         bit_words = 2 * n_groups;

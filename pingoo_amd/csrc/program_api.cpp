@@ -10,6 +10,7 @@
 
 #include "frontend.h"
 #include "program_handle.h"
+#include "tableplan.h"
 // kernels.h names HIP's vector types, through pointers only, in argument blocks this unit never touches; it is included for the sizes
 // confirm_kernel tests (confirm_tables_fit) and the residual translators' declarations.
 struct uint2;
@@ -305,6 +306,26 @@ int pwaf_program_list_scans(const pwaf_program *p, uint32_t *out, size_t cap, si
         }
     }
     *n_descs = at;
+    return PWAF_OK;
+}
+
+int pwaf_program_verdict_shape(const pwaf_program *p, uint32_t out[8]) {
+    if (!p || !p->p || !out) return fail(PWAF_E_INVALID_ARG, "pwaf_program_verdict_shape: bad argument");
+    const Program &P = *p->p;
+    // as pwaf_engine_create plans the tables and BatchRun::fill_verdict_args asks for the shape
+    TablePlan plan;
+    const size_t n_given = P.rule_status.size();  // (the caller's rules, then its routes)
+    if (int rc = plan_tables(P, n_given - std::min<size_t>(n_given, P.n_routes), P.n_routes, plan)) return rc;
+    const uint32_t mode = verdict_mode(P.flags), n_passes = verdict_pass_count(P);
+    const VerdictShape sh = verdict_shape(P.n_cols, (uint32_t)P.rules.size(), plan.n_trig, (uint32_t)P.lits.size(), (P.flags & PWAF_OPT_GLOBAL_VERDICT_TABLES) != 0, (int)mode, n_passes);
+    out[0] = mode;
+    out[1] = sh.v_cap;
+    out[2] = verdict_launchable(sh, P.n_cols) ? sh.waves : 0u;
+    out[3] = sh.per_cu;
+    out[4] = sh.lds_tables;
+    out[5] = sh.lds_bytes;
+    out[6] = n_passes;
+    out[7] = verdict_variant(n_passes) ? 1u : (uint32_t)((kMaxPasses + 1 + 63) / 64);
     return PWAF_OK;
 }
 

@@ -18,6 +18,10 @@ inline uint32_t verdict_mode(uint32_t flags) {
     return tiny ? 4u : 3u;
 }
 
+// the passes whose hit records the verdict kernel reads (VerdictArgs::n_passes): the scan passes, then the pseudo passes of the
+// field-against-field atoms and of the residual rules — what verdict_shape is computed for
+inline uint32_t verdict_pass_count(const Program &P) { return (uint32_t)P.groups.size() + (P.fcmp.empty() ? 0u : 1u) + (P.n_residual ? 1u : 0u); }
+
 // Code of a comparison atom, bits [31:24] of CmpAtomDev::col: 2 * variable + operator (0: ==, 1: <=), | kCmpComplement when the device
 // evaluates the atom complemented (!=, >). Variables: 0-4 field lengths, 5 remote_port, 6 asn, 7 + k the k-th compared header length;
 // a LAZY atom's variable is its slot in TablePlan::lazy_vars.

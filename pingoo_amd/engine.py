@@ -91,6 +91,7 @@ def lib():
     L.pwaf_program_flat_image.argtypes = [vp, C.c_uint32, C.c_uint32, vp, C.c_size_t]
     L.pwaf_program_flat_image.restype = C.c_size_t
     L.pwaf_program_list_scans.argtypes = [vp, C.POINTER(C.c_uint32), C.c_size_t, C.POINTER(C.c_size_t)]
+    L.pwaf_program_verdict_shape.argtypes = [vp, C.POINTER(C.c_uint32)]
     L.pwaf_engine_compute_units.argtypes = [vp]
     L.pwaf_engine_compute_units.restype = C.c_uint32
     L.pwaf_engine_rule_errors.argtypes = [vp, C.POINTER(C.c_uint64), C.c_size_t]
@@ -392,6 +393,16 @@ class CompiledProgram:
         for d in res:
             d["share_owner"] = -1 if d["share_owner"] == 0xFFFFFFFF else d["share_owner"]
         return res
+
+    def verdict_shape(self) -> dict:
+        """TEST HOOK (pwaf_program_verdict_shape): the verdict kernel's launch shape in every batch of an engine created from this program,
+        by the names of _abi.VERDICT_SHAPE_FIELDS — mode, capacity per wave, waves per workgroup (0: engine creation refuses the program),
+        workgroups per CU, tables in LDS, LDS bytes, the pass count it was computed for and the bitmap registers that count selects."""
+        out = (C.c_uint32 * len(_abi.VERDICT_SHAPE_FIELDS))()
+        rc = lib().pwaf_program_verdict_shape(self._h, out)
+        if rc != 0:
+            _raise(rc, lib().pwaf_last_error().decode(errors="replace"))
+        return dict(zip(_abi.VERDICT_SHAPE_FIELDS, (int(x) for x in out)))
 
     def residual_source(self, kind: int = 1) -> str:
         """Inspection hook: the specialized form of the residual rules (csrc/residual_jit.cpp). kind 0 = the rule functions alone,

@@ -90,6 +90,22 @@ def test_the_list_scan_hooks_name_their_words_and_refuse_bad_arguments():
         prog.flat_image(d["pass"], 2)
 
 
+def test_the_verdict_shape_hook_names_its_words_and_refuses_bad_arguments():
+    """pwaf_program_verdict_shape (test hook, no device): eight words by the names of _abi, a NULL program or output refused, a compiled
+    program answers the entry list at the capacity the slot bytes allow"""
+    L = engine.lib()
+    assert len(_abi.VERDICT_SHAPE_FIELDS) == 8
+    out = (C.c_uint32 * 8)()
+    assert L.pwaf_program_verdict_shape(None, out) == _abi.E_INVALID_ARG and b"pwaf_program_verdict_shape" in L.pwaf_last_error()
+    prog = engine.CompiledProgram([("m", 'http_request.path.contains("abc")', [_abi.RULE_ACTION_BLOCK])], {})
+    assert L.pwaf_program_verdict_shape(prog._h, None) == _abi.E_INVALID_ARG
+    sh = prog.verdict_shape()
+    assert (sh["mode"], sh["capacity"], sh["waves"], sh["per_cu"], sh["lds_tables"], sh["bit_regs"]) == (3, 254, 12, 2, 1, 1) and 0 < sh["lds_bytes"] <= 160 * 1024 // 2
+    assert sh["n_passes"] == prog.stats()["n_dfa_groups"]
+    tiny = engine.CompiledProgram([("m", 'http_request.path.contains("abc")', [_abi.RULE_ACTION_BLOCK])], {}, flags=_abi.OPT_TINY_VERDICT_SLOTS).verdict_shape()
+    assert (tiny["mode"], tiny["capacity"]) == (4, 8)
+
+
 def test_field_derivation_matches_golden_and_oracle(kat):
     d = kat["derive"]
     for raw, want in d["user_agent"]:
