@@ -19,6 +19,8 @@
  *                                                              pwaf_geoip_lookup / pwaf_evaluate_*_geo (PWAF_OPT_GEO_ANSWERS)
  *   get_host / get_path / UA derive  http_listener.rs:140-165,284-296; http_utils.rs:114-116
  *                                                              pwaf_derive_host / _path / _user_agent
+ *   generate_captcha_client_id       http_listener.rs:167; pingoo/captcha.rs:409-421
+ *                                                              pwaf_client_id_one / pwaf_client_ids
  *
  * Plain pointers and sizes only; no C++/torch types. Never aborts across the ABI:
  * every failure is an int status (<0) plus pwaf_last_error().
@@ -454,6 +456,43 @@ typedef struct pwaf_export_stats {
 } pwaf_export_stats;       /* 16 bytes */
 int pwaf_export_records(const pwaf_batch *in, const uint32_t *idx, uint32_t idx_cap, const uint32_t *n_idx /* nullable */, uint8_t *buf,
                         size_t buf_cap, uint32_t *rec_off /* idx_cap entries */, pwaf_export_stats *stats, void *stream);
+
+/* ---- captcha client ids (ABI 4, additive) ---------------------------------------------------------------
+ * generate_captcha_client_id (http_listener.rs:167, pingoo/captcha.rs:409-421): base64url_nopad(SHA-256(ip octets || user_agent || host)),
+ * the id that binds the verified-cookie JWT to a client (captcha.rs:125-156), is handed to the captcha endpoints (http_listener.rs:202)
+ * and is the `sub` of the challenge issued when a rule answers Captcha (captcha.rs:194-201, :437). The reference computes it for every
+ * request; a host that evaluates device-resident batches needs it for the requests of the match list whose verdict is CAPTCHA (or BYPASS
+ * on the captcha endpoints), and gets it here without copying their User-Agent and host bytes back. Cookie parsing, JWT verification and
+ * the proof of work stay on the host. pwaf_client_ids takes no engine (like pwaf_export_records): everything it needs is in the batch.
+ * Message of request i: ip[i] (its first 4 bytes when ip_is_v6[i] == 0, else all 16; bytes 4..15 of an IPv4 row are ignored), then the
+ * bytes of field[PWAF_FIELD_USER_AGENT], then those of field[PWAF_FIELD_HOST] of request i — as the batch carries them, at any length
+ * (derivation, pwaf_derive_*, is the caller's job, as it is for evaluation). The digest's 32 bytes are encoded with the URL-safe
+ * alphabet without padding (captcha.rs:420): 43 characters, then text[43] = 0.
+ * Which requests: idx == NULL (idx_cap must be 0 and n_idx NULL): every request, out[i] belongs to request i (in->n entries). Otherwise
+ * m = min(*n_idx, idx_cap), or idx_cap when n_idx == NULL, and out[j] belongs to request idx[j] for j < m; entries j >= m are not
+ * written; idx[j] >= in->n writes 44 zero bytes (the empty string); duplicates each get their entry. Nothing is written at or beyond
+ * out + m (out + n).
+ * Memory and streams: in->memory says where EVERY pointer lives, the batch's and idx, n_idx and out alike.
+ *   PWAF_MEM_DEVICE  one launch (client_id_kernel) is enqueued on `stream` (hipStream_t; NULL = HIP's default stream) of the current
+ *                    device and the call returns at once. The kernel reads *n_idx itself, so a call placed right behind
+ *                    pwaf_evaluate_device(..., match_idx, n_matches, stream) on the same stream needs no synchronisation in between.
+ *                    Nothing is allocated, nothing is copied. Loads may run past a value by fewer than 16 bytes: inside the arena or its
+ *                    PWAF_ARENA_PAD, the contract pwaf_export_records relies on. The batch is trusted as pwaf_evaluate_device trusts it,
+ *                    except that the kernel itself guards idx[j] >= n.
+ *   PWAF_MEM_HOST    synchronous, plain C++, no HIP call: works on a machine without a GPU, and reads no byte outside a value (no pad is
+ *                    assumed). A selected request whose offsets decrease in either column refuses the whole call with PWAF_E_BATCH
+ *                    (naming the entry) before anything is written.
+ * PWAF_E_INVALID_ARG, before anything runs: NULL in or out; a bad struct_size or memory; idx == NULL with idx_cap != 0 or n_idx != NULL;
+ * out not 4-byte aligned; in a batch with n > 0 a NULL ip, ip_is_v6, or User-Agent / host column. The other columns of the batch are
+ * not looked at and may be NULL.
+ * pwaf_client_id_one: the same id from req->ip, ip_is_v6, user_agent and host, on the host (no GPU): what a per-request closure calls
+ * where the reference calls generate_captcha_client_id. */
+typedef struct pwaf_client_id {
+    char text[44]; /* 43 characters of the URL-safe alphabet (A-Z a-z 0-9 - _), then NUL */
+} pwaf_client_id;
+int pwaf_client_ids(const pwaf_batch *in, const uint32_t *idx /* nullable */, uint32_t idx_cap, const uint32_t *n_idx /* nullable */,
+                    pwaf_client_id *out, void *stream);
+int pwaf_client_id_one(const pwaf_request *req, pwaf_client_id *out);
 
 /* ---- records in device memory (ABI 4, additive) ----------------------------------------------------------
  * pwaf_evaluate_records for records that already lie in DEVICE memory — what pwaf_export_records wrote, or a replay file copied to the

@@ -183,6 +183,12 @@ class ExportStats(C.Structure):
     _fields_ = [("bytes_needed", C.c_uint64), ("n_selected", C.c_uint32), ("n_written", C.c_uint32)]
 
 
+class ClientId(C.Structure):
+    """pwaf_client_id: a captcha client id (pwaf_client_ids / pwaf_client_id_one) — 43 characters of the URL-safe alphabet, then NUL."""
+
+    _fields_ = [("text", C.c_char * 44)]
+
+
 class Geo(C.Structure):
     """pwaf_geo: one GeoIP answer (PWAF_OPT_GEO_ANSWERS) — the record the rules saw as client.asn / client.country."""
 

@@ -152,6 +152,8 @@ def lib():
     L.pwaf_export_records.argtypes = [C.POINTER(_abi.Batch), vp, C.c_uint32, vp, vp, C.c_size_t, vp, vp, vp]
     L.pwaf_evaluate_records_device.argtypes = [vp, vp, C.c_size_t, vp, C.c_uint32, vp, vp, vp, vp, vp, vp]
     L.pwaf_records_scan_shape.argtypes = [C.POINTER(C.c_uint32)]
+    L.pwaf_client_ids.argtypes = [C.POINTER(_abi.Batch), vp, C.c_uint32, vp, vp, vp]
+    L.pwaf_client_id_one.argtypes = [C.POINTER(_abi.Request), vp]
     L.pwaf_async_create.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(vp)]
     L.pwaf_async_submit.argtypes = [vp, C.POINTER(_abi.Request), C.c_uint64]
     L.pwaf_async_poll.argtypes = [vp, C.POINTER(_abi.Completion), C.c_size_t]
@@ -283,6 +285,25 @@ def get_host(uri_host: Optional[bytes], host_header: Optional[bytes]) -> bytes:
     lib().pwaf_derive_host(a, len(a), int(uri_host is not None), b, len(b), int(host_header is not None), C.byref(fh), C.byref(s), C.byref(l))
     src = b if fh.value else a
     return src[s.value:s.value + l.value]
+
+
+def generate_captcha_client_id(ip, user_agent, host) -> str:
+    """captcha::generate_captcha_client_id (pingoo/captcha.rs:409-421; called at http_listener.rs:167) through pwaf_client_id_one:
+    base64url_nopad(SHA-256(ip octets || user_agent || host)), 43 characters. ip: a str or an ipaddress object; user_agent and host:
+    str or bytes, as get_user_agent / get_host derive them. Runs on the host."""
+    from .batch import ip_to_bytes16
+
+    ua, h = (x.encode() if isinstance(x, str) else bytes(x) for x in (user_agent, host))
+    st = _abi.Request()
+    st.user_agent, st.user_agent_len, st.host, st.host_len = ua, len(ua), h, len(h)
+    raw, v6 = ip_to_bytes16(str(ip))
+    C.memmove(st.ip, raw, 16)
+    st.ip_is_v6 = int(v6)
+    out = _abi.ClientId()
+    rc = lib().pwaf_client_id_one(C.byref(st), C.addressof(out))
+    if rc != 0:
+        _raise(rc, lib().pwaf_last_error().decode(errors="replace"))
+    return out.text.decode("ascii")
 
 
 def _options(flags=0, device=-1, lds_table_budget=0, max_dfa_states=0, max_table_bytes=0) -> _abi.Options:
@@ -685,6 +706,10 @@ class RuleEngine:
         if rc != 0:
             _raise(rc, lib().pwaf_last_error().decode(errors="replace"))
         return out
+
+    def client_ids(self, batch, idx=None, n_idx=None, stream=None):
+        """client_ids (below): the captcha client ids of the requests of `batch` that `idx` names; needs nothing of the engine."""
+        return client_ids(batch, idx=idx, n_idx=n_idx, stream=stream)
 
     def evaluate(self, request: Request, with_geo: bool = False):
         """RuleEngine::evaluate(Request) -> Action (pwaf_evaluate_one): a batch of one through the same device path. with_geo
@@ -1227,6 +1252,52 @@ def export_records(batch, idx, n_idx=None, cap=None, stream=None, header_names: 
     if rc != 0:
         _raise(rc, lib().pwaf_last_error().decode(errors="replace"))
     return buf[:int(cap)], rec_off[:n_list], stats
+
+
+def client_ids(batch, idx=None, n_idx=None, stream=None):
+    """The captcha client ids (generate_captcha_client_id, above) of requests of `batch` (pwaf_client_ids; include/pwaf.h): of every request
+    when idx is None (entry i belongs to request i), else of the requests the list `idx` names (entry j belongs to request idx[j]; n_idx:
+    how many entries of idx count, default all; an entry that names no request of the batch reads as ""). Takes no engine.
+    RequestBatch: idx / n_idx are numpy arrays / ints, the call is synchronous and runs on the CPU -> a list of str.
+    DeviceBatch: idx and n_idx (a one-element 32-bit tensor, or None) are device tensors — e.g. evaluate_device's match_idx / n_matches, in
+    which case the call follows the evaluation on `stream` (default: torch's current stream) without a synchronisation in between. One
+    launch is enqueued and the call returns: -> a (m, 44) uint8 tensor (43 characters and a NUL per entry; m = the entries of idx, or the
+    batch's requests) to be read after the stream is synchronised; rows at or past n_idx are not written."""
+    st = batch.as_struct()
+    if isinstance(batch, RequestBatch):
+        if idx is None:
+            assert n_idx is None
+            m = batch.n
+        else:
+            idx = np.ascontiguousarray(idx, dtype=np.uint32).reshape(-1)
+            m = len(idx) if n_idx is None else min(len(idx), int(np.asarray(n_idx).reshape(-1)[0]))
+            if not len(idx):
+                return []  # (a NULL idx would mean every request)
+        n_ref = None if n_idx is None else np.array([int(np.asarray(n_idx).reshape(-1)[0])], dtype=np.uint32)
+        out = np.zeros((max(1, m), 44), dtype=np.uint8)
+        rc = lib().pwaf_client_ids(C.byref(st), None if idx is None else idx.ctypes.data, 0 if idx is None else len(idx),
+                                   None if n_ref is None else n_ref.ctypes.data, out.ctypes.data, None)
+        if rc != 0:
+            _raise(rc, lib().pwaf_last_error().decode(errors="replace"))
+        return [row.tobytes().split(b"\0", 1)[0].decode("ascii") for row in out[:m]]
+    import torch
+
+    if idx is None:
+        assert n_idx is None
+        m = batch.n
+    else:
+        assert idx.is_contiguous() and idx.element_size() == 4 and (n_idx is None or n_idx.element_size() == 4)
+        m = idx.numel()
+    if stream is None:
+        stream = torch.cuda.current_stream(batch.device).cuda_stream
+    out = torch.empty((max(1, m), 44), dtype=torch.uint8, device=batch.device)
+    if idx is not None and not m:
+        return out[:0]  # (a NULL idx would mean every request)
+    rc = lib().pwaf_client_ids(C.byref(st), None if idx is None else idx.data_ptr(), 0 if idx is None else m,
+                               None if n_idx is None else n_idx.data_ptr(), out.data_ptr(), C.c_void_p(stream))
+    if rc != 0:
+        _raise(rc, lib().pwaf_last_error().decode(errors="replace"))
+    return out[:m]
 
 
 def records_scan_shape() -> dict:
