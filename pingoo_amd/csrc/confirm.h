@@ -1,6 +1,6 @@
 // confirm.h — the confirm tier of a filtered pass (program.h: ConfirmTable): what a flagged chunk really holds.
 //
-// ONE implementation for the device kernel (kernels.hip: confirm_kernel), for the host model pwaf_engine_tune uses to rank the DFA
+// ONE implementation for the device kernel (confirm.hip: confirm_kernel), for the host model pwaf_engine_tune uses to rank the DFA
 // rows that confirmed candidates visit, and for the CPU test hook that fuzzes the compiled tables against the oracle
 // (pwaf_program_confirm_field): the code the GPU runs is the code the CPU suite checks. The reference evaluates every string
 // predicate on every request (pingoo/rules.rs:37-51); here a literal predicate is evaluated exactly where the bigram filter pointed.
@@ -10,10 +10,14 @@
 
 #include "program.h"
 
+// PWAF_HD_INLINE: a helper for host and device that is always inlined (residual.h, which hiprtc compiles without any other header, has the
+// same definition). A plain host/device function is PWAF_HOST_DEVICE (program.h).
+#ifndef PWAF_HD_INLINE
 #if defined(__HIPCC__)
-#define PWAF_HD __host__ __device__ __forceinline__
+#define PWAF_HD_INLINE __host__ __device__ __forceinline__
 #else
-#define PWAF_HD inline
+#define PWAF_HD_INLINE inline
+#endif
 #endif
 
 namespace pwaf {
@@ -27,7 +31,7 @@ struct ConfirmView {  // plain pointers: host tables or device tables
     uint32_t init;  // the filter's state of a stream with no history (GroupFilter::init)
 };
 
-PWAF_HD uint32_t confirm_load32(const uint8_t *p) {  // request TEXT: an arena in global memory
+PWAF_HD_INLINE uint32_t confirm_load32(const uint8_t *p) {  // request TEXT: an arena in global memory
 #if defined(__HIP_DEVICE_COMPILE__)
     // (a GLOBAL load, at any byte address — gfx950 needs no alignment — instead of the FLAT load a generic pointer gets)
     return *reinterpret_cast<const __attribute__((address_space(1))) uint32_t __attribute__((aligned(1))) *>((uintptr_t)p);
@@ -40,7 +44,7 @@ PWAF_HD uint32_t confirm_load32(const uint8_t *p) {  // request TEXT: an arena i
 // 16 / 8 bytes of request text at once: a scattered load instruction costs the texture addresser a cycle per lane whatever its width
 // (DESIGN.md 6.1 found the streaming kernel bound by exactly that), so the chunk's 28 bytes are three instructions, not seven.
 struct ConfirmText4 { uint32_t x, y, z, w; };
-PWAF_HD ConfirmText4 confirm_load128(const uint8_t *p) {
+PWAF_HD_INLINE ConfirmText4 confirm_load128(const uint8_t *p) {
 #if defined(__HIP_DEVICE_COMPILE__)
     typedef unsigned int u4 __attribute__((ext_vector_type(4)));
     typedef u4 u4_u __attribute__((aligned(1)));
@@ -52,7 +56,7 @@ PWAF_HD ConfirmText4 confirm_load128(const uint8_t *p) {
     return v;
 #endif
 }
-PWAF_HD void confirm_load64(const uint8_t *p, uint32_t &lo, uint32_t &hi) {
+PWAF_HD_INLINE void confirm_load64(const uint8_t *p, uint32_t &lo, uint32_t &hi) {
 #if defined(__HIP_DEVICE_COMPILE__)
     typedef unsigned int u2 __attribute__((ext_vector_type(2)));
     typedef u2 u2_u __attribute__((aligned(1)));
@@ -69,7 +73,7 @@ PWAF_HD void confirm_load64(const uint8_t *p, uint32_t &lo, uint32_t &hi) {
 // generic pointer's low half is the LDS address: a ds_read instead of the FLAT load a generic pointer gets — a FLAT load that hits LDS
 // still takes the texture path's latency); the host ignores it.
 template <int SPACE>
-PWAF_HD uint32_t confirm_table32(const uint8_t *p) {
+PWAF_HD_INLINE uint32_t confirm_table32(const uint8_t *p) {
 #if defined(__HIP_DEVICE_COMPILE__)
     if (SPACE == 3) return *reinterpret_cast<const __attribute__((address_space(3))) uint32_t *>((uint32_t)(uintptr_t)p);
     return *reinterpret_cast<const __attribute__((address_space(1))) uint32_t *>((uintptr_t)p);
@@ -152,7 +156,7 @@ struct ConfirmChunk {
 struct ConfirmBytes {
     uint32_t w[7];
 };
-PWAF_HD ConfirmBytes confirm_chunk_bytes(const uint8_t *data, const uint32_t c, const uint32_t readable /* arena bytes + PWAF_ARENA_PAD */) {
+PWAF_HD_INLINE ConfirmBytes confirm_chunk_bytes(const uint8_t *data, const uint32_t c, const uint32_t readable /* arena bytes + PWAF_ARENA_PAD */) {
     const uint32_t base = c * 16u;
     ConfirmBytes t;
     if (base >= 8u && base + 24u <= readable) {  // (chunks are 16-aligned: every chunk but the arena's first has 8 bytes in front of it) two 16-byte loads: [base - 8, base + 24)
@@ -169,7 +173,7 @@ PWAF_HD ConfirmBytes confirm_chunk_bytes(const uint8_t *data, const uint32_t c, 
     return t;
 }
 template <class TabAt>
-PWAF_HD ConfirmChunk confirm_windows_of(const ConfirmView &cv, const ConfirmBytes &tb, const uint32_t fs, const uint32_t fe, const uint32_t c, TabAt &&tab_at) {
+PWAF_HD_INLINE ConfirmChunk confirm_windows_of(const ConfirmView &cv, const ConfirmBytes &tb, const uint32_t fs, const uint32_t fe, const uint32_t c, TabAt &&tab_at) {
     const uint32_t base = c * 16u;
     const bool pre = base >= 8u;
     // seven words, every position at a fixed place in them (the 24 steps are unrolled: no register is indexed by the position and
@@ -200,11 +204,11 @@ PWAF_HD ConfirmChunk confirm_windows_of(const ConfirmView &cv, const ConfirmByte
     return r;
 }
 template <class TabAt>
-PWAF_HD ConfirmChunk confirm_windows(const ConfirmView &cv, const uint8_t *data, const uint32_t fs, const uint32_t fe, const uint32_t c, TabAt &&tab_at) {
+PWAF_HD_INLINE ConfirmChunk confirm_windows(const ConfirmView &cv, const uint8_t *data, const uint32_t fs, const uint32_t fe, const uint32_t c, TabAt &&tab_at) {
     return confirm_windows_of(cv, confirm_chunk_bytes(data, c, c * 16u + 20u), fs, fe, c, tab_at);  // (the host's arenas: only what the narrow form reads)
 }
 // filter bin of the bigram of the chunk's idx-th completed window (ascending positions), which sits at arena position pos
-PWAF_HD uint32_t confirm_bin_of(const ConfirmChunk &ch, const uint32_t idx, const uint8_t *data, const uint32_t pos, const uint32_t mul) {
+PWAF_HD_INLINE uint32_t confirm_bin_of(const ConfirmChunk &ch, const uint32_t idx, const uint8_t *data, const uint32_t pos, const uint32_t mul) {
     if (idx < 4u) return (uint32_t)(ch.bins >> (16u * idx)) & 0xFFFu;
     const uint32_t two = confirm_load32(data + pos);  // (more than four windows completed in one chunk: rare)
     return filter_bin((uint8_t)(two & 0xFFu), (uint8_t)((two >> 8) & 0xFFu), mul);
@@ -214,9 +218,9 @@ PWAF_HD uint32_t confirm_bin_of(const ConfirmChunk &ch, const uint32_t idx, cons
 // of the chunk; returns true when a factor of a non-literal atom was confirmed (the request must be walked). head_at(bin) reads the
 // confirm table's head word. (The host's form — tune, the CPU test hook. The device kernel runs the same three steps — windows, head
 // word, entry comparison — as a per-lane state machine, so that the 64 requests of a wave each take THEIR next comparison per
-// iteration instead of the wave taking the product of the nested loops' longest trips: kernels.hip, confirm_kernel.)
+// iteration instead of the wave taking the product of the nested loops' longest trips: confirm.hip, confirm_kernel.)
 template <class TabAt, class HeadAt, class Hit>
-PWAF_HD bool confirm_chunk(const ConfirmView &cv, const uint8_t *data, const uint32_t fs, const uint32_t fe, const uint32_t c, TabAt &&tab_at, HeadAt &&head_at, Hit &&hit) {
+PWAF_HD_INLINE bool confirm_chunk(const ConfirmView &cv, const uint8_t *data, const uint32_t fs, const uint32_t fe, const uint32_t c, TabAt &&tab_at, HeadAt &&head_at, Hit &&hit) {
     const ConfirmChunk ch = confirm_windows(cv, data, fs, fe, c, tab_at);
     uint32_t mask = ch.mask, idx = 0;
     bool walk = false;

@@ -1,4 +1,4 @@
-// kernels.h — argument blocks and launch entry points of the gfx950 kernels (kernels.hip).
+// kernels.h — argument blocks and launch entry points of the gfx950 kernels (kernels.hip; the confirm tier: confirm.hip; the verdict stage: verdict.hip; the attribute stage: attr.hip).
 #pragma once
 #include <cstdint>
 #include <string>
@@ -263,6 +263,8 @@ int launch_compact(const FilterArgs *host, uint32_t count, const FilterArgs *dev
 // Sets the dynamic-LDS limit of every kernel on the CURRENT device (once per device and process; engines on several
 // devices of one process each need it).
 int configure_kernels(int device);
+// ... for kernels.hip's own kernels and, through configure_verdict_kernels, for verdict.hip's (the current device; no bookkeeping).
+int configure_verdict_kernels();
 
 // (PassInfo, the verdict kernel's pass table: program.h)
 // Field-against-field atoms (program.h: ATOM_FCMP): one lane per request compares the two strings (or their lengths); the results

@@ -1,4 +1,6 @@
-// kernels.hip — hand-written gfx950 (CDNA4, wave64) kernels of the WAF batch matcher.
+// kernels.hip — hand-written gfx950 (CDNA4, wave64) kernels of the WAF batch matcher: the overview of the pipeline, the filter stage and
+// the DFA scans, fcmp_kernel and residual_kernel. The confirm tier is confirm.hip, the verdict stage verdict.hip, the attribute stage
+// attr.hip; wave.h holds the wave-level helpers all of them share, hitrec.h the hit record that the scans and the confirm tier write.
 //
 // Data model: every predicate ("atom") of the compiled rule set is a COLUMN. The verdict kernel
 // handles requests in GROUPS of 64 (one wavefront); for a group a column is one 64-bit word whose bit r says
@@ -17,10 +19,10 @@
 //   scan_kernel<CH>  a pass without a usable prefilter: the round-1 design, a DFA over EVERY request (one persistent workgroup per CU,
 //                    lanes pull the next request of their wave's slab when done, hot rows in LDS, cold rows from the L2-resident table).
 //   fcmp_kernel      predicates between two request fields (one lane per request compares the byte ranges).
-//   attr_kernel      on the engine's low-priority side stream, forked after the filter launches: everything that is not a string scan — GeoIP record and
+//   attr_kernel      (attr.hip, with ipres_kernel / georec_kernel / dir24_kernel) on the engine's low-priority side stream, forked after the filter launches: everything that is not a string scan — GeoIP record and
 //                    ip-list membership (DIR-24-8 table + radix tries), country / integer-set membership, length / port / asn
 //                    comparisons — reduced per 64-request group to (column, 64-request mask) pairs with wave ballots.
-//   verdict_kernel   per group: turns hit records and pairs into LDS column words, finds the candidate rules through trigger lists,
+//   verdict_kernel   (verdict.hip; verdict2_kernel is its entry-list form, the default) per group: turns hit records and pairs into LDS column words, finds the candidate rules through trigger lists,
 //                    evaluates each candidate's DNF with one lane per rule, resolves first-match-wins, writes verdicts, action
 //                    counters and the compacted index list of non-Allow requests.
 //
@@ -32,27 +34,16 @@
 #include <mutex>
 #include <set>
 
-#include "confirm.h"
+#include "hitrec.h"
 #include "utf8.h"
 #include "kernels.h"
 #include "residual.h"
+#include "wave.h"
 
 namespace pwaf {
 
 static constexpr int kScanThreads = 1024;
 static constexpr int kScanWaves = kScanThreads / 64;
-static constexpr uint32_t kNone = 0xFFFFFFFFu;
-
-// Explicit address spaces: a generic pointer that may be LDS or global makes the compiler emit FLAT loads for the table
-// lookups (one flat_load per input byte through the texture path instead of ds_read_u16 — measured 5x slower).
-#define PWAF_LDS __attribute__((address_space(3)))
-#define PWAF_GLOBAL __attribute__((address_space(1)))
-typedef const PWAF_LDS uint16_t *lds_u16_ptr;
-typedef const PWAF_GLOBAL uint16_t *glb_u16_ptr;
-typedef const PWAF_LDS uint32_t *lds_u32_ptr;
-typedef const PWAF_LDS uint8_t *lds_u8_ptr;
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-typedef u32x4 u32x4_u __attribute__((aligned(1)));  // 16 bytes at any byte address (gfx950 global loads need no alignment)
 
 static constexpr uint32_t kClsBytes = 1024;  // byte-class map at LDS offset 0: 256 x uint32
 // The walk is speculative (see scan_body): a lane that has just read a special cell keeps using it as an address until the
@@ -64,65 +55,9 @@ uint32_t scan_lds_bytes(uint32_t n_hot, uint32_t stride, uint32_t n_gate_atoms) 
     return need > reach ? need : reach;
 }
 
-
 // -------------------------------------------------------------------------------------------------
 // scan
 // -------------------------------------------------------------------------------------------------
-struct Hits {
-    uint32_t a0, a1;  // local atom + 1, 0 = empty
-    uint32_t ovf;     // head of the overflow chain, kNone = not overflowed
-};
-
-// The slow path is ONE out-of-line function that takes and returns the per-request hit state BY VALUE: passing `Hits` or the
-// kernel arguments by reference would pin them in scratch memory, and every scratch access in the main loop is a vector
-// memory operation whose s_waitcnt vmcnt(0) also drains the prefetched chunk (measured: 5 us per iteration).
-struct SlowCtx {
-    const uint32_t *list_off;
-    const uint16_t *list;
-    PoolEntry *pool;
-    uint32_t *pool_count;
-    uint32_t *status;
-    uint32_t pool_cap;
-};
-
-__device__ __forceinline__ Hits pool_push(const SlowCtx &c, uint32_t atom, Hits h) {
-    const uint32_t idx = atomicAdd(c.pool_count, 1u);
-    if (idx >= c.pool_cap) {
-        atomicOr(c.status, 1u);
-        return h;
-    }
-    c.pool[idx].atom = atom;
-    c.pool[idx].next = h.ovf;
-    h.ovf = idx;
-    return h;
-}
-
-__device__ __forceinline__ Hits record_atom(const SlowCtx &c, uint32_t atom, Hits h) {
-    if (h.ovf == kNone) {
-        if (h.a0 == atom + 1 || h.a1 == atom + 1) return h;
-        if (h.a0 == 0) { h.a0 = atom + 1; return h; }
-        if (h.a1 == 0) { h.a1 = atom + 1; return h; }
-        const uint32_t x0 = h.a0 - 1, x1 = h.a1 - 1;
-        h = pool_push(c, x0, h);
-        h = pool_push(c, x1, h);
-        return pool_push(c, atom, h);
-    }
-    // overflowed: the chain holds every atom of this request; de-duplicate against it (this lane is its only writer)
-    for (uint32_t i = h.ovf; i != kNone;) {
-        const uint32_t at = __hip_atomic_load(&c.pool[i].atom, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (at == atom) return h;
-        i = __hip_atomic_load(&c.pool[i].next, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-    return pool_push(c, atom, h);
-}
-
-__device__ __noinline__ Hits emit_list(const uint32_t *list_off, const uint16_t *list, PoolEntry *pool, uint32_t *pool_count, uint32_t *status,
-                                       uint32_t pool_cap, uint32_t id, Hits h) {
-    const SlowCtx c{list_off, list, pool, pool_count, status, pool_cap};
-    const uint32_t b = list_off[id], e = list_off[id + 1];
-    for (uint32_t k = b; k < e; k++) h = record_atom(c, list[k], h);
-    return h;
-}
 // One careful DFA step of one lane (out of line, by value): used when the speculative group walk met an emitting row, a cold
 // row or a parked lane. `t` is the cell the lane read from LDS for this step.
 struct Walk {
@@ -162,59 +97,6 @@ __device__ __noinline__ Walk careful_step(const PWAF_GLOBAL unsigned char *gtab,
     }
     return w;
 }
-// The hit state a walk starts from when the request's record already holds hits (ListScanArgs::merge_rec).
-__device__ __forceinline__ Hits hits_of_record(const uint32_t rv) {
-    if (rv & REC_OVERFLOW) return Hits{0, 0, rv & ~REC_OVERFLOW};
-    return Hits{rv & 0x7FFFu, (rv >> 15) & 0x7FFFu, kNone};
-}
-// The gap passes a finished request's hits call for: OR of the per-atom masks.
-__device__ __noinline__ uint32_t gate_mask(const uint32_t *colmask_local, const PoolEntry *pool, Hits h) {
-    uint32_t need = 0;
-    if (h.ovf != kNone) {
-        for (uint32_t i = h.ovf; i != kNone;) {
-            need |= colmask_local[__hip_atomic_load(&pool[i].atom, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)];
-            i = __hip_atomic_load(&pool[i].next, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-    } else {
-        if (h.a0) need |= colmask_local[h.a0 - 1];
-        if (h.a1) need |= colmask_local[h.a1 - 1];
-    }
-    return need;
-}
-// A finished request whose hits include prefilter factors is appended to the lists of the gated passes those factors guard
-// (rare: one atomic per request and gated pass).
-__device__ __noinline__ void enqueue_mask(uint32_t *gate_lists, uint32_t *gate_count, uint32_t n, uint32_t r, uint32_t need) {
-    while (need) {
-        const uint32_t g = (uint32_t)__builtin_ctz(need);
-        need &= need - 1;
-        gate_lists[(size_t)g * n + atomicAdd(&gate_count[g], 1u)] = r;
-    }
-}
-// ... once per request and gap pass when the pass's enqueue bitmap is given (a list holds n entries; several chunks of one request — or
-// its confirm tier and its walk — may all find a factor).
-__device__ __noinline__ void enqueue_mask_once(uint32_t *gate_lists, uint32_t *gate_count, uint32_t n, uint32_t r, uint32_t need, uint32_t *enq_bits, uint32_t enq_words) {
-    while (need) {
-        const uint32_t g = (uint32_t)__builtin_ctz(need);
-        need &= need - 1;
-        if (enq_bits != nullptr) {
-            const uint32_t bit = 1u << (r & 31u);
-            if (atomicOr(&enq_bits[(size_t)g * enq_words + (r >> 5)], bit) & bit) continue;
-        }
-        gate_lists[(size_t)g * n + atomicAdd(&gate_count[g], 1u)] = r;
-    }
-}
-__device__ __forceinline__ void enqueue_gated(const uint32_t *colmask_local, const PoolEntry *pool, uint32_t *gate_lists, uint32_t *gate_count, uint32_t n,
-                                              uint32_t r, Hits h) {
-    enqueue_mask(gate_lists, gate_count, n, r, gate_mask(colmask_local, pool, h));
-}
-
-// A pass descriptor read from the device-resident table into SCALAR registers (the address is wave-uniform; through a plain
-// reference every use inside the hot loops became a reload from memory — the compiler must assume the kernel's own stores alias it —
-// and the filter launch went from 0.74 to 0.85 ms).
-// The wave's index in its workgroup, as a value the compiler KNOWS to be wave-uniform (threadIdx.x >> 6 is, but is not provably so:
-// everything derived from it — slab and group numbers, loop bounds, base addresses — would be computed per lane in vector registers
-// and every branch on it would be an exec-mask branch).
-__device__ __forceinline__ uint32_t wave_index() { return (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)); }
 
 // Scalar mode of a table (dfa.cpp, utf8.h): does a 16-byte window hold a LEAD byte (>= 0xC0: bits 7 and 6 set)? Asked once per window
 // and wave (ASCII traffic: never), so that the class fix-up below costs the common case ten vector instructions per 16 bytes.
@@ -240,21 +122,6 @@ __device__ __noinline__ uint32_t cont_class(const uint32_t own_class, const uint
     const uint32_t self_next = *reinterpret_cast<const PWAF_GLOBAL uint32_t __attribute__((aligned(1))) *>(gdata + at);  // (PWAF_ARENA_PAD covers the read behind the arena's end)
     return utf8_cont_covered(prev, self_next, back, end - at) ? own_class : ill_class;
 }
-
-template <class T>
-__device__ __forceinline__ T load_descriptor(const T *p) {
-    static_assert(sizeof(T) % 4 == 0, "descriptor size");
-    typedef uint32_t __attribute__((may_alias)) word_t;  // (the descriptor's members are read and written as plain words)
-    uint32_t w[sizeof(T) / 4];
-    const word_t *s = reinterpret_cast<const word_t *>(p);
-#pragma unroll
-    for (size_t i = 0; i < sizeof(T) / 4; i++) w[i] = (uint32_t)__builtin_amdgcn_readfirstlane((int)s[i]);
-    T out;
-    __builtin_memcpy(&out, w, sizeof(T));
-    return out;
-}
-
-#define PWAF_EMIT(id) h = emit_list(a.list_off, a.list, a.pool, a.pool_count, a.status, a.pool_cap, (id), h)
 
 // CH = 16-byte chunks a lane walks per loop iteration. 2 halves the per-byte cost of the pull / finish logic (a third of the
 // vector instructions at CH = 1) but idles a finished lane for up to 31 bytes instead of 15: it pays for long fields (URL,
@@ -954,243 +821,6 @@ __global__ __launch_bounds__(THREADS, THREADS == 512 ? 6 : 4) void lscan_kernel(
     }
 }
 
-// ---------------------------------------------------------------------------------------------------------------------------------
-// confirm tier (confirm.h; program.h: ConfirmTable)
-// ---------------------------------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void confirm_plan_kernel(ConfirmTableDev b, uint32_t *plan /* [count + 1] */) {
-    __shared__ uint32_t part[256];
-    const uint32_t t = threadIdx.x;
-    uint32_t items = 0;
-    if (t < b.count) {
-        const ConfirmArgs *pa = &b.c[t];
-        const bool dense = pa->dense_flag != nullptr && *pa->dense_flag > pa->dense_thresh;  // (walked whole this batch: nothing to confirm)
-        items = dense ? 0u : (min(*pa->pair_count, pa->pair_cap) + kConfirmThreads - 1) / kConfirmThreads;
-    }
-    part[t] = items;
-    __syncthreads();
-    for (uint32_t d = 1; d < 256; d <<= 1) {
-        const uint32_t v = t >= d ? part[t - d] : 0u;
-        __syncthreads();
-        part[t] += v;
-        __syncthreads();
-    }
-    if (t < b.count) plan[t] = part[t] - items;
-    if (t == 0) plan[b.count] = part[255];
-}
-
-// A literal atom confirmed for request r, merged into its hit record. Several lanes — other flagged chunks of the same request, in other
-// workgroups on other XCDs — may be merging at once, so every access to the shared words is a read-modify-write atomic (performed at
-// the device's coherence point; a returned atomic has completed when its value arrives, which orders an overflow entry's words before
-// the compare-and-swap that publishes it): no fences — an agent-scope fence writes back and invalidates the whole L2, and two per hit
-// took this kernel from 0.3 to 1.5 ms and its neighbours with it. An overflow chain grows like a lock-free stack (entries allocated for
-// an attempt that lost its compare-and-swap are leaked: rare, and the pool is sized per batch).
-__device__ __noinline__ void merge_atom(PoolEntry *pool, uint32_t *pool_count, uint32_t *status, uint32_t pool_cap, uint32_t *rec, uint32_t atom) {
-    auto rmw_read = [](uint32_t *p) { return atomicOr(p, 0u); };
-    auto publish = [&](uint32_t idx, uint32_t at, uint32_t next) {
-        const uint32_t t0 = atomicExch(&pool[idx].atom, at), t1 = atomicExch(&pool[idx].next, next);
-        asm volatile("" ::"v"(t0), "v"(t1));  // (both have been performed before anything below is issued)
-    };
-    uint32_t old = rmw_read(rec);
-    for (;;) {
-        uint32_t upd;
-        const uint32_t x = atom + 1u;
-        if (!(old & REC_OVERFLOW)) {
-            const uint32_t a0 = old & 0x7FFFu, a1 = (old >> 15) & 0x7FFFu;
-            if (a0 == x || a1 == x) return;
-            if (a0 == 0u) upd = old | x;
-            else if (a1 == 0u) upd = old | (x << 15);
-            else {  // a third atom: the record becomes a chain of all three
-                const uint32_t idx = atomicAdd(pool_count, 3u);
-                if (idx + 3u > pool_cap) { atomicOr(status, 1u); return; }  // (the host runs the batch again with the pool the allocator asked for)
-                publish(idx, a0 - 1u, kNone);
-                publish(idx + 1u, a1 - 1u, idx);
-                publish(idx + 2u, atom, idx + 1u);
-                upd = REC_OVERFLOW | (idx + 2u);
-            }
-        } else {
-            const uint32_t head = old & ~REC_OVERFLOW;
-            for (uint32_t i = head; i != kNone; i = rmw_read(&pool[i].next))
-                if (rmw_read(&pool[i].atom) == atom) return;
-            const uint32_t idx = atomicAdd(pool_count, 1u);
-            if (idx >= pool_cap) { atomicOr(status, 1u); return; }
-            publish(idx, atom, head);
-            upd = REC_OVERFLOW | idx;
-        }
-        const uint32_t seen = atomicCAS(rec, old, upd);
-        if (seen == old) return;
-        old = seen;
-    }
-}
-
-// One lane per (request, flagged chunk) pair; a persistent grid over device-computed work items (one workgroup's worth of pairs of
-// one pass each), like the list scan: consecutive items are mostly of one pass, whose tables are staged in LDS once — the filter
-// table and the confirm head table (16 KiB each) and, when they fit kConfirmPoolBytes, the comparison tables (entries, value / mask
-// bytes, classes); a pass whose tables do not fit reads them from the L2-resident originals through the same (generic) pointers.
-//
-// Why pairs. A request-per-lane version (this round's first) looped over the request's flagged chunks, their completed windows and
-// the windows' entries: 64 lanes in lockstep take the PRODUCT of each level's longest trip, every trip a chain of memory round
-// trips, and a wave is as slow as its unluckiest request — measured 0.32 - 0.64 ms for the ~350k benign candidates of a 10M-request
-// batch and 4 - 13 ms for the hostile stream's 11M (profiles/r4_confirm_v1_*). A pair is one chunk of text and the one or two
-// windows that completed in it: the same small amount of work in every lane, and nothing to do afterwards unless something was
-// confirmed.
-__global__ __launch_bounds__(kConfirmThreads, 8) void confirm_kernel(ConfirmTableDev b, const uint32_t *plan) {
-    __shared__ uint32_t head[kFilterEntries], ftab[kFilterEntries];  // the confirm table's head words; the pass's filter table
-    __shared__ uint32_t pool[kConfirmPoolBytes / 4];                 // entries | bytes | classes of the pass (when they fit)
-    constexpr uint32_t kConfirmQueue = 1024;
-    __shared__ uint32_t app_cnt, app_base, app_queue[kConfirmQueue];  // the workgroup's walk-list appends of the current pass
-    __builtin_amdgcn_s_setprio(3);
-    if (threadIdx.x == 0) app_cnt = 0;
-    const uint32_t total = plan[b.count];
-    const uint32_t it0 = (uint32_t)((uint64_t)total * blockIdx.x / gridDim.x), it1 = (uint32_t)((uint64_t)total * (blockIdx.x + 1) / gridDim.x);
-    for (uint32_t it = it0; it < it1;) {
-        uint32_t ps = 0;
-        for (uint32_t lo = 0, hi = b.count; lo + 1 < hi;) {  // the pass of item `it`: the last p with plan[p] <= it (uniform)
-            const uint32_t mid = (lo + hi) >> 1;
-            if (plan[mid] <= it) lo = mid;
-            else hi = mid;
-            ps = lo;
-        }
-        const uint32_t first_item = plan[ps], it_end = min(it1, plan[ps + 1]);
-        const ConfirmArgs a = load_descriptor(&b.c[ps]);
-        __syncthreads();  // (every wave is done with the previous pass's tables)
-        {
-            // 16 bytes per lane and load (two 16 KiB tables)
-            const uint4 *sh = reinterpret_cast<const uint4 *>(a.c_head), *sf = reinterpret_cast<const uint4 *>(a.ftable);
-            constexpr uint32_t kPer = kFilterEntries / 4 / kConfirmThreads;
-            uint4 vh[kPer], vf[kPer];
-#pragma unroll
-            for (uint32_t q = 0; q < kPer; q++) { vh[q] = sh[q * kConfirmThreads + threadIdx.x]; vf[q] = sf[q * kConfirmThreads + threadIdx.x]; }
-#pragma unroll
-            for (uint32_t q = 0; q < kPer; q++) {
-                reinterpret_cast<uint4 *>(head)[q * kConfirmThreads + threadIdx.x] = vh[q];
-                reinterpret_cast<uint4 *>(ftab)[q * kConfirmThreads + threadIdx.x] = vf[q];
-            }
-        }
-        // the comparison tables: LDS when they fit (generic pointers: the same comparison code reads either copy)
-        const uint32_t e_words = a.n_entries * 3u, b_words = a.n_bytes / 4u, c_words = a.n_class_words;
-        const bool in_lds = confirm_tables_fit(a.n_entries, a.n_bytes, a.n_class_words);
-        const ConfirmEntry *t_entries = a.c_entries;
-        const uint8_t *t_bytes = a.c_bytes;
-        const uint32_t *t_classes = a.c_classes;
-        if (in_lds) {
-            const uint32_t *se = reinterpret_cast<const uint32_t *>(a.c_entries), *sb = reinterpret_cast<const uint32_t *>(a.c_bytes);
-            for (uint32_t k = threadIdx.x; k < e_words; k += kConfirmThreads) pool[k] = se[k];
-            for (uint32_t k = threadIdx.x; k < b_words; k += kConfirmThreads) pool[e_words + k] = sb[k];
-            for (uint32_t k = threadIdx.x; k < c_words; k += kConfirmThreads) pool[e_words + b_words + k] = a.c_classes[k];
-            t_entries = reinterpret_cast<const ConfirmEntry *>(pool);
-            t_bytes = reinterpret_cast<const uint8_t *>(pool + e_words);
-            t_classes = pool + e_words + b_words;
-        }
-        __syncthreads();
-        const ConfirmView cv{nullptr, t_entries, t_bytes, t_classes, a.mul, a.stride, a.init};
-        const uint32_t n_p = min(*a.pair_count, a.pair_cap);
-        // A lane's chain of dependent loads — pair -> the request's offsets, the chunk's text — is issued one work item AHEAD: the
-        // next item's offsets and text (and the pair of the one after) travel while this item's windows are compared. (The kernel is
-        // bound by those round trips, not by instructions: 65 % of its wave cycles were waits with everything issued on demand.)
-        auto pair_of = [&](const uint32_t item) -> uint2 {
-            const uint32_t k = (item - first_item) * kConfirmThreads + threadIdx.x;
-            return (item < it_end && k < n_p) ? a.pairs[k] : make_uint2(kNone, 0u);  // (kNone: no pair for this lane)
-        };
-        uint2 pr_next = pair_of(it), pr_after = pair_of(it + 1u);
-        uint32_t fs_next = 0u, fe_next = 0u;
-        ConfirmBytes tb_next{};
-        if (pr_next.x != kNone) {
-            confirm_load64(reinterpret_cast<const uint8_t *>(a.off + pr_next.x), fs_next, fe_next);  // (the request's two offsets: one scattered load)
-            tb_next = confirm_chunk_bytes(a.data, pr_next.y, a.total + PWAF_ARENA_PAD);
-        }
-        for (; it < it_end; it++) {
-            const uint2 pr = pr_next;
-            const bool live = pr.x != kNone;
-            uint32_t r = live ? pr.x : 0u;  // the request that owns the chunk's first byte; a chunk that holds a field boundary also speaks for the next one(s)
-            uint32_t fs = fs_next, fe = fe_next;
-            const ConfirmBytes tb = tb_next;
-            pr_next = pr_after;
-            if (pr_next.x != kNone) {
-                confirm_load64(reinterpret_cast<const uint8_t *>(a.off + pr_next.x), fs_next, fe_next);
-                tb_next = confirm_chunk_bytes(a.data, pr_next.y, a.total + PWAF_ARENA_PAD);
-            }
-            pr_after = pair_of(it + 2u);
-            ConfirmChunk ch{0u, 0ull};
-            if (live) ch = confirm_windows_of(cv, tb, 0u, 0xFFFFFFFFu, pr.y, [&](const uint32_t bin) { return ftab[bin]; });  // (every window of the chunk: whose field it lies in is settled below)
-            // the completed windows' entries, one comparison per lane and iteration (a lane advances to ITS next entry: the wave runs
-            // as long as its longest lane, not the product of the two loops' longest trips)
-            uint32_t mask = ch.mask, cnt = 0, j = 0, e0 = 0, pos = 0, widx = 0;
-            bool walk = false;  // of request r (the one the lane is at)
-            auto settle = [&](const uint32_t rq, const uint32_t need_lits, const bool wk, const bool aggregated) -> bool {
-                // what the comparisons found for request rq: gap passes its literal hits call for, the walk list. Returns "append rq to
-                // the walk list through the workgroup's aggregated atomic" (the lane's LAST request); an earlier request of the same
-                // chunk (rare: the chunk holds a field boundary) is appended directly.
-                bool w2 = wk;
-                if (need_lits & a.shared_bits) w2 = true;  // a gap pass that shares the walk list learns of the request through the walk
-                const uint32_t direct = need_lits & ~a.shared_bits;
-                if (direct) enqueue_mask_once(a.gate_lists, a.gate_count, a.n, rq, direct, a.enq_bits, a.enq_words);
-                if (!w2 || a.walk_list == nullptr) return false;
-                const uint32_t bit = 1u << (rq & 31u);
-                if (atomicOr(&a.walk_bits[rq >> 5], bit) & bit) return false;  // already listed
-                atomicOr(&a.valid_bits[rq >> 5], bit);
-                if (aggregated) return true;
-                a.walk_list[atomicAdd(a.walk_count, 1u)] = rq;
-                return false;
-            };
-            uint32_t need = 0;  // gap passes the literal hits of request r call for
-            for (;;) {
-                if (__ballot(j < cnt || mask != 0u) == 0) break;
-                while (j >= cnt && mask != 0u) {
-                    const uint32_t k = (uint32_t)__builtin_ctz(mask);
-                    mask &= mask - 1u;
-                    pos = pr.y * 16u + k;
-                    const uint32_t bin = confirm_bin_of(ch, widx++, a.data, pos, a.mul);
-                    while (pos >= fe && r + 1u < a.n) {  // the window lies in a later field of the chunk
-                        settle(r, need, walk, false);
-                        need = 0;
-                        walk = false;
-                        r++;
-                        fs = fe;
-                        fe = a.off[r + 1];
-                    }
-                    if (pos >= fe) continue;  // the bigram starts in the arena's slack (one that starts on the field's last byte may be the window of a short factor: confirm.h)
-                    const uint32_t hd = head[bin];
-                    e0 = hd & 0xFFFFFu;
-                    cnt = hd >> 20;
-                    j = 0;
-                }
-                if (j < cnt) {
-                    const uint32_t res = in_lds ? confirm_entry<3>(t_entries, t_bytes, t_classes, e0 + j, a.data, fs, fe, pos)
-                                                : confirm_entry<1>(t_entries, t_bytes, t_classes, e0 + j, a.data, fs, fe, pos);
-                    j++;
-                    if (res == 2u) {
-                        walk = true;
-                    } else if (res & 1u) {
-                        const uint32_t atom = res >> 8;
-                        merge_atom(a.pool, a.pool_count, a.status, a.pool_cap, a.rec + r, atom);
-                        atomicOr(&a.valid_bits[r >> 5], 1u << (r & 31u));
-                        if (a.colmask_local != nullptr) need |= a.colmask_local[atom];
-                    }
-                }
-            }
-            // Nothing confirmed (the common case by far): the lane is done and has written nothing.
-            const bool append = live && settle(r, need, walk, true);
-            // The walk list: the lane parks the request in the workgroup's LDS queue (an LDS atomic, no barrier); the queue is flushed with
-            // ONE atomic on the list's length when the workgroup is done with the pass (a returned same-address atomic per request is
-            // what DESIGN.md 4.1 measured at 0.5 ms per batch; a barrier per work item cost the 16 waves their independence).
-            if (append) {
-                const uint32_t slot = atomicAdd(&app_cnt, 1u);
-                if (slot < kConfirmQueue) app_queue[slot] = r;
-                else a.walk_list[atomicAdd(a.walk_count, 1u)] = r;  // (queue full: directly — rare)
-            }
-        }
-        __syncthreads();
-        {
-            const uint32_t queued = min(app_cnt, kConfirmQueue);
-            if (threadIdx.x == 0 && queued != 0) app_base = atomicAdd(a.walk_count, queued);
-            __syncthreads();
-            for (uint32_t k = threadIdx.x; k < queued; k += kConfirmThreads) a.walk_list[app_base + k] = app_queue[k];
-            __syncthreads();
-            if (threadIdx.x == 0) app_cnt = 0;
-        }
-    }
-}
-
 int launch_scan(const ScanArgs &a, void *stream) {
     const uint32_t lds = scan_lds_bytes(a.n_hot, a.stride, a.colmask_local ? a.n_local : 0u);
     const bool wide = a.n_classes > 127;
@@ -1229,22 +859,6 @@ int upload_args_block(const void *host_pinned, void *dev, size_t bytes, void *ze
     if (n16 == 0 && z16 == 0) return 0;
     const uint32_t blocks = std::max(std::min<uint32_t>((n16 + 255) / 256, 64u), std::min<uint32_t>((z16 + 2047) / 2048, 1024u));
     hipLaunchKernelGGL(copy_args_kernel, dim3(std::max(1u, blocks)), dim3(256), 0, (hipStream_t)stream, (const uint4 *)host_pinned, (uint4 *)dev, n16, (uint4 *)zero, z16);
-    return (int)hipGetLastError();
-}
-
-int launch_confirm(const ConfirmArgs *host, uint32_t count, const ConfirmArgs *dev, uint32_t *plan, uint32_t n_cus, void *stream) {
-    if (count == 0 || host[0].n == 0) return 0;
-    if (count > 256) return (int)hipErrorInvalidValue;
-    ConfirmTableDev b{dev, count};
-    hipLaunchKernelGGL(confirm_plan_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, b, plan);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return (int)e;
-    // persistent grid: 2 workgroups of 1024 per CU (76 KiB of LDS each: 32 waves per CU), never more than the items a full batch could produce
-    uint64_t max_items = 0;
-    for (uint32_t k = 0; k < count; k++) max_items += ((uint64_t)host[k].pair_cap + kConfirmThreads - 1) / kConfirmThreads;
-    const uint32_t blocks = (uint32_t)std::min<uint64_t>(max_items, (uint64_t)std::max(1u, n_cus) * 2u);
-    const uint32_t *cplan = plan;
-    hipLaunchKernelGGL(confirm_kernel, dim3(blocks), dim3(kConfirmThreads), 0, (hipStream_t)stream, b, cplan);
     return (int)hipGetLastError();
 }
 
@@ -1591,8 +1205,10 @@ __global__ __launch_bounds__(kFilterWaves * 64) void filter_kernel(FilterMix M) 
     else filter_rows<HEADS, 2>(a, blk - a.first_block, wave, lane);
 }
 
+// (Defined below the launchers. The instantiations take their attributes from THIS first declaration, which names no __launch_bounds__: the
+// definition's (256) does not apply, the kernel is compiled for workgroups of up to 1024 threads. DESIGN.md §0.6.)
 template <uint32_t PARTS>
-__global__ void resolve_kernel(FilterTable B);  // (defined below, next to the wave scan it uses)
+__global__ void resolve_kernel(FilterTable B);
 
 // bitcount_kernel / compact_kernel: candidate bitmap -> dense ascending request list. Two launches: candidates per workgroup
 // (kCompactWords bitmap words each), then every workgroup sums the counts before it (a few hundred values) and writes its part.
@@ -1613,7 +1229,7 @@ __global__ __launch_bounds__(256) void bitcount_kernel(FilterTable B) {
     if (threadIdx.x == 0) a.block_count[blockIdx.x] = red[0];
 }
 
-__global__ void compact_kernel(FilterTable B);  // (defined below, next to the wave scan it uses)
+__global__ void compact_kernel(FilterTable B);  // (defined below the launchers)
 
 static uint32_t filter_blocks(const FilterArgs *host, uint32_t count, bool *heads) {
     uint32_t blocks = 0;
@@ -1761,57 +1377,6 @@ int launch_residual(const ResidualArgs &a, void *stream) {
     if (a.n == 0 || a.n_rules == 0) return 0;
     hipLaunchKernelGGL(residual_kernel, dim3(std::min<uint32_t>((a.n + 127) / 128, 8192u)), dim3(128), 0, (hipStream_t)stream, a);
     return (int)hipGetLastError();
-}
-
-// -------------------------------------------------------------------------------------------------
-// verdict
-// -------------------------------------------------------------------------------------------------
-__device__ __forceinline__ uint32_t ip_byte(const uint32_t w[4], uint32_t k) {
-    uint32_t word = k < 4 ? w[0] : k < 8 ? w[1] : k < 12 ? w[2] : w[3];
-    return (word >> ((k & 3) * 8)) & 0xFFu;
-}
-
-// 16-bit root, then 8-bit strides. Returns the leaf value (0 when the family has no table).
-// LDS per wave: the column file (one 64-request word per atom), a bitmap of non-zero columns, a bitmap of candidate rules
-// and the ordered candidate list.
-// Bitwise OR over the 64 lanes, in the vector ALU (DPP row shifts + the two cross-row broadcasts): no LDS, no memory.
-__device__ __forceinline__ uint32_t wave_or(uint32_t x) {
-#define PWAF_DPP_OR(ctrl, rows) x |= (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, (ctrl), (rows), 0xF, true)
-    PWAF_DPP_OR(0x111, 0xF);  // row_shr:1
-    PWAF_DPP_OR(0x112, 0xF);  // row_shr:2
-    PWAF_DPP_OR(0x114, 0xF);  // row_shr:4
-    PWAF_DPP_OR(0x118, 0xF);  // row_shr:8   -> lane 15 of each row holds its row
-    PWAF_DPP_OR(0x142, 0xA);  // row_bcast:15 into rows 1 and 3
-    PWAF_DPP_OR(0x143, 0xC);  // row_bcast:31 into rows 2 and 3 -> lane 63 holds the wave
-#undef PWAF_DPP_OR
-    return (uint32_t)__builtin_amdgcn_readlane((int)x, 63);
-}
-
-// A wave-uniform 64-bit mask into ONE lane of a register pair (v_writelane_b32): `x = lane == l ? m : x` without the compare of the
-// lane id, the two selects and the moves of the scalar pair into vector registers — two vector instructions instead of seven where a
-// kernel is bound by vector-ALU issue (attr_kernel: one such parking per present membership bit and per comparison atom). gfx9 lets
-// a VALU instruction read ONE scalar register, M0 not counted: the lane select travels in M0. (No compiler builtin for v_writelane.)
-#pragma clang diagnostic push
-#pragma clang diagnostic ignored "-Winline-asm"  // (M0 is a reserved register: naming it as clobbered is what is meant)
-__device__ __forceinline__ void park64(uint32_t &lo, uint32_t &hi, const unsigned long long m, const uint32_t l) {
-    asm volatile("s_mov_b32 m0, %3\n\ts_nop 0\n\tv_writelane_b32 %0, %2, m0\n\tv_writelane_b32 %1, %4, m0"
-                 : "+v"(lo), "+v"(hi)
-                 : "s"((uint32_t)m), "s"(l), "s"((uint32_t)(m >> 32))
-                 : "m0");
-}
-#pragma clang diagnostic pop
-
-// Inclusive prefix sum over the 64 lanes, same DPP network (no LDS round trips, unlike __shfl_up).
-__device__ __forceinline__ uint32_t wave_scan_add(uint32_t x) {
-#define PWAF_DPP_ADD(ctrl, rows) x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, (ctrl), (rows), 0xF, true)
-    PWAF_DPP_ADD(0x111, 0xF);  // row_shr:1
-    PWAF_DPP_ADD(0x112, 0xF);  // row_shr:2
-    PWAF_DPP_ADD(0x114, 0xF);  // row_shr:4
-    PWAF_DPP_ADD(0x118, 0xF);  // row_shr:8   -> inclusive scan inside each row of 16
-    PWAF_DPP_ADD(0x142, 0xA);  // row_bcast:15: rows 1 and 3 add the total of the row before
-    PWAF_DPP_ADD(0x143, 0xC);  // row_bcast:31: rows 2 and 3 add the total of rows 0-1
-#undef PWAF_DPP_ADD
-    return x;
 }
 
 // resolve_kernel: one wave per slab turns the slab's flagged chunks into candidate REQUESTS. Request-driven: the flagged 16-byte
@@ -2086,1913 +1651,6 @@ __global__ __launch_bounds__(256) void compact_kernel(FilterTable B) {
     if (blockIdx.x == n_blocks - 1 && tid == 255) *a.list_count = pos0;
 }
 
-
-// (the column files' and program tables' LDS layout — verdict_wave_lds, verdict_wave_lds_sp, verdict_v_cap, verdict_wave_lds_el,
-// verdict_tables — and the launch shape computed from it: verdictplan.h)
-
-// BR = 64-pass bitmap registers (1: up to 64 passes, else kMaxPasses)
-template <bool LT, int BR, bool SP>
-__global__ __launch_bounds__(SP ? 768 : 1024, (SP && BR == 1) ? 6 : 1) void verdict_kernel(VerdictArgs a) {  // (sparse, up to 64 passes: 6 waves per SIMD = two 12-wave workgroups per CU)
-    extern __shared__ __align__(16) unsigned char lds[];
-    const uint32_t tid = threadIdx.x, wave = wave_index(), lane = tid & 63, n_waves = blockDim.x >> 6;
-#ifdef PWAF_PROFILING
-    const uint32_t dbg_skip = a.debug_skip;  // section switches for timing experiments (wrong results when set): -DPWAF_PROFILING builds only
-#else
-    constexpr uint32_t dbg_skip = 0;
-#endif
-    const uint32_t colw = (a.n_cols + 31) / 32, rulew = (a.n_rules + 31) / 32;
-    const uint32_t v_cap = a.v_cap;  // (SP) values held in LDS; dirty columns of higher rank: the wave's spill array
-    const uint32_t wave_bytes = SP ? verdict_wave_lds_sp(a.n_cols, a.n_rules, v_cap) : verdict_wave_lds(a.n_cols, a.n_rules);
-    unsigned char *mine = lds + (size_t)wave * wave_bytes;
-    // dense: col[n_cols] | colnz[colw]; sparse: nz[colw] = {dirty bits, dirty columns before the word} | vals[v_cap]
-    unsigned long long *col = reinterpret_cast<unsigned long long *>(mine);
-    uint32_t *colnz = reinterpret_cast<uint32_t *>(col + a.n_cols);
-    uint32_t *nz = reinterpret_cast<uint32_t *>(mine);
-    unsigned long long *vals = reinterpret_cast<unsigned long long *>(mine + (size_t)colw * 8);
-    unsigned long long *spill = (SP && a.spill != nullptr) ? a.spill + (size_t)(blockIdx.x * n_waves + wave) * (a.n_cols - v_cap) : nullptr;
-    uint32_t *rulebm = SP ? reinterpret_cast<uint32_t *>(vals + v_cap) : colnz + colw;
-    uint16_t *cand = reinterpret_cast<uint16_t *>(rulebm + rulew);
-    unsigned char *tables = lds + (size_t)n_waves * wave_bytes;
-    const VerdictTables vt = verdict_tables(a.n_cols, a.n_rules, a.n_trig, a.n_lits, LT);
-    uint16_t *l_trig_off = reinterpret_cast<uint16_t *>(tables + vt.trig_off);
-    uint16_t *l_trig_rules = reinterpret_cast<uint16_t *>(tables + vt.trig_rules);
-    uint2 *l_rules = reinterpret_cast<uint2 *>(tables + vt.rules);
-    uint32_t *l_lits = reinterpret_cast<uint32_t *>(tables + vt.lits);
-    uint16_t *l_pub = reinterpret_cast<uint16_t *>(tables + vt.pub);  // public rule index, 16 bits (the pseudo rules' 0xFFFFFFFx ids keep their low half)
-    if (LT) {
-        for (uint32_t k = tid; k <= a.n_cols; k += blockDim.x) l_trig_off[k] = (uint16_t)a.trig_off[k];
-        for (uint32_t k = tid; k < a.n_trig; k += blockDim.x) l_trig_rules[k] = a.trig_rules[k];
-        for (uint32_t k = tid; k < a.n_rules; k += blockDim.x) {
-            const DevRule dr = a.rules[k];  // header without the public index (only read when the rule decides a request)
-            l_rules[k] = make_uint2(dr.lit_off, dr.lit_cnt | ((uint32_t)dr.eff_unverified << 16) | ((uint32_t)dr.eff_verified << 24));
-            l_pub[k] = (uint16_t)dr.public_idx;
-        }
-        for (uint32_t k = tid; k < a.n_lits; k += blockDim.x) l_lits[k] = a.lits[k];
-    }
-    __syncthreads();
-    const unsigned long long mybit = 1ull << lane;
-    const unsigned long long lt_mask = mybit - 1;
-    unsigned long long cnt_block = 0, cnt_captcha = 0, cnt_bypass = 0, cnt_allow = 0;  // wave-uniform tallies
-
-    // group-invariant, fetched once per wave: this lane's word of the always-candidate bitmap
-    const uint32_t h_always = lane < rulew ? a.always_rules[lane] : 0u;
-
-    // A group's inputs — the hit records of up to kPre passes, the captcha flag, the attribute kernel's pair count and first 64
-    // pairs — are requested ONE GROUP AHEAD: with ~9 waves per CU nothing else hides the ~2 us those first-touch loads take.
-    // Which passes: a list-driven (sparse) pass has a visited bitmap, and in most groups of 64 requests most such passes visited
-    // nobody (a 4096-rule set over 64 header fields has ~90 passes, a handful of them non-empty per group). The group's 64 visited
-    // bits of EVERY pass are requested TWO groups ahead, lane q holding pass q's word (dense passes: all ones); one group ahead a
-    // ballot names the non-empty passes and only those get a record load — limited to the lanes whose bit is set.
-    constexpr int kPre = kVerdictPre;
-    constexpr int kBitRegs = BR;  // 64 passes per register
-    struct Bits {
-        unsigned long long w[kBitRegs];  // lane l of w[r]: the visited bits of pass r * 64 + l for the group's 64 requests
-    };
-    struct Inputs {
-        uint32_t rv[kPre];    // the hit records of the group's first kPre non-empty passes ...
-        uint32_t base[kPre];  // ... and their first columns (wave-uniform; kNone = slot unused)
-        Bits bits;            // for the passes left over
-        unsigned long long rest[kBitRegs];  // wave-uniform: non-empty passes that got no slot (fetched inside the group: rare)
-        uint32_t flags, n_pairs;
-        uint4 pair0;
-        uint32_t res0;  // the first result word of the specialized residual program (VerdictArgs::res_match)
-    };
-    // group-invariant, per lane: the bitmap and first column of "my" pass in each register
-    const uint32_t *my_bits[kBitRegs];
-    uint32_t my_base[kBitRegs];
-    bool my_live[kBitRegs];
-#pragma unroll
-    for (int r = 0; r < kBitRegs; r++) {
-        const uint32_t ps = (uint32_t)r * 64 + lane;
-        my_live[r] = ps < a.n_passes;
-        my_bits[r] = nullptr;
-        my_base[r] = 0;
-        if (my_live[r]) {
-            const PassInfo pi = a.passes[ps];
-            const uint32_t kind = pi.kind_slot >> 24, slot = pi.kind_slot & 0xFFFFFFu;
-            if (kind == 3) my_live[r] = false;  // a short-literal pass: its columns arrive as attribute pairs, it has no records
-            my_bits[r] = kind == 1 ? a.cand_bits + (size_t)slot * a.bit_words : kind == 2 ? a.visit_bits + (size_t)slot * a.bit_words : nullptr;
-            my_base[r] = pi.base;
-        }
-    }
-    auto request_bits = [&](const uint32_t g, Bits &bt) {
-        const uint32_t gg = min(g, a.n_groups - 1);
-#pragma unroll
-        for (int r = 0; r < kBitRegs; r++) {
-            // (the bitmap of a batch whose size is not a multiple of 64 is padded to whole groups by the engine)
-            bt.w[r] = !my_live[r] ? 0ull : my_bits[r] != nullptr ? *reinterpret_cast<const unsigned long long *>(my_bits[r] + 2 * (size_t)gg) : ~0ull;
-        }
-    };
-    auto request_inputs = [&](const uint32_t g, const Bits &bt, Inputs &in) {
-        const uint32_t i = g * 64 + lane;
-        const bool valid = g < a.n_groups && i < a.n;
-        unsigned long long nz[kBitRegs];
-#pragma unroll
-        for (int r = 0; r < kBitRegs; r++) nz[r] = (uint32_t)r * 64 < a.n_passes ? __ballot(bt.w[r] != 0) : 0ull;
-#pragma unroll
-        for (int q = 0; q < kPre; q++) {
-            uint32_t ps = kNone, base = kNone;
-            unsigned long long word = 0;
-#pragma unroll
-            for (int r = 0; r < kBitRegs; r++) {
-                if (ps == kNone && nz[r] != 0) {  // wave-uniform
-                    const int l = __builtin_ctzll(nz[r]);
-                    nz[r] &= nz[r] - 1;
-                    ps = (uint32_t)r * 64 + (uint32_t)l;
-                    word = ((unsigned long long)(uint32_t)__builtin_amdgcn_readlane((int)(bt.w[r] >> 32), l) << 32) | (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)bt.w[r], l);
-                    base = (uint32_t)__builtin_amdgcn_readlane((int)my_base[r], l);
-                }
-            }
-            in.base[q] = base;
-            in.rv[q] = (ps != kNone && valid && ((word >> lane) & 1ull)) ? a.rec[(size_t)ps * a.n + i] : 0u;
-        }
-#pragma unroll
-        for (int r = 0; r < kBitRegs; r++) in.rest[r] = nz[r];
-        in.bits = bt;
-        in.flags = valid ? (uint32_t)a.flags[i] : 0u;
-        const uint32_t gg = min(g, a.n_groups - 1);
-        in.n_pairs = a.ghdr[gg];
-        in.pair0 = a.gpairs[(size_t)gg * a.pair_stride + lane];  // (the buffer is padded: reading past the group's count is harmless)
-        in.res0 = (a.res_words && valid) ? a.res_match[i] : 0u;
-    };
-    if (!SP) {
-        for (uint32_t k = lane; k < a.n_cols; k += 64) col[k] = 0;  // the column file starts clean; afterwards groups clean up after themselves
-        for (uint32_t k = lane; k < colw; k += 64) colnz[k] = 0;
-    }
-    const uint32_t g_stride = gridDim.x * n_waves;
-    Inputs cur;
-    Bits b_nxt;
-    {
-        Bits b_cur;
-        request_bits(blockIdx.x * n_waves + wave, b_cur);
-        request_inputs(blockIdx.x * n_waves + wave, b_cur, cur);
-        request_bits(blockIdx.x * n_waves + wave + g_stride, b_nxt);
-    }
-
-    for (uint32_t g = blockIdx.x * n_waves + wave; g < a.n_groups; g += g_stride) {
-        const uint32_t i = g * 64 + lane;
-        const bool valid = i < a.n;
-        const unsigned long long valid_mask = __ballot(valid);
-        Inputs nxt;
-        request_inputs(g + g_stride, b_nxt, nxt);
-        request_bits(g + 2 * g_stride, b_nxt);
-
-        // 1. clear the column file and the bitmaps; column 0 is the constant TRUE; rules that can match with every column
-        //    zero (a term made of negations only) are always candidates
-        //    (dense: only the columns the previous group dirtied are cleared — the non-zero bitmap names them; sparse: the dirty bits)
-        if (!SP) {
-            for (uint32_t wv = lane; wv < colw; wv += 64) {
-                uint32_t nzw = colnz[wv];
-                colnz[wv] = wv == 0 ? 1u : 0u;
-                while (nzw) {
-                    col[wv * 32 + (uint32_t)__builtin_ctz(nzw)] = 0;
-                    nzw &= nzw - 1;
-                }
-            }
-        } else {
-            for (uint32_t wv = lane; wv < colw; wv += 64) nz[2 * wv] = wv == 0 ? 1u : 0u;
-        }
-        for (uint32_t k = lane; k < rulew; k += 64) rulebm[k] = k < 64 ? h_always : a.always_rules[k];
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-        if (!SP && lane == 0) col[0] = ~0ull;
-
-        const uint32_t flags = cur.flags;
-        const uint4 *pairs = a.gpairs + (size_t)g * a.pair_stride;
-        const uint32_t n_pairs = cur.n_pairs;
-        const uint4 pair0 = cur.pair0;
-        const unsigned long long verified_mask = __ballot(valid && (flags & PWAF_FLAG_CAPTCHA_VERIFIED));
-
-        // Where column c's 64-request word lives. Dense: the column file. Sparse: at the column's rank among the group's dirty columns
-        // (in LDS below v_cap, in the wave's spill array beyond) — valid once the ranks are known (phase 1).
-        auto slot_of = [&](const uint32_t c) {
-            const uint32_t w = c >> 5, bits = nz[2 * w], before = nz[2 * w + 1];
-            return before + (uint32_t)__builtin_popcount(bits & ((1u << (c & 31u)) - 1u));
-        };
-        auto word_at = [&](const uint32_t slot) -> unsigned long long * { return slot < v_cap ? vals + slot : spill + (slot - v_cap); };
-        // PHASE 0 (sparse only): dirty bits. PHASE 1 (sparse): values. PHASE 2: the dense file, bits and values at once.
-        auto mark_all = [&](auto phase_tag) {
-            constexpr int PH = decltype(phase_tag)::value;
-            auto put = [&](const uint32_t c, const unsigned long long m) {  // (one lane speaks for column c)
-                if (PH == 0) atomicOr(&nz[2 * (c >> 5)], 1u << (c & 31u));
-                else if (PH == 1) atomicOr(word_at(slot_of(c)), m);
-                else {
-                    atomicOr(&col[c], m);
-                    atomicOr(&colnz[c >> 5], 1u << (c & 31));
-                }
-            };
-            // 2. scan results: each lane marks the columns its hit records name
-            auto mark_hits = [&](const uint32_t rv, const uint32_t base) {
-                if (__ballot(rv != 0) == 0) return;  // nobody in the group matched anything in this pass
-                if (rv & REC_OVERFLOW) {
-                    for (uint32_t k = rv & ~REC_OVERFLOW; k != kNone;) {
-                        const PoolEntry pe = a.pool[k];
-                        put(base + pe.atom, mybit);
-                        k = pe.next;
-                    }
-                }
-                // inline atoms: lanes that name the SAME atom (frequent atoms such as a browser User-Agent prefix are named by
-                // most of the 64 requests) are folded into one column update instead of 64 serialised LDS atomics
-#pragma unroll
-                for (int half = 0; half < 2; half++) {
-                    const uint32_t x = (rv & REC_OVERFLOW) ? 0u : (half == 0 ? rv & 0x7FFFu : (rv >> 15) & 0x7FFFu);
-                    unsigned long long todo = __ballot(x != 0);
-                    while (todo) {
-                        const uint32_t leader = (uint32_t)__builtin_ctzll(todo);
-                        const uint32_t xa = (uint32_t)__builtin_amdgcn_readlane((int)x, (int)__builtin_amdgcn_readfirstlane(leader));
-                        const unsigned long long same = __ballot(x == xa);
-                        todo &= ~same;
-                        if (lane == leader) put(base + xa - 1, same);
-                    }
-                }
-            };
-            if (!(dbg_skip & 1u)) {
-#pragma unroll
-                for (int q = 0; q < kPre; q++) {
-                    if (cur.base[q] == kNone) break;
-                    mark_hits(cur.rv[q], cur.base[q]);
-                }
-                // more than kPre non-empty passes in this group (many dense passes, or a burst of candidates): fetched here
-#pragma unroll
-                for (int r = 0; r < kBitRegs; r++) {
-                    unsigned long long m = cur.rest[r];
-                    while (m) {
-                        const int l = __builtin_ctzll(m);
-                        m &= m - 1;
-                        const uint32_t ps = (uint32_t)r * 64 + (uint32_t)l;
-                        const unsigned long long word = ((unsigned long long)(uint32_t)__builtin_amdgcn_readlane((int)(cur.bits.w[r] >> 32), l) << 32) |
-                                                        (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)cur.bits.w[r], l);
-                        const uint32_t base = (uint32_t)__builtin_amdgcn_readlane((int)my_base[r], l);
-                        mark_hits((valid && ((word >> lane) & 1ull)) ? a.rec[(size_t)ps * a.n + i] : 0u, base);
-                    }
-                }
-            }
-            // 2b. residual rules evaluated by their specialized program: one result word per request and 32 rules, transposed here into the
-            //     rules' column words (a ballot per rule that matched anybody in the group)
-            for (uint32_t w = 0; w < a.res_words; w++) {
-                const uint32_t mw = w == 0 ? cur.res0 : (valid ? a.res_match[(size_t)w * a.n + i] : 0u);
-                if (__ballot(mw != 0u) == 0ull) continue;
-                uint32_t any = mw;
-                for (uint32_t d = 1; d < 64u; d <<= 1) any |= (uint32_t)__shfl_xor((int)any, (int)d, 64);
-                any = (uint32_t)__builtin_amdgcn_readfirstlane((int)any);
-                for (; any; any &= any - 1u) {
-                    const uint32_t k = (uint32_t)__builtin_ctz(any);
-                    const unsigned long long who = __ballot(((mw >> k) & 1u) != 0u);
-                    if (lane == 0) put(a.res_base + 32u * w + k, who);
-                }
-            }
-            // 3. everything that is not a string scan (memberships, comparisons) arrives from the attribute kernel as ready-made
-            //    column words: one lane per pair (one pair per atom and group, and no scan pass owns these columns: a plain store)
-            if (!(dbg_skip & 2u)) {
-                for (uint32_t p = lane; p < n_pairs; p += 64) {
-                    const uint4 pr = p < 64 ? pair0 : pairs[p];
-                    const unsigned long long v = ((unsigned long long)pr.w << 32) | pr.z;
-                    if (PH == 0) atomicOr(&nz[2 * (pr.x >> 5)], 1u << (pr.x & 31u));
-                    else if (PH == 1) {
-                        const uint32_t sl = slot_of(pr.x);
-                        if (sl < v_cap) vals[sl] = v;
-                        else atomicOr(spill + (sl - v_cap), v);
-                    }
-                    else {
-                        col[pr.x] = v;
-                        atomicOr(&colnz[pr.x >> 5], 1u << (pr.x & 31));
-                    }
-                }
-            }
-        };
-        uint32_t n_dirty = 0;  // (sparse) dirty columns of the group
-        if (SP) {
-            mark_all(std::integral_constant<int, 0>{});
-            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-            // the ranks: dirty columns before each word (the prefix sum also lists the dirty columns for step 4)
-            for (uint32_t wb = 0; wb < colw; wb += 64) {
-                const uint32_t bits = wb + lane < colw ? nz[2 * (wb + lane)] : 0u;
-                const uint32_t pc = (uint32_t)__builtin_popcount(bits), incl = wave_scan_add(pc);
-                if (wb + lane < colw) nz[2 * (wb + lane) + 1] = n_dirty + incl - pc;
-                n_dirty += (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
-            }
-            // (column 0 = TRUE is dirty by construction and ranks first; a spilled word is reset with a read-modify-write, like everything
-            // that touches it afterwards: performed at L2 in order — a plain store could still be on its way when the first OR arrives)
-            for (uint32_t k = lane; k < n_dirty; k += 64) {
-                if (k < v_cap) vals[k] = k == 0 ? ~0ull : 0ull;
-                else atomicExch(spill + (k - v_cap), 0ull);
-            }
-            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-            mark_all(std::integral_constant<int, 1>{});
-        } else {
-            mark_all(std::integral_constant<int, 2>{});
-        }
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-        // the bitmap of non-zero columns (dense: colnz; sparse: the bit words of nz) and a column's word, for the steps below
-        auto nz_bits = [&](const uint32_t wv) { return SP ? nz[2 * wv] : colnz[wv]; };
-        auto col_word = [&](const uint32_t c) -> unsigned long long {
-            if (!SP) return col[c];
-            const uint32_t w = c >> 5, bits = nz[2 * w], before = nz[2 * w + 1];
-            if (!((bits >> (c & 31u)) & 1u)) return 0ull;
-            const uint32_t sl = before + (uint32_t)__builtin_popcount(bits & ((1u << (c & 31u)) - 1u));
-            return sl < v_cap ? vals[sl] : __hip_atomic_load(spill + (sl - v_cap), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // (a spilled word: from L2, where the ORs were performed)
-        };
-
-        // 4. candidate rules: a rule can only match some request of this group if one of its terms has a non-zero positive
-        //    column (trigger lists, one chosen literal per term) or consists of negations only (always_rules).
-        //    The non-zero columns are first LISTED (a prefix sum over the bitmap words' popcounts: the candidate array is free until
-        //    the compaction below), then one lane takes one column. (Round 4 gave a lane a whole bitmap word: the ~60 attribute columns
-        //    of a group sit in a handful of neighbouring words, so a few lanes walked eight to sixteen columns one after the other,
-        //    each a chain of three dependent LDS reads, while the other sixty waited.)
-        if (!(dbg_skip & 8u)) {
-            uint32_t n_nz = 0;
-            for (uint32_t wb = 0; wb < colw; wb += 64) {
-                uint32_t nzv = wb + lane < colw ? nz_bits(wb + lane) : 0u;
-                const uint32_t pc = (uint32_t)__builtin_popcount(nzv), incl = wave_scan_add(pc);
-                uint32_t pos = n_nz + incl - pc;
-                while (nzv) {
-                    if (pos < a.n_rules) cand[pos] = (uint16_t)((wb + lane) * 32 + (uint32_t)__builtin_ctz(nzv));  // (n_cols < 65536: launch_verdict)
-                    pos++;
-                    nzv &= nzv - 1;
-                }
-                n_nz += (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
-            }
-            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-            if (n_nz <= a.n_rules) {
-                for (uint32_t j = lane; j < n_nz; j += 64) {
-                    const uint32_t c = cand[j];
-                    const uint32_t kb = LT ? (uint32_t)l_trig_off[c] : a.trig_off[c], ke = LT ? (uint32_t)l_trig_off[c + 1] : a.trig_off[c + 1];
-                    for (uint32_t k = kb; k < ke; k++) {
-                        const uint32_t r = LT ? (uint32_t)l_trig_rules[k] : (uint32_t)a.trig_rules[k];
-                        atomicOr(&rulebm[r >> 5], 1u << (r & 31));
-                    }
-                }
-            } else {  // (more non-zero columns than the list holds: word by word)
-                for (uint32_t wv = lane; wv < colw; wv += 64) {
-                    uint32_t nzv = nz_bits(wv);
-                    while (nzv) {
-                        const uint32_t c = wv * 32 + (uint32_t)__builtin_ctz(nzv);
-                        nzv &= nzv - 1;
-                        const uint32_t kb = LT ? (uint32_t)l_trig_off[c] : a.trig_off[c], ke = LT ? (uint32_t)l_trig_off[c + 1] : a.trig_off[c + 1];
-                        for (uint32_t k = kb; k < ke; k++) {
-                            const uint32_t r = LT ? (uint32_t)l_trig_rules[k] : (uint32_t)a.trig_rules[k];
-                            atomicOr(&rulebm[r >> 5], 1u << (r & 31));
-                        }
-                    }
-                }
-            }
-        }
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-        // ordered compaction of the rule bitmap into the candidate list (ascending rule index = evaluation order)
-        uint32_t n_cand = 0;
-        for (uint32_t wb = 0; wb < rulew && !(dbg_skip & 16u); wb += 64) {
-            const uint32_t word = wb + lane < rulew ? rulebm[wb + lane] : 0u;
-            const uint32_t pc = (uint32_t)__builtin_popcount(word), incl = wave_scan_add(pc);
-            uint32_t pos = n_cand + incl - pc, wrd = word;
-            while (wrd) {
-                cand[pos++] = (uint16_t)((wb + lane) * 32 + (uint32_t)__builtin_ctz(wrd));
-                wrd &= wrd - 1;
-            }
-            n_cand += (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
-        }
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-
-        // 5. evaluate candidates: one lane per rule, 64 requests per ALU op. Each candidate's 64-request match word goes to LDS;
-        //    then every REQUEST lane scans the words in rule order for its own bit (broadcast reads), so first-match-wins needs
-        //    no lane-to-lane traffic
-        unsigned long long pending = valid_mask;
-        bool undecided = valid;
-        uint32_t my_action = PWAF_ACTION_ALLOW, my_rule = PWAF_RULE_NONE;
-        for (uint32_t base = 0; base < n_cand && pending != 0 && !(dbg_skip & 32u); base += 64) {
-            unsigned long long fire = 0;
-            if (base + lane < n_cand) {
-                const uint32_t my_cand = cand[base + lane];
-                uint32_t lit_off, lit_cnt, eff_u, eff_v;
-                if (LT) {
-                    const uint2 hdr = l_rules[my_cand];
-                    lit_off = hdr.x;
-                    lit_cnt = hdr.y & 0xFFFFu;
-                    eff_u = (hdr.y >> 16) & 0xFFu;
-                    eff_v = hdr.y >> 24;
-                } else {
-                    const DevRule dr = a.rules[my_cand];
-                    lit_off = dr.lit_off;
-                    lit_cnt = dr.lit_cnt;
-                    eff_u = dr.eff_unverified;
-                    eff_v = dr.eff_verified;
-                }
-                unsigned long long acc_or = 0, acc_and = ~0ull;
-                // literals four at a time: the four literal words are requested together, then the four column words — two
-                // LDS round trips per four literals instead of eight dependent ones (a padding literal is column 0 = TRUE)
-                for (uint32_t k = lit_off; k < lit_off + lit_cnt; k += 4) {
-                    uint32_t lit[4];
-#pragma unroll
-                    for (int q = 0; q < 4; q++) lit[q] = k + q < lit_off + lit_cnt ? (LT ? l_lits[k + q] : a.lits[k + q]) : 0u;
-                    unsigned long long cw[4];
-#pragma unroll
-                    for (int q = 0; q < 4; q++) cw[q] = (lit[q] & LIT_LAZY) ? 0ull : col_word(lit[q] & LIT_ATOM_MASK);  // (no LAZY literal reaches this kernel — engine.cpp packs them for verdict2 only — but its low bits are no column)
-#pragma unroll
-                    for (int q = 0; q < 4; q++) {
-                        acc_and &= (lit[q] & LIT_NEG) ? ~cw[q] : cw[q];
-                        if (lit[q] & LIT_TERM_END) {
-                            acc_or |= acc_and;
-                            acc_and = ~0ull;
-                        }
-                    }
-                }
-                // a match only decides when the rule's action list yields an effect for that client
-                fire = acc_or & ((eff_u ? ~verified_mask : 0ull) | (eff_v ? verified_mask : 0ull));
-            }
-            if (dbg_skip & 256u) fire = 0;
-            // first match wins: the candidates that fire for ANYBODY (a few per group: most candidates' terms stay false) are taken in
-            // rule order, each word broadcast from its lane — a request's rule is the first word that holds its bit. (Round 4 parked
-            // all 64 words in LDS and every request lane read them back, sixteen rounds of four broadcast reads per 64 candidates.)
-            unsigned long long firing = (dbg_skip & 128u) ? 0ull : __ballot(fire != 0);
-            uint32_t first = kNone;
-            while (firing != 0 && pending != 0) {
-                const int j = __builtin_ctzll(firing);
-                firing &= firing - 1;
-                const unsigned long long fj = (((unsigned long long)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(fire >> 32), j) << 32) |
-                                               (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)fire, j)) & pending;
-                if (fj & mybit) first = (uint32_t)j;
-                pending &= ~fj;
-            }
-            if (undecided && first != kNone) {
-                undecided = false;
-                const uint32_t jc = cand[base + first];
-                uint32_t eff_u, eff_v;
-                if (LT) {
-                    const uint32_t y = l_rules[jc].y;
-                    eff_u = (y >> 16) & 0xFFu;
-                    eff_v = y >> 24;
-                    const uint32_t pi = l_pub[jc];
-                    my_rule = pi >= 0xFFF0u ? 0xFFFF0000u | pi : pi;
-                } else {
-                    const DevRule dr = a.rules[jc];
-                    eff_u = dr.eff_unverified;
-                    eff_v = dr.eff_verified;
-                    my_rule = dr.public_idx;
-                }
-                my_action = (verified_mask & mybit) ? eff_v : eff_u;
-            }
-        }
-
-        if (dbg_skip & 64u) my_rule = n_cand;  // profiling aid: report the candidate count instead of the deciding rule
-        // 6. outputs
-        if (valid) {
-            uint2 v;
-            v.x = my_action;  // action in byte 0, pad bytes zero
-            v.y = my_rule;
-            *reinterpret_cast<uint2 *>(&a.out[i]) = v;
-        }
-        const unsigned long long m_block = __ballot(valid && my_action == PWAF_ACTION_BLOCK);
-        const unsigned long long m_captcha = __ballot(valid && my_action == PWAF_ACTION_CAPTCHA);
-        const unsigned long long m_bypass = __ballot(valid && my_action == PWAF_ACTION_BYPASS);
-        cnt_block += (unsigned)__builtin_popcountll(m_block);
-        cnt_captcha += (unsigned)__builtin_popcountll(m_captcha);
-        cnt_bypass += (unsigned)__builtin_popcountll(m_bypass);
-        cnt_allow += (unsigned)__builtin_popcountll(valid_mask & ~(m_block | m_captcha | m_bypass));
-        if (a.match_idx != nullptr) {
-            // compaction of non-Allow requests: wave ballot + prefix popcount, one atomic per group
-            const unsigned long long hit = m_block | m_captcha | m_bypass;
-            if (hit) {
-                uint32_t basei = 0;
-                if (lane == 0) basei = atomicAdd(a.n_matches, (uint32_t)__builtin_popcountll(hit));
-                basei = __builtin_amdgcn_readfirstlane(basei);
-                if (hit & mybit) a.match_idx[basei + (uint32_t)__builtin_popcountll(hit & lt_mask)] = i;
-            }
-        }
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-        cur = nxt;
-    }
-    // Action counters: one atomic per counter and WORKGROUP. (One per wave was measured at 0.25 ms of a 0.6 ms kernel: at the end of
-    // every round of workgroups thousands of same-address atomics queue up at the L2.)
-    __syncthreads();  // every wave is done with its column file: the start of LDS can hold the tallies
-    unsigned long long *tally = reinterpret_cast<unsigned long long *>(lds);
-    if (lane == 0) {
-        tally[wave * 4 + PWAF_ACTION_ALLOW] = cnt_allow;
-        tally[wave * 4 + PWAF_ACTION_BLOCK] = cnt_block;
-        tally[wave * 4 + PWAF_ACTION_CAPTCHA] = cnt_captcha;
-        tally[wave * 4 + PWAF_ACTION_BYPASS] = cnt_bypass;
-    }
-    __syncthreads();
-    if (a.counts != nullptr && tid < 4) {
-        unsigned long long sum = 0;
-        for (uint32_t wv = 0; wv < n_waves; wv++) sum += tally[wv * 4 + tid];
-        if (sum) atomicAdd(&a.counts[tid], sum);
-    }
-}
-
-// -------------------------------------------------------------------------------------------------
-// verdict, ENTRY-LIST form (round 6; the default: VerdictArgs::sparse_mode 3, 4 = its test hook with 8 entry slots)
-// -------------------------------------------------------------------------------------------------
-// What a group of 64 requests knows about its columns arrives as a LIST already: the attribute kernel's (column, mask) pairs, one per
-// atom that holds for somebody, and per scan pass a handful of distinct atoms named by the hit records. The sparse column file above
-// turns that list into {dirty bits, rank, value} in two marking passes with a prefix sum between them and a third walk over the bitmap
-// to list the dirty columns again for the trigger step — 0.14 ms of marking and 0.08 ms of listing / triggers in a 0.31 ms kernel
-// (profiles/r6_verdict_sections.txt). Here an entry keeps the place it is appended at:
-//     slot[column]  one BYTE per column: 0 = clean, 1 + entry index, 255 = the entry lies beyond e_cap: its word is spill[column]
-//     vals[e], ecol[e]  the entry's 64-request word and its column (to clean slot[] after the group: only the entries are touched)
-// One pass over the inputs, a whole batch of up to 64 entries per instruction: lane k of the batch registers writes slot, value and column
-// of entry n + k and walks the column's trigger list. The hit records' atoms are first gathered into the batch registers with
-// v_writelane (one entry per DISTINCT atom of a pass: lanes naming the same atom are folded by a ballot). Column 0 = TRUE is entry 0
-// for the life of the wave. A column's word for the DNF step is two dependent LDS reads (slot, value), like the sparse file's.
-// Duplicates: a column belongs to one pass; inside a pass only an overflow chain (a request with more than two atoms) can name a column that
-// another lane's record already named — a pass with such a record appends one column at a time through a lookup of slot[] (rare).
-// (a wave's LDS: verdictplan.h, verdict_wave_lds_el)
-
-// one wave-uniform (column, mask) into lane l of three registers (see park64)
-#pragma clang diagnostic push
-#pragma clang diagnostic ignored "-Winline-asm"
-__device__ __forceinline__ void park96(uint32_t &c, uint32_t &lo, uint32_t &hi, const uint32_t col, const unsigned long long m, const uint32_t l) {
-    // (scalar registers whatever the register allocator did with the wave-uniform values: under scalar-register pressure it keeps some in
-    // vector registers and hands THOSE to an "s" operand)
-    const uint32_t s_col = (uint32_t)__builtin_amdgcn_readfirstlane((int)col), s_l = (uint32_t)__builtin_amdgcn_readfirstlane((int)l);
-    const uint32_t s_lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)m), s_hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(m >> 32));
-    asm volatile("s_mov_b32 m0, %4\n\ts_nop 0\n\tv_writelane_b32 %0, %3, m0\n\tv_writelane_b32 %1, %5, m0\n\tv_writelane_b32 %2, %6, m0"
-                 : "+v"(c), "+v"(lo), "+v"(hi)
-                 : "s"(s_col), "s"(s_l), "s"(s_lo), "s"(s_hi)
-                 : "m0");
-}
-#pragma clang diagnostic pop
-
-// HITS (PWAF_OPT_RULE_HITS, only when a hit output was asked for): every candidate's match word is reported, not only the first firing one.
-// The candidate loop then runs to the end of the list, a lane keeps acc_or beside fire, and per chunk of 64 candidates the non-zero words
-// of caller rules are queued for a.hits (the wave's queue leaves up to 64 entries at a time: one atomic on n_hits per flush). Requests answered by a gate are
-// masked out: the two gate pseudo rules are device rules 0 and 1 (compile.cpp prepends them), the candidate list ascends, so they stand
-// in the FIRST chunk and a gated request is decided (both gates always take effect) before that chunk's words are appended.
-// (HITS, up to 64 passes: 5 waves per SIMD. The plain kernel fills its 80 registers at 6; the queue's three more put one into scratch there.
-// A CU then holds ONE 12-wave workgroup at a time; the persistent grid is unchanged, its workgroups take turns.)
-// ROUTES (an engine created with routes, only when a route output was asked for; never with HITS): the caller's routes are the device rules
-// [a.route_base, a.n_rules), behind every rule, with effects {ALLOW, ALLOW}: they never fire. A lane that holds one keeps its match word
-// where a rule's lane keeps `fire`; the candidate list ascends, so a chunk's route lanes are its upper lanes (one wave-uniform mask). A second
-// ordered pick over those lanes, against `rpending`, gives each request its first route, whatever its verdict: the loop runs until both
-// the verdicts and the routes of the group are known.
-template <bool LT, int BR, bool HITS, bool ROUTES>
-__global__ __launch_bounds__(768, BR == 1 ? (HITS ? 5 : 6) : 1) void verdict2_kernel(VerdictArgs a) {
-    static_assert(!(HITS && ROUTES), "one call answers one of the reports");
-    extern __shared__ __align__(16) unsigned char lds[];
-    const uint32_t tid = threadIdx.x, wave = wave_index(), lane = tid & 63, n_waves = blockDim.x >> 6;
-#ifdef PWAF_PROFILING
-    const uint32_t dbg_skip = a.debug_skip;
-#else
-    constexpr uint32_t dbg_skip = 0;
-#endif
-    const uint32_t rulew = (a.n_rules + 31) / 32;
-    const uint32_t e_cap = a.v_cap;  // entries held in LDS (entry 0 = TRUE included); later entries: the wave's spill array, by column
-    const uint32_t wave_bytes = verdict_wave_lds_el(a.n_cols, a.n_rules, e_cap);
-    unsigned char *mine = lds + (size_t)wave * wave_bytes;
-    unsigned long long *vals = reinterpret_cast<unsigned long long *>(mine);
-    uint32_t *rulebm = reinterpret_cast<uint32_t *>(vals + e_cap);
-    uint16_t *ecol = reinterpret_cast<uint16_t *>(rulebm + rulew);
-    uint16_t *cand = reinterpret_cast<uint16_t *>(reinterpret_cast<unsigned char *>(ecol) + ((e_cap * 2 + 3) & ~3u));
-    uint8_t *slot = reinterpret_cast<unsigned char *>(cand) + ((a.n_rules * 2 + 3) & ~3u);
-    const uint32_t slot_words = ((a.n_cols + 7) & ~7u) / 4;
-    unsigned long long *spill = a.spill + (size_t)(blockIdx.x * n_waves + wave) * a.n_cols;
-    unsigned char *tables = lds + (size_t)n_waves * wave_bytes;
-    const VerdictTables vt = verdict_tables(a.n_cols, a.n_rules, a.n_trig, a.n_lits, LT);
-    uint16_t *l_trig_off = reinterpret_cast<uint16_t *>(tables + vt.trig_off);
-    uint16_t *l_trig_rules = reinterpret_cast<uint16_t *>(tables + vt.trig_rules);
-    uint2 *l_rules = reinterpret_cast<uint2 *>(tables + vt.rules);
-    uint32_t *l_lits = reinterpret_cast<uint32_t *>(tables + vt.lits);
-    uint16_t *l_pub = reinterpret_cast<uint16_t *>(tables + vt.pub);
-    if (LT) {
-        for (uint32_t k = tid; k <= a.n_cols; k += blockDim.x) l_trig_off[k] = (uint16_t)a.trig_off[k];
-        for (uint32_t k = tid; k < a.n_trig; k += blockDim.x) l_trig_rules[k] = a.trig_rules[k];
-        for (uint32_t k = tid; k < a.n_rules; k += blockDim.x) {
-            const DevRule dr = a.rules[k];
-            l_rules[k] = make_uint2(dr.lit_off, dr.lit_cnt | ((uint32_t)dr.eff_unverified << 16) | ((uint32_t)dr.eff_verified << 24));
-            l_pub[k] = (uint16_t)dr.public_idx;
-        }
-        for (uint32_t k = tid; k < a.n_lits; k += blockDim.x) l_lits[k] = a.lits[k];
-    }
-    // the wave's slot bytes start clean; entry 0 is column 0 = TRUE
-    for (uint32_t k = lane; k < slot_words; k += 64) reinterpret_cast<uint32_t *>(slot)[k] = 0u;
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-    if (lane == 0) {
-        slot[0] = 1;
-        vals[0] = ~0ull;
-        ecol[0] = 0;
-    }
-    __syncthreads();
-    const unsigned long long mybit = 1ull << lane;
-    const unsigned long long lt_mask = mybit - 1;
-    unsigned long long cnt_block = 0, cnt_captcha = 0, cnt_bypass = 0, cnt_allow = 0;
-    // (HITS) the wave's entries wait in three registers, lane k = entry k, and leave up to 64 at a time: ONE atomic on n_hits and one coalesced
-    // store per flush. (One returning atomic per wave and chunk of candidates was measured at 1.5 ms of a 1.78 ms kernel for 10M requests x
-    // 1024 rules: ~7 entries per group, a few hundred thousand same-address atomics that the L2 performs one after the other.) An entry is
-    // {rule | k << 16, mask}: its group is the k-th of this wave counted from q_g0, the group of the queue's first entry.
-    uint32_t q_rk = 0, q_lo = 0, q_hi = 0, q_n = 0, q_g0 = 0, q_k = 0;
-    const uint32_t q_stride = gridDim.x * n_waves;
-    auto q_flush = [&]() {
-        if (q_n == 0) return;
-        uint32_t slot0 = 0;
-        if (lane == 0) slot0 = atomicAdd(a.n_hits, q_n);
-        slot0 = __builtin_amdgcn_readfirstlane(slot0);
-        const uint32_t at = slot0 + lane;
-        if (lane < q_n && at < a.hits_cap) {  // (never at or beyond hits + hits_cap, whatever the counter held)
-            pwaf_rule_hit h;
-            h.rule_idx = q_rk & 0xFFFFu;
-            h.group = q_g0 + (q_rk >> 16) * q_stride;
-            h.mask = ((unsigned long long)q_hi << 32) | q_lo;
-            a.hits[at] = h;
-        }
-        q_n = 0;
-    };
-    const uint32_t h_always = lane < rulew ? a.always_rules[lane] : 0u;
-    const bool true_triggers = a.trig_off[1] != a.trig_off[0];  // rules whose chosen positive literal is the constant TRUE (`expression: None`)
-
-    // inputs one group ahead, visited bits two groups ahead: see verdict_kernel
-    // (<= 64 passes: a group of the 1k-rule set has one dense pass and two or three non-empty sparse ones; every slot costs a dozen instructions per group
-    // whether it is used or not — the rest are fetched inside the group)
-    constexpr int kPre = BR == 1 ? 4 : kVerdictPre;
-    constexpr int kBitRegs = BR;
-    struct Bits {
-        unsigned long long w[kBitRegs];
-    };
-    struct Inputs {
-        uint32_t rv[kPre];
-        uint32_t base[kPre];
-        Bits bits;
-        unsigned long long rest[kBitRegs];
-        uint32_t flags, n_pairs;
-        uint4 pair0;
-        uint32_t res0;
-        // the lazy comparison variables (VerdictArgs::lazy_var, at most two), RAW — nothing here may wait for a load: a length as the request's END
-        // offset (its start is the neighbour lane's end; lane 0's is fetched when an atom is evaluated: rare), the port as it is
-        uint32_t lraw[2];
-    };
-    const uint32_t *my_bits[kBitRegs];
-    uint32_t my_base[kBitRegs];
-    bool my_live[kBitRegs];
-#pragma unroll
-    for (int r = 0; r < kBitRegs; r++) {
-        const uint32_t ps = (uint32_t)r * 64 + lane;
-        my_live[r] = ps < a.n_passes;
-        my_bits[r] = nullptr;
-        my_base[r] = 0;
-        if (my_live[r]) {
-            const PassInfo pi = a.passes[ps];
-            const uint32_t kind = pi.kind_slot >> 24, sl = pi.kind_slot & 0xFFFFFFu;
-            if (kind == 3) my_live[r] = false;
-            my_bits[r] = kind == 1 ? a.cand_bits + (size_t)sl * a.bit_words : kind == 2 ? a.visit_bits + (size_t)sl * a.bit_words : nullptr;
-            my_base[r] = pi.base;
-        }
-    }
-    auto request_bits = [&](const uint32_t g, Bits &bt) {
-        const uint32_t gg = min(g, a.n_groups - 1);
-#pragma unroll
-        for (int r = 0; r < kBitRegs; r++)
-            bt.w[r] = !my_live[r] ? 0ull : my_bits[r] != nullptr ? *reinterpret_cast<const unsigned long long *>(my_bits[r] + 2 * (size_t)gg) : ~0ull;
-    };
-    auto request_inputs = [&](const uint32_t g, const Bits &bt, Inputs &in) {
-        const uint32_t i = g * 64 + lane;
-        const bool valid = g < a.n_groups && i < a.n;
-        unsigned long long nzp[kBitRegs];
-        // The visited words (the youngest loads in flight: request_bits of the previous turn) are waited for HERE, once. Every use below
-        // sits under a wave-uniform condition, where the compiler waits for ALL outstanding loads again — after the first slot that
-        // means for the record load just issued: one exposed round trip per prefetch slot.
-#pragma unroll
-        for (int r = 0; r < kBitRegs; r++) asm volatile("" ::"v"(bt.w[r]));
-#pragma unroll
-        for (int r = 0; r < kBitRegs; r++) nzp[r] = (uint32_t)r * 64 < a.n_passes ? __ballot(bt.w[r] != 0) : 0ull;
-#pragma unroll
-        for (int q = 0; q < kPre; q++) {
-            uint32_t ps = kNone, base = kNone;
-            unsigned long long word = 0;
-#pragma unroll
-            for (int r = 0; r < kBitRegs; r++) {
-                if (ps == kNone && nzp[r] != 0) {
-                    const int l = __builtin_ctzll(nzp[r]);
-                    nzp[r] &= nzp[r] - 1;
-                    ps = (uint32_t)r * 64 + (uint32_t)l;
-                    word = ((unsigned long long)(uint32_t)__builtin_amdgcn_readlane((int)(bt.w[r] >> 32), l) << 32) | (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)bt.w[r], l);
-                    base = (uint32_t)__builtin_amdgcn_readlane((int)my_base[r], l);
-                }
-            }
-            in.base[q] = base;
-            in.rv[q] = (ps != kNone && valid && ((word >> lane) & 1ull)) ? a.rec[(size_t)ps * a.n + i] : 0u;
-        }
-#pragma unroll
-        for (int r = 0; r < kBitRegs; r++) in.rest[r] = nzp[r];
-        in.bits = bt;
-        in.flags = valid ? (uint32_t)a.flags[i] : 0u;
-        const uint32_t gg = min(g, a.n_groups - 1);
-        {
-            // one register, three group-wide words: lane 0 = the attribute kernel's pair count, lane 1 + s = the group's FIRST offset of lazy length
-            // variable s (lane 0's start: every other lane's start is its neighbour's end)
-            const uint32_t *src = a.ghdr + gg;
-#pragma unroll
-            for (uint32_t sl = 0; sl < 2; sl++) {
-                if (sl >= a.n_lazy_var) break;
-                const uint32_t vi = a.lazy_var[sl];
-                if (vi != 5u && lane == 1u + sl) src = (vi < 5u ? a.off[vi] : a.hoff[vi - 7u]) + gg * 64u;
-            }
-            in.n_pairs = *src;
-        }
-        in.pair0 = a.gpairs[(size_t)gg * a.pair_stride + lane];
-        in.res0 = (a.res_words && valid) ? a.res_match[i] : 0u;
-        in.lraw[0] = in.lraw[1] = 0u;
-        const uint32_t ii = valid ? i : 0u;
-#pragma unroll
-        for (uint32_t sl = 0; sl < 2; sl++) {
-            if (sl >= a.n_lazy_var || (dbg_skip & 2048u)) break;  // (wave-uniform)
-            const uint32_t vi = a.lazy_var[sl];
-            if (vi == 5u) {
-                in.lraw[sl] = a.port[ii];
-            } else {
-                const uint32_t *o = vi < 5u ? a.off[vi] : a.hoff[vi - 7u];
-                in.lraw[sl] = o[ii + 1];
-            }
-        }
-    };
-    const uint32_t g_stride = gridDim.x * n_waves;
-    Inputs cur;
-    Bits b_nxt;
-    {
-        Bits b_cur;
-        request_bits(blockIdx.x * n_waves + wave, b_cur);
-        request_inputs(blockIdx.x * n_waves + wave, b_cur, cur);
-        request_bits(blockIdx.x * n_waves + wave + g_stride, b_nxt);
-    }
-
-    for (uint32_t g = blockIdx.x * n_waves + wave; g < a.n_groups; g += g_stride) {
-        const uint32_t i = g * 64 + lane;
-        const bool valid = i < a.n;
-        const unsigned long long valid_mask = __ballot(valid);
-        Inputs nxt;
-        request_inputs(g + g_stride, b_nxt, nxt);
-        request_bits(g + 2 * g_stride, b_nxt);
-
-        // 1. the rule bitmap starts from the rules that need no positive column (a term made of negations only)
-        for (uint32_t k = lane; k < rulew; k += 64) rulebm[k] = k < 64 ? h_always : a.always_rules[k];
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-
-        const uint32_t flags = cur.flags;
-        const uint4 *pairs = a.gpairs + (size_t)g * a.pair_stride;
-        const uint32_t n_pairs = (uint32_t)__builtin_amdgcn_readlane((int)cur.n_pairs, 0);
-        const unsigned long long verified_mask = __ballot(valid && (flags & PWAF_FLAG_CAPTCHA_VERIFIED));
-
-        uint32_t n_entries = 1;  // (entry 0 = TRUE)
-        // a column's rules: the rule bitmap gets the trigger list of every appended column
-        auto triggers = [&](const uint32_t c) {
-            if (dbg_skip & 8u) return;
-            const uint32_t kb = LT ? (uint32_t)l_trig_off[c] : a.trig_off[c], ke = LT ? (uint32_t)l_trig_off[c + 1] : a.trig_off[c + 1];
-            for (uint32_t k = kb; k < ke; k++) {
-                const uint32_t r = LT ? (uint32_t)l_trig_rules[k] : (uint32_t)a.trig_rules[k];
-                atomicOr(&rulebm[r >> 5], 1u << (r & 31));
-            }
-        };
-        // `cnt` entries, lane k < cnt holding entry n_entries + k (distinct columns, none of them appended before)
-        if (true_triggers && lane == 0) triggers(0);  // (entry 0 = TRUE is never appended: a match-all rule is filed under column 0)
-        auto append_batch = [&](const uint32_t c, const uint32_t lo, const uint32_t hi, const uint32_t cnt) {
-            if (lane < cnt) {
-                const uint32_t e = n_entries + lane;
-                const unsigned long long m = ((unsigned long long)hi << 32) | lo;
-                if (e < e_cap) {
-                    slot[c] = (uint8_t)(e + 1u);
-                    vals[e] = m;
-                    ecol[e] = (uint16_t)c;
-                } else {
-                    slot[c] = 255;
-                    atomicExch(spill + c, m);  // (a read-modify-write, like everything that touches a spilled word: performed at L2 in order)
-                }
-                triggers(c);
-            }
-            n_entries += cnt;
-        };
-        // the batch registers: the attribute kernel's first pairs are entries as they come (lane k = pair k); the scans' entries are gathered
-        // behind them one (wave-uniform) column at a time — one batch, one append, in the common case
-        const uint32_t n_first = (dbg_skip & 2u) ? 0u : min(n_pairs, 64u);
-        uint32_t b_col = cur.pair0.x, b_lo = cur.pair0.z, b_hi = cur.pair0.w, bn = n_first;
-        if (bn == 64) {
-            append_batch(b_col, b_lo, b_hi, 64);
-            bn = 0;
-        }
-        auto flush = [&]() {
-            if (bn == 0) return;
-            append_batch(b_col, b_lo, b_hi, bn);
-            bn = 0;
-        };
-        auto append = [&](const uint32_t c, const unsigned long long m) {
-            park96(b_col, b_lo, b_hi, c, m, bn);
-            if (++bn == 64) flush();
-        };
-        // one wave-uniform column that MAY have an entry already (passes with overflow chains): through slot[]
-        auto merge_or_append = [&](const uint32_t c, const unsigned long long m) {
-            const uint32_t s = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)slot[c]);
-            if (s == 0) {
-                const uint32_t e = n_entries++;
-                if (lane == 0) {
-                    if (e < e_cap) {
-                        slot[c] = (uint8_t)(e + 1u);
-                        vals[e] = m;
-                        ecol[e] = (uint16_t)c;
-                    } else {
-                        slot[c] = 255;
-                        atomicExch(spill + c, m);
-                    }
-                    triggers(c);
-                }
-            } else if (lane == 0) {
-                if (s < 255u) vals[s - 1u] |= m;
-                else atomicOr(spill + c, m);
-            }
-            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-        };
-        // 2. scan results: per pass one entry per DISTINCT atom its records name (lanes naming the same atom are one ballot)
-        auto mark_hits = [&](const uint32_t rv, const uint32_t base) {
-            if (__ballot(rv != 0) == 0) return;
-            const bool chained = (rv & REC_OVERFLOW) != 0;
-            const bool any_chain = __ballot(chained) != 0;
-            if (any_chain) {
-                flush();
-                __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-            }
-            const uint32_t x0 = chained ? 0u : rv & 0x7FFFu, x1 = chained ? 0u : (rv >> 15) & 0x7FFFu;
-            unsigned long long t0 = __ballot(x0 != 0), t1 = __ballot(x1 != 0);
-            while ((t0 | t1) != 0) {
-                uint32_t xa;
-                if (t0 != 0) xa = (uint32_t)__builtin_amdgcn_readlane((int)x0, __builtin_ctzll(t0));
-                else xa = (uint32_t)__builtin_amdgcn_readlane((int)x1, __builtin_ctzll(t1));
-                const unsigned long long s0 = __ballot(x0 == xa), s1 = __ballot(x1 == xa);
-                t0 &= ~s0;
-                t1 &= ~s1;
-                if (any_chain) merge_or_append(base + xa - 1u, s0 | s1);
-                else append(base + xa - 1u, s0 | s1);
-            }
-            if (any_chain) {
-                // the chains, all lanes advancing together: per step the distinct atoms of the lanes that still have one
-                uint32_t k = chained ? rv & ~REC_OVERFLOW : kNone;
-                while (__ballot(k != kNone) != 0) {
-                    uint32_t x = 0;
-                    if (k != kNone) {
-                        const PoolEntry pe = a.pool[k];
-                        x = pe.atom + 1u;
-                        k = pe.next;
-                    }
-                    unsigned long long todo = __ballot(x != 0);
-                    while (todo != 0) {
-                        const uint32_t xa = (uint32_t)__builtin_amdgcn_readlane((int)x, __builtin_ctzll(todo));
-                        const unsigned long long same = __ballot(x == xa);
-                        todo &= ~same;
-                        merge_or_append(base + xa - 1u, same);
-                    }
-                }
-            }
-        };
-        if (!(dbg_skip & 1u)) {
-#pragma unroll
-            for (int q = 0; q < kPre; q++) {
-                if (cur.base[q] == kNone) break;
-                mark_hits(cur.rv[q], cur.base[q]);
-            }
-#pragma unroll
-            for (int r = 0; r < kBitRegs; r++) {
-                unsigned long long m = cur.rest[r];
-                while (m) {
-                    const int l = __builtin_ctzll(m);
-                    m &= m - 1;
-                    const uint32_t ps = (uint32_t)r * 64 + (uint32_t)l;
-                    const unsigned long long word = ((unsigned long long)(uint32_t)__builtin_amdgcn_readlane((int)(cur.bits.w[r] >> 32), l) << 32) |
-                                                    (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)cur.bits.w[r], l);
-                    const uint32_t base = (uint32_t)__builtin_amdgcn_readlane((int)my_base[r], l);
-                    mark_hits((valid && ((word >> lane) & 1ull)) ? a.rec[(size_t)ps * a.n + i] : 0u, base);
-                }
-            }
-        }
-        // 2b. the specialized residual program's result words: one entry per rule that matched anybody in the group
-        for (uint32_t w = 0; w < a.res_words; w++) {
-            const uint32_t mw = w == 0 ? cur.res0 : (valid ? a.res_match[(size_t)w * a.n + i] : 0u);
-            if (__ballot(mw != 0u) == 0ull) continue;
-            for (uint32_t any = wave_or(mw); any; any &= any - 1u) {
-                const uint32_t k = (uint32_t)__builtin_ctz(any);
-                append(a.res_base + 32u * w + k, __ballot(((mw >> k) & 1u) != 0u));
-            }
-        }
-        flush();
-        // 3. the attribute kernel's pairs beyond the first 64 (rare)
-        if (!(dbg_skip & 2u)) {
-            for (uint32_t p0 = 64; p0 < n_pairs; p0 += 64) {
-                const uint32_t cnt = min(64u, n_pairs - p0);
-                uint4 pr = make_uint4(0u, 0u, 0u, 0u);
-                if (lane < cnt) pr = pairs[p0 + lane];
-                append_batch(pr.x, pr.z, pr.w, cnt);
-            }
-        }
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-        // a column's word: two dependent LDS reads, no branch (entry 0 = TRUE stands in for a clean column's index) — unless the group
-        // appended more entries than LDS holds (wave-uniform, rare): then a spilled word comes from L2, where the ORs were performed
-        const bool spilled = n_entries > e_cap;
-        auto col_word = [&](const uint32_t c) -> unsigned long long {
-            const uint32_t s = slot[c];
-            if (!spilled) {
-                const unsigned long long v = vals[s ? s - 1u : 0u];
-                return s ? v : 0ull;
-            }
-            if (s == 0) return 0ull;
-            return s < 255u ? vals[s - 1u] : __hip_atomic_load(spill + c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        };
-
-        // 4. ordered compaction of the rule bitmap into the candidate list (ascending rule index = evaluation order)
-        uint32_t n_cand = 0;
-        for (uint32_t wb = 0; wb < rulew && !(dbg_skip & 16u); wb += 64) {
-            const uint32_t word = wb + lane < rulew ? rulebm[wb + lane] : 0u;
-            const uint32_t pc = (uint32_t)__builtin_popcount(word), incl = wave_scan_add(pc);
-            uint32_t pos = n_cand + incl - pc, wrd = word;
-            while (wrd) {
-                cand[pos++] = (uint16_t)((wb + lane) * 32 + (uint32_t)__builtin_ctz(wrd));
-                wrd &= wrd - 1;
-            }
-            n_cand += (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
-        }
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-
-        // 5. evaluate candidates: one lane per rule, 64 requests per ALU op; first match wins (see verdict_kernel)
-        unsigned long long pending = valid_mask;
-        uint32_t n_exact = 0;
-        bool undecided = valid;
-        uint32_t my_action = PWAF_ACTION_ALLOW, my_rule = PWAF_RULE_NONE;
-        unsigned long long gated = 0;  // (HITS) requests answered by a gate pseudo rule: known after the first chunk
-        unsigned long long rpending = ROUTES ? valid_mask : 0ull;  // (ROUTES) requests whose route is not known yet
-        uint32_t my_route = PWAF_ROUTE_NONE;
-        for (uint32_t base = 0; base < n_cand && (HITS || pending != 0 || (ROUTES && rpending != 0)) && !(dbg_skip & 32u); base += 64) {
-            unsigned long long fire = 0, eff_mask = 0;
-            unsigned long long match = 0;  // (HITS) the rule's match word whatever its actions
-            uint32_t lit_off = 0, lit_cnt = 0;
-            bool lazy_seen = false;
-            bool is_route = false;
-            if (base + lane < n_cand) {
-                const uint32_t my_cand = cand[base + lane];
-                if (ROUTES) is_route = my_cand >= a.route_base;
-                uint32_t eff_u, eff_v;
-                if (LT) {
-                    const uint2 hdr = l_rules[my_cand];
-                    lit_off = hdr.x;
-                    lit_cnt = hdr.y & 0xFFFFu;
-                    eff_u = (hdr.y >> 16) & 0xFFu;
-                    eff_v = hdr.y >> 24;
-                } else {
-                    const DevRule dr = a.rules[my_cand];
-                    lit_off = dr.lit_off;
-                    lit_cnt = dr.lit_cnt;
-                    eff_u = dr.eff_unverified;
-                    eff_v = dr.eff_verified;
-                }
-                unsigned long long acc_or = 0, acc_and = ~0ull;
-                for (uint32_t k = lit_off; k < lit_off + lit_cnt; k += 4) {
-                    uint32_t lit[4];
-#pragma unroll
-                    for (int q = 0; q < 4; q++) lit[q] = k + q < lit_off + lit_cnt ? (LT ? l_lits[k + q] : a.lits[k + q]) : 0u;
-                    unsigned long long cw[4];
-#pragma unroll
-                    // (a LAZY literal's low bits are its constant, operator and slot, not a column — up to 0x7FFFF: it must not index slot[]
-                    // or the spill array; its word is not used below)
-                    for (int q = 0; q < 4; q++) cw[q] = (lit[q] & LIT_LAZY) ? 0ull : col_word(lit[q] & LIT_ATOM_MASK);
-#pragma unroll
-                    for (int q = 0; q < 4; q++) {
-                        // a LAZY comparison atom reads as TRUE here, negated or not: what comes out is a superset of the rule's matches
-                        const unsigned long long t = (lit[q] & LIT_NEG) ? ~cw[q] : cw[q];
-                        acc_and &= (lit[q] & LIT_LAZY) ? ~0ull : t;
-                        lazy_seen = lazy_seen || (lit[q] & LIT_LAZY) != 0u;
-                        if (lit[q] & LIT_TERM_END) {
-                            acc_or |= acc_and;
-                            acc_and = ~0ull;
-                        }
-                    }
-                }
-                eff_mask = (eff_u ? ~verified_mask : 0ull) | (eff_v ? verified_mask : 0ull);
-                // (ROUTES: a route's lane keeps its match word in `fire` — its own eff_mask is 0 — through the exact evaluation below)
-                if (ROUTES && is_route) eff_mask = valid_mask;
-                fire = acc_or & eff_mask;
-                if (HITS) match = acc_or & valid_mask;
-            }
-            // Rules with lazy comparison atoms whose OTHER literals hold for somebody (rare): the rule again, exactly, one request per lane —
-            // an eager literal's bit from its column word, a lazy one from the request's own value (fetched with the group's inputs)
-            // (HITS: also for a rule whose match word is non-zero while no action of its takes effect for those requests)
-            if (dbg_skip & 512u) n_exact += (uint32_t)__builtin_popcountll(__ballot(lazy_seen && (HITS ? match : fire) != 0));
-            for (unsigned long long need = (dbg_skip & 1024u) ? 0ull : __ballot(lazy_seen && (HITS ? match : fire) != 0); need != 0; need &= need - 1) {
-                const int j = __builtin_ctzll(need);
-                const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)lit_off, j), cn = (uint32_t)__builtin_amdgcn_readlane((int)lit_cnt, j);
-                const unsigned long long em = ((unsigned long long)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(eff_mask >> 32), j) << 32) |
-                                              (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)eff_mask, j);
-                bool r_or = false, r_and = true;
-                for (uint32_t k = lo; k < lo + cn; k++) {
-                    const uint32_t lit = (uint32_t)__builtin_amdgcn_readfirstlane((int)(LT ? l_lits[k] : a.lits[k]));
-                    bool bit;
-                    if (lit & LIT_LAZY) {
-                        const uint32_t cc = lit & 0xFFFFu, sl = (lit >> 17) & 1u;
-                        const uint32_t raw = sl ? cur.lraw[1] : cur.lraw[0];  // (no dynamic index: the inputs stay in registers)
-                        uint32_t v = raw;
-                        if (a.lazy_var[sl] != 5u) {  // length = end - the neighbour's end (lane 0: the group's first offset)
-                            const uint32_t st0 = sl ? (uint32_t)__builtin_amdgcn_readlane((int)cur.n_pairs, 2) : (uint32_t)__builtin_amdgcn_readlane((int)cur.n_pairs, 1);
-                            v = raw - (uint32_t)__builtin_amdgcn_update_dpp((int)st0, (int)raw, 0x138 /* wave_shr:1 */, 0xF, 0xF, false);
-                        }
-                        bit = (lit & 0x10000u) ? v <= cc : v == cc;
-                        if (lit & 0x40000u) bit = !bit;  // (the atom's polarity on the device: engine.cpp, POLARITY)
-                    } else {
-                        bit = ((col_word(lit & LIT_ATOM_MASK) >> lane) & 1ull) != 0ull;
-                    }
-                    if (lit & LIT_NEG) bit = !bit;
-                    r_and = r_and && bit;
-                    if (lit & LIT_TERM_END) {
-                        r_or = r_or || r_and;
-                        r_and = true;
-                    }
-                }
-                const unsigned long long exact_all = __ballot(r_or && valid);
-                if (HITS) {  // the match word is the exact result WITHOUT the action mask (fire follows from it below)
-                    uint32_t m_lo = (uint32_t)match, m_hi = (uint32_t)(match >> 32);
-                    park64(m_lo, m_hi, exact_all, (uint32_t)j);
-                    match = ((unsigned long long)m_hi << 32) | m_lo;
-                } else {
-                    uint32_t f_lo = (uint32_t)fire, f_hi = (uint32_t)(fire >> 32);
-                    park64(f_lo, f_hi, exact_all & em, (uint32_t)j);
-                    fire = ((unsigned long long)f_hi << 32) | f_lo;
-                }
-            }
-            // (HITS: one word less to keep through the loop above; the same value on every valid request, and `pending` holds no other)
-            if (HITS) fire = match & eff_mask;
-            unsigned long long firing = __ballot(fire != 0);
-            unsigned long long rfiring = 0;
-            if (ROUTES) {  // the route lanes' words are picked apart from the rules': they decide no verdict
-                const unsigned long long rlanes = __ballot(is_route);
-                rfiring = firing & rlanes;
-                firing &= ~rlanes;
-            }
-            uint32_t first = kNone;
-            while (firing != 0 && pending != 0) {
-                const int j = __builtin_ctzll(firing);
-                firing &= firing - 1;
-                const unsigned long long fj = (((unsigned long long)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(fire >> 32), j) << 32) |
-                                               (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)fire, j)) & pending;
-                if (fj & mybit) first = (uint32_t)j;
-                pending &= ~fj;
-            }
-            if (undecided && first != kNone) {
-                undecided = false;
-                const uint32_t jc = cand[base + first];
-                uint32_t eff_u, eff_v;
-                if (LT) {
-                    const uint32_t y = l_rules[jc].y;
-                    eff_u = (y >> 16) & 0xFFu;
-                    eff_v = y >> 24;
-                    const uint32_t pi = l_pub[jc];
-                    my_rule = pi >= 0xFFF0u ? 0xFFFF0000u | pi : pi;
-                } else {
-                    const DevRule dr = a.rules[jc];
-                    eff_u = dr.eff_unverified;
-                    eff_v = dr.eff_verified;
-                    my_rule = dr.public_idx;
-                }
-                my_action = (verified_mask & mybit) ? eff_v : eff_u;
-            }
-            if (ROUTES) {
-                // the second ordered pick: the first route lane whose word holds the request (a request leaves rpending once)
-                uint32_t rfirst = kNone;
-                while (rfiring != 0 && rpending != 0) {
-                    const int j = __builtin_ctzll(rfiring);
-                    rfiring &= rfiring - 1;
-                    const unsigned long long rj = (((unsigned long long)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(fire >> 32), j) << 32) |
-                                                   (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)fire, j)) & rpending;
-                    if (rj & mybit) rfirst = (uint32_t)j;
-                    rpending &= ~rj;
-                }
-                if (rfirst != kNone) {
-                    const uint32_t jc = cand[base + rfirst];
-                    my_route = LT ? (uint32_t)l_pub[jc] : a.rules[jc].public_idx;
-                }
-            }
-            if (HITS) {
-                if (base == 0) gated = __ballot(valid && !undecided && my_rule >= 0xFFFFFFF0u);
-                // (a gate pseudo rule's own word is a subset of `gated`: nothing of it is left, so every non-zero word is a caller rule's)
-                const unsigned long long word = match & ~gated;
-                unsigned long long has = __ballot(word != 0);
-                if (has != 0) {
-                    uint32_t pub = 0;  // the caller's index of this lane's rule (< 65520: engine.cpp)
-                    if (word != 0) {
-                        const uint32_t c = cand[base + lane];
-                        pub = LT ? (uint32_t)l_pub[c] : a.rules[c].public_idx;
-                        if (a.rule_hits != nullptr) atomicAdd(&a.rule_hits[pub], (unsigned long long)__builtin_popcountll(word));
-                    }
-                    if (a.n_hits != nullptr) {
-                        if (q_n + (uint32_t)__builtin_popcountll(has) > 64u) q_flush();
-                        if (q_n == 0) {
-                            q_g0 = g;
-                            q_k = 0;
-                        }
-                        for (; has != 0; has &= has - 1) {  // one entry per lane with a word, into lane q_n of the queue registers
-                            const int j = __builtin_ctzll(has);
-                            const unsigned long long wj = ((unsigned long long)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(word >> 32), j) << 32) |
-                                                          (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)word, j);
-                            park96(q_rk, q_lo, q_hi, (uint32_t)__builtin_amdgcn_readlane((int)pub, j) | (q_k << 16), wj, q_n);
-                            q_n++;
-                        }
-                    }
-                }
-            }
-        }
-        if (dbg_skip & 512u) my_rule = n_exact;  // profiling aid: rules evaluated exactly for their lazy comparison atoms
-        if (dbg_skip & 64u) my_rule = n_cand | (n_entries << 16);  // profiling aid: candidates and entries of the group instead of the deciding rule
-
-        // 6. outputs
-        if (valid) {
-            uint2 v;
-            v.x = my_action;
-            v.y = my_rule;
-            *reinterpret_cast<uint2 *>(&a.out[i]) = v;
-            if (ROUTES) a.route[i] = my_route;  // (one coalesced 4-byte store per lane; PWAF_ROUTE_NONE where no route matched)
-        }
-        const unsigned long long m_block = __ballot(valid && my_action == PWAF_ACTION_BLOCK);
-        const unsigned long long m_captcha = __ballot(valid && my_action == PWAF_ACTION_CAPTCHA);
-        const unsigned long long m_bypass = __ballot(valid && my_action == PWAF_ACTION_BYPASS);
-        cnt_block += (unsigned)__builtin_popcountll(m_block);
-        cnt_captcha += (unsigned)__builtin_popcountll(m_captcha);
-        cnt_bypass += (unsigned)__builtin_popcountll(m_bypass);
-        cnt_allow += (unsigned)__builtin_popcountll(valid_mask & ~(m_block | m_captcha | m_bypass));
-        if (a.match_idx != nullptr) {
-            const unsigned long long hit = m_block | m_captcha | m_bypass;
-            if (hit) {
-                uint32_t basei = 0;
-                if (lane == 0) basei = atomicAdd(a.n_matches, (uint32_t)__builtin_popcountll(hit));
-                basei = __builtin_amdgcn_readfirstlane(basei);
-                if (hit & mybit) a.match_idx[basei + (uint32_t)__builtin_popcountll(hit & lt_mask)] = i;
-            }
-        }
-        // 7. the group cleans up after itself: the slot bytes of its entries (all of slot[] when entries went beyond e_cap: their columns
-        //    are not listed)
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-        if (n_entries <= e_cap) {
-            for (uint32_t e = 1u + lane; e < n_entries; e += 64) slot[ecol[e]] = 0;
-        } else {
-            for (uint32_t k = lane; k < slot_words; k += 64) reinterpret_cast<uint32_t *>(slot)[k] = 0u;
-            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-            if (lane == 0) slot[0] = 1;
-        }
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-        if (HITS && q_n != 0 && ++q_k == 0x10000u) q_flush();  // (an entry's group index relative to the queue's first has 16 bits)
-        cur = nxt;
-    }
-    if (HITS && a.n_hits != nullptr) q_flush();
-    __syncthreads();
-    unsigned long long *tally = reinterpret_cast<unsigned long long *>(lds);
-    if (lane == 0) {
-        tally[wave * 4 + PWAF_ACTION_ALLOW] = cnt_allow;
-        tally[wave * 4 + PWAF_ACTION_BLOCK] = cnt_block;
-        tally[wave * 4 + PWAF_ACTION_CAPTCHA] = cnt_captcha;
-        tally[wave * 4 + PWAF_ACTION_BYPASS] = cnt_bypass;
-    }
-    __syncthreads();
-    if (a.counts != nullptr && tid < 4) {
-        unsigned long long sum = 0;
-        for (uint32_t wv = 0; wv < n_waves; wv++) sum += tally[wv * 4 + tid];
-        if (sum) atomicAdd(&a.counts[tid], sum);
-    }
-}
-
-// -------------------------------------------------------------------------------------------------
-// attributes: everything about a request that is NOT a string scan — GeoIP record, ip-list membership, country / integer-set
-// membership, length / port / asn comparisons — reduced per 64-request group to a list of (column, 64-request mask) pairs
-// -------------------------------------------------------------------------------------------------
-// The lookups are chains of dependent gathers (DIR-24 / trie levels, membership rows); the kernel keeps only its small constant tables
-// in LDS (see the last point below) and does not depend on the scans, so it runs BESIDE them on the engine's side stream at the lowest
-// wave priority. One wave = one 64-request group; the verdict kernel only copies the group's pairs into its column file.
-//
-// What keeps it short (round 2: it had become the longest kernel, 2.8 GB fetched for 0.38 GB of input):
-//   * everything that is a function of the GeoIP record — country-table bits, asn-set bits and the asn comparisons — is folded at
-//     engine creation into a CLASS row, and records with equal rows share a class (a few hundred classes for 600k records: the
-//     table is cache-resident, class 0 = "no predicate holds" needs no row at all);
-//   * IPv4: ONE gather into a 2^24 x 4-byte table (DIR-24-8, 64 MiB) yields class | membership-set id << 16; prefixes longer than
-//     /24 and oversized ids escape to an 8-byte side table and continue in the 8-bit trie nodes;
-//   * a group's inputs are requested TWO groups ahead and its DIR-24 / root entries ONE group ahead, so the long-latency loads of the
-//     next groups are in flight while the current group's rows are transposed (few waves per CU: nothing else hides them);
-//   * the constant tables the group loop reads AFTER it has issued that prefetch — the (source word, bit) -> column table, the
-//     comparison atoms and short literals beyond the 64 held in registers — are staged once per workgroup in LDS. Read from global
-//     memory (the stores to the pair list may alias them, so the compiler cannot hoist the loads) each read was followed by a wait for
-//     ALL outstanding loads — they return in order — which drained the prefetch once per group: one exposed L2 round trip per present
-//     source word on top of it. LDS reads are counted apart from the vector-memory loads, so the prefetch stays in flight.
-static constexpr uint32_t DIR_ESCAPE = 0x80000000u;
-
-// ipres_kernel (round 3): the address lookups of the attribute path as a kernel of their own — one lane per request, ~20 registers,
-// full occupancy. Round 2 did them inside attr_kernel, whose transposes need ~128 registers (4 waves per SIMD) and whose waves each
-// walked one 64-request group at a time: every group waited for its own DIR-24 line (a miss to the Infinity Cache / HBM) and then
-// for the trie levels of its few IPv6 lanes, with 16 waves per CU to hide it all — 0.44 ms alone for 10M requests, the longest
-// kernel of the step. Here 32 waves per CU overlap those waits, and an IPv4 address behind the DIR-24 table costs ONE gather (round 2
-// also fetched both 16-bit root entries for every lane and threw them away). Output: the GeoIP CLASS and the ip-list membership SET
-// of every request, packed into one word (class | set << 16) when both fit 16 bits (else two words).
-//
-// COARSE (csrc/dirtable.h; launch shape: ipres_shape()): the workgroup stages the coarse bitmap — one bit per block of
-// 2^dir_coarse_shift /24s, at most 64 KiB — in LDS, and an IPv4 lane reads its block's bit there before anything else. Clear = the
-// answer is dir_common and the lane issues no global load at all: an LDS gather takes neither a texture-addresser slot nor an
-// L1 -> L2 request, which are what bound this kernel. Set = the lookup goes on as without the level. 8 waves per SIMD as before.
-template <bool PACKED, bool COARSE>
-__global__ __launch_bounds__(COARSE ? 1024 : 256, COARSE ? 8 : 1) void ipres_kernel(VerdictArgs a) {
-    // A lookup is a chain of dependent accesses (address bytes -> first level -> run bitmap -> value; IPv6: root -> trie nodes), each an
-    // L2 / Infinity-Cache round trip: with one request per lane at a time the kernel was latency-bound even at 32 waves per CU (0.24 ms
-    // for 10M requests, 19 chains per lane one after the other). Every lane now walks U = 4 requests in lockstep: each phase issues
-    // the loads of all four before any is used.
-    constexpr uint32_t U = 4;
-    extern __shared__ uint4 ipres_lds[];  // COARSE: the coarse bitmap (dir_coarse_bytes)
-    const bool from_row = a.asn == nullptr;
-#ifdef PWAF_PROFILING
-    // timing experiments (wrong results): bit 16 = no table lookups for IPv4, bit 17 = no trie walks for IPv6
-    const bool dir = a.dir_chunks != nullptr && !((a.debug_skip >> 16) & 1u);
-    const bool skip_v6 = (a.debug_skip >> 17) & 1u, skip_v4 = (a.debug_skip >> 16) & 1u;
-#else
-    const bool dir = a.dir_chunks != nullptr;
-    constexpr bool skip_v6 = false, skip_v4 = false;
-#endif
-    const uint32_t T = gridDim.x * blockDim.x;
-    uint32_t i0 = blockIdx.x * blockDim.x + threadIdx.x;
-    uint4 raw[U];
-    uint32_t v6b[U];
-    // the addresses and families of the lane's four requests (a dead slot re-reads the lane's first request)
-    auto load_inputs = [&](uint32_t base) {
-#pragma unroll
-        for (uint32_t u = 0; u < U; u++) {
-            const uint32_t j = base + u * T < a.n ? base + u * T : base;
-            raw[u] = *reinterpret_cast<const uint4 *>(a.ip + (size_t)j * 16);
-            v6b[u] = a.ip_is_v6[j];
-        }
-    };
-    bool loaded = false;
-    if (COARSE) {
-        // Staged BEHIND the first sweep's address loads, so that both share one round trip (loads return in order: the wait for the
-        // bitmap's words covers the addresses): 16-byte loads, four in flight per lane — the whole bitmap in one trip at 64 KiB / 1024
-        // or 32 KiB / 512 threads. A lane without a request (the last workgroup) stages with the others and loads request 0.
-        load_inputs(i0 < a.n ? i0 : 0u);
-        loaded = true;
-        const uint4 *src = reinterpret_cast<const uint4 *>(a.dir_coarse);
-        const uint32_t n16 = a.dir_coarse_bytes >> 4;
-        for (uint32_t j = threadIdx.x; j < n16; j += 4u * blockDim.x) {
-            uint4 w[4];
-#pragma unroll
-            for (uint32_t q = 0; q < 4; q++) w[q] = src[min(j + q * blockDim.x, n16 - 1u)];
-#pragma unroll
-            for (uint32_t q = 0; q < 4; q++)
-                if (j + q * blockDim.x < n16) ipres_lds[j + q * blockDim.x] = w[q];
-        }
-        __syncthreads();
-    }
-    for (; i0 < a.n; i0 += T * U) {
-        uint32_t idx[U], ipw[U][4], eg[U], ei[U], k[U];
-        bool live[U], v6[U], geo_walk[U], chunked[U];
-        if (!loaded) load_inputs(i0);
-        loaded = false;
-#pragma unroll
-        for (uint32_t u = 0; u < U; u++) {
-            idx[u] = i0 + u * T;
-            live[u] = idx[u] < a.n;
-        }
-        uint32_t first[U], top16[U];
-#pragma unroll
-        for (uint32_t u = 0; u < U; u++) {
-            ipw[u][0] = raw[u].x; ipw[u][1] = raw[u].y; ipw[u][2] = raw[u].z; ipw[u][3] = raw[u].w;
-            v6[u] = v6b[u] != 0;
-            // GeoipDB::lookup, pingoo/geoip.rs:73-91: loopback / multicast are "not found"
-            geo_walk[u] = false;
-            if (from_row && a.has_geo) {
-                if (!v6[u]) {
-                    const uint32_t b0 = ipw[u][0] & 0xFFu;
-                    geo_walk[u] = !(b0 == 127u || (b0 & 0xF0u) == 0xE0u);
-                } else {
-                    const bool loopback = ipw[u][0] == 0 && ipw[u][1] == 0 && ipw[u][2] == 0 && ipw[u][3] == 0x01000000u;
-                    geo_walk[u] = !(loopback || (ipw[u][0] & 0xFFu) == 0xFFu);
-                }
-            }
-            top16[u] = (ip_byte(ipw[u], 0) << 8) | ip_byte(ipw[u], 1);
-            // phase 1: the /16's line of the compressed DIR table (IPv4) — bitmap word, run counts, where the values live — or the two
-            // 16-bit roots
-            eg[u] = ei[u] = TRIE_LEAF;
-            chunked[u] = !v6[u] && dir;
-            first[u] = 0;
-            if (!chunked[u] && !(v6[u] ? skip_v6 : skip_v4)) {
-                if (geo_walk[u]) eg[u] = (v6[u] ? a.geo_root6 : a.geo_root4)[top16[u]];  // (the engine substitutes an all-leaf root for a family without prefixes)
-                if (a.n_ip_lists) ei[u] = (v6[u] ? a.ip_root6 : a.ip_root4)[top16[u]];
-            }
-        }
-        // phase 1b: the coarse bit of the address's block of /24s (LDS), then for the lanes it leaves the summary bit (L2-resident
-        // bitmap): 0 = the table's most common entry, no gather
-        uint32_t look[U];
-#pragma unroll
-        for (uint32_t u = 0; u < U; u++) {
-            look[u] = chunked[u] ? 1u : 0u;
-            if (COARSE && chunked[u]) {
-                const uint32_t blk = ((top16[u] << 8) | ip_byte(ipw[u], 2)) >> a.dir_coarse_shift;
-                look[u] = (reinterpret_cast<const uint32_t *>(ipres_lds)[blk >> 5] >> (blk & 31u)) & 1u;
-            }
-        }
-#pragma unroll
-        for (uint32_t u = 0; u < U; u++) {
-            if (look[u] && a.dir_summary != nullptr) {
-                const uint32_t blk = ((top16[u] << 8) | ip_byte(ipw[u], 2)) >> a.dir_sum_shift;
-                look[u] = (a.dir_summary[blk >> 5] >> (blk & 31u)) & 1u;
-            }
-        }
-        uint4 rec4[U];
-#pragma unroll
-        for (uint32_t u = 0; u < U; u++) {
-            rec4[u] = make_uint4(0u, 0u, 0u, 0u);
-            // ONE 16-byte gather: the record of the address's group of 32 /24s
-            if (look[u]) rec4[u] = *reinterpret_cast<const uint4 *>(a.dir_chunks + (size_t)top16[u] * kDirChunkWords + 4u * (ip_byte(ipw[u], 2) >> 5));
-        }
-        // phase 2: the run's entry — carried into the group, the first run inside it, or (rarely) a further run from dir_vals
-        uint32_t e24[U];
-#pragma unroll
-        for (uint32_t u = 0; u < U; u++) {
-            e24[u] = a.dir_common;
-            if (look[u]) {
-                const uint32_t rank = (uint32_t)__builtin_popcount(rec4[u].x & (0xFFFFFFFFu >> (31u - (ip_byte(ipw[u], 2) & 31u))));  // run starts at or before the /24, inside its group
-                e24[u] = rank == 0 ? rec4[u].y : rank == 1 ? rec4[u].z : a.dir_vals[rec4[u].w + rank - 2u];
-            }
-        }
-        // phase 4: escapes (a prefix longer than /24, or an id too large for the packed entry: rare)
-#pragma unroll
-        for (uint32_t u = 0; u < U; u++) {
-            k[u] = 2;
-            if (!v6[u] && dir) {
-                k[u] = 3;
-                if (e24[u] & DIR_ESCAPE) {
-                    const uint2 esc = a.dir_esc[e24[u] & ~DIR_ESCAPE];
-                    eg[u] = esc.x;
-                    ei[u] = esc.y;
-                } else {
-                    eg[u] = TRIE_LEAF | (e24[u] & 0xFFFFu);
-                    ei[u] = TRIE_LEAF | (e24[u] >> 16);
-                }
-            }
-            if (!geo_walk[u]) eg[u] = TRIE_LEAF | a.geo_default;  // no lookup: the default record's class
-            if (a.n_ip_lists == 0) ei[u] = TRIE_LEAF;
-        }
-        // phase 5: the remaining trie levels (IPv6, escapes), all four walks advancing together
-        for (;;) {
-            bool more = false;
-#pragma unroll
-            for (uint32_t u = 0; u < U; u++) more = more || !((eg[u] & ei[u]) & TRIE_LEAF);
-            if (!more) break;
-            uint32_t ng[U], ni[U];
-#pragma unroll
-            for (uint32_t u = 0; u < U; u++) {
-                const uint32_t byte = ip_byte(ipw[u], k[u] < 16 ? k[u] : 15u);
-                ng[u] = (eg[u] & TRIE_LEAF) ? eg[u] : a.geo_nodes[(size_t)eg[u] * 256 + byte];
-                ni[u] = (ei[u] & TRIE_LEAF) ? ei[u] : a.ip_nodes[(size_t)ei[u] * 256 + byte];
-            }
-#pragma unroll
-            for (uint32_t u = 0; u < U; u++) {
-                if (!((eg[u] & ei[u]) & TRIE_LEAF)) k[u]++;
-                eg[u] = ng[u];
-                ei[u] = ni[u];
-            }
-        }
-#pragma unroll
-        for (uint32_t u = 0; u < U; u++) {
-            if (!live[u]) continue;
-            const uint32_t cls = eg[u] & ~TRIE_LEAF, set_id = ei[u] & ~TRIE_LEAF;
-            if (PACKED) a.ipres[idx[u]] = cls | (set_id << 16);
-            else reinterpret_cast<uint2 *>(a.ipres)[idx[u]] = make_uint2(cls, set_id);
-        }
-    }
-}
-
-// georec_kernel (PWAF_OPT_GEO_ANSWERS): the GeoIP RECORD of every request — what the reference keeps in its RequestContext and sends
-// upstream (http_listener.rs:143-157,183-191; http_proxy_service.rs:174-189). ipres_kernel's shape (one lane per request, no LDS, U = 4
-// requests per lane in lockstep, every phase's loads issued before any is used) over ONE table: the record-leaf trie and its own
-// compressed IPv4 table (csrc/georec.h: an entry is the record id, or DIR_ESCAPE | the trie node to continue from). One dependent
-// 8-byte gather of the record and one 8-byte store end it. A batch that carries asn / country columns gets them echoed.
-__global__ __launch_bounds__(256) void georec_kernel(GeoRecArgs a) {
-    constexpr uint32_t U = 4;
-    const uint32_t T = gridDim.x * 256u;
-    if (a.asn != nullptr) {
-        for (uint32_t i = blockIdx.x * 256u + threadIdx.x; i < a.n; i += T) a.out[i] = make_uint2(a.asn[i], (uint32_t)a.country[i]);
-        return;
-    }
-    const bool dir = a.chunks != nullptr;
-    for (uint32_t i0 = blockIdx.x * 256u + threadIdx.x; i0 < a.n; i0 += T * U) {
-        uint32_t idx[U], ipw[U][4], e[U], k[U], top16[U], v6b[U];
-        bool live[U], chunked[U];
-        uint4 raw[U];
-#pragma unroll
-        for (uint32_t u = 0; u < U; u++) {
-            idx[u] = i0 + u * T;
-            live[u] = idx[u] < a.n;
-            const uint32_t j = live[u] ? idx[u] : i0;
-            raw[u] = *reinterpret_cast<const uint4 *>(a.ip + (size_t)j * 16);
-            v6b[u] = a.ip_is_v6[j];
-        }
-        // family and exclusion (GeoipDB::lookup, pingoo/geoip.rs:73-91: loopback / multicast are "not found"), then phase 1: the 16-bit
-        // root (IPv6, or IPv4 without a table)
-#pragma unroll
-        for (uint32_t u = 0; u < U; u++) {
-            ipw[u][0] = raw[u].x; ipw[u][1] = raw[u].y; ipw[u][2] = raw[u].z; ipw[u][3] = raw[u].w;
-            const bool v6 = v6b[u] != 0;
-            bool walk = a.has_geo != 0;
-            if (!v6) {
-                const uint32_t b0 = ipw[u][0] & 0xFFu;
-                walk = walk && !(b0 == 127u || (b0 & 0xF0u) == 0xE0u);
-            } else {
-                const bool loopback = ipw[u][0] == 0 && ipw[u][1] == 0 && ipw[u][2] == 0 && ipw[u][3] == 0x01000000u;
-                walk = walk && !(loopback || (ipw[u][0] & 0xFFu) == 0xFFu);
-            }
-            top16[u] = (ip_byte(ipw[u], 0) << 8) | ip_byte(ipw[u], 1);
-            e[u] = TRIE_LEAF;  // record 0: the default
-            k[u] = 2;
-            chunked[u] = walk && !v6 && dir;
-            if (walk && !chunked[u]) e[u] = (v6 ? a.root6 : a.root4)[top16[u]];
-        }
-        // phase 1b: the summary bit of the address's block of /24s: 0 = the table's most common entry, no gather
-        uint32_t look[U];
-#pragma unroll
-        for (uint32_t u = 0; u < U; u++) {
-            look[u] = chunked[u] ? 1u : 0u;
-            if (chunked[u] && a.summary != nullptr) {
-                const uint32_t blk = ((top16[u] << 8) | ip_byte(ipw[u], 2)) >> a.sum_shift;
-                look[u] = (a.summary[blk >> 5] >> (blk & 31u)) & 1u;
-            }
-        }
-        // ONE 16-byte gather: the record of the address's group of 32 /24s
-        uint4 rec4[U];
-#pragma unroll
-        for (uint32_t u = 0; u < U; u++) {
-            rec4[u] = make_uint4(0u, 0u, 0u, 0u);
-            if (look[u]) rec4[u] = *reinterpret_cast<const uint4 *>(a.chunks + (size_t)top16[u] * kDirChunkWords + 4u * (ip_byte(ipw[u], 2) >> 5));
-        }
-        // phase 2: the run's entry — carried into the group, the first run inside it, or a further run from vals
-        uint32_t e24[U];
-#pragma unroll
-        for (uint32_t u = 0; u < U; u++) {
-            e24[u] = a.common;
-            if (look[u]) {
-                const uint32_t rank = (uint32_t)__builtin_popcount(rec4[u].x & (0xFFFFFFFFu >> (31u - (ip_byte(ipw[u], 2) & 31u))));
-                e24[u] = rank == 0 ? rec4[u].y : rank == 1 ? rec4[u].z : a.vals[rec4[u].w + rank - 2u];
-            }
-        }
-        // phase 4: an escape continues in the trie node the entry names, with the address's last byte
-#pragma unroll
-        for (uint32_t u = 0; u < U; u++)
-            if (chunked[u]) {
-                k[u] = 3;
-                e[u] = (e24[u] & DIR_ESCAPE) ? (e24[u] & ~DIR_ESCAPE) : (TRIE_LEAF | e24[u]);
-            }
-        // phase 5: the remaining trie levels (IPv6, escapes), all walks advancing together
-        for (;;) {
-            bool more = false;
-#pragma unroll
-            for (uint32_t u = 0; u < U; u++) more = more || !(e[u] & TRIE_LEAF);
-            if (!more) break;
-            uint32_t ne[U];
-#pragma unroll
-            for (uint32_t u = 0; u < U; u++) ne[u] = (e[u] & TRIE_LEAF) ? e[u] : a.nodes[(size_t)e[u] * 256 + ip_byte(ipw[u], k[u] < 16 ? k[u] : 15u)];
-#pragma unroll
-            for (uint32_t u = 0; u < U; u++) {
-                k[u]++;
-                e[u] = ne[u];
-            }
-        }
-        // the record itself: one 8-byte gather, one 8-byte store
-        uint2 r[U];
-#pragma unroll
-        for (uint32_t u = 0; u < U; u++) r[u] = reinterpret_cast<const uint2 *>(a.recs)[e[u] & ~TRIE_LEAF];
-#pragma unroll
-        for (uint32_t u = 0; u < U; u++)
-            if (live[u]) a.out[idx[u]] = make_uint2(r[u].x, r[u].y & 0xFFFFu);
-    }
-}
-
-struct AttrIn {
-    uint32_t cls, set_id;
-    uint32_t port, len[5], asn, country;
-    uint32_t sstart, slen;  // the short-literal field's value: offset and length
-};
-
-// (__launch_bounds__(256, 7) — 72 registers, 7 waves per SIMD at the price of 3-5 spilled dwords — was measured: 0.229 ms alone against
-// 0.227, nothing.)
-// SMALL: the rule set's membership rows fit 4 ip-set words, 2 country words and one word each of port sets, asn sets and asn
-// comparisons (a 1k-rule set with 124 CIDR lists does): 9 row registers instead of 36.
-// Atoms beyond the 64 that live in registers, staged in LDS for the group loop (the chunks beyond these are re-read from global memory
-// per group: a rule set with more than 256 eager comparison atoms or 128 short literals).
-static constexpr uint32_t kAttrCmpStaged = 192, kAttrShortStaged = 64;
-template <bool PACKED, bool SMALL>
-__global__ __launch_bounds__(256) void attr_kernel(VerdictArgs a) {
-    constexpr uint32_t SW = SMALL ? 4 : kSetWordsMax, CW = SMALL ? 2 : kCcWordsMax, IW = SMALL ? 1 : kIntWordsMax, QW = SMALL ? 1 : kAcmpWordsMax;
-    // LDS (one array): the rows of bit_col this instantiation can meet, in the order of the transposes below (slot -> source word:
-    // SW ip-set words, CW country words, IW port-set words, IW asn-set words, QW asn-comparison words), then the staged comparison
-    // atoms {col, c} and the staged short literals {col, len_exact, lit_lo, lit_hi}. 1.1 KiB + 2.5 KiB (SMALL), 4.5 KiB + 2.5 KiB.
-    constexpr uint32_t kSlotCc = SW, kSlotPort = SW + CW, kSlotAsn = SW + CW + IW, kSlotAcmp = SW + CW + 2 * IW, kSlots = SW + CW + 2 * IW + QW;
-    constexpr uint32_t kLdsCmp = kSlots * 32, kLdsShort = kLdsCmp + 2 * kAttrCmpStaged, kLdsWords = kLdsShort + 4 * kAttrShortStaged;
-    __shared__ uint32_t tab[kLdsWords];
-#ifdef PWAF_PROFILING
-    if (a.debug_skip & 0x80000000u) __builtin_amdgcn_s_setprio(3);  // timing experiment
-#endif
-    const uint32_t lane = threadIdx.x & 63, wave = wave_index();
-    const bool from_row = a.asn == nullptr;  // asn / country come from the engine's own GeoIP record (or its default)
-#ifdef PWAF_PROFILING
-    // timing experiments (wrong results): which part of the kernel costs what
-    const bool skip_rows = (a.debug_skip >> 18) & 1u, skip_transpose = (a.debug_skip >> 19) & 1u, skip_cmp = (a.debug_skip >> 20) & 1u;
-#else
-    constexpr bool skip_rows = false, skip_transpose = false, skip_cmp = false;
-#endif
-    // group-invariant: the first 64 comparison atoms, one per lane (col | code << 24, constant)
-    uint32_t h_col = 0, h_c = 0;
-    if (lane < a.n_cmp) {
-        h_col = a.cmp[lane].col;
-        h_c = a.cmp[lane].c;
-    }
-    const uint32_t g_stride = gridDim.x * 4;
-    // stage A: the fixed-width inputs of a group. Every load is UNCONDITIONAL: a column the rule set does not read (or the batch does not
-    // carry) is replaced by element 0 of a column that always exists — one cached line for the whole wave, its value discarded. A load
-    // under a wave-uniform condition becomes a branch around it, and the compiler waits for ALL outstanding loads where the branches
-    // join: one exposed round trip per length column, in the middle of the prefetch.
-    const uint32_t *const asn_col = from_row ? a.off[0] : a.asn;
-    const uint16_t *const country_col = from_row ? a.port : a.country;
-    const uint32_t *const short_col = a.n_short ? a.short_off : a.off[0];
-    const uint8_t *const short_bytes = a.n_short ? a.short_data : reinterpret_cast<const uint8_t *>(a.off[0]);
-    auto load_in = [&](const uint32_t g, AttrIn &in) {
-        const uint32_t i0 = g * 64 + lane;
-        const uint32_t i = (g < a.n_groups && i0 < a.n) ? i0 : 0u;
-        if (PACKED) {
-            const uint32_t w = a.ipres[i];
-            in.cls = w & 0xFFFFu;
-            in.set_id = w >> 16;
-        } else {
-            const uint2 w = reinterpret_cast<const uint2 *>(a.ipres)[i];
-            in.cls = w.x;
-            in.set_id = w.y;
-        }
-        in.port = a.port[i];
-#pragma unroll
-        for (int f = 0; f < 5; f++) {  // (wave-uniform: only the lengths some comparison atom reads)
-            const bool used = (a.cmp_vars >> f) & 1u;
-            const uint32_t j = used ? i : 0u;
-            const uint32_t d = a.off[f][j + 1] - a.off[f][j];
-            in.len[f] = used ? d : 0u;
-        }
-        const uint32_t ja = from_row ? 0u : i, js = a.n_short ? i : 0u;
-        const uint32_t v_asn = asn_col[ja], v_country = country_col[ja], s0 = short_col[js], s1 = short_col[js + 1];
-        in.asn = from_row ? 0u : v_asn;
-        in.country = from_row ? 0u : v_country;
-        in.sstart = a.n_short ? s0 : 0u;
-        in.slen = a.n_short ? s1 - s0 : 0u;
-    };
-    // stage B: the short-literal field's first 8 bytes (arenas carry 16 readable slack bytes)
-    auto load_short = [&](const AttrIn &in, uint32_t &s_lo, uint32_t &s_hi) {
-        typedef uint2 __attribute__((aligned(1))) uint2_u;
-        const uint2 sv = *reinterpret_cast<const uint2_u *>(short_bytes + in.sstart);  // (no short literals: the first 8 bytes of a column that exists, unused)
-        s_lo = sv.x;
-        s_hi = sv.y;
-    };
-    AttrIn cur, nxt;
-    uint32_t c_slo, c_shi;
-    const uint32_t g0 = blockIdx.x * 4 + wave;
-    load_in(g0, cur);
-    load_in(g0 + g_stride, nxt);
-    load_short(cur, c_slo, c_shi);
-    // group-invariant: the first 64 short-literal atoms, one per lane
-    ShortAtom h_short{0, 0, 0, 0};
-    if (lane < a.n_short) h_short = a.short_atoms[lane];
-    // the LDS tables, once per workgroup (behind the first groups' input loads, so that all of them share one round trip)
-    for (uint32_t t = threadIdx.x; t < kSlots * 32; t += 256) {
-        const uint32_t s = t >> 5;
-        const uint32_t src = s < kSlotCc ? kSrcSet + s : s < kSlotPort ? kSrcCc + (s - kSlotCc) : s < kSlotAsn ? kSrcPort + (s - kSlotPort) : s < kSlotAcmp ? kSrcAsn + (s - kSlotAsn) : kSrcAcmp + (s - kSlotAcmp);
-        tab[t] = a.bit_col[src * 32 + (t & 31u)];
-    }
-    for (uint32_t t = threadIdx.x; t < kAttrCmpStaged && 64 + t < a.n_cmp; t += 256) {
-        tab[kLdsCmp + 2 * t] = a.cmp[64 + t].col;
-        tab[kLdsCmp + 2 * t + 1] = a.cmp[64 + t].c;
-    }
-    for (uint32_t t = threadIdx.x; t < kAttrShortStaged && 64 + t < a.n_short; t += 256) {
-        const ShortAtom s = a.short_atoms[64 + t];
-        tab[kLdsShort + 4 * t] = s.col;
-        tab[kLdsShort + 4 * t + 1] = s.len_exact;
-        tab[kLdsShort + 4 * t + 2] = s.lit_lo;
-        tab[kLdsShort + 4 * t + 3] = s.lit_hi;
-    }
-    __syncthreads();
-
-    for (uint32_t g = g0; g < a.n_groups; g += g_stride) {
-        const uint32_t i = g * 64 + lane;
-        const bool valid = i < a.n;
-        const unsigned long long valid_mask = __ballot(valid);
-        uint4 *pairs = a.gpairs + (size_t)g * a.pair_stride;
-        uint32_t n_pairs = 0;  // wave-uniform
-        // lane-private (column, mask) -> the group's pair list, in lane order
-        auto emit_pairs = [&](const bool has, const uint32_t c, const uint32_t lo, const uint32_t hi) {
-            const unsigned long long em = __ballot(has);
-            if (has) pairs[n_pairs + __builtin_amdgcn_mbcnt_hi((uint32_t)(em >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)em, 0u))] = make_uint4(c, 0u, lo, hi);  // (emitting lanes below this one)
-            n_pairs += (uint32_t)__builtin_popcountll(em);
-        };
-        const uint32_t port = cur.port;
-        const uint32_t cls = cur.cls, set_id = cur.set_id;
-
-        // ---- 1. membership rows: every row word of the request requested together, then ONE wait ----
-        uint32_t asn = cur.asn, r_geo = 0;
-        if (!from_row) {
-            const uint32_t c0 = (cur.country & 0xFFu) - 'A', c1 = (cur.country >> 8) - 'A';
-            r_geo = (c0 < 26u && c1 < 26u) ? c0 * 26u + c1 : 23u * 26u + 23u;  // invalid input is treated as "XX"
-        }
-        uint32_t r_int[2] = {0, 0};
-#pragma unroll
-        for (int var = 0; var < 2; var++) {
-            // integer sets: ONE binary search per request over the union of every set tested against the variable
-            if (!valid || a.iu_n[var] == 0 || (var == 1 && from_row)) continue;
-            const long long v = var == VAR_PORT ? (long long)port : (long long)asn;
-            uint32_t lo = 0, hi = a.iu_n[var];
-            while (lo < hi) {
-                const uint32_t mid = (lo + hi) >> 1;
-                if (a.iu_vals[var][mid] < v) lo = mid + 1;
-                else hi = mid;
-            }
-            if (lo < a.iu_n[var] && a.iu_vals[var][lo] == v) r_int[var] = lo + 1;
-        }
-        // sources (kernels.h kSrc*): ip-set row, country words, port-set row, asn-set words, asn comparisons
-        const uint32_t *srow = a.set_masks + (size_t)set_id * a.set_words;
-        const uint32_t *crow = from_row ? a.class_rows + (size_t)cls * a.class_words : a.country_masks + (size_t)r_geo * a.cc_words;
-        const uint32_t *prow = a.iu_masks[0] + (size_t)r_int[0] * a.iu_words[0];
-        const uint32_t *arow = from_row ? crow + a.cc_words : a.iu_masks[1] + (size_t)r_int[1] * a.iu_words[1];
-        const uint32_t *qrow = crow + a.cc_words + a.iu_words[1];
-        const bool rows_on = valid && !skip_rows;
-        const bool have_s = rows_on && a.n_ip_lists && set_id, have_c = rows_on && (from_row ? cls != 0 : true), have_p = rows_on && r_int[0],
-                   have_a = rows_on && (from_row ? cls != 0 : r_int[1] != 0), have_q = rows_on && from_row && cls != 0;
-        uint32_t rs[SW], rc[CW], rp[IW], ra[IW], rq[QW];
-#pragma unroll
-        for (uint32_t q = 0; q < SW; q++) rs[q] = (q < a.set_words && have_s) ? srow[q] : 0u;
-#pragma unroll
-        for (uint32_t q = 0; q < CW; q++) rc[q] = (q < a.cc_words && have_c) ? crow[q] : 0u;
-#pragma unroll
-        for (uint32_t q = 0; q < IW; q++) rp[q] = (q < a.iu_words[0] && have_p) ? prow[q] : 0u;
-#pragma unroll
-        for (uint32_t q = 0; q < IW; q++) ra[q] = (q < a.iu_words[1] && have_a) ? arow[q] : 0u;
-#pragma unroll
-        for (uint32_t q = 0; q < QW; q++) rq[q] = (q < a.acmp_words && have_q) ? qrow[q] : 0u;
-
-        // ---- 2. prefetch: inputs of the group after next, the next group's short-literal bytes ----
-        AttrIn nn;
-        load_in(g + 2 * g_stride, nn);
-        uint32_t n_slo, n_shi;
-        load_short(nxt, n_slo, n_shi);
-        // The rows are waited for HERE, once, with the prefetch behind them still in flight. Left to the first use inside each transpose,
-        // the wait is placed where paths with and without a pair store join, and is counted for the path without: behind every
-        // store it then also waits for one more load of the prefetch.
-#pragma unroll
-        for (uint32_t q = 0; q < SW; q++) asm volatile("" : "+v"(rs[q]));
-#pragma unroll
-        for (uint32_t q = 0; q < CW; q++) asm volatile("" : "+v"(rc[q]));
-#pragma unroll
-        for (uint32_t q = 0; q < IW; q++) asm volatile("" : "+v"(rp[q]), "+v"(ra[q]));
-#pragma unroll
-        for (uint32_t q = 0; q < QW; q++) asm volatile("" : "+v"(rq[q]));
-
-        // ---- 3. transposes: one ballot per bit that ANY of the 64 requests has set (wave-wide OR first, so absent bits cost
-        //         nothing); lane b keeps bit b's request mask and owns that atom's pair ----
-        auto transpose = [&](const uint32_t w, const uint32_t slot) {
-            const uint32_t orw0 = wave_or(w);
-            if (orw0 == 0) return;
-            // (the mask is PARKED in lane b with v_writelane: two vector instructions per bit — a compare of the lane id and two
-            // selects, with the mask moved into vector registers first, were seven; the kernel is bound by vector-ALU issue)
-            uint32_t mine_lo = 0, mine_hi = 0;
-            for (uint32_t orw = orw0; orw; orw &= orw - 1) {
-                const uint32_t b = (uint32_t)__builtin_ctz(orw);
-                const unsigned long long m = __ballot((w & (1u << b)) != 0u);
-                park64(mine_lo, mine_hi, m, b);
-            }
-            const bool owner = lane < 32 && ((orw0 >> lane) & 1u);
-            const uint32_t c = owner ? tab[slot * 32 + (lane & 31u)] : 0u;  // (source word, bit) -> column, 0 = no such atom (LDS: no wait on the prefetch)
-            emit_pairs(c != 0, c, mine_lo, mine_hi);
-        };
-        if (!skip_transpose) {
-#pragma unroll
-            for (uint32_t q = 0; q < SW; q++) if (q < a.set_words) transpose(rs[q], q);  // (uniform conditions)
-#pragma unroll
-            for (uint32_t q = 0; q < CW; q++) if (q < a.cc_words) transpose(rc[q], kSlotCc + q);
-#pragma unroll
-            for (uint32_t q = 0; q < IW; q++) if (q < a.iu_words[0]) transpose(rp[q], kSlotPort + q);
-#pragma unroll
-            for (uint32_t q = 0; q < IW; q++) if (q < a.iu_words[1]) transpose(ra[q], kSlotAsn + q);
-#pragma unroll
-            for (uint32_t q = 0; q < QW; q++) if (q < a.acmp_words) transpose(rq[q], kSlotAcmp + q);
-        }
-
-        // Comparison atoms (lengths, port, asn against constants): the engine has reduced them to `v == c` / `v <= c` on 32-bit
-        // values and tagged each with code = 2 * variable + operator; an atom is a scalar broadcast of its constant, one
-        // vector compare and a ballot parked in the atom's lane. (asn comparisons of engine-resolved records are class-row bits.)
-        for (uint32_t base = 0; base < a.n_cmp && !skip_cmp; base += 64) {
-            uint32_t m_col = h_col, m_c = h_c;
-            if (base != 0) {  // more than 64 comparison atoms: the later chunks come from LDS (beyond the staged ones: re-read per group)
-                m_col = m_c = 0;
-                if (base + lane < a.n_cmp) {
-                    if (base < 64 + kAttrCmpStaged) {  // (uniform)
-                        m_col = tab[kLdsCmp + 2 * (base - 64 + lane)];
-                        m_c = tab[kLdsCmp + 2 * (base - 64 + lane) + 1];
-                    } else {
-                        m_col = a.cmp[base + lane].col;
-                        m_c = a.cmp[base + lane].c;
-                        asm volatile("" : "+v"(m_col), "+v"(m_c));  // (the wait for this load belongs HERE, not where the branches join)
-                    }
-                }
-            }
-            const uint32_t my_code = base + lane < a.n_cmp ? (m_col >> 24) & 0x7Fu : 0xFFu;
-            const unsigned long long flip_atoms = __ballot(base + lane < a.n_cmp && ((m_col >> 31) & 1u) != 0u);  // atoms evaluated complemented (engine.cpp, POLARITY)
-            uint32_t acc_lo = 0, acc_hi = 0;
-            auto cmp_var = [&](const uint32_t v, const int vi) {
-#pragma unroll
-                for (int op = 0; op < 2; op++) {
-                    unsigned long long todo = __ballot(my_code == (uint32_t)(2 * vi + op));
-                    while (todo) {
-                        const uint32_t j = (uint32_t)__builtin_ctzll(todo);
-                        todo &= todo - 1;
-                        const uint32_t c = (uint32_t)__builtin_amdgcn_readlane((int)m_c, (int)j);
-                        unsigned long long m = __ballot(op == 0 ? v == c : v <= c);
-                        if ((flip_atoms >> j) & 1ull) m = ~m;
-                        park64(acc_lo, acc_hi, m & valid_mask, j);
-                    }
-                }
-            };
-#pragma unroll
-            for (int f = 0; f < 5; f++)
-                if ((a.cmp_vars >> f) & 1u) cmp_var(cur.len[f], f);
-            if ((a.cmp_vars >> 5) & 1u) cmp_var(port, 5);
-            if (!from_row && ((a.cmp_vars >> 6) & 1u)) cmp_var(asn, 6);
-            for (uint32_t f = 0; f < a.n_hlen; f++) {  // EXTENSION: lengths of header columns (rare: fetched here, not prefetched)
-                const uint32_t ii = valid ? i : 0u;
-                cmp_var(a.hoff[f][ii + 1] - a.hoff[f][ii], 7 + (int)f);
-            }
-            emit_pairs((acc_lo | acc_hi) != 0, m_col & 0xFFFFFFu, acc_lo, acc_hi);
-        }
-        // Short-literal atoms (kernels.h: ShortAtom): the field's first 8 bytes against each literal under its length mask — a
-        // scalar broadcast of the atom, two vector compares and a ballot parked in the atom's lane.
-        for (uint32_t base = 0; base < a.n_short; base += 64) {
-            ShortAtom m = h_short;
-            if (base != 0) {
-                m = ShortAtom{0, 0, 0, 0};
-                if (base + lane < a.n_short) {
-                    const uint32_t *s = tab + kLdsShort + 4 * (base - 64 + lane);
-                    if (base < 64 + kAttrShortStaged) {  // (uniform)
-                        m = ShortAtom{s[0], s[1], s[2], s[3]};
-                    } else {
-                        m = a.short_atoms[base + lane];
-                        asm volatile("" : "+v"(m.col), "+v"(m.len_exact), "+v"(m.lit_lo), "+v"(m.lit_hi));  // (as above)
-                    }
-                }
-            }
-            const uint32_t cnt = min(64u, a.n_short - base);
-            uint32_t acc_lo = 0, acc_hi = 0;
-            for (uint32_t j = 0; j < cnt; j++) {
-                const uint32_t le = (uint32_t)__builtin_amdgcn_readlane((int)m.len_exact, (int)j), len = le & 0xFFu;
-                const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)m.lit_lo, (int)j), hi = (uint32_t)__builtin_amdgcn_readlane((int)m.lit_hi, (int)j);
-                const uint32_t mlo = len >= 4 ? 0xFFFFFFFFu : (1u << (8 * len)) - 1u, mhi = len >= 8 ? 0xFFFFFFFFu : len > 4 ? (1u << (8 * (len - 4))) - 1u : 0u;
-                // (the length test is chosen by a SCALAR branch — `exact` is the atom's, not the request's — and the two masked compares
-                // are one: xor, xor-and, and-or, compare)
-                const unsigned long long len_ok = (le >> 8) ? __ballot(cur.slen == len) : __ballot(cur.slen >= len);
-                const unsigned long long hit = __ballot((((c_slo ^ lo) & mlo) | ((c_shi ^ hi) & mhi)) == 0u) & len_ok & valid_mask;
-                park64(acc_lo, acc_hi, hit, j);
-            }
-            emit_pairs((acc_lo | acc_hi) != 0, m.col, acc_lo, acc_hi);
-        }
-        if (lane == 0) a.ghdr[g] = n_pairs;
-        cur = nxt;
-        nxt = nn;
-        c_slo = n_slo;
-        c_shi = n_shi;
-    }
-}
-
-// Flattens the first 24 bits of the GeoIP trie (leaves = class ids) and the ip-list trie (leaves = membership-set ids), IPv4 family,
-// into one table of 4-byte entries: class | set << 16 when both walks end within 24 bits with ids that fit (class < 65536,
-// set < 32768), otherwise DIR_ESCAPE | index of an 8-byte {geo entry, set entry} pair from which the attribute kernel continues.
-// Two launches: `esc == nullptr` only counts the escapes.
-__global__ __launch_bounds__(256) void dir24_kernel(VerdictArgs a, uint32_t *out, uint2 *esc, uint32_t *esc_count) {
-    const uint32_t x = blockIdx.x * 256 + threadIdx.x;  // the top 24 address bits
-    if (x >= (1u << 24)) return;
-    uint32_t eg = a.geo_root4[x >> 8];
-    if (!(eg & TRIE_LEAF)) eg = a.geo_nodes[(size_t)eg * 256 + (x & 0xFFu)];
-    uint32_t ei = a.ip_root4[x >> 8];
-    if (!(ei & TRIE_LEAF)) ei = a.ip_nodes[(size_t)ei * 256 + (x & 0xFFu)];
-    const uint32_t vg = eg & ~TRIE_LEAF, vi = ei & ~TRIE_LEAF;
-    if ((eg & ei & TRIE_LEAF) && vg < 65536u && vi < 32768u) {
-        if (out) out[x] = vg | (vi << 16);
-        return;
-    }
-    const uint32_t idx = atomicAdd(esc_count, 1u);
-    if (esc) {
-        esc[idx] = make_uint2(eg, ei);
-        out[x] = DIR_ESCAPE | idx;
-    }
-}
-
-int launch_dir24(const VerdictArgs &a, void *out, void *esc, void *esc_count, void *stream) {
-    hipLaunchKernelGGL(dir24_kernel, dim3((1u << 24) / 256), dim3(256), 0, (hipStream_t)stream, a, (uint32_t *)out, (uint2 *)esc, (uint32_t *)esc_count);
-    return (int)hipGetLastError();
-}
-
-// Launch shape of the COARSE instantiation. The bitmap is staged per workgroup and held for the whole (persistent) launch, so the shape
-// trades how many lookups end in LDS against the waves and the LDS left on a CU for the kernels of the main stream (DESIGN.md §6.1:
-// the three shapes measured in the step). 1: two 1024-thread workgroups per CU, 64 KiB each (/19 blocks); 2: four 512-thread
-// workgroups, 32 KiB each (/18); 3: one 1024-thread workgroup, 64 KiB; 0: no coarse level.
-#ifndef PWAF_IPRES_SHAPE
-#define PWAF_IPRES_SHAPE 1
-#endif
-IpresShape ipres_shape() {
-    static const IpresShape shapes[4] = {{256, 0, 8}, {1024, 64 * 1024, 2}, {512, 32 * 1024, 4}, {1024, 64 * 1024, 1}};
-#ifdef PWAF_PROFILING
-    static const uint32_t pick = getenv("PWAF_IPRES_SHAPE") ? (uint32_t)atoi(getenv("PWAF_IPRES_SHAPE")) & 3u : (uint32_t)PWAF_IPRES_SHAPE;
-#else
-    const uint32_t pick = PWAF_IPRES_SHAPE;
-#endif
-    return shapes[pick];
-}
-
-// address lookups: one lane per request at full occupancy (grid-stride; 8 workgroups of 256 per CU, or ipres_shape() with a coarse bitmap)
-int launch_ipres(const VerdictArgs &a, void *stream) {
-    if (a.n == 0) return 0;
-#ifdef PWAF_PROFILING
-    static const uint32_t forced = getenv("PWAF_IPRES_BLOCKS") ? (uint32_t)atoi(getenv("PWAF_IPRES_BLOCKS")) : 0u;
-#else
-    const uint32_t forced = 0;
-#endif
-    if (a.dir_coarse != nullptr) {
-        const IpresShape sh = ipres_shape();
-        // (the kernel indexes the bitmap by the address alone: its size must be the one the shift implies)
-        if (a.dir_coarse_shift > 17u || a.dir_coarse_bytes != (1u << 21) >> a.dir_coarse_shift || a.dir_coarse_bytes > sh.coarse_bytes) return (int)hipErrorInvalidValue;
-        const uint32_t blocks = std::min<uint32_t>((a.n + sh.threads - 1) / sh.threads, forced ? forced : sh.wg_per_cu * std::max(1u, a.attr_blocks));
-        if (a.ipres_packed) hipLaunchKernelGGL((ipres_kernel<true, true>), dim3(blocks), dim3(sh.threads), a.dir_coarse_bytes, (hipStream_t)stream, a);
-        else hipLaunchKernelGGL((ipres_kernel<false, true>), dim3(blocks), dim3(sh.threads), a.dir_coarse_bytes, (hipStream_t)stream, a);
-        return (int)hipGetLastError();
-    }
-    const uint32_t blocks = std::min<uint32_t>((a.n + 255) / 256, forced ? forced : 8 * std::max(1u, a.attr_blocks));
-    if (a.ipres_packed) hipLaunchKernelGGL((ipres_kernel<true, false>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, a);
-    else hipLaunchKernelGGL((ipres_kernel<false, false>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, a);
-    return (int)hipGetLastError();
-}
-
-// GeoIP records: ipres_kernel's geometry (grid-stride; 8 workgroups of 256 per CU)
-int launch_georec(const GeoRecArgs &a, void *stream) {
-    if (a.n == 0) return 0;
-    const uint32_t blocks = std::min<uint32_t>((a.n + 255) / 256, 8 * std::max(1u, a.n_cus));
-    hipLaunchKernelGGL(georec_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, a);
-    return (int)hipGetLastError();
-}
-
-int launch_attr(const VerdictArgs &a, void *stream) {
-    if (a.n == 0) return 0;
-    // rows, transposes, comparisons (after launch_ipres on the same stream). A persistent grid of six workgroups per CU at the default wave priority 0, while the filter
-    // waves raise theirs to 3: the attribute waves take the issue slots the filter leaves idle instead of competing for them
-    // (measured on MI355X next to the stream filter: 512 / 768 / 1024 / 1536 / 2048 workgroups -> 2.00 / 2.00 / 1.98 / 1.94 / 1.94 ms per step).
-#ifdef PWAF_PROFILING
-    static const uint32_t forced = getenv("PWAF_ATTR_BLOCKS") ? (uint32_t)atoi(getenv("PWAF_ATTR_BLOCKS")) : 0u;
-#else
-    const uint32_t forced = 0;
-#endif
-    const uint32_t blocks = std::min<uint32_t>((a.n_groups + 3) / 4, forced ? forced : 6 * std::max(1u, a.attr_blocks));
-    const bool small = a.set_words <= 4 && a.cc_words <= 2 && a.iu_words[0] <= 1 && a.iu_words[1] <= 1 && a.acmp_words <= 1;
-    if (a.ipres_packed && small) hipLaunchKernelGGL((attr_kernel<true, true>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, a);
-    else if (a.ipres_packed) hipLaunchKernelGGL((attr_kernel<true, false>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, a);
-    else if (small) hipLaunchKernelGGL((attr_kernel<false, true>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, a);
-    else hipLaunchKernelGGL((attr_kernel<false, false>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, a);
-    return (int)hipGetLastError();
-}
-
-// (the workgroup shape of the verdict kernels — verdict_shape, verdict_blocks_sp, kLdsPerGroup: verdictplan.h)
-int launch_verdict(const VerdictArgs &a, void *stream) {
-    VerdictShape sh = verdict_shape(a.n_cols, a.n_rules, a.n_trig, a.n_lits, a.force_global_tables != 0, (int)a.sparse_mode, a.n_passes);
-    if (!verdict_launchable(sh, a.n_cols)) return (int)hipErrorInvalidValue;  // (engine_create refuses such programs)
-    if (sh.sparse == 1 && (a.v_cap != sh.v_cap || (sh.v_cap < a.n_cols && a.spill == nullptr))) return (int)hipErrorInvalidValue;
-    if (sh.sparse == 2 && (a.v_cap != sh.v_cap || a.spill == nullptr)) return (int)hipErrorInvalidValue;
-#ifdef PWAF_PROFILING
-    static const uint32_t cap_waves = getenv("PWAF_VERDICT_WAVES") ? (uint32_t)atoi(getenv("PWAF_VERDICT_WAVES")) : 0u;  // timing experiment: fewer waves per CU (same results)
-    if (cap_waves && cap_waves < sh.waves) sh.waves = cap_waves;
-#endif
-    constexpr int kBRmax = (kMaxPasses + 1 + 63) / 64;
-    int variant = verdict_variant(a.n_passes);
-#ifdef PWAF_PROFILING
-    static const int forced_variant = getenv("PWAF_VERDICT_VARIANT") ? atoi(getenv("PWAF_VERDICT_VARIANT")) : -1;  // a MORE general variant may be forced (same results)
-    if (forced_variant >= 0 && forced_variant < variant) variant = forced_variant;
-#endif
-    const void *fns[2][2][2] = {{{reinterpret_cast<const void *>(verdict_kernel<false, kBRmax, false>), reinterpret_cast<const void *>(verdict_kernel<false, 1, false>)},
-                                 {reinterpret_cast<const void *>(verdict_kernel<true, kBRmax, false>), reinterpret_cast<const void *>(verdict_kernel<true, 1, false>)}},
-                                {{reinterpret_cast<const void *>(verdict_kernel<false, kBRmax, true>), reinterpret_cast<const void *>(verdict_kernel<false, 1, true>)},
-                                 {reinterpret_cast<const void *>(verdict_kernel<true, kBRmax, true>), reinterpret_cast<const void *>(verdict_kernel<true, 1, true>)}}};
-    const void *fns2[3][2][2] = {{{reinterpret_cast<const void *>(verdict2_kernel<false, kBRmax, false, false>), reinterpret_cast<const void *>(verdict2_kernel<false, 1, false, false>)},
-                                  {reinterpret_cast<const void *>(verdict2_kernel<true, kBRmax, false, false>), reinterpret_cast<const void *>(verdict2_kernel<true, 1, false, false>)}},
-                                 {{reinterpret_cast<const void *>(verdict2_kernel<false, kBRmax, true, false>), reinterpret_cast<const void *>(verdict2_kernel<false, 1, true, false>)},
-                                  {reinterpret_cast<const void *>(verdict2_kernel<true, kBRmax, true, false>), reinterpret_cast<const void *>(verdict2_kernel<true, 1, true, false>)}},
-                                 {{reinterpret_cast<const void *>(verdict2_kernel<false, kBRmax, false, true>), reinterpret_cast<const void *>(verdict2_kernel<false, 1, false, true>)},
-                                  {reinterpret_cast<const void *>(verdict2_kernel<true, kBRmax, false, true>), reinterpret_cast<const void *>(verdict2_kernel<true, 1, false, true>)}}};
-    // the rule-hit variants only when a hit output was asked for (PWAF_OPT_RULE_HITS engines; the entry-list kernel only: engine_create)
-    const bool want_hits = a.n_hits != nullptr || a.rule_hits != nullptr;
-    if (want_hits && (sh.sparse != 2 || (a.hits == nullptr && a.n_hits != nullptr && a.hits_cap != 0))) return (int)hipErrorInvalidValue;
-    // the route variants only when a route output was asked for (engines created with routes; the entry-list kernel only; one report per call)
-    const bool want_routes = a.route != nullptr;
-    if (want_routes && (sh.sparse != 2 || want_hits || a.route_base > a.n_rules)) return (int)hipErrorInvalidValue;
-    const void *fn = sh.sparse == 2 ? fns2[want_routes ? 2 : want_hits ? 1 : 0][sh.lds_tables ? 1 : 0][variant] : fns[sh.sparse ? 1 : 0][sh.lds_tables ? 1 : 0][variant];
-    uint32_t blocks = (a.n_groups + sh.waves - 1) / sh.waves;
-#ifdef PWAF_PROFILING
-    static const uint32_t forced_cap = getenv("PWAF_VERDICT_BLOCKS") ? (uint32_t)atoi(getenv("PWAF_VERDICT_BLOCKS")) : 0u;
-#else
-    const uint32_t forced_cap = 0;
-#endif
-    // with LDS tables a workgroup fills a CU: one persistent workgroup per CU (measured: 0.331 ms vs 0.346 at 4 per CU — every
-    // workgroup stages 25 KiB of tables and clears its column files once); small workgroups: a few rounds per CU
-    const uint32_t cap = (forced_cap && !sh.sparse) ? forced_cap : sh.sparse ? verdict_blocks_sp(sh, a.attr_blocks) : sh.lds_tables ? std::max(1u, a.attr_blocks) : 2048u;
-    if (blocks > cap) blocks = cap;
-    if (blocks == 0) return 0;
-    void *args[] = {const_cast<VerdictArgs *>(&a)};
-    hipError_t e = hipLaunchKernel(fn, dim3(blocks), dim3(sh.waves * 64), args, sh.lds_bytes, (hipStream_t)stream);
-    return (int)(e != hipSuccess ? e : hipGetLastError());
-}
-
 // hipFuncSetAttribute applies to the CURRENT device: every device an engine is created on needs its own call (a per-thread
 // or per-process "already configured" flag left the second device of a multi-GPU host at the 64 KiB default).
 int configure_kernels(int device) {
@@ -4003,22 +1661,13 @@ int configure_kernels(int device) {
     const void *fns[] = {reinterpret_cast<const void *>(scan_kernel<1, false>), reinterpret_cast<const void *>(scan_kernel<2, false>),
                          reinterpret_cast<const void *>(scan_kernel<4, false>), reinterpret_cast<const void *>(scan_kernel<1, true>),
                          reinterpret_cast<const void *>(scan_kernel<2, true>), reinterpret_cast<const void *>(scan_kernel<4, true>),
-                         reinterpret_cast<const void *>(verdict_kernel<true, (kMaxPasses + 1 + 63) / 64, false>), reinterpret_cast<const void *>(verdict_kernel<false, (kMaxPasses + 1 + 63) / 64, false>),
-                         reinterpret_cast<const void *>(verdict_kernel<true, 1, false>), reinterpret_cast<const void *>(verdict_kernel<false, 1, false>),
-                         reinterpret_cast<const void *>(verdict_kernel<true, (kMaxPasses + 1 + 63) / 64, true>), reinterpret_cast<const void *>(verdict_kernel<false, (kMaxPasses + 1 + 63) / 64, true>),
-                         reinterpret_cast<const void *>(verdict_kernel<true, 1, true>), reinterpret_cast<const void *>(verdict_kernel<false, 1, true>),
-                         reinterpret_cast<const void *>(verdict2_kernel<true, (kMaxPasses + 1 + 63) / 64, false, false>), reinterpret_cast<const void *>(verdict2_kernel<false, (kMaxPasses + 1 + 63) / 64, false, false>),
-                         reinterpret_cast<const void *>(verdict2_kernel<true, 1, false, false>), reinterpret_cast<const void *>(verdict2_kernel<false, 1, false, false>),
-                         reinterpret_cast<const void *>(verdict2_kernel<true, (kMaxPasses + 1 + 63) / 64, true, false>), reinterpret_cast<const void *>(verdict2_kernel<false, (kMaxPasses + 1 + 63) / 64, true, false>),
-                         reinterpret_cast<const void *>(verdict2_kernel<true, 1, true, false>), reinterpret_cast<const void *>(verdict2_kernel<false, 1, true, false>),
-                         reinterpret_cast<const void *>(verdict2_kernel<true, (kMaxPasses + 1 + 63) / 64, false, true>), reinterpret_cast<const void *>(verdict2_kernel<false, (kMaxPasses + 1 + 63) / 64, false, true>),
-                         reinterpret_cast<const void *>(verdict2_kernel<true, 1, false, true>), reinterpret_cast<const void *>(verdict2_kernel<false, 1, false, true>),
                          reinterpret_cast<const void *>(filter_kernel<true>), reinterpret_cast<const void *>(filter_kernel<false>),
                          lscan_fn(false), lscan_fn(true)};
     for (const void *fn : fns) {
         hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsPerGroup);
         if (e != hipSuccess) return (int)e;
     }
+    if (int e = configure_verdict_kernels()) return e;
     done.insert(device);
     return 0;
 }

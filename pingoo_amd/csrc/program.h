@@ -265,7 +265,7 @@ static constexpr uint32_t LIT_TERM_END = 1u << 31;  // last literal of its conju
 static constexpr uint32_t LIT_ATOM_MASK = (1u << 24) - 1;
 // DEVICE copy of the literals only (tableplan.cpp; never in Program::lits): a LAZY comparison atom — `length / port op constant` that is no rule's
 // trigger — is not evaluated per group by the attribute kernel; its literal carries an index into VerdictArgs::lazy instead of a column and the
-// verdict kernel evaluates it for the few rules whose other literals already hold for somebody (kernels.hip: verdict2_kernel)
+// verdict kernel evaluates it for the few rules whose other literals already hold for somebody (verdict.hip: verdict2_kernel)
 static constexpr uint32_t LIT_LAZY = 1u << 29;  // then bits [15:0] = the constant (<= 65534... any 16-bit value), bit 16 = operator (0: ==, 1: <=), bit 17 = slot of the variable (VerdictArgs::lazy_var), bit 18 = the atom is evaluated complemented (!=, >)
 static constexpr uint32_t LIT_LAZY_CONST_MASK = 0xFFFFu, LIT_LAZY_OP = 1u << 16, LIT_LAZY_SLOT = 1u << 17, LIT_LAZY_COMPLEMENT = 1u << 18;  // the fields of such a word
 

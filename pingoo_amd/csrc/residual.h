@@ -9,7 +9,7 @@
 // `Bool(true)` = the rule matches. The result lands in the hit record of a pseudo pass, one column per residual rule; the verdict
 // kernel treats it like any other atom, so rule order / first-match-wins / actions are untouched.
 //
-// This file is shared by the device kernel (kernels.hip) and by a TEST-ONLY host build (tests/rvm_host.cpp): the same interpreter
+// This file is shared by the device kernel (kernels.hip: residual_kernel) and by a TEST-ONLY host build (tests/rvm_host.cpp): the same interpreter
 // source runs under g++ so that the CPU suite can fuzz it against the oracle without a GPU. The product library exports no host
 // evaluation entry point.
 //
@@ -35,18 +35,25 @@ typedef __SIZE_TYPE__ size_t;
 #define INT64_MAX __INT64_MAX__
 #endif
 
+// PWAF_HD_INLINE: a helper for host and device that is always inlined (confirm.h has the same definition; this file is handed to hiprtc
+// as it stands, so it relies on no other header).
+#ifndef PWAF_HD_INLINE
 #if defined(__HIPCC__)
-#define PWAF_HD __host__ __device__ __forceinline__
+#define PWAF_HD_INLINE __host__ __device__ __forceinline__
+#else
+#define PWAF_HD_INLINE inline
+#endif
+#endif
+#if defined(__HIPCC__)
 #define PWAF_HD_NOINLINE __host__ __device__ __noinline__
 #else
-#define PWAF_HD inline
 #define PWAF_HD_NOINLINE inline
 #endif
 // The string helpers: out of line in the interpreter (one copy, called from a dozen places of a program that is decoded at run time);
 // in line in the SPECIALIZED form (residual_jit.cpp, compiled by hiprtc), where the source of nearly every string — which field, a
 // constant, a rope — is a literal at the call site and the dispatch inside them folds away.
 #if defined(__HIPCC_RTC__)
-#define PWAF_HD_STR PWAF_HD
+#define PWAF_HD_STR PWAF_HD_INLINE
 // Loops over the segments of a rope: unrolled in the specialized form, where the segment count is a literal once the concatenation
 // that built the rope is inlined — the lane's heap is then indexed by constants only and lives in registers, not in scratch memory
 // (measured: 0.68 ms per 10M requests for ONE rule matching a regex against host + ":" + method with the heap in scratch).
@@ -173,16 +180,16 @@ struct Machine {
 };
 
 // ---- helpers -------------------------------------------------------------------------------------------------------------------------
-PWAF_HD Val mk(uint32_t t, uint32_t a = 0, uint64_t p = 0) { Val v; v.t = t; v.a = a; v.p = p; return v; }
-PWAF_HD Val mk_bool(bool b) { return mk(T_BOOL, 0, b ? 1u : 0u); }
-PWAF_HD Val mk_int(int64_t i) { return mk(T_INT, 0, (uint64_t)i); }
-PWAF_HD Val mk_flt(double d) { uint64_t u; __builtin_memcpy(&u, &d, 8); return mk(T_FLT, 0, u); }
-PWAF_HD double as_flt(const Val &v) { double d; __builtin_memcpy(&d, &v.p, 8); return d; }
-PWAF_HD uint32_t str_src(const Val &v) { return (uint32_t)(v.p >> 48); }
+PWAF_HD_INLINE Val mk(uint32_t t, uint32_t a = 0, uint64_t p = 0) { Val v; v.t = t; v.a = a; v.p = p; return v; }
+PWAF_HD_INLINE Val mk_bool(bool b) { return mk(T_BOOL, 0, b ? 1u : 0u); }
+PWAF_HD_INLINE Val mk_int(int64_t i) { return mk(T_INT, 0, (uint64_t)i); }
+PWAF_HD_INLINE Val mk_flt(double d) { uint64_t u; __builtin_memcpy(&u, &d, 8); return mk(T_FLT, 0, u); }
+PWAF_HD_INLINE double as_flt(const Val &v) { double d; __builtin_memcpy(&d, &v.p, 8); return d; }
+PWAF_HD_INLINE uint32_t str_src(const Val &v) { return (uint32_t)(v.p >> 48); }
 
 template <class T>
-PWAF_HD const T *section(const Machine &m, uint32_t off) { return reinterpret_cast<const T *>(m.blob + off); }
-PWAF_HD const Val *items_of(const Machine &m, const Val &l) {
+PWAF_HD_INLINE const T *section(const Machine &m, uint32_t off) { return reinterpret_cast<const T *>(m.blob + off); }
+PWAF_HD_INLINE const Val *items_of(const Machine &m, const Val &l) {
     return (l.p & kHeapBit) ? &m.heap[(uint32_t)(l.p & 0xFFFFFFFFu)] : section<Val>(m, m.h->consts) + (uint32_t)(l.p & 0xFFFFFFFFu);
 }
 
@@ -190,18 +197,18 @@ PWAF_HD const Val *items_of(const Machine &m, const Val &l) {
 // are global loads instead of flat ones.
 #if defined(__HIP_DEVICE_COMPILE__)
 template <class T>
-PWAF_HD const T *in_global(const T *p) { return (const T *)(const __attribute__((address_space(1))) T *)p; }
+PWAF_HD_INLINE const T *in_global(const T *p) { return (const T *)(const __attribute__((address_space(1))) T *)p; }
 #else
 template <class T>
-PWAF_HD const T *in_global(const T *p) { return p; }
+PWAF_HD_INLINE const T *in_global(const T *p) { return p; }
 #endif
 // Eight bytes at any address (strings are read a word at a time: a lane's string lives in its own cache lines, so every load
 // instruction of a wave touches up to 64 of them — the cost is per instruction, not per byte). Reads up to 7 bytes past the string:
 // field arenas carry PWAF_ARENA_PAD, the program image ends in padding, the inline buffer (≤ 6 value bytes) has 16.
 typedef uint64_t __attribute__((aligned(1), may_alias)) u64_unaligned;
-PWAF_HD uint64_t load8(const uint8_t *p) { return *reinterpret_cast<const u64_unaligned *>(p); }
+PWAF_HD_INLINE uint64_t load8(const uint8_t *p) { return *reinterpret_cast<const u64_unaligned *>(p); }
 // Bytes of a non-rope string (nullptr for a rope).
-PWAF_HD const uint8_t *flat_ptr(const Machine &m, const Val &s, uint8_t (&inl)[16]) {
+PWAF_HD_INLINE const uint8_t *flat_ptr(const Machine &m, const Val &s, uint8_t (&inl)[16]) {
     const uint32_t src = str_src(s);
     const uint32_t off = (uint32_t)(s.p & 0xFFFFFFFFu);
     if (src < S_CONST) return in_global(m.q.data[src]) + in_global(m.q.off[src])[m.q.r] + off;
@@ -241,7 +248,7 @@ PWAF_HD_STR bool str_eq_at(const Machine &m, const Val &h, uint32_t at, const Va
         if (str_byte(m, h, at + k) != str_byte(m, n, k)) return false;
     return true;
 }
-PWAF_HD int str_cmp(const Machine &m, const Val &a, const Val &b) {  // bytewise, like std::string_view::compare
+PWAF_HD_INLINE int str_cmp(const Machine &m, const Val &a, const Val &b) {  // bytewise, like std::string_view::compare
     const uint32_t n = a.a < b.a ? a.a : b.a;
     if (str_src(a) != S_ROPE && str_src(b) != S_ROPE) {
         uint8_t i1[16], i2[16];
@@ -264,13 +271,13 @@ PWAF_HD int str_cmp(const Machine &m, const Val &a, const Val &b) {  // bytewise
     }
     return a.a < b.a ? -1 : a.a > b.a ? 1 : 0;
 }
-PWAF_HD bool str_find(const Machine &m, const Val &h, const Val &n) {
+PWAF_HD_INLINE bool str_find(const Machine &m, const Val &h, const Val &n) {
     if (n.a > h.a) return false;
     for (uint32_t s = 0; s + n.a <= h.a; s++)
         if (str_eq_at(m, h, s, n)) return true;
     return false;
 }
-PWAF_HD bool net_contains(const NetItem &nt, const uint8_t *ip, uint32_t v6) {  // ipnetwork semantics: family must match, mask compare
+PWAF_HD_INLINE bool net_contains(const NetItem &nt, const uint8_t *ip, uint32_t v6) {  // ipnetwork semantics: family must match, mask compare
     if ((nt.v6 != 0) != (v6 != 0)) return false;
     const uint32_t bytes = v6 ? 16u : 4u;
     uint32_t left = nt.prefix;
@@ -285,11 +292,11 @@ PWAF_HD bool net_contains(const NetItem &nt, const uint8_t *ip, uint32_t v6) {  
 
 // A value slot of a map, read: a constant map's T_REF slots name a request value (the map itself costs no stack slot and no heap item,
 // whatever its size — a headers map of 64 names as a value; until round 6 its entries were pushed and popped: 2 x 64 stack slots).
-PWAF_HD Val op_field(const Machine &m, uint32_t f);
-PWAF_HD Val op_country(const Machine &m);
-PWAF_HD Val op_port(const Machine &m);
-PWAF_HD Val op_asn(const Machine &m);
-PWAF_HD Val deref(const Machine &m, const Val &v) {
+PWAF_HD_INLINE Val op_field(const Machine &m, uint32_t f);
+PWAF_HD_INLINE Val op_country(const Machine &m);
+PWAF_HD_INLINE Val op_port(const Machine &m);
+PWAF_HD_INLINE Val op_asn(const Machine &m);
+PWAF_HD_INLINE Val deref(const Machine &m, const Val &v) {
     if (v.t != T_REF) return v;
     switch (v.a) {
         case R_FIELD: return op_field(m, (uint32_t)v.p);
@@ -348,9 +355,9 @@ struct Eq {
 };
 template <>
 struct Eq<-1> {
-    static PWAF_HD bool eq(const Machine &, const Val &, const Val &) { return false; }  // unreachable: nesting is bounded at compile time
+    static PWAF_HD_INLINE bool eq(const Machine &, const Val &, const Val &) { return false; }  // unreachable: nesting is bounded at compile time
 };
-PWAF_HD bool val_eq(const Machine &m, const Val &a, const Val &b) {
+PWAF_HD_INLINE bool val_eq(const Machine &m, const Val &a, const Val &b) {
     // scalars in line (the same answers as the general comparison above): in the specialized form one operand's type is usually known
     // at compile time, and the out-of-line general comparison — with the registers it needs — is then never referenced
     if (a.t == T_INT && b.t == T_FLT) return (double)(int64_t)a.p == as_flt(b);
@@ -366,7 +373,7 @@ PWAF_HD bool val_eq(const Machine &m, const Val &a, const Val &b) {
 }
 
 // -1 / 0 / 1, or 2 when not comparable (D5)
-PWAF_HD int val_cmp(const Machine &m, const Val &a, const Val &b) {
+PWAF_HD_INLINE int val_cmp(const Machine &m, const Val &a, const Val &b) {
     const bool an = a.t == T_INT || a.t == T_FLT, bn = b.t == T_INT || b.t == T_FLT;
     if (a.t == T_INT && b.t == T_INT) return (int64_t)a.p < (int64_t)b.p ? -1 : (int64_t)a.p > (int64_t)b.p ? 1 : 0;
     if (an && bn) {
@@ -421,7 +428,7 @@ PWAF_HD_STR bool list_contains(const Machine &m, const Val &l, const Val &x) {
     }
     return false;
 }
-PWAF_HD bool map_has(const Machine &m, const Val &mp, const Val &key, Val *out) {
+PWAF_HD_INLINE bool map_has(const Machine &m, const Val &mp, const Val &key, Val *out) {
     const Val *it = items_of(m, mp);
     for (uint32_t k = 0; k < mp.a; k++)
         if (it[2 * k].a == key.a && str_eq_at(m, it[2 * k], 0, key)) {
@@ -513,44 +520,44 @@ PWAF_HD_STR bool regex_match(const Machine &m, uint32_t id, const Val &s) {
 }
 // recv.matches(<literal pattern>) with the table's mode known (what op_call's FN_MATCHES case does, for the specialized program)
 template <bool SCALAR>
-PWAF_HD Val op_matches(const Machine &m, uint32_t aux, const Val &recv, const Val &arg) {
+PWAF_HD_INLINE Val op_matches(const Machine &m, uint32_t aux, const Val &recv, const Val &arg) {
     if (recv.t == T_ERR || arg.t == T_ERR || recv.t != T_STR || arg.t != T_STR || aux == 0xFFFu) return mk(T_ERR);  // (an invalid pattern is an execution error)
     return mk_bool(regex_match_t<SCALAR>(m, aux, recv));
 }
 
-PWAF_HD Val arith(uint32_t op /* B_ADD.. */, const Val &l, const Val &r, Machine &m);
+PWAF_HD_INLINE Val arith(uint32_t op /* B_ADD.. */, const Val &l, const Val &r, Machine &m);
 
 // ---- the operations of the stack program ------------------------------------------------------------------------------------------------
 // One function per instruction, shared by the interpreter below (run_rule: decodes the program per request) and by the SPECIALIZED form
 // of a rule set (residual_jit.cpp: the same program translated instruction by instruction into straight-line calls of these functions
 // with the stack slots as local variables and the constants as literals, compiled for the device when the engine is created).
 // BinOp numbering of frontend.h: B_OR 0, B_AND 1, B_EQ 2, B_NE 3, B_LT 4, B_LE 5, B_GT 6, B_GE 7, B_IN 8, B_ADD 9, B_SUB 10, B_MUL 11, B_DIV 12, B_MOD 13
-PWAF_HD Val op_field(const Machine &m, uint32_t f) {
+PWAF_HD_INLINE Val op_field(const Machine &m, uint32_t f) {
     const uint32_t *off = in_global(m.q.off[f]) + m.q.r;
     return mk(T_STR, off[1] - off[0], (uint64_t)f << 48);
 }
-PWAF_HD Val op_country(const Machine &m) { return mk(T_STR, 2, ((uint64_t)S_INLINE << 48) | (m.q.country & 0xFFFFu)); }
-PWAF_HD Val op_port(const Machine &m) { return mk_int((int64_t)m.q.port); }
-PWAF_HD Val op_asn(const Machine &m) { return mk_int((int64_t)m.q.asn); }
-PWAF_HD Val op_not(const Val &x) {
+PWAF_HD_INLINE Val op_country(const Machine &m) { return mk(T_STR, 2, ((uint64_t)S_INLINE << 48) | (m.q.country & 0xFFFFu)); }
+PWAF_HD_INLINE Val op_port(const Machine &m) { return mk_int((int64_t)m.q.port); }
+PWAF_HD_INLINE Val op_asn(const Machine &m) { return mk_int((int64_t)m.q.asn); }
+PWAF_HD_INLINE Val op_not(const Val &x) {
     if (x.t == T_ERR) return x;
     return x.t == T_BOOL ? mk_bool(x.p == 0) : mk(T_ERR);
 }
-PWAF_HD Val op_neg(const Val &x) {
+PWAF_HD_INLINE Val op_neg(const Val &x) {
     if (x.t == T_INT) return (int64_t)x.p == INT64_MIN ? mk(T_ERR) : mk_int(-(int64_t)x.p);
     if (x.t == T_FLT) return mk_flt(-as_flt(x));
     return mk(T_ERR);
 }
 // The left operand of && (is_or false) / || (true), popped: true = it decides (`out` = the result: the operand itself, or an error when
 // it is not a Bool) and the right operand is skipped; false = the right operand is evaluated and IS the result (after op_bool_chk).
-PWAF_HD bool op_logic_left(bool is_or, const Val &l, Val &out) {
+PWAF_HD_INLINE bool op_logic_left(bool is_or, const Val &l, Val &out) {
     if (l.t != T_BOOL) { out = mk(T_ERR); return true; }
     if (is_or == (l.p != 0)) { out = l; return true; }
     return false;
 }
-PWAF_HD Val op_bool_chk(const Val &x) { return x.t == T_BOOL ? x : mk(T_ERR); }  // the right operand of && / || must be a Bool (an error stays an error)
-PWAF_HD uint32_t op_cond(const Val &c) { return c.t != T_BOOL ? 2u : c.p == 0 ? 1u : 0u; }  // 0: then branch, 1: else branch, 2: not a Bool (the conditional is an error)
-PWAF_HD Val op_mklist(Machine &m, const Val *items, uint32_t n) {
+PWAF_HD_INLINE Val op_bool_chk(const Val &x) { return x.t == T_BOOL ? x : mk(T_ERR); }  // the right operand of && / || must be a Bool (an error stays an error)
+PWAF_HD_INLINE uint32_t op_cond(const Val &c) { return c.t != T_BOOL ? 2u : c.p == 0 ? 1u : 0u; }  // 0: then branch, 1: else branch, 2: not a Bool (the conditional is an error)
+PWAF_HD_INLINE Val op_mklist(Machine &m, const Val *items, uint32_t n) {
     bool err = false;
     for (uint32_t k = 0; k < n; k++) err = err || items[k].t == T_ERR;
     if (err || m.heap_n + n > kHeap) return mk(T_ERR);  // (the compiler bounds heap use statically; the check here is the safety net behind it)
@@ -558,7 +565,7 @@ PWAF_HD Val op_mklist(Machine &m, const Val *items, uint32_t n) {
     for (uint32_t k = 0; k < n; k++) m.heap[m.heap_n++] = items[k];
     return v;
 }
-PWAF_HD Val op_mkmap(Machine &m, const Val *kv /* key, value, key, value ... */, uint32_t n) {
+PWAF_HD_INLINE Val op_mkmap(Machine &m, const Val *kv /* key, value, key, value ... */, uint32_t n) {
     bool err = false;
     for (uint32_t k = 0; k < 2 * n; k++) err = err || kv[k].t == T_ERR || ((k & 1) == 0 && kv[k].t != T_STR);
     if (err || m.heap_n + 2 * n > kHeap) return mk(T_ERR);
@@ -574,7 +581,7 @@ PWAF_HD Val op_mkmap(Machine &m, const Val *kv /* key, value, key, value ... */,
     m.heap_n = base + 2 * cnt;
     return mk(T_MAP, cnt, kHeapBit | base);
 }
-PWAF_HD Val op_index(const Machine &m, const Val &o, const Val &i) {
+PWAF_HD_INLINE Val op_index(const Machine &m, const Val &o, const Val &i) {
     Val v = mk(T_ERR);
     if (o.t == T_ERR || i.t == T_ERR) {}
     else if (o.t == T_MAP) { if (i.t == T_STR) { Val out; if (map_has(m, o, i, &out)) v = out; } }
@@ -589,14 +596,14 @@ PWAF_HD Val op_index(const Machine &m, const Val &o, const Val &i) {
     }
     return v;
 }
-PWAF_HD Val op_select(const Machine &m, const Val &o, const Val &key) {
+PWAF_HD_INLINE Val op_select(const Machine &m, const Val &o, const Val &key) {
     if (o.t == T_ERR) return o;
     Val got;
     if (o.t == T_MAP && map_has(m, o, key, &got)) return got;
     return mk(T_ERR);
 }
 // recv.fn(arg): argc is 0 (length) or 1 (the compiler turns every other arity into R_FAIL); `arg` is ignored when argc == 0
-PWAF_HD Val op_call(const Machine &m, uint32_t fn, uint32_t argc, uint32_t aux, const Val &recv, const Val &arg) {
+PWAF_HD_INLINE Val op_call(const Machine &m, uint32_t fn, uint32_t argc, uint32_t aux, const Val &recv, const Val &arg) {
     Val v = mk(T_ERR);
     if (recv.t == T_ERR || (argc && arg.t == T_ERR)) return v;
     switch (fn) {
@@ -634,7 +641,7 @@ PWAF_HD Val op_call(const Machine &m, uint32_t fn, uint32_t argc, uint32_t aux, 
     }
     return v;
 }
-PWAF_HD Val op_bin(Machine &m, uint32_t op, const Val &l, const Val &r) {
+PWAF_HD_INLINE Val op_bin(Machine &m, uint32_t op, const Val &l, const Val &r) {
     Val v = mk(T_ERR);
     if (l.t == T_ERR || r.t == T_ERR) return v;
     switch (op) {
@@ -655,7 +662,7 @@ PWAF_HD Val op_bin(Machine &m, uint32_t op, const Val &l, const Val &r) {
 }
 // 1 = the rule's program ends in Bool(true) (the rule matches), 2 = it ends in an execution ERROR (what the reference logs with warn!
 // and treats as "no match": pingoo/rules.rs:41-45), 0 = anything else (false, or a non-Bool value: no match, no error).
-PWAF_HD uint32_t rule_result(const Val &top) { return top.t == T_ERR ? 2u : (top.t == T_BOOL && top.p == 1) ? 1u : 0u; }
+PWAF_HD_INLINE uint32_t rule_result(const Val &top) { return top.t == T_ERR ? 2u : (top.t == T_BOOL && top.p == 1) ? 1u : 0u; }
 
 // ---- the interpreter: one rule, one request ---------------------------------------------------------------------------------------------
 PWAF_HD_NOINLINE uint32_t run_rule(Machine &m, uint32_t rule) {
@@ -730,7 +737,7 @@ PWAF_HD_NOINLINE uint32_t run_rule(Machine &m, uint32_t rule) {
     }
 }
 
-PWAF_HD Val arith(uint32_t op, const Val &l, const Val &r, Machine &m) {
+PWAF_HD_INLINE Val arith(uint32_t op, const Val &l, const Val &r, Machine &m) {
     const Val ERR = mk(T_ERR);
     if (l.t == T_INT && r.t == T_INT) {
         const int64_t a = (int64_t)l.p, b = (int64_t)r.p;

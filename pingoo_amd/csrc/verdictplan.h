@@ -1,27 +1,30 @@
 // verdictplan.h — the launch shape of the verdict kernels and the LDS layout it is computed from: entry capacity, waves per workgroup,
-// workgroups per CU, program tables in LDS or not. The layout helpers are what the kernels themselves lay their LDS out with (kernels.hip:
+// workgroups per CU, program tables in LDS or not. The layout helpers are what the kernels themselves lay their LDS out with (verdict.hip:
 // verdict_kernel, verdict2_kernel); verdict_shape and verdict_blocks_sp are host code. No HIP header in here: hipcc compiles it into
-// kernels.hip (the helpers then also for the device), g++ into program_api.cpp (pwaf_program_verdict_shape) and tests/verdictplan_host.cpp
+// verdict.hip (the helpers then also for the device), g++ into program_api.cpp (pwaf_program_verdict_shape) and tests/verdictplan_host.cpp
 // — the CPU suite checks the shape over sizes up to the limits (tests/test_verdict_edges_cpu.py).
 #pragma once
 #include <stdint.h>
 
 #include <algorithm>
 
+// PWAF_HOST_DEVICE: a plain function for host and device (program.h's definition, repeated for the programs that include this file alone)
+#ifndef PWAF_HOST_DEVICE
 #if defined(__HIPCC__)
-#define PWAF_HD __host__ __device__
+#define PWAF_HOST_DEVICE __host__ __device__
 #else
-#define PWAF_HD
+#define PWAF_HOST_DEVICE
+#endif
 #endif
 
 namespace pwaf {
 
 struct VerdictShape {
     uint32_t waves, lds_bytes, lds_tables;
-    uint32_t sparse, v_cap, per_cu;  // sparse: 1 = the sparse column file, 2 = the entry list (verdict2_kernel); (kernels.hip: verdict_kernel<.., SP>): value slots per wave, workgroups per CU
+    uint32_t sparse, v_cap, per_cu;  // sparse: 1 = the sparse column file, 2 = the entry list (verdict2_kernel); (verdict.hip: verdict_kernel<.., SP>): value slots per wave, workgroups per CU
 };
 
-PWAF_HD static inline uint32_t verdict_wave_lds(uint32_t n_cols, uint32_t n_rules) {
+PWAF_HOST_DEVICE static inline uint32_t verdict_wave_lds(uint32_t n_cols, uint32_t n_rules) {
     const uint32_t colw = (n_cols + 31) / 32, rulew = (n_rules + 31) / 32;
     return ((n_cols * 8 + colw * 4 + rulew * 4 + n_rules * 2) + 15) & ~15u;  // columns, bitmaps, candidates (also: the list of non-zero columns)
 }
@@ -33,17 +36,17 @@ PWAF_HD static inline uint32_t verdict_wave_lds(uint32_t n_cols, uint32_t n_rule
 // column's rank among the dirty ones: ~4 KiB per wave whatever the rule set, i.e. two workgroups of 12 waves per CU. A group is marked
 // twice — bits first (the ranks need all of them), values second — and a value read is two dependent LDS reads instead of one. A group
 // with more dirty columns than the value array holds (v_cap) keeps the rest in a per-wave spill array in global memory (same results).
-PWAF_HD static inline uint32_t verdict_wave_lds_sp(uint32_t n_cols, uint32_t n_rules, uint32_t v_cap) {
+PWAF_HOST_DEVICE static inline uint32_t verdict_wave_lds_sp(uint32_t n_cols, uint32_t n_rules, uint32_t v_cap) {
     const uint32_t colw = (n_cols + 31) / 32, rulew = (n_rules + 31) / 32;
     return ((colw * 8 + v_cap * 8 + rulew * 4 + n_rules * 2) + 15) & ~15u;  // {dirty bits, rank} per 32 columns, values, rule bitmap, candidates
 }
-PWAF_HD static inline uint32_t verdict_v_cap(uint32_t n_cols, bool tiny) {
+PWAF_HOST_DEVICE static inline uint32_t verdict_v_cap(uint32_t n_cols, bool tiny) {
     const uint32_t v = tiny ? 8u : 256u + n_cols / 16u;
     return v < n_cols ? v : n_cols;
 }
 
 // ENTRY LIST (verdict2_kernel): vals | rule bitmap | entry columns (u16) | candidates (u16) | slot bytes
-PWAF_HD static inline uint32_t verdict_wave_lds_el(uint32_t n_cols, uint32_t n_rules, uint32_t e_cap) {
+PWAF_HOST_DEVICE static inline uint32_t verdict_wave_lds_el(uint32_t n_cols, uint32_t n_rules, uint32_t e_cap) {
     const uint32_t rulew = (n_rules + 31) / 32;
     return (e_cap * 8 + rulew * 4 + ((e_cap * 2 + 3) & ~3u) + ((n_rules * 2 + 3) & ~3u) + ((n_cols + 7) & ~7u) + 15) & ~15u;
 }
@@ -54,7 +57,7 @@ PWAF_HD static inline uint32_t verdict_wave_lds_el(uint32_t n_cols, uint32_t n_r
 struct VerdictTables {
     uint32_t bitcol, trig_off, trig_rules, rules, lits, pub, end;  // byte offsets from the start of the table region
 };
-PWAF_HD static inline VerdictTables verdict_tables(uint32_t n_cols, uint32_t n_rules, uint32_t n_trig, uint32_t n_lits, bool lt) {
+PWAF_HOST_DEVICE static inline VerdictTables verdict_tables(uint32_t n_cols, uint32_t n_rules, uint32_t n_trig, uint32_t n_lits, bool lt) {
     VerdictTables t;
     t.bitcol = 0;
     t.trig_off = 0;

@@ -24,10 +24,10 @@ from pingoo_amd.engine import CompiledProgram
 B, CAP = _abi.RULE_ACTION_BLOCK, _abi.RULE_ACTION_CAPTCHA
 CHUNK = 16
 SLAB = 128 * 1024      # csrc/kernels.h:203  kStreamSlab: the bytes one wave of filter_kernel / resolve_kernel owns
-RESOLVE_SPARSE = 128   # csrc/kernels.hip:1841  resolve_kernel, kResolveSparse: flagged chunks up to which a slab is resolved chunk by chunk
-OWNER_BOUND = 4096     # csrc/kernels.hip:1949  resolve_kernel, `h = min(a.n, lo + 4096u)`: the owner search of the chunk-driven path
-RESET_BOUND = 48       # csrc/kernels.hip:1964  resolve_kernel, `steps < 48u`: the record reset of the chunk-driven path
-QUEUE = 1024           # csrc/kernels.hip:1039  confirm_kernel, kConfirmQueue: a workgroup's queue of walk-list appends
+RESOLVE_SPARSE = 128   # csrc/kernels.hip, resolve_kernel: kResolveSparse, flagged chunks up to which a slab is resolved chunk by chunk
+OWNER_BOUND = 4096     # csrc/kernels.hip, resolve_kernel: `h = min(a.n, lo + 4096u)`, the owner search of the chunk-driven path
+RESET_BOUND = 48       # csrc/kernels.hip, resolve_kernel: `steps < 48u`, the record reset of the chunk-driven path
+QUEUE = 1024           # csrc/confirm.hip, confirm_kernel: kConfirmQueue, a workgroup's queue of walk-list appends
 POOL_WORDS = 10240     # csrc/kernels.h:183  kConfirmPoolBytes / 4: confirm_kernel's LDS pool for entries + bytes + classes
 CONFIRM_THREADS = 1024  # csrc/kernels.h:182  kConfirmThreads: pairs per work item of confirm_kernel
 MI355X_CUS = 256       # launch_confirm's grid is 2 workgroups per compute unit; the CPU suite builds case J for this device

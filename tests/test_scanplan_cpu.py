@@ -26,7 +26,7 @@ SRC = os.path.join(HERE, "scanplan_host.cpp")
 UNITS = COMPILER_UNITS + ["scanplan.cpp"]
 B = _abi.RULE_ACTION_BLOCK
 K_GAP_LISTS = 32  # (program.h: kGapLists)
-LDS_NARROW, LDS_WIDE = 48 * 1024, 144 * 1024  # (kernels.hip: list_shape(0), list_shape(2))
+LDS_NARROW, LDS_WIDE = 48 * 1024, 144 * 1024  # (csrc/scanplan.cpp: list_shape(0), list_shape(2))
 FIELD_METHOD, N_FIELDS = 3, 5
 OK = {"stage": "ok", "rc": 0, "rule_index": U32, "message": ""}
 

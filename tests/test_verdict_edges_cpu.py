@@ -128,7 +128,7 @@ def test_the_cases_know_the_kernels_prefetch_depth():
     import re
     csrc = os.path.join(os.path.dirname(HERE), "pingoo_amd", "csrc")
     general = int(re.search(r"static constexpr int kVerdictPre = (\d+);", open(os.path.join(csrc, "kernels.h")).read()).group(1))
-    hip = open(os.path.join(csrc, "kernels.hip")).read()
+    hip = open(os.path.join(csrc, "verdict.hip")).read()
     body = hip[hip.index("void verdict2_kernel(VerdictArgs a)"):]
     m = re.search(r"constexpr int kPre = BR == 1 \? (\d+) : kVerdictPre;", body)
     assert m is not None and VC.K_PRE_BY_BR == {1: int(m.group(1)), 4: general}

@@ -3,7 +3,7 @@ request BY CONSTRUCTION, base batches laid out by 64-request groups, and two ind
 
   reference()   numpy, written from the rule list: the first rule in order whose expression holds and whose action takes effect for the
                 request's verified bit, the four counters, the hit matrix, the first route. Not the engine, not a model of the kernel.
-  GroupModel    what verdict2_kernel (csrc/kernels.hip) does with a group, from the program's tables (the plan of tests/tableplan_host.cpp:
+  GroupModel    what verdict2_kernel (csrc/verdict.hip) does with a group, from the program's tables (the plan of tests/tableplan_host.cpp:
                 device rules and literals, trigger lists, the always-bitmap; the dump's pass ranges) and the truth table: the attribute
                 pairs, the distinct atoms per scan pass and the lanes with an overflow chain, the entries appended at each of the three
                 append sites in the kernel's order, the candidate count, whether the group spills.
@@ -830,7 +830,7 @@ def targets(c, flags):
         t["a chain atom merged into an LDS entry"] = any(("lds" in [w for _, w in m.merges]) for m in ms)
         t["a chain atom merged into a spilled entry"] = any(("spill" in [w for _, w in m.merges]) for m in ms)
         t["a chain appends the entry that spills"] = any(m.spill_by_chain for m in ms)
-        # A chain is a stack (csrc/kernels.hip: record_atom / merge_atom push at the head): a lane that walks its field alone leaves its atoms in
+        # A chain is a stack (csrc/hitrec.h: record_atom, csrc/confirm.hip: merge_atom push at the head): a lane that walks its field alone leaves its atoms in
         # the reverse of their order in the field. Two lanes with the same tokens in the same order then name every atom at the same step; two
         # lanes of equal length whose tokens are shifted name a common atom at different steps — in field order or its reverse alike. (Behind
         # the confirm tier several chunk lanes push one request's atoms and the order is the device's: the no-prefilter leg walks alone.)
