@@ -18,7 +18,7 @@
  *   geoip record -> RequestContext   http_listener.rs:143-157,183-191; upstream headers http_proxy_service.rs:174-189
  *                                                              pwaf_geoip_lookup / pwaf_evaluate_*_geo (PWAF_OPT_GEO_ANSWERS)
  *   get_host / get_path / UA derive  http_listener.rs:140-165,284-296; http_utils.rs:114-116
- *                                                              pwaf_derive_host / _path / _user_agent
+ *                                                              pwaf_derive_host / _path / _user_agent; pwaf_derive_batch
  *   generate_captcha_client_id       http_listener.rs:167; pingoo/captcha.rs:409-421
  *                                                              pwaf_client_id_one / pwaf_client_ids
  *
@@ -493,6 +493,71 @@ typedef struct pwaf_client_id {
 int pwaf_client_ids(const pwaf_batch *in, const uint32_t *idx /* nullable */, uint32_t idx_cap, const uint32_t *n_idx /* nullable */,
                     pwaf_client_id *out, void *stream);
 int pwaf_client_id_one(const pwaf_request *req, pwaf_client_id *out);
+
+/* ---- derived columns of a raw batch (ABI 4, additive) -----------------------------------------------------
+ * Every evaluation entry point takes the fields AFTER the reference's own derivation (http_listener.rs:140-165, :284-296;
+ * http_utils.rs:114-116). pwaf_derive_host / _path / _user_agent (below) answer it per request on the host; pwaf_derive_batch answers it
+ * for a whole batch whose parsed but underived bytes lie in one place — a replay file copied to the device once, a capture — and writes
+ * three columns the evaluation reads as they are. It takes no engine (like pwaf_export_records and pwaf_client_ids).
+ * Input: raw->field[PWAF_FIELD_HOST] holds the Host header's value bytes, field[PWAF_FIELD_PATH] uri.path(), field[PWAF_FIELD_USER_AGENT]
+ * the User-Agent header's value bytes; no other member of *raw is looked at (they may be NULL). extra (nullable) carries what a raw batch
+ * has beyond that: uri.host() per request and which of the three sources a request has at all. raw->memory says where EVERY pointer lives:
+ * the batch's, extra's columns, out[]'s, stats and scratch. Input offsets need not begin at 0 (a slab view); output offsets do.
+ * Per request i, exactly pwaf_derive_path / _user_agent / _host:
+ *   path        the raw value without its trailing '/' bytes.
+ *   user_agent  "" when PWAF_RAW_HAS_USER_AGENT is clear; "" when a byte of the value is neither TAB nor 0x20..0x7E; else the value
+ *               trimmed of ' ' and TAB at both ends, and "" when more than 256 bytes remain (256 are kept).
+ *   host        with PWAF_RAW_HAS_URI_HOST: the URI's host trimmed of 0x09..0x0D and 0x20, "" when more than 256 bytes remain; no byte
+ *               check; the Host header is not consulted even when the result is "". Otherwise the Host header, taken like the
+ *               User-Agent under PWAF_RAW_HAS_HOST_HEADER.
+ *   The bytes of a value whose present bit is clear are ignored, and so are unknown bits of a present byte. A NULL uri_host.data or
+ *   .offsets means that no request has a URI host: PWAF_RAW_HAS_URI_HOST then counts as clear.
+ * Output, out[0] host, out[1] path, out[2] user_agent: offsets[0..n] are always written completely (they are sizes, offsets[0] == 0);
+ * data receives the kept bytes back to back, and the PWAF_ARENA_PAD bytes behind the column's last byte are written as zero where they lie
+ * below cap, which makes the column a valid PWAF_MEM_DEVICE arena. Nothing is written at or beyond data + cap, offsets + n + 1 or
+ * stats + 1, and nothing between bytes[c] + 16 and cap. With bytes[c] + PWAF_ARENA_PAD <= cap the column is complete — always so when cap
+ * is at least the raw column's bytes + 16; for host: the Host headers' bytes + the URI hosts' bytes + 16, because each request takes its
+ * host from one of the two columns and a batch may take every byte of both — otherwise stats->overflow says so and which of that
+ * column's BYTES were written is unspecified: a caller looks at overflow before it reads such a column. n == 0 writes offsets[0] = 0 (where offsets is given), the pads and stats.
+ * Memory and streams:
+ *   PWAF_MEM_HOST    synchronous, plain C++, no HIP call: works on a machine without a GPU and reads no byte outside a value (no pad is
+ *                    assumed). scratch and stream are ignored. A request whose offsets decrease in a column it reads refuses the whole
+ *                    call with PWAF_E_BATCH (naming the request and the column) before anything is written.
+ *   PWAF_MEM_DEVICE  at most three launches (derive_span_kernel, derive_base_kernel, derive_copy_kernel) are enqueued on `stream`
+ *                    (hipStream_t; NULL = HIP's default stream) of the current device and the call returns at once. No memset, nothing
+ *                    allocated, nothing copied. scratch: pwaf_derive_scratch_bytes(n) bytes of device memory, 16-byte aligned, the
+ *                    call's own until the launches have run. The batch is trusted as pwaf_evaluate_device trusts it. Loads may run
+ *                    past a value's end by fewer than 16 bytes, inside the arena or its PWAF_ARENA_PAD (the URI hosts' arena too); they
+ *                    never begin before the value. A caller copies its pwaf_batch, points the three fields at out[], sets their
+ *                    field_bytes to 0 (the engine then asks for offsets[n] on the same stream) and calls pwaf_evaluate_device on the
+ *                    same stream without a synchronisation of its own.
+ * PWAF_E_INVALID_ARG, before anything runs: NULL raw, out or stats; a bad struct_size (raw's or extra's) or memory; stats not 8-byte
+ * aligned; n > 0xFFFFFFF0 / 256 (a derived host or User-Agent column could pass 32 bits: the caller splits such a batch); with n > 0 a
+ * NULL host, path or User-Agent column or a NULL out[c].offsets; a NULL out[c].data with cap != 0; out[c].data not 16-byte aligned or
+ * offsets not 4-byte aligned; in DEVICE mode scratch NULL, not 16-byte aligned or smaller than pwaf_derive_scratch_bytes(n). */
+#define PWAF_RAW_HAS_URI_HOST 1u    /* req.uri().host() is Some (HTTP/2, absolute-form) */
+#define PWAF_RAW_HAS_HOST_HEADER 2u /* a Host header is present */
+#define PWAF_RAW_HAS_USER_AGENT 4u  /* a User-Agent header is present */
+typedef struct pwaf_raw_columns { /* what a raw batch carries beyond pwaf_batch */
+    uint32_t struct_size, reserved;
+    pwaf_strcol uri_host;   /* uri.host() bytes per request; data / offsets may be NULL: no request has one */
+    const uint8_t *present; /* n x PWAF_RAW_HAS_*; NULL: HOST_HEADER | USER_AGENT for every request, no URI host */
+} pwaf_raw_columns;
+typedef struct pwaf_derived_col {
+    uint8_t *data;
+    uint32_t *offsets; /* n+1 */
+    uint64_t cap;      /* bytes of data */
+} pwaf_derived_col;
+typedef struct pwaf_derive_stats { /* 32 bytes, OVERWRITTEN */
+    uint64_t bytes[3]; /* offsets[n] of the derived host, path, user_agent column, whether or not it fitted */
+    uint32_t n;        /* requests derived */
+    uint32_t overflow; /* bit c set: bytes[c] + PWAF_ARENA_PAD > out[c].cap, that column's BYTES are incomplete */
+} pwaf_derive_stats;
+size_t pwaf_derive_scratch_bytes(uint32_t n); /* DEVICE mode scratch for a batch of n; HOST mode needs none */
+int pwaf_derive_batch(const pwaf_batch *raw, const pwaf_raw_columns *extra /* nullable */, pwaf_derived_col out[3] /* host, path, user_agent */,
+                      pwaf_derive_stats *stats, void *scratch, size_t scratch_bytes, void *stream);
+/* TEST HOOK, CPU: [0] requests per tile, [1] tiles per step of the base launch, [2] requests per workgroup of the copy launch, [3] 0 */
+int pwaf_derive_scan_shape(uint32_t out[4]);
 
 /* ---- records in device memory (ABI 4, additive) ----------------------------------------------------------
  * pwaf_evaluate_records for records that already lie in DEVICE memory — what pwaf_export_records wrote, or a replay file copied to the

@@ -42,6 +42,11 @@ ADDRESS_TABLE_FIELDS = ("escapes", "n_vals", "has_summary", "shift", "common", "
 CONFIRM_SHAPE_FIELDS = ("entries", "bytes", "class_words", "in_lds", "longest", "top_class_pos", "widest_bin", "has_walk")
 # pwaf_records_scan_shape (test hook): the meaning of out[0..3] (pwaf_evaluate_records_device's scan: records per tile, tiles per phase-2 step)
 RECORDS_SCAN_SHAPE_FIELDS = ("tile", "step", "zero2", "zero3")
+# pwaf_derive_scan_shape (test hook): the meaning of out[0..3] (pwaf_derive_batch's scan: requests per tile, tiles per step of the base launch,
+# requests per workgroup of the copy launch)
+DERIVE_SCAN_SHAPE_FIELDS = ("tile", "step", "copy_group", "zero3")
+# pwaf_raw_columns.present: which of its sources a raw request has (pwaf_derive_batch)
+RAW_HAS_URI_HOST, RAW_HAS_HOST_HEADER, RAW_HAS_USER_AGENT = 1, 2, 4
 # pwaf_program_list_scans (test hook): the meaning of a descriptor's PWAF_LIST_SCAN_WORDS words (share_owner 0xFFFFFFFF: none)
 LIST_SCAN_FIELDS = ("phase", "pass", "tier", "threads", "hot_bytes", "n_hot", "n_delta", "behind_filter", "merge_rec", "dense_mode", "share_owner", "need_bit",
                     "launch", "launch_count", "wg_per_cu", "zero15")
@@ -187,6 +192,24 @@ class ClientId(C.Structure):
     """pwaf_client_id: a captcha client id (pwaf_client_ids / pwaf_client_id_one) — 43 characters of the URL-safe alphabet, then NUL."""
 
     _fields_ = [("text", C.c_char * 44)]
+
+
+class RawColumns(C.Structure):
+    """pwaf_raw_columns: what a raw batch carries beyond pwaf_batch (pwaf_derive_batch) — the URI hosts and the present bytes."""
+
+    _fields_ = [("struct_size", C.c_uint32), ("reserved", C.c_uint32), ("uri_host", StrCol), ("present", C.c_void_p)]
+
+
+class DerivedCol(C.Structure):
+    """pwaf_derived_col: one output column of pwaf_derive_batch — data, offsets (n + 1) and the bytes data has room for."""
+
+    _fields_ = [("data", C.c_void_p), ("offsets", C.c_void_p), ("cap", C.c_uint64)]
+
+
+class DeriveStats(C.Structure):
+    """pwaf_derive_stats: offsets[n] of the derived host, path and user_agent column, the requests derived, one overflow bit per column."""
+
+    _fields_ = [("bytes", C.c_uint64 * 3), ("n", C.c_uint32), ("overflow", C.c_uint32)]
 
 
 class Geo(C.Structure):

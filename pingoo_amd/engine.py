@@ -154,6 +154,10 @@ def lib():
     L.pwaf_records_scan_shape.argtypes = [C.POINTER(C.c_uint32)]
     L.pwaf_client_ids.argtypes = [C.POINTER(_abi.Batch), vp, C.c_uint32, vp, vp, vp]
     L.pwaf_client_id_one.argtypes = [C.POINTER(_abi.Request), vp]
+    L.pwaf_derive_scratch_bytes.argtypes = [C.c_uint32]
+    L.pwaf_derive_scratch_bytes.restype = C.c_size_t
+    L.pwaf_derive_batch.argtypes = [C.POINTER(_abi.Batch), C.POINTER(_abi.RawColumns), C.POINTER(_abi.DerivedCol), vp, vp, C.c_size_t, vp]
+    L.pwaf_derive_scan_shape.argtypes = [C.POINTER(C.c_uint32)]
     L.pwaf_async_create.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(vp)]
     L.pwaf_async_submit.argtypes = [vp, C.POINTER(_abi.Request), C.c_uint64]
     L.pwaf_async_poll.argtypes = [vp, C.POINTER(_abi.Completion), C.c_size_t]
@@ -710,6 +714,10 @@ class RuleEngine:
     def client_ids(self, batch, idx=None, n_idx=None, stream=None):
         """client_ids (below): the captcha client ids of the requests of `batch` that `idx` names; needs nothing of the engine."""
         return client_ids(batch, idx=idx, n_idx=n_idx, stream=stream)
+
+    def derive_batch(self, batch, uri_host=None, present=None, stream=None):
+        """derive_batch (below): the derived host, path and user_agent columns of a raw batch; needs nothing of the engine."""
+        return derive_batch(batch, uri_host=uri_host, present=present, stream=stream)
 
     def evaluate(self, request: Request, with_geo: bool = False):
         """RuleEngine::evaluate(Request) -> Action (pwaf_evaluate_one): a batch of one through the same device path. with_geo
@@ -1300,6 +1308,125 @@ def client_ids(batch, idx=None, n_idx=None, stream=None):
     return out[:m]
 
 
+DERIVED_FIELDS = (0, 2, 4)  # PWAF_FIELD_HOST, _PATH, _USER_AGENT: pwaf_derive_batch's out[0..2]
+
+
+def derive_stats(stats) -> dict:
+    """The 32 bytes of a pwaf_derive_stats (a device tensor once its stream is synchronised, a numpy array or bytes) -> {bytes: [host, path,
+    user_agent], n, overflow}."""
+    raw = stats.cpu().numpy().tobytes() if hasattr(stats, "cpu") else bytes(stats)
+    s = _abi.DeriveStats.from_buffer_copy(raw[:C.sizeof(_abi.DeriveStats)])
+    return {"bytes": [int(b) for b in s.bytes], "n": int(s.n), "overflow": int(s.overflow)}
+
+
+def derive_scan_shape() -> dict:
+    """TEST HOOK (pwaf_derive_scan_shape): the shape of derive_batch's scan, by the names of _abi.DERIVE_SCAN_SHAPE_FIELDS."""
+    out = (C.c_uint32 * 4)()
+    rc = lib().pwaf_derive_scan_shape(out)
+    if rc != 0:
+        _raise(rc, lib().pwaf_last_error().decode(errors="replace"))
+    return dict(zip(_abi.DERIVE_SCAN_SHAPE_FIELDS, (int(x) for x in out)))
+
+
+def derive_batch(batch, uri_host=None, present=None, stream=None):
+    """The reference's own derivation of host, path and User-Agent (get_host / get_path / get_user_agent above) for a whole batch
+    (pwaf_derive_batch; include/pwaf.h). `batch`'s host, path and user_agent columns hold the RAW values: the Host header's value,
+    uri.path() and the User-Agent header's value. uri_host: uri.host() per request; present: n bytes of _abi.RAW_HAS_* saying which of
+    the three sources a request has (default: a Host header and a User-Agent, no URI host). Takes no engine.
+    RequestBatch: uri_host is a (data, offsets) numpy pair (needs `present`) or a list of bytes | None, whose entries set RAW_HAS_URI_HOST
+    themselves; the call is synchronous and runs on the CPU -> a new RequestBatch with the three columns replaced and every other shared.
+    DeviceBatch: uri_host is a (data, offsets) pair of device tensors and present a device tensor; at most three launches are enqueued on
+    `stream` (default: torch's current stream) and the call returns -> (DeviceBatch, stats): the new DeviceBatch shares the untouched
+    tensors, owns the derived columns (room: the raw column's bytes + 16; host: the Host headers' + the URI hosts' bytes + 16, so no
+    column can overflow) and reports field_bytes 0 for them, so evaluate_device on the same stream follows without a synchronisation by the
+    caller; stats is a 32-byte tensor for derive_stats() once the stream is synchronised. `stream` must be the stream torch allocates on
+    when the call is made (its current stream, e.g. inside `with torch.cuda.stream(s)`): the outputs and the scratch come from torch's
+    caching allocator, which may hand their memory to other work of ITS stream once they are dropped. A DeviceBatch that derive_batch
+    returned is not a raw batch and is refused."""
+    n = batch.n
+    host_mode = isinstance(batch, RequestBatch)
+    keep = []
+    extra = None
+    uri_bytes = 0
+    if host_mode:
+        if present is not None:
+            present = np.ascontiguousarray(present, dtype=np.uint8).reshape(-1)
+            assert len(present) == n
+        if isinstance(uri_host, (list, tuple)) and not (len(uri_host) == 2 and isinstance(uri_host[0], np.ndarray)):
+            assert len(uri_host) == n
+            vals = [b"" if v is None else (v.encode() if isinstance(v, str) else bytes(v)) for v in uri_host]
+            has = np.array([_abi.RAW_HAS_URI_HOST if v is not None else 0 for v in uri_host], dtype=np.uint8).reshape(-1)
+            rest = np.full(n, _abi.RAW_HAS_HOST_HEADER | _abi.RAW_HAS_USER_AGENT, dtype=np.uint8) if present is None else present & ~np.uint8(_abi.RAW_HAS_URI_HOST)
+            present = (rest | has).astype(np.uint8)
+            uo = np.zeros(n + 1, dtype=np.uint32)
+            if n:
+                uo[1:] = np.cumsum([len(v) for v in vals], dtype=np.uint64).astype(np.uint32)
+            uri_host = (np.frombuffer(b"".join(vals) + b"\0" * _abi.ARENA_PAD, dtype=np.uint8).copy(), uo)
+        elif uri_host is not None:
+            if present is None:
+                raise ValueError("derive_batch: a uri_host column needs `present` to say which requests have a URI host")
+            uri_host = (np.ascontiguousarray(uri_host[0], dtype=np.uint8), np.ascontiguousarray(uri_host[1], dtype=np.uint32))
+            assert len(uri_host[1]) == n + 1
+        if uri_host is not None:
+            uri_bytes = int(uri_host[1][-1]) - int(uri_host[1][0])
+        ptr = lambda a: a.ctypes.data  # noqa: E731
+        raw_bytes = [int(batch.offsets[f][-1]) - int(batch.offsets[f][0]) for f in DERIVED_FIELDS]
+    else:
+        import torch
+
+        if uri_host is not None:
+            assert present is not None, "derive_batch: a uri_host column needs `present` to say which requests have a URI host"
+            assert uri_host[0].is_contiguous() and uri_host[1].is_contiguous() and uri_host[1].element_size() == 4 and uri_host[1].numel() == n + 1
+            uri_bytes = uri_host[0].numel()  # (an upper bound: the arena with its pad)
+        if present is not None:
+            assert present.is_contiguous() and present.element_size() == 1 and present.numel() == n
+        ptr = lambda t: t.data_ptr()  # noqa: E731
+        raw_bytes = [batch.field_bytes[f] for f in DERIVED_FIELDS]
+        if any(b is None for b in raw_bytes):
+            raise ValueError("derive_batch: this DeviceBatch holds derived columns (their sizes are not known on the host): it is not a raw batch")
+        if stream is None:
+            stream = torch.cuda.current_stream(batch.device).cuda_stream
+    if uri_host is not None or present is not None:
+        extra = _abi.RawColumns()
+        extra.struct_size = C.sizeof(_abi.RawColumns)
+        if uri_host is not None:
+            extra.uri_host.data, extra.uri_host.offsets = ptr(uri_host[0]), ptr(uri_host[1])
+        if present is not None:
+            extra.present = ptr(present)
+        keep += [uri_host, present]
+    # room in which no column can overflow: a request takes its host from the Host header or from the URI, so a batch may keep both columns' bytes
+    caps = [raw_bytes[0] + uri_bytes + _abi.ARENA_PAD, raw_bytes[1] + _abi.ARENA_PAD, raw_bytes[2] + _abi.ARENA_PAD]
+    st = batch.as_struct()
+    out = (_abi.DerivedCol * 3)()
+    if host_mode:
+        data = [_aligned_bytes(c) for c in caps]
+        offs = [np.zeros(n + 1, dtype=np.uint32) for _ in caps]
+        stats = np.zeros(C.sizeof(_abi.DeriveStats) // 8, dtype=np.uint64)
+        scratch, scratch_bytes = None, 0
+    else:
+        data = [torch.empty(c, dtype=torch.uint8, device=batch.device) for c in caps]
+        offs = [torch.empty(n + 1, dtype=torch.int32, device=batch.device) for _ in caps]
+        stats = torch.empty(C.sizeof(_abi.DeriveStats), dtype=torch.uint8, device=batch.device)
+        scratch_bytes = int(lib().pwaf_derive_scratch_bytes(n))
+        scratch = torch.empty(max(16, scratch_bytes), dtype=torch.uint8, device=batch.device)
+    for c in range(3):
+        out[c].data, out[c].offsets, out[c].cap = ptr(data[c]), ptr(offs[c]), caps[c]
+    rc = lib().pwaf_derive_batch(C.byref(st), None if extra is None else C.byref(extra), out, ptr(stats), None if scratch is None else ptr(scratch), scratch_bytes,
+                                 None if host_mode else C.c_void_p(stream))
+    if rc != 0:
+        _raise(rc, lib().pwaf_last_error().decode(errors="replace"))
+    if host_mode:
+        if derive_stats(stats)["overflow"]:  # (cannot happen with the caps above: a column's bytes would be incomplete)
+            raise PwafError(_abi.E_BATCH, f"derive_batch: a derived column did not fit its room: {derive_stats(stats)}")
+        new_data, new_offs = list(batch.data), list(batch.offsets)
+        for c, f in enumerate(DERIVED_FIELDS):
+            new_data[f], new_offs[f] = data[c], offs[c]
+        return RequestBatch(new_data, new_offs, batch.ip, batch.ip_is_v6, batch.port, batch.flags, batch.asn, batch.country, dict(batch.headers))
+    derived = DeviceBatch.adopt(batch, {f: (data[c], offs[c]) for c, f in enumerate(DERIVED_FIELDS)})
+    derived._derive_scratch = (scratch, keep)  # (the launches' own until they have run)
+    return derived, stats
+
+
 def records_scan_shape() -> dict:
     """TEST HOOK (pwaf_records_scan_shape): the shape of evaluate_records_device's scan, by the names of _abi.RECORDS_SCAN_SHAPE_FIELDS."""
     out = (C.c_uint32 * 4)()
@@ -1337,6 +1464,23 @@ class DeviceBatch:
         self.country = None if batch.country is None else t(batch.country.view(np.int16))
         self.headers = {name: (t(d), t(o.view(np.int32)), int(o[-1])) for name, (d, o) in batch.headers.items()}
         self._empty = None
+
+    @classmethod
+    def adopt(cls, other: "DeviceBatch", columns: dict) -> "DeviceBatch":
+        """A DeviceBatch that shares every tensor of `other` except the fields `columns` names: {field id: (data, offsets)} device tensors
+        that already hold a valid arena (derive_batch's outputs). Their sizes are not known on the host: as_struct() reports field_bytes 0
+        for them and the engine asks for offsets[n] on its stream."""
+        b = cls.__new__(cls)
+        b.device, b.n, b.algorithmic_bytes = other.device, other.n, other.algorithmic_bytes
+        b.field_bytes, b.arena_bytes = list(other.field_bytes), list(other.arena_bytes)
+        b.data, b.offsets = list(other.data), list(other.offsets)
+        for f, (d, o) in columns.items():
+            b.data[f], b.offsets[f] = d, o
+            b.field_bytes[f], b.arena_bytes[f] = None, 0  # (None: not known on the host)
+        b.ip, b.ip_is_v6, b.port, b.flags, b.asn, b.country = other.ip, other.ip_is_v6, other.port, other.flags, other.asn, other.country
+        b.headers = dict(other.headers)
+        b._empty = None
+        return b
 
     def as_struct(self, header_names: Sequence[str] = ()) -> _abi.Batch:
         import torch
