@@ -1,4 +1,4 @@
-// filter.cpp — the bigram prefilter of a scan pass (program.h: GroupFilter; kernels.hip: filter_kernel).
+// filter.cpp — the bigram prefilter of a scan pass (program.h: GroupFilter; filter.hip: filter_kernel).
 //
 // The reference evaluates every string predicate of every rule on every request (pingoo/rules.rs:37-51). Nearly all of them are
 // false for nearly all requests — that is what a WAF rule set looks like — so the device first asks a much cheaper question per

@@ -1,5 +1,5 @@
-// hitrec.h — the per-request HIT RECORD as the kernels that write one build it (the scans, fcmp_kernel and residual_kernel in kernels.hip;
-// confirm.hip): two atoms inline, more through an overflow chain in the batch's pool (kernels.h: PoolEntry,
+// hitrec.h — the per-request HIT RECORD as the kernels that write one build it (the scans in scan.hip, fcmp_kernel and residual_kernel in
+// kernels.hip, confirm.hip): two atoms inline, more through an overflow chain in the batch's pool (kernels.h: PoolEntry,
 // REC_OVERFLOW), and the enqueueing of a finished request into the gap passes its hits call for. Device code only.
 #pragma once
 #include "kernels.h"
@@ -70,6 +70,8 @@ __device__ __forceinline__ Hits hits_of_record(const uint32_t rv) {
     if (rv & REC_OVERFLOW) return Hits{0, 0, rv & ~REC_OVERFLOW};
     return Hits{rv & 0x7FFFu, (rv >> 15) & 0x7FFFu, kNone};
 }
+// ... and its inverse: the record a finished walk stores (kernels.h: REC_OVERFLOW).
+__device__ __forceinline__ uint32_t record_of_hits(const Hits h) { return h.ovf != kNone ? (REC_OVERFLOW | h.ovf) : (h.a0 | (h.a1 << 15)); }
 // The gap passes a finished request's hits call for: OR of the per-atom masks.
 __device__ __noinline__ inline uint32_t gate_mask(const uint32_t *colmask_local, const PoolEntry *pool, Hits h) {
     uint32_t need = 0;

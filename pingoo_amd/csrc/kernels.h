@@ -1,4 +1,4 @@
-// kernels.h — argument blocks and launch entry points of the gfx950 kernels (kernels.hip; the confirm tier: confirm.hip; the verdict stage: verdict.hip; the attribute stage: attr.hip).
+// kernels.h — argument blocks and launch entry points of the gfx950 kernels (the DFA scans: scan.hip; the filter stage: filter.hip; the confirm tier: confirm.hip; the verdict stage: verdict.hip; the attribute stage: attr.hip; the rest: kernels.hip).
 #pragma once
 #include <cstdint>
 #include <string>
@@ -188,13 +188,13 @@ struct ConfirmTableDev {
     const ConfirmArgs *c;  // device
     uint32_t count;
 };
-// `plan`: count + 1 words of device scratch (work-item prefix sums, written on the same stream)
+// (confirm.hip) `plan`: count + 1 words of device scratch (work-item prefix sums, written on the same stream)
 int launch_confirm(const ConfirmArgs *host, uint32_t count, const ConfirmArgs *dev, uint32_t *plan, uint32_t n_cus, void *stream);
 
 // ---- bigram prefilter (program.h: GroupFilter) ------------------------------------------------------------------------------
 // The shift-or state only remembers the last four bigrams, so a field's arena is processed as ONE flat byte stream: a wave takes a
 // slab of kStreamSlab consecutive bytes and walks it kStreamIter bytes per iteration — four rows of 1 KiB, every lane one 16-byte
-// chunk of each row, the state a chunk starts from handed over by its neighbour lane (kernels.hip: filter_rows) — with no
+// chunk of each row, the state a chunk starts from handed over by its neighbour lane (filter.hip: filter_rows) — with no
 // per-request logic at all in the loop: every load instruction is one contiguous KiB (every line is fetched exactly once; the
 // per-request-lane version fetched 2x the arena because 7 MB of half-consumed lines per XCD thrashed L2), no lane ever idles,
 // and a window that straddles a request boundary can only ADD a candidate.
@@ -246,6 +246,7 @@ struct FilterArgs {
 // 15 KB of descriptors, kernel arguments hold 8). The host builds the descriptors of EVERY launch of a batch before the first one, writes
 // them into a page-locked slot and one copy launch on the batch's stream moves the block (engine_impl.h: Scratch::args): stream-ordered,
 // one launch per batch whatever the number of passes.
+// (kernels.hip: copy_args_kernel)
 int upload_args_block(const void *host_pinned, void *dev, size_t bytes, void *zero /* nullable: a block to clear in the same launch */, size_t zero_bytes, void *stream);
 struct FilterTable {
     const FilterArgs *f;  // device
@@ -255,15 +256,17 @@ struct FilterMix {  // the fused filter launch: the stride-1 passes and the stri
     const FilterArgs *f1, *f2;  // device
     uint32_t count1, count2, blocks1, blocks2;
 };
-// `host` = the same `count` descriptors as `dev` (launch geometry). launch_filter: ONE launch, the passes of stride 1 and of stride 2
+// (filter.hip) `host` = the same `count` descriptors as `dev` (launch geometry). launch_filter: ONE launch, the passes of stride 1 and of stride 2
 // as two tables (either may be empty), first_block numbered within each by the caller.
 int launch_filter(const FilterArgs *host1, uint32_t count1, const FilterArgs *dev1, const FilterArgs *host2, uint32_t count2, const FilterArgs *dev2, void *stream);
 int launch_resolve(const FilterArgs *host, uint32_t count, const FilterArgs *dev, void *stream);
 int launch_compact(const FilterArgs *host, uint32_t count, const FilterArgs *dev, void *stream);  // bitcount_kernel, then compact_kernel
 // Sets the dynamic-LDS limit of every kernel on the CURRENT device (once per device and process; engines on several
-// devices of one process each need it).
+// devices of one process each need it). kernels.hip keeps the per-device bookkeeping ...
 int configure_kernels(int device);
-// ... for kernels.hip's own kernels and, through configure_verdict_kernels, for verdict.hip's (the current device; no bookkeeping).
+// ... and every unit with such kernels raises the limit of its own (the current device; no bookkeeping): scan.hip, filter.hip, verdict.hip.
+int configure_scan_kernels();
+int configure_filter_kernels();
 int configure_verdict_kernels();
 
 // (PassInfo, the verdict kernel's pass table: program.h)
@@ -280,7 +283,7 @@ struct FcmpArgs {
     uint32_t pool_cap;
     uint32_t *status;
 };
-int launch_fcmp(const FcmpArgs &a, void *stream);
+int launch_fcmp(const FcmpArgs &a, void *stream);  // (kernels.hip)
 // Residual rules (residual.h): one lane per request interprets every residual rule's stack program; rule k that ends in Bool(true) is
 // local atom k of the pseudo pass whose hit records `rec` holds.
 struct ResidualArgs {
@@ -303,7 +306,7 @@ struct ResidualArgs {
     uint32_t *status;
     unsigned long long *rule_errors;  // [n_rules], accumulated over the engine's batches: requests for which the rule's evaluation ended in an error
 };
-int launch_residual(const ResidualArgs &a, void *stream);
+int launch_residual(const ResidualArgs &a, void *stream);  // (kernels.hip)
 // The SPECIALIZED form (residual_jit.cpp: the same programs as straight-line device code, compiled by hiprtc when the engine is created —
 // rtc.cpp): rvm_jit_kernel evaluates every rule for every request and writes one match bit per (request, rule) — match_words[w * n + r]
 // bit k = rule 32 w + k — which the verdict kernel reads in place of the pseudo pass's hit records (VerdictArgs::res_match), and counts
@@ -459,6 +462,7 @@ struct VerdictArgs {
 };
 
 // Launchers (hipStream_t passed as void*). Return hipError_t as int.
+// scan.hip: launch_scan, launch_scan_gated, scan_lds_bytes (below)
 int launch_scan(const ScanArgs &a, void *stream);
 struct GatedTable {
     const ListScanArgs *g;  // device
@@ -468,7 +472,8 @@ struct GatedTable {
 // (ListShape, the workgroup shape of the list scan: scanplan.h)
 // `plan`: count + 1 words of device scratch (the work-item prefix sums, written by lscan_plan_kernel on the same stream)
 int launch_scan_gated(const ListScanArgs *host, uint32_t count, const ListScanArgs *dev, uint32_t *plan, const ListShape &shape, void *stream);
-int launch_verdict(const VerdictArgs &a, void *stream);
+int launch_verdict(const VerdictArgs &a, void *stream);  // (verdict.hip)
+// attr.hip: launch_ipres, ipres_shape, launch_attr, launch_dir24, launch_georec
 int launch_ipres(const VerdictArgs &a, void *stream);  // address lookups -> a.ipres; then, on the same stream:
 // Launch shape of ipres_kernel<.., COARSE>: threads per workgroup, LDS bytes for the coarse bitmap (the budget dirtable::compress
 // gets; 0 = no coarse level, the 256-thread kernel without LDS), workgroups per CU
@@ -493,7 +498,7 @@ struct GeoRecArgs {
     uint2 *out;  // n x 8 bytes
 };
 int launch_georec(const GeoRecArgs &a, void *stream);
-uint32_t scan_lds_bytes(uint32_t n_hot, uint32_t stride, uint32_t n_gate_atoms);
+uint32_t scan_lds_bytes(uint32_t n_hot, uint32_t stride, uint32_t n_gate_atoms);  // (scan.hip: the dynamic LDS of a scan_kernel launch)
 // VerdictShape, verdict_shape, verdict_blocks_sp: verdictplan.h (host code that g++ compiles too)
 
 }  // namespace pwaf

@@ -1,6 +1,6 @@
 // lscan_split.h — how the list-driven DFA passes of a batch are cut into list-scan launches (host code only).
 //
-// launch_scan_gated (kernels.hip) takes at most kListLaunchMax descriptors: lscan_plan_kernel gives each one of its 256 threads. Phase 0
+// launch_scan_gated (scan.hip) takes at most kListLaunchMax descriptors: lscan_plan_kernel gives each one of its 256 threads. Phase 0
 // (the passes behind a prefilter and the identity passes) holds up to two descriptors per pass — a confirm pass's dense alternative and
 // its R-tier walk — so 250 passes can need 500. A phase with more is split into consecutive launches on the batch's stream, each with a
 // plan region of its own (2 * count + 1 words: work-item prefix sums and total, then the entries per item of every descriptor). A pass's

@@ -448,7 +448,7 @@ PWAF_HD_STR bool regex_match_t(const Machine &m, uint32_t id, const Val &s) {
     // is its own symbol, a well-formed sequence is ONE symbol — its scalar's class from the two-stage map — taken when its last byte
     // arrives (the string may be a rope: the sequence may straddle two segments), a lead byte that the next byte does not continue is
     // the ill-formed class and that byte is then read on its own; a continuation byte that continues nothing is the ill-formed class too, as for the
-    // table walkers of kernels.hip (utf8.h decodes at the lead byte there and asks of a continuation byte whether a sequence holds it).
+    // table walkers of scan.hip (utf8.h decodes at the lead byte there and asks of a continuation byte whether a sequence holds it).
     const RegexDesc &d = section<RegexDesc>(m, m.h->regexes)[id];
     const uint16_t *trans = section<uint16_t>(m, d.trans);
     const uint8_t *cm = m.blob + d.classmap, *fl = m.blob + d.flags;

@@ -464,7 +464,7 @@ int tune_host(const Program &P, const pwaf_batch *sample, TuneOut &T) {
         // Stride 2 halves the table lookups per byte: a stride-1 pass is bound by them (LDS), a stride-2 pass by HBM. A pass takes it
         // when its factors stay selective with two to four sampled bigrams per alignment: at most two points more of the sample
         // flagged than at stride 1 (a candidate costs about ten times a filtered byte), never above 25 %. Every pass decides for
-        // itself: both strides run in ONE launch with their workgroups interleaved (kernels.hip: filter_kernel).
+        // itself: both strides run in ONE launch with their workgroups interleaved (filter.hip: filter_kernel).
         // PWAF_OPT_FILTER_STRIDE2 takes it wherever it can be built.
         std::vector<GroupFilter> alt(P.groups.size());
         for (size_t k = 0; k < P.groups.size(); k++) {

@@ -1,6 +1,6 @@
 // utf8.h — the symbol a walker reads at a LEAD byte of a table in scalar mode (dfa.cpp): the class of the scalar value the bytes encode.
 //
-// ONE implementation for every walker: the device kernels (kernels.hip: lscan_kernel, scan_kernel; residual.h), the host walks of
+// ONE implementation for every walker: the device kernels (scan.hip: lscan_kernel, scan_kernel; residual.h), the host walks of
 // pwaf_engine_tune and the CPU test hooks. The reference's strings are Rust str — always well-formed (pingoo/rules.rs:16-25) — and the
 // regex crate matches their SCALAR VALUES (regex 1.12.2, Cargo.lock:1694-1700); an ill-formed byte (no Rust str holds one) is a symbol
 // of its own that no class matches (ScalarMap::ill_class).

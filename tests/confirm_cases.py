@@ -23,13 +23,13 @@ from pingoo_amd.engine import CompiledProgram
 
 B, CAP = _abi.RULE_ACTION_BLOCK, _abi.RULE_ACTION_CAPTCHA
 CHUNK = 16
-SLAB = 128 * 1024      # csrc/kernels.h:203  kStreamSlab: the bytes one wave of filter_kernel / resolve_kernel owns
-RESOLVE_SPARSE = 128   # csrc/kernels.hip, resolve_kernel: kResolveSparse, flagged chunks up to which a slab is resolved chunk by chunk
-OWNER_BOUND = 4096     # csrc/kernels.hip, resolve_kernel: `h = min(a.n, lo + 4096u)`, the owner search of the chunk-driven path
-RESET_BOUND = 48       # csrc/kernels.hip, resolve_kernel: `steps < 48u`, the record reset of the chunk-driven path
+SLAB = 128 * 1024      # csrc/kernels.h, kStreamSlab: the bytes one wave of filter_kernel / resolve_kernel owns
+RESOLVE_SPARSE = 128   # csrc/filter.hip, resolve_kernel: kResolveSparse, flagged chunks up to which a slab is resolved chunk by chunk
+OWNER_BOUND = 4096     # csrc/filter.hip, resolve_kernel: `h = min(a.n, lo + 4096u)`, the owner search of the chunk-driven path
+RESET_BOUND = 48       # csrc/filter.hip, resolve_kernel: `steps < 48u`, the record reset of the chunk-driven path
 QUEUE = 1024           # csrc/confirm.hip, confirm_kernel: kConfirmQueue, a workgroup's queue of walk-list appends
-POOL_WORDS = 10240     # csrc/kernels.h:183  kConfirmPoolBytes / 4: confirm_kernel's LDS pool for entries + bytes + classes
-CONFIRM_THREADS = 1024  # csrc/kernels.h:182  kConfirmThreads: pairs per work item of confirm_kernel
+POOL_WORDS = 10240     # csrc/kernels.h, kConfirmPoolBytes / 4: confirm_kernel's LDS pool for entries + bytes + classes
+CONFIRM_THREADS = 1024  # csrc/kernels.h, kConfirmThreads: pairs per work item of confirm_kernel
 MI355X_CUS = 256       # launch_confirm's grid is 2 workgroups per compute unit; the CPU suite builds case J for this device
 
 
@@ -75,7 +75,7 @@ class Arena:
 # the numpy model of filter_kernel over a whole arena
 # ---------------------------------------------------------------------------------------------------------
 def window_positions(g, data, total):
-    """filter_kernel restated (csrc/kernels.hip, filter_rows): ONE shift-or automaton over the arena as a flat byte stream, started in
+    """filter_kernel restated (csrc/filter.hip, filter_rows): ONE shift-or automaton over the arena as a flat byte stream, started in
     the pass's init state at byte 0, a lookup table[bin(fold(b[i]), fold(b[i + 1]))] at every stride-th byte i, state = state << 8 |
     mask; a window completed at i when the state's top byte has a zero bit. Nothing depends on where requests begin or end.
     -> bool per arena byte of the chunks that begin before `total` (the bytes behind `total` are the arena's slack)."""

@@ -1,6 +1,6 @@
 """Shared builders of the list-scan edge suites (tests/test_lscan_edges_cpu.py, tests/test_gpu_lscan_edges.py); no GPU import.
 
-lscan_kernel (csrc/kernels.hip) walks every list-driven DFA pass: the R-tier walks behind the confirm tier, the whole-pass dense
+lscan_kernel (csrc/scan.hip) walks every list-driven DFA pass: the R-tier walks behind the confirm tier, the whole-pass dense
 alternative, the candidate lists of a PWAF_OPT_NO_CONFIRM engine, the gap passes and the identity passes. A state it reads is a row staged
 in LDS (state < n_hot), an 8-byte delta record over a base row (the next n_delta states) or a row of the L2-resident flat table. Here:
 
@@ -702,7 +702,7 @@ MI355X_CUS = 256  # (the CPU suite builds the wave cases for this device; the de
 
 
 def entries_per_item(lists, n_waves):
-    """lscan_plan_kernel restated as data (csrc/kernels.hip): the list entries ONE WAVE takes of each list of a launch. lists: the
+    """lscan_plan_kernel restated as data (csrc/scan.hip): the list entries ONE WAVE takes of each list of a launch. lists: the
     lengths of the launch's lists in descriptor order; n_waves = compute units x workgroups per CU x threads / 64. A wave walks its
     entries one per lane: lane l of item `it` walks list entry (it - first) * epi + l, so a wave is FULL only from epi == 64 on."""
     room = n_waves - len(lists) if n_waves > len(lists) else 1

@@ -1,6 +1,6 @@
 """Shared builders of the streaming-scan edge suites (tests/test_scan_edges_cpu.py, tests/test_gpu_scan_edges.py); no GPU import.
 
-scan_kernel<CH, WIDE> (csrc/kernels.hip: scan_body) walks a DFA over EVERY request of a pass: every pass of a PWAF_OPT_NO_PREFILTER
+scan_kernel<CH, WIDE> (csrc/scan.hip: scan_body) walks a DFA over EVERY request of a pass: every pass of a PWAF_OPT_NO_PREFILTER
 engine, every pass without a usable prefilter. A wave takes a contiguous share of the batch in blocks of 64 offsets, a lane pulls the
 next request while it is on its last 16 * CH bytes, steps run in speculative groups of four over hot rows in LDS, and a lane that meets
 a cold row parks on the sentinel row. Here:
@@ -33,7 +33,7 @@ B, CAP = _abi.RULE_ACTION_BLOCK, _abi.RULE_ACTION_CAPTCHA
 NP, HITS = _abi.OPT_NO_PREFILTER, _abi.OPT_RULE_HITS
 PLAIN, EMIT, COLD = "plain hot", "emitting hot", "cold"
 KINDS = (PLAIN, EMIT, COLD)
-# what the cases rest on (csrc/kernels.hip: launch_scan, scan_body; csrc/scanplan.cpp: tune_host)
+# what the cases rest on (csrc/scan.hip: launch_scan, scan_body; csrc/scanplan.cpp: tune_host)
 WAVES_PER_WG, MIN_PER_WAVE, OFFSET_BLOCK, CH2_MEAN, CH4_MEAN = 16, 256, 64, 48, 80
 MI355X_CUS = 256  # (the CPU suite builds the tiled batch's shape for this device; the device suite for the one it runs on)
 FIELD_NAMES = ("host", "url", "path", "method", "user_agent")

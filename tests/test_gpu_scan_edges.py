@@ -1,4 +1,4 @@
-"""scan_kernel<CH, WIDE> at its edges on the device (csrc/kernels.hip: scan_body): the DFA walk over EVERY request of a pass -- every pass
+"""scan_kernel<CH, WIDE> at its edges on the device (csrc/scan.hip: scan_body): the DFA walk over EVERY request of a pass -- every pass
 of a PWAF_OPT_NO_PREFILTER engine, every pass without a usable prefilter -- which three other edge suites use as their cross-check. The
 cases are built by tests/scan_cases.py, which proves each one's shape on the host from the scan-plan harness before anything is sent;
 tests/test_scan_edges_cpu.py makes the same assertions without a device and walks every request through the streaming table:

@@ -65,7 +65,7 @@ def test_the_constants_the_cases_rest_on():
     ceil(n / waves); tune_host: 48 and 80 bytes"""
     assert SC.shares(1) == (1, 1, [(0, 1)]) and SC.shares(4096)[:2] == (1, 256) and SC.shares(4097)[:2] == (2, 129)
     assert SC.shares(4096 * 256 + 777, 256)[:2] == (256, 257) and SC.shares(10 ** 7, 256)[0] == 256
-    src = open(SC.SP.HERE + "/../pingoo_amd/csrc/kernels.hip").read() + open(SC.SP.HERE + "/../pingoo_amd/csrc/scanplan.cpp").read()
+    src = open(SC.SP.HERE + "/../pingoo_amd/csrc/scan.hip").read() + open(SC.SP.HERE + "/../pingoo_amd/csrc/scanplan.cpp").read()
     for text in ("uint32_t waves = (a.n + 255) / 256;", "static constexpr int kScanThreads = 1024;", "const uint32_t f_base = blk + 64;", "const uint32_t t4 = 80u, t2 = 48u;"):
         assert text in src, text
 
@@ -228,7 +228,7 @@ def test_case_v_five_plain_passes_and_the_method_pass_once_tuned():
 # that the cases bite: scan_body's walk of ONE request restated over the harness's tables, with two of its lines switchable
 # ---------------------------------------------------------------------------------------------------------
 def kernel_walk(m, arena, p, end, ch, mutation=None):
-    """csrc/kernels.hip, scan_body, sections 2 and 3 for one lane and one request [p, end) of `arena` (tables without scalar mode): the
+    """csrc/scan.hip, scan_body, sections 2 and 3 for one lane and one request [p, end) of `arena` (tables without scalar mode): the
     chunks as the prefetch addresses them (a chunk the field does not reach, and an empty field's, is the arena's first 16 bytes), the
     classes with bytes past the field's end as the STAY cell, the speculative groups of four over the LDS copy (hot rows, then a
     sentinel row of 0xFFFF), redo / chain / careful_step, the END cell from the global table for a parked lane. -> the set of atoms.
