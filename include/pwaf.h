@@ -21,6 +21,8 @@
  *                                                              pwaf_derive_host / _path / _user_agent; pwaf_derive_batch
  *   generate_captcha_client_id       http_listener.rs:167; pingoo/captcha.rs:409-421
  *                                                              pwaf_client_id_one / pwaf_client_ids
+ *   cookie split + validate_captcha_verified_cookie            http_listener.rs:169-181,222-236; pingoo/captcha.rs:125-156; jwt/jwt.rs:198-327
+ *                                                              pwaf_verify_cookie_one / pwaf_verify_cookies (pwaf_keyset)
  *
  * Plain pointers and sizes only; no C++/torch types. Never aborts across the ABI:
  * every failure is an int status (<0) plus pwaf_last_error().
@@ -189,7 +191,7 @@ typedef struct pwaf_compile_error {
 #define PWAF_MEM_HOST 0u
 #define PWAF_MEM_DEVICE 1u
 
-#define PWAF_FLAG_CAPTCHA_VERIFIED 1u /* http_listener.rs:222-236, decided on the host (JWT) */
+#define PWAF_FLAG_CAPTCHA_VERIFIED 1u /* http_listener.rs:222-236 (JWT): the caller's, or pwaf_verify_cookies' flags_out */
 
 typedef struct pwaf_strcol {
     const uint8_t *data;
@@ -493,6 +495,69 @@ typedef struct pwaf_client_id {
 int pwaf_client_ids(const pwaf_batch *in, const uint32_t *idx /* nullable */, uint32_t idx_cap, const uint32_t *n_idx /* nullable */,
                     pwaf_client_id *out, void *stream);
 int pwaf_client_id_one(const pwaf_request *req, pwaf_client_id *out);
+
+/* ---- captcha-verified cookies (ABI 4, additive) -------------------------------------------------------------
+ * Gate C of the reference (http_listener.rs:169-181, :222-236): split the Cookie header, find `__pingoo_captcha_verified`, and run
+ * CaptchaManager::validate_captcha_verified_cookie (pingoo/captcha.rs:125-156) on it, which is jwt::parse_header, the key looked up by
+ * `kid`, and jwt::parse_and_verify (jwt/jwt.rs:198-327: an Ed25519 signature, then exp / nbf / aud / iss), then sub == client id and
+ * challenge_passed. The answer is PWAF_FLAG_CAPTCHA_VERIFIED of pwaf_batch.flags, which until now had to be made on the host, request by
+ * request. pwaf_verify_cookies answers it for every request of a batch, or for the requests a list names, where the batch lives, and can
+ * write the flags column the evaluation reads next on the same stream. It takes no engine (like pwaf_client_ids). DESIGN.md §5.1.6
+ * states the semantics rule by rule; in short:
+ *   cookie  a header value with a byte that is neither TAB nor 0x20..0x7E has no cookies; split on ';', each segment trimmed and cut at
+ *           its first '='; the first cookie named exactly `__pingoo_captcha_verified` is the token, a pair of '"' around it removed.
+ *   token   three parts; the third is base64url without padding of exactly 64 bytes; the header names the key by `kid` (alg "EdDSA",
+ *           typ "JWT"); Ed25519 as aws-lc's ED25519_verify does it; then the claims: exp >= now - 5, nbf <= now + 5, aud == iss ==
+ *           "pingoo", challenge_passed == true, sub == the client id computed from ip, User-Agent and host (pwaf_client_ids' message).
+ *   subset  header and claims are read in a flat subset of JSON (one object, no escapes, no nesting, integers). A token outside it, or
+ *           whose signed part is longer than PWAF_COOKIE_MAX_SIGNED_BYTES, is UNDECIDED if its signature verifies under a key of the set
+ *           (the holder of a signing key wrote it: the host decides with its own library) and INVALID otherwise.
+ * Keys (captcha.rs:77-123, :525-548; jwt/jwk.rs): pwaf_keyset_create decompresses each x (an encoding that is not a canonical point on
+ * the curve: PWAF_E_INVALID_ARG), precomputes the multiples of -A the verifier adds, and uploads them with the kids to `device`
+ * (device < 0: host only; the DEVICE mode then answers PWAF_E_DEVICE). 1..PWAF_KEYSET_MAX_KEYS keys, each kid 1..PWAF_KEYSET_MAX_KID
+ * bytes (captcha.rs:526 refuses an empty one); two keys with one kid are refused. The set is read-only afterwards: any number of calls
+ * on any streams may share it. pwaf_keyset_destroy(NULL) is a no-op; destroy after the last call that uses the set has run.
+ * pwaf_verify_cookies: `cookies` holds each request's FIRST Cookie header value ("" when there is none; the reference looks at no
+ * other, http_listener.rs:169-172), `now` is Unix seconds (a parameter: nothing here reads a clock). idx / idx_cap / n_idx mean exactly
+ * what they mean for pwaf_client_ids: idx == NULL (idx_cap 0, n_idx NULL): every request, status[i] belongs to request i; otherwise
+ * m = min(*n_idx, idx_cap), or idx_cap when n_idx == NULL, status[j] belongs to request idx[j] for j < m, entries j >= m are not written,
+ * idx[j] >= in->n gets PWAF_COOKIE_ABSENT. flags_out (nullable, in->n entries) is written only when idx == NULL:
+ * (in->flags ? in->flags[i] : 0) with PWAF_FLAG_CAPTCHA_VERIFIED set for VERIFIED and cleared otherwise; it may be in->flags itself.
+ * Memory and streams: in->memory says where EVERY pointer lives: the batch's, cookies', idx, n_idx, status and flags_out alike.
+ *   PWAF_MEM_DEVICE  a 16-byte memset and two launches (cookie_locate_kernel, cookie_verify_kernel) are enqueued on `stream` (hipStream_t;
+ *                    NULL = HIP's default stream) of the current device, which must be the key set's, and the call returns at once. The
+ *                    kernels read *n_idx and the number of located tokens themselves, so the call may follow pwaf_evaluate_device on
+ *                    the same stream and be followed by one without a synchronisation. scratch: pwaf_verify_cookies_scratch_bytes(k)
+ *                    bytes of device memory, 16-byte aligned, k = idx_cap (in->n when idx == NULL), the call's own until the launches
+ *                    have run. Loads may run past a value by fewer than 16 bytes (PWAF_ARENA_PAD, the cookies' arena too). The batch is
+ *                    trusted as pwaf_evaluate_device trusts it, except that the kernels guard idx[j] >= n.
+ *   PWAF_MEM_HOST    synchronous, plain C++, no HIP call; reads no byte outside a value; scratch and stream are ignored. A selected
+ *                    request whose offsets decrease in the cookies, User-Agent or host column refuses the call with PWAF_E_BATCH.
+ * PWAF_E_INVALID_ARG, before anything runs: NULL ks, in, cookies or status; a bad struct_size or memory; idx == NULL with idx_cap != 0
+ * or n_idx != NULL; in a batch with n > 0 a NULL ip, ip_is_v6, cookies / User-Agent / host column; in DEVICE mode scratch NULL, not
+ * 16-byte aligned or too small.
+ * pwaf_verify_cookie_one: the same answer for one request on the host (no GPU), from req->ip, ip_is_v6, user_agent and host and the
+ * first Cookie header's value (cookie == NULL: none): what a per-request closure calls where the reference runs http_listener.rs:222-236. */
+#define PWAF_COOKIE_ABSENT 0u    /* no such cookie: captcha_verified = false, the rules run (http_listener.rs:222-227) */
+#define PWAF_COOKIE_VERIFIED 1u  /* a valid cookie: captcha_verified = true (:232) */
+#define PWAF_COOKIE_INVALID 2u   /* the reference answers serve_captcha() (:234) */
+#define PWAF_COOKIE_UNDECIDED 3u /* signed by a key of the set, but not parsed here: the host decides with its own library */
+#define PWAF_KEYSET_MAX_KEYS 8u
+#define PWAF_KEYSET_MAX_KID 64u
+#define PWAF_COOKIE_MAX_SIGNED_BYTES 8192u /* header '.' claims of a token, in base64url characters */
+typedef struct pwaf_ed25519_key {
+    const char *kid; /* NUL-terminated, 1..PWAF_KEYSET_MAX_KID bytes (jwt/jwk.rs:17) */
+    uint8_t x[32];   /* the public key: RFC 8032 §5.1.2 encoding (the JWK's "x", jwt/jwk.rs:32-33) */
+} pwaf_ed25519_key;
+typedef struct pwaf_keyset pwaf_keyset;
+int pwaf_keyset_create(const pwaf_ed25519_key *keys, uint32_t n, int device, pwaf_keyset **out);
+void pwaf_keyset_destroy(pwaf_keyset *ks);
+size_t pwaf_verify_cookies_scratch_bytes(uint32_t n); /* DEVICE mode scratch for n entries; HOST mode needs none */
+int pwaf_verify_cookies(const pwaf_keyset *ks, const pwaf_batch *in, const pwaf_strcol *cookies, int64_t now, const uint32_t *idx /* nullable */,
+                        uint32_t idx_cap, const uint32_t *n_idx /* nullable */, uint8_t *status, uint8_t *flags_out /* nullable */, void *scratch,
+                        size_t scratch_bytes, void *stream);
+int pwaf_verify_cookie_one(const pwaf_keyset *ks, const pwaf_request *req, const char *cookie /* nullable */, uint32_t cookie_len, int64_t now,
+                           uint8_t *status);
 
 /* ---- derived columns of a raw batch (ABI 4, additive) -----------------------------------------------------
  * Every evaluation entry point takes the fields AFTER the reference's own derivation (http_listener.rs:140-165, :284-296;

@@ -33,6 +33,9 @@ MEM_HOST, MEM_DEVICE = 0, 1
 FLAG_CAPTCHA_VERIFIED = 1
 ROUTE_NONE = 0xFFFFFFFF  # PWAF_ROUTE_NONE: no route matches the request (pwaf_evaluate_*_routes)
 RECORD_NONE = 0xFFFFFFFF  # PWAF_RECORD_NONE: the list entry has no record in the buffer (pwaf_export_records)
+# pwaf_verify_cookies / pwaf_verify_cookie_one: one status per request (gate C, http_listener.rs:222-236)
+COOKIE_ABSENT, COOKIE_VERIFIED, COOKIE_INVALID, COOKIE_UNDECIDED = 0, 1, 2, 3
+KEYSET_MAX_KEYS, KEYSET_MAX_KID, COOKIE_MAX_SIGNED_BYTES = 8, 64, 8192
 N_FIELDS = 5
 FIELD_NAMES = ("host", "url", "path", "method", "user_agent")
 ARENA_PAD = 16
@@ -192,6 +195,12 @@ class ClientId(C.Structure):
     """pwaf_client_id: a captcha client id (pwaf_client_ids / pwaf_client_id_one) — 43 characters of the URL-safe alphabet, then NUL."""
 
     _fields_ = [("text", C.c_char * 44)]
+
+
+class Ed25519Key(C.Structure):
+    """pwaf_ed25519_key: one verifying key of a pwaf_keyset — the kid (NUL-terminated) and the public key's 32-byte encoding."""
+
+    _fields_ = [("kid", C.c_char_p), ("x", C.c_uint8 * 32)]
 
 
 class RawColumns(C.Structure):

@@ -139,3 +139,59 @@ def load_geoip(paths: Sequence[str] = GEOIP_DATABASE_PATHS):
             except Exception as err:  # noqa: BLE001
                 raise ConfigError(f"error loading geoip database ({p}): {err}") from err
     return None
+
+
+CAPTCHA_JWKS_PATH = "/etc/pingoo/captcha_jwks.json"
+
+
+def load_captcha_jwks(path_or_bytes=CAPTCHA_JWKS_PATH) -> List[Tuple[str, bytes]]:
+    """The captcha verifying keys, [(kid, x)] for engine.KeySet, from the reference's JWKS file (CaptchaManager::new, captcha.rs:77-109;
+    validate_jwk, :525-548; the shape of jwt/jwk.rs:6-52): {"keys": [{"kid", "use", "alg", "kty", "crv", "x", "d"}]}, x and d base64url
+    without padding. Only EdDSA / OKP / Ed25519 entries are keys here; anything else raises ConfigError with the reference's message.
+    `d` (the private seed) is looked at only to see that it is present, as the reference does, and is never kept. A str is a path,
+    bytes are the file's content."""
+    import base64
+    import json
+
+    if isinstance(path_or_bytes, (bytes, bytearray)):
+        content = bytes(path_or_bytes)
+    else:
+        try:
+            with open(path_or_bytes, "rb") as f:
+                content = f.read()
+        except OSError as err:
+            raise ConfigError(f"error reading captcha JWKS file: {err}") from err
+    try:
+        jwks = json.loads(content)
+        entries = jwks["keys"]
+        assert isinstance(entries, list) and all(isinstance(e, dict) for e in entries)
+    except Exception as err:  # noqa: BLE001
+        raise ConfigError(f"error parsing captcha JWKS file: {err}") from err
+    keys = []
+    for jwk in entries:
+        kid = jwk.get("kid")
+        if not isinstance(kid, str) or jwk.get("use") not in ("sig", "enc") or not isinstance(jwk.get("alg"), str):
+            raise ConfigError("error parsing captcha JWKS file: a key needs `kid`, `use` and `alg`")
+        if not kid.strip():
+            raise ConfigError("JWK key ID is empty")  # captcha.rs:526-528
+        if jwk["alg"] != "EdDSA":
+            raise ConfigError(f"captcha: JWT algorithm {jwk['alg']} not suported for key {kid}. Only EdDSA is currently supported.")  # :530-537
+        if jwk.get("kty") != "OKP" or jwk.get("crv") != "Ed25519" or not isinstance(jwk.get("x"), str):
+            raise ConfigError(f"error parsing captcha JWKS file: key {kid}: an EdDSA key is kty OKP, crv Ed25519 with `x`")
+        if jwk.get("d") is None:
+            raise ConfigError(f"captcha: Private key is missing for key {kid}")  # :540-548
+        x_text = jwk["x"]
+        try:
+            if "=" in x_text or len(x_text) % 4 == 1:
+                raise ValueError("not base64url without padding")
+            x = base64.urlsafe_b64decode(x_text + "=" * (-len(x_text) % 4))
+            if base64.urlsafe_b64encode(x).rstrip(b"=").decode() != x_text:
+                raise ValueError("not base64url without padding")
+        except Exception as err:  # noqa: BLE001
+            raise ConfigError(f"error parsing captcha JWKS file: key {kid}: x: {err}") from err
+        if len(x) != 32:
+            raise ConfigError(f"{kid} is not a valid JWK: an Ed25519 public key has 32 bytes, x has {len(x)}")  # jwt::Error::InvalidJwk
+        keys.append((kid, x))
+    if not keys:
+        raise ConfigError("captcha JWKS file is empty")  # captcha.rs:102-104
+    return keys

@@ -154,6 +154,13 @@ def lib():
     L.pwaf_records_scan_shape.argtypes = [C.POINTER(C.c_uint32)]
     L.pwaf_client_ids.argtypes = [C.POINTER(_abi.Batch), vp, C.c_uint32, vp, vp, vp]
     L.pwaf_client_id_one.argtypes = [C.POINTER(_abi.Request), vp]
+    L.pwaf_keyset_create.argtypes = [C.POINTER(_abi.Ed25519Key), C.c_uint32, C.c_int, C.POINTER(vp)]
+    L.pwaf_keyset_destroy.argtypes = [vp]
+    L.pwaf_keyset_destroy.restype = None
+    L.pwaf_verify_cookies_scratch_bytes.argtypes = [C.c_uint32]
+    L.pwaf_verify_cookies_scratch_bytes.restype = C.c_size_t
+    L.pwaf_verify_cookies.argtypes = [vp, C.POINTER(_abi.Batch), C.POINTER(_abi.StrCol), C.c_int64, vp, C.c_uint32, vp, vp, vp, vp, C.c_size_t, vp]
+    L.pwaf_verify_cookie_one.argtypes = [vp, C.POINTER(_abi.Request), vp, C.c_uint32, C.c_int64, C.POINTER(C.c_uint8)]
     L.pwaf_derive_scratch_bytes.argtypes = [C.c_uint32]
     L.pwaf_derive_scratch_bytes.restype = C.c_size_t
     L.pwaf_derive_batch.argtypes = [C.POINTER(_abi.Batch), C.POINTER(_abi.RawColumns), C.POINTER(_abi.DerivedCol), vp, vp, C.c_size_t, vp]
@@ -714,6 +721,14 @@ class RuleEngine:
     def client_ids(self, batch, idx=None, n_idx=None, stream=None):
         """client_ids (below): the captcha client ids of the requests of `batch` that `idx` names; needs nothing of the engine."""
         return client_ids(batch, idx=idx, n_idx=n_idx, stream=stream)
+
+    def verify_cookies(self, keyset, batch, cookies, now, idx=None, n_idx=None, flags_out=None, stream=None):
+        """verify_cookies (below): gate C for the requests of `batch`; needs nothing of the engine."""
+        return verify_cookies(keyset, batch, cookies, now, idx=idx, n_idx=n_idx, flags_out=flags_out, stream=stream)
+
+    def verify_cookie(self, keyset, request, cookie, now):
+        """verify_cookie (below): gate C for one request, on the host; needs nothing of the engine."""
+        return verify_cookie(keyset, request, cookie, now)
 
     def derive_batch(self, batch, uri_host=None, present=None, stream=None):
         """derive_batch (below): the derived host, path and user_agent columns of a raw batch; needs nothing of the engine."""
@@ -1306,6 +1321,139 @@ def client_ids(batch, idx=None, n_idx=None, stream=None):
     if rc != 0:
         _raise(rc, lib().pwaf_last_error().decode(errors="replace"))
     return out[:m]
+
+
+class KeySet:
+    """The captcha verifying keys (pwaf_keyset; the reference's CaptchaManager::verifying_keys, captcha.rs:77-123): `keys` is a sequence of
+    (kid, x) with x the 32 bytes of an Ed25519 public key, e.g. config.load_captcha_jwks()'s. Creation decompresses each key, precomputes
+    the multiples the verifier adds and, with a device, uploads them. device: None = host only (verify_cookies then takes RequestBatches
+    and verify_cookie single requests); an ordinal, "cuda:N" or a torch.device = that GPU as well. Read-only afterwards: any number of
+    calls on any streams may share it. close() (or the garbage collector) frees it, after the last call that uses it has run."""
+
+    def __init__(self, keys, device=None):
+        keys = [(kid.encode() if isinstance(kid, str) else bytes(kid), bytes(x)) for kid, x in keys]
+        if device is None:
+            ordinal = -1
+        elif isinstance(device, int):
+            ordinal = device
+        else:
+            import torch
+
+            d = torch.device(device)
+            ordinal = torch.cuda.current_device() if d.index is None else d.index
+        arr = (_abi.Ed25519Key * max(1, len(keys)))()
+        for k, (kid, x) in enumerate(keys):
+            if len(x) != 32:
+                raise ValueError(f"KeySet: key {k}: x has {len(x)} bytes, an Ed25519 public key has 32")
+            if b"\0" in kid:
+                raise ValueError(f"KeySet: key {k}: the kid contains a NUL byte")
+            arr[k].kid = kid
+            C.memmove(arr[k].x, x, 32)
+        h = C.c_void_p()
+        rc = lib().pwaf_keyset_create(arr, len(keys), ordinal, C.byref(h))
+        if rc != 0:
+            _raise(rc, lib().pwaf_last_error().decode(errors="replace"))
+        self._h, self.device, self.kids = h, ordinal, [kid.decode(errors="replace") for kid, _ in keys]
+
+    def close(self):
+        h, self._h = getattr(self, "_h", None), None
+        if h:
+            lib().pwaf_keyset_destroy(h)
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:  # noqa: BLE001 (interpreter shutdown: the library may be gone)
+            pass
+
+
+def cookie_column(cookies):
+    """[bytes | str | None per request] (None: no Cookie header) -> (data with PWAF_ARENA_PAD zero bytes behind it, offsets) numpy arrays"""
+    vals = [b"" if v is None else (v.encode() if isinstance(v, str) else bytes(v)) for v in cookies]
+    off = np.zeros(len(vals) + 1, dtype=np.uint32)
+    if vals:
+        off[1:] = np.cumsum([len(v) for v in vals], dtype=np.uint64).astype(np.uint32)
+    return np.frombuffer(b"".join(vals) + b"\0" * _abi.ARENA_PAD, dtype=np.uint8).copy(), off
+
+
+def verify_cookies(keyset, batch, cookies, now, idx=None, n_idx=None, flags_out=None, stream=None):
+    """Gate C of the reference (http_listener.rs:169-181, :222-236; captcha.rs:125-156; jwt.rs:198-327) for requests of `batch`
+    (pwaf_verify_cookies; include/pwaf.h): one _abi.COOKIE_* status per request — of every request when idx is None (entry i belongs to
+    request i), else of the requests the list `idx` names (n_idx: how many entries count; an entry that names no request reads ABSENT).
+    cookies: each request's FIRST Cookie header value — a (data, offsets) pair where the batch lives, or a list of bytes | str | None.
+    now: Unix seconds. flags_out (only with idx None): n bytes that receive the batch's flags with FLAG_CAPTCHA_VERIFIED set exactly for
+    the VERIFIED requests; it may be the batch's own flags. Takes no engine.
+    RequestBatch: numpy arguments, synchronous, on the CPU -> a numpy uint8 array.
+    DeviceBatch: device tensors (a list of cookies is uploaded); a memset and two launches are enqueued on `stream` (default: torch's
+    current stream, which must be the stream torch allocates on when the call is made: the scratch comes from its caching allocator) and
+    the call returns -> a uint8 tensor to be read after the stream is synchronised; entries at or past n_idx are not written. With
+    flags_out = batch.flags an evaluate_device on the same stream follows without a synchronisation by the caller."""
+    st = batch.as_struct()
+    col = _abi.StrCol()
+    if isinstance(batch, RequestBatch):
+        data, off = cookies if isinstance(cookies, tuple) else cookie_column(cookies)
+        data, off = np.ascontiguousarray(data, dtype=np.uint8), np.ascontiguousarray(off, dtype=np.uint32)
+        assert len(off) == batch.n + 1
+        col.data, col.offsets = data.ctypes.data, off.ctypes.data
+        if idx is None:
+            assert n_idx is None
+            m = batch.n
+        else:
+            idx = np.ascontiguousarray(idx, dtype=np.uint32).reshape(-1)
+            m = len(idx) if n_idx is None else min(len(idx), int(np.asarray(n_idx).reshape(-1)[0]))
+            if not len(idx):
+                return np.zeros(0, dtype=np.uint8)  # (a NULL idx would mean every request)
+        n_ref = None if n_idx is None else np.array([int(np.asarray(n_idx).reshape(-1)[0])], dtype=np.uint32)
+        if flags_out is not None:
+            assert isinstance(flags_out, np.ndarray) and flags_out.dtype == np.uint8 and flags_out.flags.c_contiguous and flags_out.size == batch.n
+        out = np.zeros(max(1, m), dtype=np.uint8)
+        rc = lib().pwaf_verify_cookies(keyset._h, C.byref(st), C.byref(col), int(now), None if idx is None else idx.ctypes.data, 0 if idx is None else len(idx),
+                                       None if n_ref is None else n_ref.ctypes.data, out.ctypes.data, None if flags_out is None else flags_out.ctypes.data, None, 0, None)
+        if rc != 0:
+            _raise(rc, lib().pwaf_last_error().decode(errors="replace"))
+        return out[:m]
+    import torch
+
+    if not isinstance(cookies, tuple):
+        data, off = cookie_column(cookies)
+        cookies = (torch.from_numpy(data).to(batch.device), torch.from_numpy(off.view(np.int32)).to(batch.device))
+    data, off = cookies
+    assert data.is_contiguous() and off.is_contiguous() and off.element_size() == 4 and off.numel() == batch.n + 1
+    col.data, col.offsets = data.data_ptr(), off.data_ptr()
+    if idx is None:
+        assert n_idx is None
+        m = batch.n
+    else:
+        assert idx.is_contiguous() and idx.element_size() == 4 and (n_idx is None or n_idx.element_size() == 4)
+        m = idx.numel()
+    if flags_out is not None:
+        assert flags_out.is_contiguous() and flags_out.element_size() == 1 and flags_out.numel() == batch.n
+    if stream is None:
+        stream = torch.cuda.current_stream(batch.device).cuda_stream
+    out = torch.empty(max(1, m), dtype=torch.uint8, device=batch.device)
+    if not m:
+        return out[:0]  # (a NULL idx would mean every request)
+    need = int(lib().pwaf_verify_cookies_scratch_bytes(m))
+    scratch = torch.empty(need, dtype=torch.uint8, device=batch.device)
+    rc = lib().pwaf_verify_cookies(keyset._h, C.byref(st), C.byref(col), int(now), None if idx is None else idx.data_ptr(), 0 if idx is None else m,
+                                   None if n_idx is None else n_idx.data_ptr(), out.data_ptr(), None if flags_out is None else flags_out.data_ptr(),
+                                   scratch.data_ptr(), need, C.c_void_p(stream))
+    if rc != 0:
+        _raise(rc, lib().pwaf_last_error().decode(errors="replace"))
+    return out[:m]
+
+
+def verify_cookie(keyset, request, cookie, now) -> int:
+    """Gate C for one request on the host (pwaf_verify_cookie_one): `cookie` is the first Cookie header's value (bytes | str | None: no
+    header) -> _abi.COOKIE_ABSENT / _VERIFIED / _INVALID / _UNDECIDED. What a per-request closure calls at http_listener.rs:222-236."""
+    st, keep = _request_struct(request)
+    c = None if cookie is None else (cookie.encode() if isinstance(cookie, str) else bytes(cookie))
+    out = C.c_uint8(0xEE)
+    rc = lib().pwaf_verify_cookie_one(keyset._h, C.byref(st), c, 0 if c is None else len(c), int(now), C.byref(out))
+    del keep
+    if rc != 0:
+        _raise(rc, lib().pwaf_last_error().decode(errors="replace"))
+    return int(out.value)
 
 
 DERIVED_FIELDS = (0, 2, 4)  # PWAF_FIELD_HOST, _PATH, _USER_AGENT: pwaf_derive_batch's out[0..2]
