@@ -23,6 +23,8 @@
  *                                                              pwaf_client_id_one / pwaf_client_ids
  *   cookie split + validate_captcha_verified_cookie            http_listener.rs:169-181,222-236; pingoo/captcha.rs:125-156; jwt/jwt.rs:198-327
  *                                                              pwaf_verify_cookie_one / pwaf_verify_cookies (pwaf_keyset)
+ *   CaptchaManager::api_verify up to issuing the cookie      pingoo/captcha.rs:241-333; jwt/jwt.rs:198-327
+ *                                                              pwaf_verify_pow_one / pwaf_verify_pow (pwaf_keyset)
  *
  * Plain pointers and sizes only; no C++/torch types. Never aborts across the ABI:
  * every failure is an int status (<0) plus pwaf_last_error().
@@ -558,6 +560,50 @@ int pwaf_verify_cookies(const pwaf_keyset *ks, const pwaf_batch *in, const pwaf_
                         size_t scratch_bytes, void *stream);
 int pwaf_verify_cookie_one(const pwaf_keyset *ks, const pwaf_request *req, const char *cookie /* nullable */, uint32_t cookie_len, int64_t now,
                            uint8_t *status);
+
+/* ---- captcha proof-of-work submissions (ABI 4, additive) ----------------------------------------------------
+ * A POST to /__pingoo/captcha/api/verify reaches CaptchaManager::api_verify (pingoo/captcha.rs:241-333), which finds the
+ * `__pingoo_captcha` cookie, runs jwt::parse_header, looks the key up by `kid`, runs jwt::parse_and_verify into CaptchaCookieJwtClaims
+ * (captcha.rs:61-67; jwt/jwt.rs:198-327), reads the body (CaptchaVerifyRequestBody: hash, nonce), and then checks sub == client id, the
+ * hash's leading zeroes against the difficulty, and hash == SHA-256(challenge || nonce). The evaluation answers PWAF_ACTION_BYPASS /
+ * PWAF_RULE_CAPTCHA_ENDPOINT for these requests and lists them in match_idx; pwaf_verify_pow answers the check for the requests of a
+ * batch, or for those a list names, where the batch lives. Parsing the body (JSON, hex) and issuing the verified cookie to a submission
+ * that PASSED (captcha.rs:335-346: it needs the signing key) stay the host's; a request without a usable body is not put into the call.
+ * It takes no engine. DESIGN.md §5.1.7 states the semantics rule by rule; in short:
+ *   cookie  as pwaf_verify_cookies splits the header, with the name `__pingoo_captcha` exactly (`__pingoo_captcha_verified` is another
+ *           cookie). None: ABSENT.
+ *   token   three parts, 64 bytes of signature, header with kid / alg "EdDSA" / typ "JWT" as for pwaf_verify_cookies; else FAILED.
+ *   claims  read in the flat subset PLUS one escape inside string values: the six bytes \u0000 stand for one byte 0x00 (the reference's
+ *           challenge and client id are 43 characters and a NUL, which serde_json writes so). exp >= now - 5, nbf <= now + 5, aud == iss
+ *           == "pingoo"; sub's decoded bytes are the 44 bytes of pwaf_client_id.text for the request; challenge a string; difficulty an
+ *           integer 0..255; the leading zero nibbles of hash (high nibble of byte 0 first) number at least difficulty; SHA-256(decoded
+ *           challenge || nonce) == hash. Any one failing: FAILED, whatever the signature says (every failure of api_verify is one response).
+ *   order   the signature is checked LAST, and only for an entry that passed every check above: then PASSED or FAILED. A header or claims
+ *           outside the subset, or a signed part above PWAF_COOKIE_MAX_SIGNED_BYTES: UNDECIDED if the signature verifies (under the
+ *           header's key; under any key of the set where the header is not parsed), FAILED otherwise. A flood of wrong hashes never
+ *           reaches the curve arithmetic.
+ * pwaf_verify_pow: `cookies` means what it means for pwaf_verify_cookies (the FIRST Cookie header's value, "" for none); `nonce` is a
+ * string column and `hash` 32 bytes per request, both indexed by request like the batch: CaptchaVerifyRequestBody after serde has read it.
+ * idx / idx_cap / n_idx, PWAF_MEM_HOST / PWAF_MEM_DEVICE (in->memory says where EVERY pointer lives, hash and nonce included), `now`, the
+ * key set, the trust in the batch, PWAF_ARENA_PAD (behind the nonce arena too), scratch (pwaf_verify_pow_scratch_bytes(k), 16-byte
+ * aligned) and the stream rules are word for word those of pwaf_verify_cookies above; an entry with idx[j] >= in->n reads PWAF_POW_ABSENT.
+ *   PWAF_MEM_DEVICE  a 16-byte memset and two launches (pow_check_kernel, pow_verify_kernel) on `stream`; nothing is allocated or copied.
+ *                    Diagnostic: after the stream has run, word 0 (uint32) of scratch holds the number of entries that were handed to
+ *                    the signature stage; entries decided by the cheap checks are not among them.
+ *   PWAF_MEM_HOST    synchronous, plain C++, no HIP call; reads no byte outside a value. A selected request whose offsets decrease in the
+ *                    cookies, nonce, User-Agent or host column refuses the call with PWAF_E_BATCH, naming the entry, nothing written.
+ * PWAF_E_INVALID_ARG as for pwaf_verify_cookies, plus: a NULL hash; a NULL nonce, or with n > 0 a NULL nonce column.
+ * pwaf_verify_pow_one: the same answer for one request on the host (no GPU); cookie == NULL: no Cookie header. */
+#define PWAF_POW_ABSENT 0u    /* no __pingoo_captcha cookie (captcha.rs:247-253) */
+#define PWAF_POW_PASSED 1u    /* every check of api_verify holds: the host issues the verified cookie (captcha.rs:335-346) */
+#define PWAF_POW_FAILED 2u    /* the reference answers its error response (any of captcha.rs:256-333) */
+#define PWAF_POW_UNDECIDED 3u /* signed by a key of the set, but not parsed here: the host decides with its own library */
+size_t pwaf_verify_pow_scratch_bytes(uint32_t n); /* DEVICE mode scratch for n entries; HOST mode needs none */
+int pwaf_verify_pow(const pwaf_keyset *ks, const pwaf_batch *in, const pwaf_strcol *cookies, const uint8_t *hash /* n x 32 */,
+                    const pwaf_strcol *nonce, int64_t now, const uint32_t *idx /* nullable */, uint32_t idx_cap, const uint32_t *n_idx /* nullable */,
+                    uint8_t *status, void *scratch, size_t scratch_bytes, void *stream);
+int pwaf_verify_pow_one(const pwaf_keyset *ks, const pwaf_request *req, const char *cookie /* nullable */, uint32_t cookie_len,
+                        const uint8_t hash[32], const char *nonce /* nullable with nonce_len 0 */, uint32_t nonce_len, int64_t now, uint8_t *status);
 
 /* ---- derived columns of a raw batch (ABI 4, additive) -----------------------------------------------------
  * Every evaluation entry point takes the fields AFTER the reference's own derivation (http_listener.rs:140-165, :284-296;

@@ -36,6 +36,8 @@ RECORD_NONE = 0xFFFFFFFF  # PWAF_RECORD_NONE: the list entry has no record in th
 # pwaf_verify_cookies / pwaf_verify_cookie_one: one status per request (gate C, http_listener.rs:222-236)
 COOKIE_ABSENT, COOKIE_VERIFIED, COOKIE_INVALID, COOKIE_UNDECIDED = 0, 1, 2, 3
 KEYSET_MAX_KEYS, KEYSET_MAX_KID, COOKIE_MAX_SIGNED_BYTES = 8, 64, 8192
+# pwaf_verify_pow / pwaf_verify_pow_one: one status per proof-of-work submission (CaptchaManager::api_verify, captcha.rs:241-333)
+POW_ABSENT, POW_PASSED, POW_FAILED, POW_UNDECIDED = 0, 1, 2, 3
 N_FIELDS = 5
 FIELD_NAMES = ("host", "url", "path", "method", "user_agent")
 ARENA_PAD = 16

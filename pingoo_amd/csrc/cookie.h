@@ -6,6 +6,8 @@
 // One header, compiled three ways, like clientid.h: by cookie.hip for the device (cookie_locate_kernel, cookie_verify_kernel: one request /
 // one candidate per lane), by the same unit for the host (the HOST mode, pwaf_verify_cookie_one and key-set creation) and by
 // tests/cookie_host.cpp (g++ under the sanitizers). No HIP include: compiled as plain C++ it needs <stdint.h> and <string.h> only.
+// csrc/pow.h (pwaf_verify_pow) is built on it: the scan takes the cookie's name (locate_named), the subset reader one
+// escape as a template switch (parse_flat_as); gate C uses both as it always did (locate, parse_flat).
 //
 // What is in it, in order: the cookie scan and the token split; base64url; SHA-512 (FIPS 180-4); arithmetic mod 2^255 - 19 on ten
 // 26/25-bit limbs with 64-bit products and mod L (the group order) on 32-bit words; the double-scalar multiplication [S]B + [k](-A) over
@@ -119,10 +121,8 @@ struct Token {  // where the token's parts lie in the cookie value
     PWAF_CK_HD uint32_t signed_len() const { return hdr_len + 1u + claims_len; }
 };
 PWAF_CK_HD bool is_blank(uint32_t b) { return b == ' ' || b == '\t'; }
-// PWAF_COOKIE_ABSENT, PWAF_COOKIE_INVALID or kCandidate with *t
-PWAF_CK_HD uint8_t locate(const uint8_t *v, uint32_t len, Token *t) {
-    const char kName[] = "__pingoo_captcha_verified";
-    const uint32_t kNameLen = sizeof kName - 1;
+// PWAF_COOKIE_ABSENT, PWAF_COOKIE_INVALID or kCandidate with *t, for the first cookie named exactly kName[0 .. kNameLen)
+PWAF_CK_HD uint8_t locate_named(const uint8_t *v, uint32_t len, Token *t, const char *kName, const uint32_t kNameLen) {
     bool bad = false, found = false, in_value = false;
     uint32_t name0 = 0, name1 = 0, val0 = 0, val1 = 0, tok0 = 0, tok1 = 0;  // [first, last + 1) of the bytes that are not blank; 0, 0: none
     for (uint32_t q0 = 0; q0 <= len; q0 += 16) {  // (q == len closes the last segment)
@@ -169,6 +169,10 @@ PWAF_CK_HD uint8_t locate(const uint8_t *v, uint32_t len, Token *t) {
     if (!decode_signature(v + dot1 + 1, kSigChars, r, s)) return PWAF_COOKIE_INVALID;
     t->at = tok0, t->hdr_len = dot0 - tok0, t->claims_len = dot1 - dot0 - 1u;
     return kCandidate;
+}
+PWAF_CK_HD uint8_t locate(const uint8_t *v, uint32_t len, Token *t) {
+    const char kName[] = "__pingoo_captcha_verified";
+    return locate_named(v, len, t, kName, sizeof kName - 1);
 }
 
 // ---- SHA-512 (FIPS 180-4 §4.1.3, §4.2.3, §5.1.2, §6.4) --------------------------------------------------------------------------------------
@@ -550,24 +554,34 @@ PWAF_CK_HD bool text_is(const B64 &s, uint32_t at, uint32_t len, const char *lit
 }
 PWAF_CK_HD bool is_json_space(uint32_t b) { return b == ' ' || b == '\t' || b == '\n' || b == '\r'; }
 // false: outside the subset (or a known name twice). out[k] is the value of names.name[k]; unknown names are skipped.
-PWAF_CK_HD bool parse_flat(const B64 &s, const Names &names, Value out[kMaxNames]) {
+// kNulEscape (the claims of pwaf_verify_pow only): inside a string VALUE the six bytes \u0000 are read as one byte 0x00;
+// the value's [at, at + len) stays the text as it stands, and whoever reads it skips six bytes at a backslash (escape_aware_byte). Every
+// other backslash, and every backslash in a name, stays outside the subset.
+template <bool kNulEscape>
+PWAF_CK_HD bool parse_flat_as(const B64 &s, const Names &names, Value out[kMaxNames]) {
     PWAF_CK_UNROLL
     for (uint32_t k = 0; k < kMaxNames; k++) out[k] = Value{kAbsent, 0, 0, 0};
     const uint32_t n = s.bytes;
     uint32_t q = 0, seen = 0;
 #define PWAF_CK_SKIP_SPACE() \
     while (q < n && is_json_space(b64_byte(s, q))) q++
-#define PWAF_CK_STRING(at_var, len_var)              \
-    {                                                \
-        at_var = ++q;                                \
-        for (;; q++) {                               \
-            if (q >= n) return false;                \
-            const uint32_t b = b64_byte(s, q);       \
-            if (b == '"') break;                     \
-            if (b - 0x20u > 0x5Eu || b == '\\') return false; \
-        }                                            \
-        len_var = q - at_var;                        \
-        q++;                                         \
+#define PWAF_CK_STRING(at_var, len_var, escapes)                                                                      \
+    {                                                                                                                 \
+        at_var = ++q;                                                                                                 \
+        for (;; q++) {                                                                                                \
+            if (q >= n) return false;                                                                                 \
+            const uint32_t b = b64_byte(s, q);                                                                        \
+            if (b == '"') break;                                                                                      \
+            if (b - 0x20u > 0x5Eu) return false;                                                                      \
+            if (b == '\\') {                                                                                          \
+                if (!(escapes) || q + 5u >= n || b64_byte(s, q + 1) != 'u') return false;                             \
+                for (uint32_t z = 2; z < 6; z++)                                                                      \
+                    if (b64_byte(s, q + z) != '0') return false;                                                      \
+                q += 5;                                                                                               \
+            }                                                                                                         \
+        }                                                                                                             \
+        len_var = q - at_var;                                                                                         \
+        q++;                                                                                                          \
     }
     PWAF_CK_SKIP_SPACE();
     if (q >= n || b64_byte(s, q) != '{') return false;
@@ -580,7 +594,7 @@ PWAF_CK_HD bool parse_flat(const B64 &s, const Names &names, Value out[kMaxNames
             PWAF_CK_SKIP_SPACE();
             if (q >= n || b64_byte(s, q) != '"') return false;
             uint32_t name_at, name_len;
-            PWAF_CK_STRING(name_at, name_len)
+            PWAF_CK_STRING(name_at, name_len, false)
             PWAF_CK_SKIP_SPACE();
             if (q >= n || b64_byte(s, q) != ':') return false;
             q++;
@@ -590,7 +604,7 @@ PWAF_CK_HD bool parse_flat(const B64 &s, const Names &names, Value out[kMaxNames
             const uint32_t b = b64_byte(s, q);
             if (b == '"') {
                 v.kind = kString;
-                PWAF_CK_STRING(v.at, v.len)
+                PWAF_CK_STRING(v.at, v.len, kNulEscape)
             } else if (b == 't' || b == 'f' || b == 'n') {
                 const char *lit = b == 't' ? "true" : b == 'f' ? "false" : "null";
                 const uint32_t len = b == 'f' ? 5u : 4u;
@@ -643,6 +657,13 @@ PWAF_CK_HD bool parse_flat(const B64 &s, const Names &names, Value out[kMaxNames
     return q == n;
 #undef PWAF_CK_STRING
 #undef PWAF_CK_SKIP_SPACE
+}
+PWAF_CK_HD bool parse_flat(const B64 &s, const Names &names, Value out[kMaxNames]) { return parse_flat_as<false>(s, names, out); }
+// the next byte of a string value that parse_flat_as<true> accepted, *q moving over it: a backslash there begins \u0000
+PWAF_CK_HD uint32_t escape_aware_byte(const B64 &s, uint32_t *q) {
+    const uint32_t b = b64_byte(s, *q);
+    *q += b == '\\' ? 6u : 1u;
+    return b == '\\' ? 0u : b;
 }
 PWAF_CK_HD bool string_or_absent(const Value &v) { return v.kind == kAbsent || v.kind == kString; }
 
@@ -868,3 +889,9 @@ inline bool build_key(const uint8_t enc[32], const char *kid, uint32_t kid_len, 
 
 }  // namespace cookie
 }  // namespace pwaf
+
+struct pwaf_keyset {  // include/pwaf.h's opaque type: cookie.hip creates and destroys it, cookie.hip and pow.hip read it
+    pwaf::cookie::KeySetData data;
+    pwaf::cookie::KeySetData *dev;  // NULL: host only
+    int device;
+};

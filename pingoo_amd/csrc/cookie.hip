@@ -91,12 +91,6 @@ int launch_verify_cookies(const Args &a, void *stream) {
 int fail(int code, const std::string &msg);  // program_api.cpp: records pwaf_last_error()
 }  // namespace pwaf
 
-struct pwaf_keyset {
-    pwaf::cookie::KeySetData data;
-    pwaf::cookie::KeySetData *dev;  // NULL: host only
-    int device;
-};
-
 extern "C" int pwaf_keyset_create(const pwaf_ed25519_key *keys, uint32_t n, int device, pwaf_keyset **out) {
     namespace K = pwaf::cookie;
     using pwaf::fail;

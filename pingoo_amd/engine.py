@@ -161,6 +161,10 @@ def lib():
     L.pwaf_verify_cookies_scratch_bytes.restype = C.c_size_t
     L.pwaf_verify_cookies.argtypes = [vp, C.POINTER(_abi.Batch), C.POINTER(_abi.StrCol), C.c_int64, vp, C.c_uint32, vp, vp, vp, vp, C.c_size_t, vp]
     L.pwaf_verify_cookie_one.argtypes = [vp, C.POINTER(_abi.Request), vp, C.c_uint32, C.c_int64, C.POINTER(C.c_uint8)]
+    L.pwaf_verify_pow_scratch_bytes.argtypes = [C.c_uint32]
+    L.pwaf_verify_pow_scratch_bytes.restype = C.c_size_t
+    L.pwaf_verify_pow.argtypes = [vp, C.POINTER(_abi.Batch), C.POINTER(_abi.StrCol), vp, C.POINTER(_abi.StrCol), C.c_int64, vp, C.c_uint32, vp, vp, vp, C.c_size_t, vp]
+    L.pwaf_verify_pow_one.argtypes = [vp, C.POINTER(_abi.Request), vp, C.c_uint32, vp, vp, C.c_uint32, C.c_int64, C.POINTER(C.c_uint8)]
     L.pwaf_derive_scratch_bytes.argtypes = [C.c_uint32]
     L.pwaf_derive_scratch_bytes.restype = C.c_size_t
     L.pwaf_derive_batch.argtypes = [C.POINTER(_abi.Batch), C.POINTER(_abi.RawColumns), C.POINTER(_abi.DerivedCol), vp, vp, C.c_size_t, vp]
@@ -729,6 +733,14 @@ class RuleEngine:
     def verify_cookie(self, keyset, request, cookie, now):
         """verify_cookie (below): gate C for one request, on the host; needs nothing of the engine."""
         return verify_cookie(keyset, request, cookie, now)
+
+    def verify_pow(self, keyset, batch, cookies, hashes, nonces, now, idx=None, n_idx=None, stream=None):
+        """verify_pow (below): the proof-of-work check for the requests of `batch`; needs nothing of the engine."""
+        return verify_pow(keyset, batch, cookies, hashes, nonces, now, idx=idx, n_idx=n_idx, stream=stream)
+
+    def verify_pow_one(self, keyset, request, cookie, hash, nonce, now):
+        """verify_pow_one (below): the proof-of-work check for one request, on the host; needs nothing of the engine."""
+        return verify_pow_one(keyset, request, cookie, hash, nonce, now)
 
     def derive_batch(self, batch, uri_host=None, present=None, stream=None):
         """derive_batch (below): the derived host, path and user_agent columns of a raw batch; needs nothing of the engine."""
@@ -1450,6 +1462,118 @@ def verify_cookie(keyset, request, cookie, now) -> int:
     c = None if cookie is None else (cookie.encode() if isinstance(cookie, str) else bytes(cookie))
     out = C.c_uint8(0xEE)
     rc = lib().pwaf_verify_cookie_one(keyset._h, C.byref(st), c, 0 if c is None else len(c), int(now), C.byref(out))
+    del keep
+    if rc != 0:
+        _raise(rc, lib().pwaf_last_error().decode(errors="replace"))
+    return int(out.value)
+
+
+def pow_handed(status) -> int:
+    """The diagnostic of a verify_pow call on a DeviceBatch: the number of entries that were handed to the signature stage (word 0 of the
+    call's scratch, which the returned tensor keeps reachable as `status.pow_scratch`). Call it after the stream is synchronised."""
+    scratch = getattr(status, "pow_scratch", None)
+    return 0 if scratch is None else int(scratch[:4].cpu().numpy().view(np.uint32)[0])
+
+
+def _hash_rows(hashes, n):
+    """[32 bytes per request] | an (n, 32) uint8 array -> a C-contiguous (n, 32) numpy array"""
+    if isinstance(hashes, np.ndarray):
+        arr = np.ascontiguousarray(hashes, dtype=np.uint8).reshape(-1, 32)
+    else:
+        rows = [bytes(h) for h in hashes]
+        assert all(len(h) == 32 for h in rows), "a proof-of-work hash has 32 bytes"
+        arr = np.frombuffer(b"".join(rows), dtype=np.uint8).reshape(-1, 32).copy()
+    assert len(arr) == n
+    return arr
+
+
+def verify_pow(keyset, batch, cookies, hashes, nonces, now, idx=None, n_idx=None, stream=None):
+    """The check of CaptchaManager::api_verify (captcha.rs:241-333; jwt.rs:198-327) for proof-of-work submissions among the requests of
+    `batch` (pwaf_verify_pow; include/pwaf.h): one _abi.POW_* status per request — of every request when idx is None, else of the requests
+    the list `idx` names (n_idx: how many entries count; an entry that names no request reads ABSENT), e.g. the match_idx / n_matches of
+    an evaluation, which lists the requests on /__pingoo/captcha/api/verify. cookies: as for verify_cookies. hashes: 32 bytes per request
+    (a list of bytes or an (n, 32) uint8 array / tensor); nonces: a (data, offsets) column where the batch lives, or a list of
+    bytes | str: CaptchaVerifyRequestBody after the host has parsed it. now: Unix seconds. PASSED means the host issues the verified
+    cookie; that, and parsing the body, stay on the host. Takes no engine.
+    RequestBatch: numpy arguments, synchronous, on the CPU -> a numpy uint8 array.
+    DeviceBatch: device tensors (lists are uploaded); a memset and two launches are enqueued on `stream` (default: torch's current
+    stream, from whose allocator the scratch comes) and the call returns -> a uint8 tensor to be read after the stream is
+    synchronised (entries at or past n_idx are not written); it keeps the call's scratch reachable as `.pow_scratch`, whose word 0
+    pow_handed(status) reads: the diagnostic."""
+    st = batch.as_struct()
+    col, ncol = _abi.StrCol(), _abi.StrCol()
+    if isinstance(batch, RequestBatch):
+        data, off = cookies if isinstance(cookies, tuple) else cookie_column(cookies)
+        data, off = np.ascontiguousarray(data, dtype=np.uint8), np.ascontiguousarray(off, dtype=np.uint32)
+        ndata, noff = nonces if isinstance(nonces, tuple) else cookie_column(nonces)
+        ndata, noff = np.ascontiguousarray(ndata, dtype=np.uint8), np.ascontiguousarray(noff, dtype=np.uint32)
+        assert len(off) == batch.n + 1 and len(noff) == batch.n + 1
+        col.data, col.offsets, ncol.data, ncol.offsets = data.ctypes.data, off.ctypes.data, ndata.ctypes.data, noff.ctypes.data
+        rows = _hash_rows(hashes, batch.n)
+        hbuf = rows if batch.n else np.zeros((1, 32), dtype=np.uint8)
+        if idx is None:
+            assert n_idx is None
+            m = batch.n
+        else:
+            idx = np.ascontiguousarray(idx, dtype=np.uint32).reshape(-1)
+            m = len(idx) if n_idx is None else min(len(idx), int(np.asarray(n_idx).reshape(-1)[0]))
+            if not len(idx):
+                return np.zeros(0, dtype=np.uint8)  # (a NULL idx would mean every request)
+        n_ref = None if n_idx is None else np.array([int(np.asarray(n_idx).reshape(-1)[0])], dtype=np.uint32)
+        out = np.zeros(max(1, m), dtype=np.uint8)
+        rc = lib().pwaf_verify_pow(keyset._h, C.byref(st), C.byref(col), hbuf.ctypes.data, C.byref(ncol), int(now), None if idx is None else idx.ctypes.data,
+                                   0 if idx is None else len(idx), None if n_ref is None else n_ref.ctypes.data, out.ctypes.data, None, 0, None)
+        if rc != 0:
+            _raise(rc, lib().pwaf_last_error().decode(errors="replace"))
+        return out[:m]
+    import torch
+
+    def column(values):
+        if isinstance(values, tuple):
+            return values
+        d, o = cookie_column(values)
+        return torch.from_numpy(d).to(batch.device), torch.from_numpy(o.view(np.int32)).to(batch.device)
+
+    (data, off), (ndata, noff) = column(cookies), column(nonces)
+    for d, o in ((data, off), (ndata, noff)):
+        assert d.is_contiguous() and o.is_contiguous() and o.element_size() == 4 and o.numel() == batch.n + 1
+    col.data, col.offsets, ncol.data, ncol.offsets = data.data_ptr(), off.data_ptr(), ndata.data_ptr(), noff.data_ptr()
+    if not torch.is_tensor(hashes):
+        hashes = torch.from_numpy(_hash_rows(hashes, batch.n)).to(batch.device)
+    assert hashes.is_contiguous() and hashes.element_size() == 1 and hashes.numel() == 32 * batch.n
+    if idx is None:
+        assert n_idx is None
+        m = batch.n
+    else:
+        assert idx.is_contiguous() and idx.element_size() == 4 and (n_idx is None or n_idx.element_size() == 4)
+        m = idx.numel()
+    if stream is None:
+        stream = torch.cuda.current_stream(batch.device).cuda_stream
+    out = torch.empty(max(1, m), dtype=torch.uint8, device=batch.device)
+    if not m:
+        return out[:0]  # (a NULL idx would mean every request)
+    need = int(lib().pwaf_verify_pow_scratch_bytes(m))
+    scratch = torch.empty(need, dtype=torch.uint8, device=batch.device)
+    rc = lib().pwaf_verify_pow(keyset._h, C.byref(st), C.byref(col), hashes.data_ptr(), C.byref(ncol), int(now), None if idx is None else idx.data_ptr(),
+                               0 if idx is None else m, None if n_idx is None else n_idx.data_ptr(), out.data_ptr(), scratch.data_ptr(), need, C.c_void_p(stream))
+    if rc != 0:
+        _raise(rc, lib().pwaf_last_error().decode(errors="replace"))
+    status = out[:m]
+    status.pow_scratch = scratch
+    return status
+
+
+def verify_pow_one(keyset, request, cookie, hash, nonce, now) -> int:
+    """The proof-of-work check for one request on the host (pwaf_verify_pow_one): `cookie` is the first Cookie header's value (bytes | str |
+    None: no header), `hash` the body's 32 bytes, `nonce` its string -> _abi.POW_ABSENT / _PASSED / _FAILED / _UNDECIDED."""
+    st, keep = _request_struct(request)
+    c = None if cookie is None else (cookie.encode() if isinstance(cookie, str) else bytes(cookie))
+    nv = nonce.encode() if isinstance(nonce, str) else bytes(nonce)
+    h = bytes(hash)
+    if len(h) != 32:
+        raise ValueError(f"verify_pow_one: the hash has {len(h)} bytes, a SHA-256 digest has 32")
+    out = C.c_uint8(0xEE)
+    rc = lib().pwaf_verify_pow_one(keyset._h, C.byref(st), c, 0 if c is None else len(c), h, nv, len(nv), int(now), C.byref(out))
     del keep
     if rc != 0:
         _raise(rc, lib().pwaf_last_error().decode(errors="replace"))
