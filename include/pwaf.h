@@ -25,6 +25,8 @@
  *                                                              pwaf_verify_cookie_one / pwaf_verify_cookies (pwaf_keyset)
  *   CaptchaManager::api_verify up to issuing the cookie      pingoo/captcha.rs:241-333; jwt/jwt.rs:198-327
  *                                                              pwaf_verify_pow_one / pwaf_verify_pow (pwaf_keyset)
+ *   serde_json::from_reader -> CaptchaVerifyRequestBody      pingoo/captcha.rs:50-57,291
+ *                                                              pwaf_parse_pow_body_one / pwaf_parse_pow_bodies
  *
  * Plain pointers and sizes only; no C++/torch types. Never aborts across the ABI:
  * every failure is an int status (<0) plus pwaf_last_error().
@@ -567,8 +569,9 @@ int pwaf_verify_cookie_one(const pwaf_keyset *ks, const pwaf_request *req, const
  * (captcha.rs:61-67; jwt/jwt.rs:198-327), reads the body (CaptchaVerifyRequestBody: hash, nonce), and then checks sub == client id, the
  * hash's leading zeroes against the difficulty, and hash == SHA-256(challenge || nonce). The evaluation answers PWAF_ACTION_BYPASS /
  * PWAF_RULE_CAPTCHA_ENDPOINT for these requests and lists them in match_idx; pwaf_verify_pow answers the check for the requests of a
- * batch, or for those a list names, where the batch lives. Parsing the body (JSON, hex) and issuing the verified cookie to a submission
- * that PASSED (captcha.rs:335-346: it needs the signing key) stay the host's; a request without a usable body is not put into the call.
+ * batch, or for those a list names, where the batch lives. pwaf_parse_pow_bodies (below) reads hash and nonce out of the bodies where they
+ * lie; issuing the verified cookie to a submission that PASSED (captcha.rs:335-346: it needs the signing key) stays the host's; a request
+ * without a usable body is not put into the call, or its status is not read.
  * It takes no engine. DESIGN.md §5.1.7 states the semantics rule by rule; in short:
  *   cookie  as pwaf_verify_cookies splits the header, with the name `__pingoo_captcha` exactly (`__pingoo_captcha_verified` is another
  *           cookie). None: ABSENT.
@@ -669,6 +672,76 @@ int pwaf_derive_batch(const pwaf_batch *raw, const pwaf_raw_columns *extra /* nu
                       pwaf_derive_stats *stats, void *scratch, size_t scratch_bytes, void *stream);
 /* TEST HOOK, CPU: [0] requests per tile, [1] tiles per step of the base launch, [2] requests per workgroup of the copy launch, [3] 0 */
 int pwaf_derive_scan_shape(uint32_t out[4]);
+
+/* ---- captcha proof-of-work request bodies (ABI 4, additive) --------------------------------------------------
+ * The body of a POST to /__pingoo/captcha/api/verify is what serde_json::from_reader makes CaptchaVerifyRequestBody {#[serde(with = "hex")]
+ * hash: [u8; 32], nonce: String} of (pingoo/captcha.rs:50-57, :291); the genuine client sends {"nonce":"<decimal>","hash":"<64 hex>"}
+ * (captcha/src/index.tsx:64,145). pwaf_parse_pow_bodies reads the bodies of a batch, or of the requests a list names, where they lie, and
+ * writes exactly what pwaf_verify_pow reads next on the same stream: hash[n][32] and a nonce string column, both indexed BY REQUEST, and
+ * one status byte per entry (the nonce column is a pwaf_derived_col, as pwaf_derive_batch above writes them). It takes no engine and no key set. DESIGN.md §5.1.8 states the semantics decision by decision (D-B1 to
+ * D-B10); in short, with ws = {0x20, 0x09, 0x0A, 0x0D}, read left to right, the FIRST deciding event wins:
+ *   subset     ws* '{' members '}' ws*, a member being ws* key ws* ':' ws* value ws*, members separated by ','; key and value are strings
+ *              that end at the first '"' behind their opening one; the keys are exactly `hash` and `nonce`, once each, in either order;
+ *              hash's text is exactly 64 hexadecimal digits of either case (decoded high nibble first), nonce's text is any bytes below
+ *              0x80 (any length, 0 included) and is the value as it stands. That is OK.
+ *   MALFORMED  only where the reference's parse certainly fails: an empty or all-ws body; a first byte other than '{' or '['; a key or a
+ *              known key's value that does not begin with '"'; a missing ':' ; a byte other than ',' or '}' behind a value; the body's end
+ *              inside the object; a string without a closing '"' or with a byte below 0x20; a known key twice; a hash text that is not 64
+ *              hexadecimal digits; `hash` or `nonce` missing at '}'; anything but ws behind '}'.
+ *   UNDECIDED  everything else: a body longer than PWAF_POW_BODY_MAX_BYTES (nothing of it is read); '[' as the first byte; a '\' inside a
+ *              string; a key with a byte >= 0x80 or other than `hash` / `nonce` (serde skips an unknown member's value, which may be any
+ *              JSON); a nonce with a byte >= 0x80. The host parses such a body with its own library, as it did before.
+ * `bodies` holds each request's body bytes ("" for a request without one); `memory` says where EVERY pointer lives: the column's, idx,
+ * n_idx, status, hash, nonce's, stats and scratch. Input offsets need not begin at 0. idx / idx_cap / n_idx mean exactly what they mean
+ * for pwaf_client_ids: idx == NULL (idx_cap 0, n_idx NULL): every request, status[i] belongs to request i; otherwise m = min(*n_idx,
+ * idx_cap), or idx_cap when n_idx == NULL, status[j] belongs to request idx[j] for j < m, entries j >= m are not written, idx[j] >= n
+ * reads PWAF_BODY_NONE, and a request named twice gets the same answer twice.
+ * Output: nonce->offsets[0..n] are always written completely (offsets[0] == 0); a request that is not selected, or whose status is not OK,
+ * has a nonce of length 0. The hash row of a selected request that is not OK is 32 zero bytes; rows of unselected requests are not
+ * written. nonce->data receives the nonces back to back in request order, and the PWAF_ARENA_PAD bytes behind the column's last byte are
+ * written as zero where they lie below cap, which makes the column a valid PWAF_MEM_DEVICE arena. Nothing is written at or beyond data +
+ * cap, offsets + n + 1, status + m or stats + 1, and nothing between nonce_bytes + 16 and cap. With nonce_bytes + PWAF_ARENA_PAD <= cap
+ * the column is complete — always so when cap is at least the bodies' bytes + 16 — otherwise stats->overflow says so and which of the
+ * column's BYTES were written is unspecified. The caller reads pwaf_verify_pow's status only where the body status is OK; for MALFORMED
+ * it sends the error response (captcha.rs:293-296); for UNDECIDED it runs serde_json as before.
+ *   PWAF_MEM_DEVICE  at most one memset (with a list: it zeroes nonce->offsets) and three launches (powbody_parse_kernel,
+ *                    powbody_base_kernel, powbody_copy_kernel) are enqueued on `stream` (hipStream_t; NULL = HIP's default stream) of the
+ *                    current device and the call returns at once. Nothing is allocated, nothing is copied. The kernels read *n_idx
+ *                    themselves, so the call may stand between pwaf_evaluate_device(..., match_idx, n_matches, stream) and
+ *                    pwaf_verify_pow on one stream with no synchronisation anywhere. scratch: pwaf_parse_pow_bodies_scratch_bytes(n)
+ *                    bytes of device memory, 16-byte aligned, the call's own until the launches have run. The column is trusted as
+ *                    pwaf_evaluate_device trusts a batch, except that the kernels guard idx[j] >= n. Loads are 16 bytes at the body's own
+ *                    alignment; they may pass a body's end by fewer than 16 bytes (the arena carries PWAF_ARENA_PAD behind its last
+ *                    byte) and never begin before the body.
+ *   PWAF_MEM_HOST    synchronous, plain C++, no HIP call: works on a machine without a GPU and reads no byte outside a value. scratch
+ *                    and stream are ignored. A selected request whose body offsets decrease refuses the call with PWAF_E_BATCH (naming
+ *                    the entry) before anything is written.
+ * PWAF_E_INVALID_ARG, before anything runs: NULL bodies, status, hash, nonce or stats; a bad memory; idx == NULL with idx_cap != 0 or
+ * n_idx != NULL; n > 0xFFFFFFF0 / PWAF_POW_BODY_MAX_BYTES (the nonce column could pass 32 bits: the caller splits such a batch); stats not
+ * 8-byte aligned; with n > 0 a NULL bodies column or a NULL nonce->offsets; a NULL nonce->data with cap != 0; nonce->data not 16-byte
+ * aligned or offsets not 4-byte aligned; in DEVICE mode scratch NULL, not 16-byte aligned or too small.
+ * pwaf_parse_pow_body_one: the same answer for one body on the host (no GPU): status, the 32 bytes (zero unless OK) and the nonce as
+ * body[*nonce_at, +*nonce_len) (0, 0 unless OK): what a per-request closure calls in front of pwaf_verify_pow_one. */
+#define PWAF_BODY_NONE 0u       /* idx[j] >= n: not a request */
+#define PWAF_BODY_OK 1u         /* hash and nonce are what serde_json hands api_verify (captcha.rs:291) */
+#define PWAF_BODY_MALFORMED 2u  /* the reference's parse fails: its error response (captcha.rs:293-296) */
+#define PWAF_BODY_UNDECIDED 3u  /* outside the subset parsed here: the host parses it with its own library */
+#define PWAF_POW_BODY_MAX_BYTES 4096u
+typedef struct pwaf_body_stats { /* 32 bytes, OVERWRITTEN */
+    uint64_t nonce_bytes;        /* nonce.offsets[n], whether or not it fitted */
+    uint32_t n, n_ok, n_malformed, n_undecided; /* entries looked at and their statuses */
+    uint32_t overflow;           /* 1: nonce_bytes + PWAF_ARENA_PAD > nonce->cap, the column's BYTES are incomplete */
+    uint32_t reserved;
+} pwaf_body_stats;
+size_t pwaf_parse_pow_bodies_scratch_bytes(uint32_t n); /* DEVICE mode scratch for a batch of n; HOST mode needs none */
+int pwaf_parse_pow_bodies(const pwaf_strcol *bodies, uint32_t n, uint32_t memory, const uint32_t *idx /* nullable */, uint32_t idx_cap,
+                          const uint32_t *n_idx /* nullable */, uint8_t *status, uint8_t *hash /* n x 32 */, pwaf_derived_col *nonce,
+                          pwaf_body_stats *stats, void *scratch, size_t scratch_bytes, void *stream);
+int pwaf_parse_pow_body_one(const uint8_t *body, uint32_t len, uint8_t *status, uint8_t hash[32], uint32_t *nonce_at,
+                            uint32_t *nonce_len); /* the nonce is body[nonce_at, +nonce_len) */
+/* TEST HOOK, CPU: [0] entries per tile, [1] tiles per step of the base launch, [2] requests per workgroup of the copy launch, [3] the
+ * least bound on the parse launch's workgroups with a list */
+int pwaf_parse_pow_scan_shape(uint32_t out[4]);
 
 /* ---- records in device memory (ABI 4, additive) ----------------------------------------------------------
  * pwaf_evaluate_records for records that already lie in DEVICE memory — what pwaf_export_records wrote, or a replay file copied to the

@@ -38,6 +38,9 @@ COOKIE_ABSENT, COOKIE_VERIFIED, COOKIE_INVALID, COOKIE_UNDECIDED = 0, 1, 2, 3
 KEYSET_MAX_KEYS, KEYSET_MAX_KID, COOKIE_MAX_SIGNED_BYTES = 8, 64, 8192
 # pwaf_verify_pow / pwaf_verify_pow_one: one status per proof-of-work submission (CaptchaManager::api_verify, captcha.rs:241-333)
 POW_ABSENT, POW_PASSED, POW_FAILED, POW_UNDECIDED = 0, 1, 2, 3
+# pwaf_parse_pow_bodies / pwaf_parse_pow_body_one: one status per proof-of-work request body (CaptchaVerifyRequestBody, captcha.rs:50-57, :291)
+BODY_NONE, BODY_OK, BODY_MALFORMED, BODY_UNDECIDED = 0, 1, 2, 3
+POW_BODY_MAX_BYTES = 4096
 N_FIELDS = 5
 FIELD_NAMES = ("host", "url", "path", "method", "user_agent")
 ARENA_PAD = 16
@@ -50,6 +53,9 @@ RECORDS_SCAN_SHAPE_FIELDS = ("tile", "step", "zero2", "zero3")
 # pwaf_derive_scan_shape (test hook): the meaning of out[0..3] (pwaf_derive_batch's scan: requests per tile, tiles per step of the base launch,
 # requests per workgroup of the copy launch)
 DERIVE_SCAN_SHAPE_FIELDS = ("tile", "step", "copy_group", "zero3")
+# pwaf_parse_pow_scan_shape (test hook): the meaning of out[0..3] (pwaf_parse_pow_bodies' scan: entries per tile, tiles per step of the base
+# launch, requests per workgroup of the copy launch, the least bound on the parse launch's workgroups with a list)
+PARSE_POW_SCAN_SHAPE_FIELDS = ("tile", "step", "copy_group", "min_groups")
 # pwaf_raw_columns.present: which of its sources a raw request has (pwaf_derive_batch)
 RAW_HAS_URI_HOST, RAW_HAS_HOST_HEADER, RAW_HAS_USER_AGENT = 1, 2, 4
 # pwaf_program_list_scans (test hook): the meaning of a descriptor's PWAF_LIST_SCAN_WORDS words (share_owner 0xFFFFFFFF: none)
@@ -221,6 +227,13 @@ class DeriveStats(C.Structure):
     """pwaf_derive_stats: offsets[n] of the derived host, path and user_agent column, the requests derived, one overflow bit per column."""
 
     _fields_ = [("bytes", C.c_uint64 * 3), ("n", C.c_uint32), ("overflow", C.c_uint32)]
+
+
+class BodyStats(C.Structure):
+    """pwaf_body_stats: offsets[n] of the nonce column pwaf_parse_pow_bodies wrote, the entries looked at and their statuses, the overflow bit."""
+
+    _fields_ = [("nonce_bytes", C.c_uint64), ("n", C.c_uint32), ("n_ok", C.c_uint32), ("n_malformed", C.c_uint32), ("n_undecided", C.c_uint32),
+                ("overflow", C.c_uint32), ("reserved", C.c_uint32)]
 
 
 class Geo(C.Structure):

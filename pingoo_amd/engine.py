@@ -165,6 +165,11 @@ def lib():
     L.pwaf_verify_pow_scratch_bytes.restype = C.c_size_t
     L.pwaf_verify_pow.argtypes = [vp, C.POINTER(_abi.Batch), C.POINTER(_abi.StrCol), vp, C.POINTER(_abi.StrCol), C.c_int64, vp, C.c_uint32, vp, vp, vp, C.c_size_t, vp]
     L.pwaf_verify_pow_one.argtypes = [vp, C.POINTER(_abi.Request), vp, C.c_uint32, vp, vp, C.c_uint32, C.c_int64, C.POINTER(C.c_uint8)]
+    L.pwaf_parse_pow_bodies_scratch_bytes.argtypes = [C.c_uint32]
+    L.pwaf_parse_pow_bodies_scratch_bytes.restype = C.c_size_t
+    L.pwaf_parse_pow_bodies.argtypes = [C.POINTER(_abi.StrCol), C.c_uint32, C.c_uint32, vp, C.c_uint32, vp, vp, vp, C.POINTER(_abi.DerivedCol), vp, vp, C.c_size_t, vp]
+    L.pwaf_parse_pow_body_one.argtypes = [vp, C.c_uint32, C.POINTER(C.c_uint8), vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
+    L.pwaf_parse_pow_scan_shape.argtypes = [C.POINTER(C.c_uint32)]
     L.pwaf_derive_scratch_bytes.argtypes = [C.c_uint32]
     L.pwaf_derive_scratch_bytes.restype = C.c_size_t
     L.pwaf_derive_batch.argtypes = [C.POINTER(_abi.Batch), C.POINTER(_abi.RawColumns), C.POINTER(_abi.DerivedCol), vp, vp, C.c_size_t, vp]
@@ -741,6 +746,14 @@ class RuleEngine:
     def verify_pow_one(self, keyset, request, cookie, hash, nonce, now):
         """verify_pow_one (below): the proof-of-work check for one request, on the host; needs nothing of the engine."""
         return verify_pow_one(keyset, request, cookie, hash, nonce, now)
+
+    def parse_pow_bodies(self, bodies, n=None, idx=None, n_idx=None, stream=None, cap=None):
+        """parse_pow_bodies (below): hash and nonce out of proof-of-work request bodies, as verify_pow takes them; needs nothing of the engine."""
+        return parse_pow_bodies(bodies, n=n, idx=idx, n_idx=n_idx, stream=stream, cap=cap)
+
+    def parse_pow_body_one(self, body):
+        """parse_pow_body_one (below): one proof-of-work request body, on the host; needs nothing of the engine."""
+        return parse_pow_body_one(body)
 
     def derive_batch(self, batch, uri_host=None, present=None, stream=None):
         """derive_batch (below): the derived host, path and user_agent columns of a raw batch; needs nothing of the engine."""
@@ -1578,6 +1591,124 @@ def verify_pow_one(keyset, request, cookie, hash, nonce, now) -> int:
     if rc != 0:
         _raise(rc, lib().pwaf_last_error().decode(errors="replace"))
     return int(out.value)
+
+
+def body_column(bodies):
+    """[bytes | str | None per request] (None: no body) -> (data with PWAF_ARENA_PAD zero bytes behind it, offsets) numpy arrays, as cookie_column"""
+    return cookie_column(bodies)
+
+
+def body_stats(stats) -> dict:
+    """The 32 bytes of a pwaf_body_stats (a device tensor once its stream is synchronised, a numpy array or bytes) -> {nonce_bytes, n, n_ok,
+    n_malformed, n_undecided, overflow}."""
+    raw = stats.cpu().numpy().tobytes() if hasattr(stats, "cpu") else bytes(stats)
+    s = _abi.BodyStats.from_buffer_copy(raw[:C.sizeof(_abi.BodyStats)])
+    return {"nonce_bytes": int(s.nonce_bytes), "n": int(s.n), "n_ok": int(s.n_ok), "n_malformed": int(s.n_malformed), "n_undecided": int(s.n_undecided),
+            "overflow": int(s.overflow)}
+
+
+def parse_pow_scan_shape() -> dict:
+    """TEST HOOK (pwaf_parse_pow_scan_shape): the shape of parse_pow_bodies' scan, by the names of _abi.PARSE_POW_SCAN_SHAPE_FIELDS."""
+    out = (C.c_uint32 * 4)()
+    rc = lib().pwaf_parse_pow_scan_shape(out)
+    if rc != 0:
+        _raise(rc, lib().pwaf_last_error().decode(errors="replace"))
+    return dict(zip(_abi.PARSE_POW_SCAN_SHAPE_FIELDS, (int(x) for x in out)))
+
+
+def parse_pow_bodies(bodies, n=None, idx=None, n_idx=None, stream=None, cap=None):
+    """What serde_json makes CaptchaVerifyRequestBody of (captcha.rs:50-57, :291), for the proof-of-work request bodies of a batch
+    (pwaf_parse_pow_bodies; include/pwaf.h) -> (status, hashes, nonce_col, stats): one _abi.BODY_* status per entry — of every request
+    when idx is None, else of the requests the list `idx` names (n_idx: how many entries count; an entry that names no request reads
+    BODY_NONE), e.g. the match_idx / n_matches of an evaluation; hashes (n, 32) and nonce_col = (data, offsets) indexed BY REQUEST, which
+    verify_pow(..., hashes, nonce_col, ...) takes as they stand; stats: 32 bytes for body_stats(). The caller reads verify_pow's status
+    only where the body status is BODY_OK; MALFORMED is the reference's error response, UNDECIDED a body the host parses with its own
+    library. bodies: a list of bytes | str | None (host memory, as body_column makes it a column), or a (data, offsets) pair of numpy
+    arrays (HOST mode) or of device tensors (DEVICE mode); n defaults to the offsets' length - 1. cap: the nonce column's room in bytes
+    (default: the bodies' bytes + 16, in which no batch overflows). Takes no engine.
+    HOST mode: synchronous, on the CPU -> numpy arrays. DEVICE mode: at most a memset and three launches are enqueued on `stream`
+    (default: torch's current stream, which must be the stream torch allocates on when the call is made: outputs and scratch come from
+    its caching allocator) and the call returns -> tensors to be read after the stream is synchronised; status entries at or past n_idx
+    and hash rows of unselected requests are not written. The scratch stays reachable as `status.body_scratch`."""
+    if not isinstance(bodies, tuple):
+        bodies = body_column(bodies)
+    data, off = bodies
+    host_mode = isinstance(off, np.ndarray)
+    col, ncol = _abi.StrCol(), _abi.DerivedCol()
+    if host_mode:
+        data, off = np.ascontiguousarray(data, dtype=np.uint8), np.ascontiguousarray(off, dtype=np.uint32)
+        if n is None:
+            n = len(off) - 1
+        assert len(off) >= n + 1
+        col.data, col.offsets = data.ctypes.data, off.ctypes.data
+        if idx is None:
+            assert n_idx is None
+            m = n
+        else:
+            idx = np.ascontiguousarray(idx, dtype=np.uint32).reshape(-1)
+            m = len(idx) if n_idx is None else min(len(idx), int(np.asarray(n_idx).reshape(-1)[0]))
+        n_ref = None if n_idx is None else np.array([int(np.asarray(n_idx).reshape(-1)[0])], dtype=np.uint32)
+        if cap is None:
+            cap = (int(off[n]) - int(off[0]) if n else 0) + _abi.ARENA_PAD
+        status = np.zeros(max(1, m), dtype=np.uint8)
+        hashes = np.zeros((max(1, n), 32), dtype=np.uint8)
+        ndata, noff = _aligned_bytes(cap), np.zeros(n + 1, dtype=np.uint32)
+        stats = np.zeros(C.sizeof(_abi.BodyStats) // 8, dtype=np.uint64)
+        ncol.data, ncol.offsets, ncol.cap = ndata.ctypes.data, noff.ctypes.data, cap
+        # (an empty list is not a NULL idx, which would mean every request)
+        keep_idx = idx if idx is None or len(idx) else np.zeros(1, dtype=np.uint32)
+        rc = lib().pwaf_parse_pow_bodies(C.byref(col), n, _abi.MEM_HOST, None if idx is None else keep_idx.ctypes.data, 0 if idx is None else len(idx),
+                                         None if n_ref is None else n_ref.ctypes.data, status.ctypes.data, hashes.ctypes.data, C.byref(ncol), stats.ctypes.data, None, 0, None)
+        if rc != 0:
+            _raise(rc, lib().pwaf_last_error().decode(errors="replace"))
+        return status[:m], hashes[:n], (ndata, noff), stats.view(np.uint8)
+    import torch
+
+    assert data.is_contiguous() and off.is_contiguous() and off.element_size() == 4
+    if n is None:
+        n = off.numel() - 1
+    assert off.numel() >= n + 1
+    device = off.device
+    col.data, col.offsets = data.data_ptr(), off.data_ptr()
+    if idx is None:
+        assert n_idx is None
+        m = n
+    else:
+        assert idx.is_contiguous() and idx.element_size() == 4 and (n_idx is None or n_idx.element_size() == 4)
+        m = idx.numel()
+    if stream is None:
+        stream = torch.cuda.current_stream(device).cuda_stream
+    if cap is None:
+        cap = data.numel() + _abi.ARENA_PAD  # (an upper bound without a synchronisation: the arena with its pad)
+    status = torch.empty(max(1, m), dtype=torch.uint8, device=device)
+    hashes = torch.empty((max(1, n), 32), dtype=torch.uint8, device=device)
+    ndata = torch.empty(max(16, cap), dtype=torch.uint8, device=device)
+    noff = torch.empty(n + 1, dtype=torch.int32, device=device)
+    stats = torch.empty(C.sizeof(_abi.BodyStats), dtype=torch.uint8, device=device)
+    need = int(lib().pwaf_parse_pow_bodies_scratch_bytes(n))
+    scratch = torch.empty(need, dtype=torch.uint8, device=device)
+    keep_idx = idx if idx is None or m else torch.zeros(1, dtype=torch.int32, device=device)
+    ncol.data, ncol.offsets, ncol.cap = ndata.data_ptr(), noff.data_ptr(), cap
+    rc = lib().pwaf_parse_pow_bodies(C.byref(col), n, _abi.MEM_DEVICE, None if idx is None else keep_idx.data_ptr(), 0 if idx is None else m,
+                                     None if n_idx is None else n_idx.data_ptr(), status.data_ptr(), hashes.data_ptr(), C.byref(ncol), stats.data_ptr(), scratch.data_ptr(), need,
+                                     C.c_void_p(stream))
+    if rc != 0:
+        _raise(rc, lib().pwaf_last_error().decode(errors="replace"))
+    status = status[:m]
+    status.body_scratch = (scratch, keep_idx, bodies)
+    return status, hashes[:n], (ndata, noff), stats
+
+
+def parse_pow_body_one(body):
+    """One proof-of-work request body on the host (pwaf_parse_pow_body_one) -> (status, hash, nonce): an _abi.BODY_* status, the 32 bytes
+    and the nonce's bytes (32 zero bytes and b"" unless the status is BODY_OK): what a per-request closure hands verify_pow_one."""
+    b = body.encode() if isinstance(body, str) else bytes(body)
+    buf = (C.c_uint8 * max(1, len(b))).from_buffer_copy(b or b"\0")
+    st, h, at, ln = C.c_uint8(0xEE), (C.c_uint8 * 32)(), C.c_uint32(0), C.c_uint32(0)
+    rc = lib().pwaf_parse_pow_body_one(C.addressof(buf), len(b), C.byref(st), C.addressof(h), C.byref(at), C.byref(ln))
+    if rc != 0:
+        _raise(rc, lib().pwaf_last_error().decode(errors="replace"))
+    return int(st.value), bytes(h), b[at.value:at.value + ln.value]
 
 
 DERIVED_FIELDS = (0, 2, 4)  # PWAF_FIELD_HOST, _PATH, _USER_AGENT: pwaf_derive_batch's out[0..2]
