@@ -1024,6 +1024,24 @@ int pwaf_engine_address_tables(const pwaf_engine *, uint32_t out[8]);
  * present / shift / bytes / blocks set for the record table of a PWAF_OPT_GEO_ANSWERS engine (all 0: that table has no such level);
  * the rest 0. The reference has no counterpart. */
 int pwaf_engine_coarse_tables(const pwaf_engine *, uint32_t out[16]);
+/* TEST HOOK (needs an engine and a batch it has evaluated; read-only): what filter_kernel left for scan pass `group` in the scratch
+ * context that served the engine's most recent batch — one of pwaf_evaluate_batch* or of pwaf_evaluate_device* on the default stream
+ * (batches on other streams are not looked at). Waits for that batch, then copies from the buffers the kernels wrote; nothing is
+ * launched. info[0] = slab0, the first 128 KiB slab of the arena the pass streamed (not 0: a slab view), info[1] = the slabs it
+ * streamed (0: the arena had none — every field empty, or the batch never reached the prefilter), info[2] = the pass's sampling
+ * stride, info[3] = 1 when the pass has a pair list (a confirm tier), info[4] = the pair list's length as filter_kernel left it (the
+ * sum of the slabs' counts; 0 without a list), info[5] = PWAF_FILTER_SLAB_ROWS, info[6..7] = 0. With info[1] = S: rows = S *
+ * PWAF_FILTER_SLAB_ROWS words, the pass's chunk bitmap as it lies in memory — word r of slab s: bit l = the 16-byte chunk at arena
+ * byte (slab0 + s) * 131072 + 1024 r + 16 l holds a position that completed a window; EVERY word of every streamed slab, those of the
+ * iterations the arena's last slab does not have included; per_slab[s] = the slab's flagged chunks as counted by its wave; pair_base[s]
+ * = where the slab's pairs begin in the pair list (written as 0 for a pass without one). Each of the three arrays may be NULL (not
+ * wanted); cap_rows / cap_slabs = the room of rows / of per_slab and pair_base each, PWAF_E_INVALID_ARG when it does not suffice — call
+ * once with the arrays NULL for info[1]. Also PWAF_E_INVALID_ARG: a pass without a prefilter, an engine that has evaluated nothing,
+ * and an engine whose latest host batch and latest default-stream device batch lie in two contexts (which came last is not recorded:
+ * the hook keeps a copy of the batch's filter descriptors per context and puts nothing else on the batch path). Not to be called
+ * beside another call on the same engine. The reference has no counterpart. */
+#define PWAF_FILTER_SLAB_ROWS 128
+int pwaf_engine_filter_flags(pwaf_engine *, uint32_t group, uint32_t info[8], uint64_t *rows, size_t cap_rows, uint32_t *per_slab, uint32_t *pair_base, size_t cap_slabs);
 int pwaf_program_stats(const pwaf_program *, pwaf_stats *out);
 
 /* ---- host-side field derivation (what the reference does before building RequestData) ------ */

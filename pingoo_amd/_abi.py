@@ -68,6 +68,9 @@ FLAT_SHAPE_FIELDS = ("n_states", "n_classes", "scalar_mode", "ill_class", "n_ful
 # pwaf_engine_coarse_tables (test hook): the meaning of out[0..15]
 COARSE_TABLE_FIELDS = ("present", "shift", "bytes", "blocks_set", "summary_blocks_set", "threads", "wg_per_cu", "zero7",
                        "rec_present", "rec_shift", "rec_bytes", "rec_blocks_set", "zero12", "zero13", "zero14", "zero15")
+# pwaf_engine_filter_flags (test hook): the meaning of info[0..7]; FILTER_SLAB_ROWS = PWAF_FILTER_SLAB_ROWS, the 64-bit row words per 128 KiB slab
+FILTER_FLAGS_FIELDS = ("slab0", "slabs", "stride", "has_pairs", "pair_count", "slab_rows", "zero6", "zero7")
+FILTER_SLAB_ROWS = 128
 # pwaf_engine_geo_answer_tables (test hook): the meaning of out[0..7]
 GEO_ANSWER_TABLE_FIELDS = ("has_table", "escapes", "n_vals", "has_summary", "shift", "common", "records", "zero")
 

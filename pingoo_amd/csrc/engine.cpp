@@ -455,6 +455,48 @@ int pwaf_engine_coarse_tables(const pwaf_engine *e, uint32_t out[16]) {
     // out[8..11]: the record table (georec_kernel) has no coarse level
     return PWAF_OK;
 }
+// TEST HOOK: what filter_kernel left in the context of the engine's latest batch (include/pwaf.h). Host code and device-to-host copies only.
+int pwaf_engine_filter_flags(pwaf_engine *e, uint32_t group, uint32_t info[8], uint64_t *rows, size_t cap_rows, uint32_t *per_slab, uint32_t *pair_base, size_t cap_slabs) {
+    if (!e || !info) return fail(PWAF_E_INVALID_ARG, "pwaf_engine_filter_flags: NULL argument");
+    if (group >= e->groups.size() || !e->groups[group].filtered) return fail(PWAF_E_INVALID_ARG, "pwaf_engine_filter_flags: pass " + std::to_string(group) + " has no prefilter");
+    HIP_TRY(hipSetDevice(e->device));
+    // the context of the latest host batch (its own stream) or default-stream device batch: acquire_context keeps each kind on ONE context
+    Scratch *S = nullptr;
+    for (auto &c : e->ctx) {
+        std::lock_guard<std::mutex> lock(c->mu);
+        if (!c->used || !(c->last_own || c->last == nullptr)) continue;
+        if (S) return fail(PWAF_E_INVALID_ARG, "pwaf_engine_filter_flags: host batches and default-stream device batches were mixed on this engine: which came last is not recorded");
+        S = c.get();
+    }
+    if (!S) return fail(PWAF_E_INVALID_ARG, "pwaf_engine_filter_flags: the engine has evaluated nothing");
+    std::lock_guard<std::mutex> lock(S->mu);
+    HIP_TRY(hipEventSynchronize(S->done));
+    uint32_t fi = 0;  // the pass's index among the filtered passes (pipeline.cpp: build_filter_args)
+    for (uint32_t k = 0; k < group; k++) fi += e->groups[k].filtered ? 1u : 0u;
+    for (int i = 0; i < 8; i++) info[i] = 0;
+    info[2] = e->groups[group].filter.stride;
+    info[3] = e->groups[group].confirm ? 1u : 0u;
+    info[5] = PWAF_FILTER_SLAB_ROWS;
+    static_assert(PWAF_FILTER_SLAB_ROWS == kStreamSlab / 1024, "one 64-bit word per KiB row of a slab");
+    if (fi >= S->last_filter.size()) return PWAF_OK;  // (the batch never reached the prefilter: no slab)
+    const FilterArgs &f = S->last_filter[fi];
+    const size_t slabs = (size_t)(((uint64_t)f.total + kStreamSlab - 1) / kStreamSlab) - f.slab0;
+    info[0] = f.slab0;
+    info[1] = (uint32_t)slabs;
+    info[2] = f.stride;
+    info[3] = f.pairs ? 1u : 0u;
+    if ((rows && cap_rows < slabs * PWAF_FILTER_SLAB_ROWS) || ((per_slab || pair_base) && cap_slabs < slabs))
+        return fail(PWAF_E_INVALID_ARG, "pwaf_engine_filter_flags: the pass streamed " + std::to_string(slabs) + " slabs, the arrays are shorter");
+    if (f.pairs) HIP_TRY(hipMemcpy(&info[4], f.pair_count, 4, hipMemcpyDeviceToHost));
+    if (!slabs) return PWAF_OK;
+    if (rows) HIP_TRY(hipMemcpy(rows, f.chunk_bits, slabs * PWAF_FILTER_SLAB_ROWS * 8, hipMemcpyDeviceToHost));
+    if (per_slab) HIP_TRY(hipMemcpy(per_slab, f.sub_count, slabs * 4, hipMemcpyDeviceToHost));
+    if (pair_base) {
+        if (f.pairs) HIP_TRY(hipMemcpy(pair_base, f.pair_base, slabs * 4, hipMemcpyDeviceToHost));
+        else memset(pair_base, 0, slabs * 4);
+    }
+    return PWAF_OK;
+}
 int pwaf_engine_geo_answer_tables(const pwaf_engine *e, uint32_t out[8]) {
     if (!e || !out) return fail(PWAF_E_INVALID_ARG, "pwaf_engine_geo_answer_tables: NULL argument");
     if (int rc = need_geo_answers(e, "pwaf_engine_geo_answer_tables")) return rc;

@@ -168,6 +168,7 @@ struct Scratch {
     DevBuf zero_block;
     View ctrl, cand_bits, visit_bits, walk_bits;
     DevBuf chunk_bits, cand_cnt;  // filter_kernel's chunk bitmaps and per-slab counts
+    std::vector<pwaf::FilterArgs> last_filter;  // the filter descriptors of the context's latest batch, for pwaf_engine_filter_flags (TEST HOOK; run_pipeline swaps them in)
     DevBuf need;                           // per sharing owner: gap-pass mask of every entry of its candidate list
     DevBuf pairs;                          // per filtered pass with a confirm tier: resolve_kernel's (request, flagged chunk) pairs
     DevBuf zero_off;                       // n + 1 zero offsets: the column of a header the batch does not carry

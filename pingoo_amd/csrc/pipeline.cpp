@@ -903,6 +903,7 @@ int KernelTimer::end(const char *name, uint64_t alg_bytes, hipStream_t side) {
 // way the batch leaves (ArgSlotMark).
 int run_pipeline(pwaf_engine *e, Scratch &S, const pwaf_batch &db /* device pointers */, pwaf_verdict *d_out, pwaf_counts *d_counts, uint32_t *d_match_idx,
                  uint32_t *d_n_matches, hipStream_t stream, bool totals_known, const std::vector<uint32_t> *col_begin, bool sync_status, pwaf_geo *d_geo, const ReportOut *d_rep) {
+    S.last_filter.clear();  // (pwaf_engine_filter_flags answers for this batch from here on: nothing until its descriptors are swapped in below)
     if (db.n == 0) return PWAF_OK;
     BatchRun b(e, S, db, stream, col_begin);
     b.d_geo = d_geo;
@@ -936,6 +937,7 @@ int run_pipeline(pwaf_engine *e, Scratch &S, const pwaf_batch &db /* device poin
     if (b.sw.dump_counts && (rc = b.dump_counts())) return rc;
     if ((rc = b.arg_slot.record())) return rc;
     b.prof.commit();
+    S.last_filter.swap(b.fall);  // (kept for pwaf_engine_filter_flags, a test hook: no copy, the batch's vector changes hands)
     return PWAF_OK;
 }
 

@@ -206,6 +206,7 @@ def lib():
     L.pwaf_async_poll_geo.restype = C.c_size_t
     L.pwaf_engine_geo_answer_tables.argtypes = [vp, C.POINTER(C.c_uint32)]
     L.pwaf_engine_coarse_tables.argtypes = [vp, C.POINTER(C.c_uint32)]
+    L.pwaf_engine_filter_flags.argtypes = [vp, C.c_uint32, C.POINTER(C.c_uint32), vp, C.c_size_t, vp, vp, C.c_size_t]
     L.pwaf_geoip_from_mmdb.argtypes = [C.c_char_p, C.c_size_t, C.POINTER(C.POINTER(_abi.GeoipEntry)), C.POINTER(C.c_size_t)]
     L.pwaf_geoip_from_file_image.argtypes = [C.c_char_p, C.c_char_p, C.c_size_t, C.POINTER(C.POINTER(_abi.GeoipEntry)), C.POINTER(C.c_size_t)]
     L.pwaf_zstd_decompress.argtypes = [C.c_char_p, C.c_size_t, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]
@@ -565,6 +566,29 @@ class RuleEngine:
         if rc != 0:
             _raise(rc, lib().pwaf_last_error().decode(errors="replace"))
         return dict(zip(_abi.COARSE_TABLE_FIELDS, (int(x) for x in out)))
+
+    def filter_flags(self, group: int) -> dict:
+        """TEST HOOK (pwaf_engine_filter_flags): what filter_kernel left for scan pass `group` in the engine's most recent batch (a host
+        batch, or a device batch on the default stream) -> slab0, slabs, stride (ints), chunks (bool per 16-byte chunk of the streamed
+        slabs, chunk c at arena byte slab0 * 131072 + 16 c; every row word of every slab), per_slab (the waves' own counts), pair_base
+        (where each slab's pairs begin) and pair_count (both None for a pass without a pair list)."""
+        L = lib()
+        info = (C.c_uint32 * len(_abi.FILTER_FLAGS_FIELDS))()
+        rc = L.pwaf_engine_filter_flags(self._h, group, info, None, 0, None, None, 0)
+        if rc != 0:
+            _raise(rc, L.pwaf_last_error().decode(errors="replace"))
+        d = dict(zip(_abi.FILTER_FLAGS_FIELDS, (int(x) for x in info)))
+        assert d["slab_rows"] == _abi.FILTER_SLAB_ROWS
+        slabs = d["slabs"]
+        rows = np.zeros(slabs * _abi.FILTER_SLAB_ROWS, dtype="<u8")
+        per_slab, pair_base = np.zeros(slabs, dtype=np.uint32), np.zeros(slabs, dtype=np.uint32)
+        if slabs:
+            rc = L.pwaf_engine_filter_flags(self._h, group, info, rows.ctypes.data, len(rows), per_slab.ctypes.data, pair_base.ctypes.data, slabs)
+            if rc != 0:
+                _raise(rc, L.pwaf_last_error().decode(errors="replace"))
+        has_pairs = bool(d["has_pairs"])
+        return dict(slab0=d["slab0"], slabs=slabs, stride=d["stride"], chunks=np.unpackbits(rows.view(np.uint8), bitorder="little").astype(bool), per_slab=per_slab,
+                    pair_base=pair_base if has_pairs else None, pair_count=d["pair_count"] if has_pairs else None)
 
     def geo_answer_tables(self) -> dict:
         """TEST HOOK (pwaf_engine_geo_answer_tables; OPT_GEO_ANSWERS engines): the shape of the record tables, by the names of

@@ -74,15 +74,20 @@ class Arena:
 # ---------------------------------------------------------------------------------------------------------
 # the numpy model of filter_kernel over a whole arena
 # ---------------------------------------------------------------------------------------------------------
-def window_positions(g, data, total):
+def window_positions(g, data, total, behind=None):
     """filter_kernel restated (csrc/filter.hip, filter_rows): ONE shift-or automaton over the arena as a flat byte stream, started in
     the pass's init state at byte 0, a lookup table[bin(fold(b[i]), fold(b[i + 1]))] at every stride-th byte i, state = state << 8 |
     mask; a window completed at i when the state's top byte has a zero bit. Nothing depends on where requests begin or end.
-    -> bool per arena byte of the chunks that begin before `total` (the bytes behind `total` are the arena's slack)."""
+    -> bool per arena byte of the chunks that begin before `total` (the bytes behind `total` are the arena's slack).
+    `behind`: the byte the stream's LAST position -- byte n - 1 of the last chunk, n = total rounded up to whole chunks -- is paired with
+    at stride 1. None: the arena's own byte n, which is what a case needs to prove its shape; the byte the kernel really pairs it with
+    is not the arena's (tests/filter_cases.py: byte_behind, which the device comparison uses)."""
     n = (int(total) + CHUNK - 1) // CHUNK * CHUNK
     d = np.zeros(n + 1, dtype=np.uint32)
     k = min(len(data), n + 1)
     d[:k] = data[:k]
+    if behind is not None:
+        d[n] = int(behind)
     d &= ~((d >> 1) & 0x20)  # program.h: filter_fold
     bins = (((d[:-1] | (d[1:] << 8)) * int(g["f_mul"])) & 0xFFFF) >> 4
     s = int(g["f_stride"])

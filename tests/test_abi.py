@@ -76,6 +76,7 @@ def test_the_list_scan_hooks_name_their_words_and_refuse_bad_arguments():
     assert int(re.search(r"#define PWAF_LIST_SCAN_WORDS (\d+)", src).group(1)) == len(_abi.LIST_SCAN_FIELDS) == 16 and len(_abi.FLAT_SHAPE_FIELDS) == 7
     n = C.c_size_t(7)
     assert L.pwaf_engine_compute_units(None) == 0
+    assert L.pwaf_engine_filter_flags(None, 0, None, None, 0, None, None, 0) == _abi.E_INVALID_ARG and b"pwaf_engine_filter_flags" in L.pwaf_last_error()
     assert L.pwaf_program_flat_image(None, 0, 0, None, 0) == 0 and L.pwaf_program_list_scans(None, None, 0, C.byref(n)) == _abi.E_INVALID_ARG
     prog = engine.CompiledProgram([("m", 'http_request.method.matches("P[A-Z]{5}$")', [_abi.RULE_ACTION_BLOCK])], {})
     (d,) = [x for x in prog.list_scans() if not x["behind_filter"]]  # the method's identity pass: the default shape, every row staged

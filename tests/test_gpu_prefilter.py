@@ -39,7 +39,7 @@ def test_literal_heavy_fuzz_filtered_matches_oracle(seed):
 
 def test_heads_and_candidates_at_slab_and_chunk_boundaries():
     """Requests of every length around the 16/32-byte chunking, factors placed at the very start / end of a field and straddling
-    chunk boundaries, head literals present / absent / truncated, across more than one 2048-request slab."""
+    chunk boundaries, head literals present / absent / truncated, across more than one slab (128 KiB of arena: csrc/kernels.h, kStreamSlab)."""
     rules = [("ua", '!http_request.user_agent.starts_with("Mozilla/") && http_request.path.contains("/.env")', [B]),
              ("exact", 'http_request.user_agent == "curl/8.5.0"', [CAP]),
              ("tail", 'http_request.url.ends_with("x9k2")', [B]),
