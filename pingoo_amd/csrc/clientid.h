@@ -16,12 +16,7 @@
 #include <string.h>
 
 #include "pwaf.h"
-
-#if defined(__HIPCC__) || defined(__HIP__)
-#define PWAF_CID_HD __host__ __device__ inline
-#else
-#define PWAF_CID_HD inline
-#endif
+#include "service.h"
 
 namespace pwaf {
 namespace clientid {
@@ -32,7 +27,7 @@ static constexpr uint32_t kIdWords = 11;  // sizeof(pwaf_client_id) / 4: 43 char
 static_assert(sizeof(pwaf_client_id) == 4 * kIdWords, "pwaf_client_id layout");
 
 // ---- SHA-256 (FIPS 180-4) ---------------------------------------------------------------------------------------------------------
-PWAF_CID_HD uint32_t rotr(uint32_t x, uint32_t n) {
+PWAF_SVC_HD uint32_t rotr(uint32_t x, uint32_t n) {
 #if defined(__has_builtin)
 #if __has_builtin(__builtin_rotateright32)
     return __builtin_rotateright32(x, n);  // v_alignbit_b32
@@ -45,20 +40,20 @@ PWAF_CID_HD uint32_t rotr(uint32_t x, uint32_t n) {
 }
 // both in the bit-select shape "z ^ (x & (y ^ z))", which the compiler turns into ONE instruction (v_bfi_b32; on gfx950 v_bitop3_b32):
 // Ch = e ? f : g bitwise, Maj = (a ^ b) ? c : b bitwise
-PWAF_CID_HD uint32_t ch(uint32_t e, uint32_t f, uint32_t g) { return g ^ (e & (f ^ g)); }
-PWAF_CID_HD uint32_t maj(uint32_t a, uint32_t b, uint32_t c) { return b ^ ((a ^ b) & (c ^ b)); }
+PWAF_SVC_HD uint32_t ch(uint32_t e, uint32_t f, uint32_t g) { return g ^ (e & (f ^ g)); }
+PWAF_SVC_HD uint32_t maj(uint32_t a, uint32_t b, uint32_t c) { return b ^ ((a ^ b) & (c ^ b)); }
 // a ^ b ^ c: one v_bitop3_b32 (truth table 0x96) on gfx950, which the compiler does not form from two xors by itself
-PWAF_CID_HD uint32_t xor3(uint32_t a, uint32_t b, uint32_t c) {
+PWAF_SVC_HD uint32_t xor3(uint32_t a, uint32_t b, uint32_t c) {
 #if defined(__HIP_DEVICE_COMPILE__) && defined(__gfx950__)
     return __builtin_amdgcn_bitop3_b32(a, b, c, 0x96);
 #else
     return a ^ b ^ c;
 #endif
 }
-PWAF_CID_HD uint32_t big0(uint32_t x) { return xor3(rotr(x, 2), rotr(x, 13), rotr(x, 22)); }
-PWAF_CID_HD uint32_t big1(uint32_t x) { return xor3(rotr(x, 6), rotr(x, 11), rotr(x, 25)); }
-PWAF_CID_HD uint32_t small0(uint32_t x) { return xor3(rotr(x, 7), rotr(x, 18), x >> 3); }
-PWAF_CID_HD uint32_t small1(uint32_t x) { return xor3(rotr(x, 17), rotr(x, 19), x >> 10); }
+PWAF_SVC_HD uint32_t big0(uint32_t x) { return xor3(rotr(x, 2), rotr(x, 13), rotr(x, 22)); }
+PWAF_SVC_HD uint32_t big1(uint32_t x) { return xor3(rotr(x, 6), rotr(x, 11), rotr(x, 25)); }
+PWAF_SVC_HD uint32_t small0(uint32_t x) { return xor3(rotr(x, 7), rotr(x, 18), x >> 3); }
+PWAF_SVC_HD uint32_t small1(uint32_t x) { return xor3(rotr(x, 17), rotr(x, 19), x >> 10); }
 
 // One round with the state's roles rotated by the caller and every index a literal: the schedule is a rolling window of 16 words that
 // stays in registers (a w[] indexed at run time would live in scratch).
@@ -80,7 +75,7 @@ PWAF_CID_HD uint32_t small1(uint32_t x) { return xor3(rotr(x, 17), rotr(x, 19), 
     PWAF_SHA_ROUND(b, c, d, e, f, g, h, a, (t) + 7, k7)
 
 // state += compress(state, w); w[] (the block's 16 big-endian words) is used up
-PWAF_CID_HD void compress(uint32_t state[8], uint32_t w[16]) {
+PWAF_SVC_HD void compress(uint32_t state[8], uint32_t w[16]) {
     uint32_t a = state[0], b = state[1], c = state[2], d = state[3], e = state[4], f = state[5], g = state[6], h = state[7];
     PWAF_SHA_ROUNDS8(0, 0x428a2f98u, 0x71374491u, 0xb5c0fbcfu, 0xe9b5dba5u, 0x3956c25bu, 0x59f111f1u, 0x923f82a4u, 0xab1c5ed5u)
     PWAF_SHA_ROUNDS8(8, 0xd807aa98u, 0x12835b01u, 0x243185beu, 0x550c7dc3u, 0x72be5d74u, 0x80deb1feu, 0x9bdc06a7u, 0xc19bf174u)
@@ -99,15 +94,15 @@ PWAF_CID_HD void compress(uint32_t state[8], uint32_t w[16]) {
 struct Message {
     const uint8_t *ip, *ua, *host;  // a run of length 0 is never dereferenced (its pointer may be NULL)
     uint32_t ip_len, ua_len, host_len;
-    PWAF_CID_HD uint64_t bytes() const { return (uint64_t)ip_len + ua_len + host_len; }
-    PWAF_CID_HD uint64_t blocks() const { return (bytes() + 9u + 63u) >> 6; }  // the 0x80 byte and the 8-byte length ride in the last one
+    PWAF_SVC_HD uint64_t bytes() const { return (uint64_t)ip_len + ua_len + host_len; }
+    PWAF_SVC_HD uint64_t blocks() const { return (bytes() + 9u + 63u) >> 6; }  // the 0x80 byte and the 8-byte length ride in the last one
 };
-PWAF_CID_HD Message make_message(const uint8_t *ip16, uint8_t ip_is_v6, const uint8_t *ua, uint32_t ua_len, const uint8_t *host, uint32_t host_len) {
+PWAF_SVC_HD Message make_message(const uint8_t *ip16, uint8_t ip_is_v6, const uint8_t *ua, uint32_t ua_len, const uint8_t *host, uint32_t host_len) {
     return Message{ip16, ua, host, ip_is_v6 ? 16u : 4u, ua_len, host_len};
 }
 
 // The low `run` (1..16) bytes at s, the rest 0.
-PWAF_CID_HD chunk_t load_run(const uint8_t *s, uint32_t run) {
+PWAF_SVC_HD chunk_t load_run(const uint8_t *s, uint32_t run) {
     chunk_t v = 0;
 #if defined(__HIP_DEVICE_COMPILE__)
     memcpy(&v, s, 16);  // one 16-byte load at the run's own alignment; it may pass the value's end by up to 15 bytes
@@ -118,13 +113,13 @@ PWAF_CID_HD chunk_t load_run(const uint8_t *s, uint32_t run) {
     return v;
 }
 // what the run [start, start + len) of the message puts into the chunk [p0, p0 + 16)
-PWAF_CID_HD chunk_t run_part(uint64_t p0, const uint8_t *s, uint64_t start, uint32_t len) {
+PWAF_SVC_HD chunk_t run_part(uint64_t p0, const uint8_t *s, uint64_t start, uint32_t len) {
     const uint64_t end = start + len, lo = p0 > start ? p0 : start, hi = p0 + 16u < end ? p0 + 16u : end;
     if (lo >= hi) return 0;
     return load_run(s + (lo - start), (uint32_t)(hi - lo)) << (8u * (uint32_t)(lo - p0));
 }
 // block b (< m.blocks()) of the padded message as 16 big-endian words
-PWAF_CID_HD void load_block(const Message &m, uint64_t b, uint32_t w[16]) {
+PWAF_SVC_HD void load_block(const Message &m, uint64_t b, uint32_t w[16]) {
     const uint64_t total = m.bytes();
 #if defined(__HIP_DEVICE_COMPILE__)
 #pragma unroll
@@ -149,12 +144,12 @@ PWAF_CID_HD void load_block(const Message &m, uint64_t b, uint32_t w[16]) {
 
 // ---- base64url without padding (captcha.rs:420) -------------------------------------------------------------------------------------
 // 0..25 'A'.., 26..51 'a'.., 52..61 '0'.., 62 '-', 63 '_': branch-free
-PWAF_CID_HD uint32_t b64_char(uint32_t v) { return v + 65u + (v >= 26u ? 6u : 0u) - (v >= 52u ? 75u : 0u) - (v >= 62u ? 13u : 0u) + (v >= 63u ? 49u : 0u); }
+PWAF_SVC_HD uint32_t b64_char(uint32_t v) { return v + 65u + (v >= 26u ? 6u : 0u) - (v >= 52u ? 75u : 0u) - (v >= 62u ? 13u : 0u) + (v >= 63u ? 49u : 0u); }
 // 24 bits -> four characters, the first in the low byte (memory order)
-PWAF_CID_HD uint32_t b64_quad(uint32_t v) { return b64_char(v >> 18) | b64_char((v >> 12) & 63u) << 8 | b64_char((v >> 6) & 63u) << 16 | b64_char(v & 63u) << 24; }
+PWAF_SVC_HD uint32_t b64_quad(uint32_t v) { return b64_char(v >> 18) | b64_char((v >> 12) & 63u) << 8 | b64_char((v >> 6) & 63u) << 16 | b64_char(v & 63u) << 24; }
 // the digest (8 big-endian words) -> the 44 bytes of a pwaf_client_id as 11 words in memory order: word j holds the 24 bits at bit 24 j of
 // the digest; the last one has 16 bits left (three characters) and the NUL
-PWAF_CID_HD void encode(const uint32_t h[8], uint32_t out[kIdWords]) {
+PWAF_SVC_HD void encode(const uint32_t h[8], uint32_t out[kIdWords]) {
 #if defined(__HIP_DEVICE_COMPILE__)
 #pragma unroll
 #endif
@@ -167,7 +162,7 @@ PWAF_CID_HD void encode(const uint32_t h[8], uint32_t out[kIdWords]) {
 }
 
 // The id of one message: what every lane of client_id_kernel runs, and the host.
-PWAF_CID_HD void client_id_words(const Message &m, uint32_t out[kIdWords]) {
+PWAF_SVC_HD void client_id_words(const Message &m, uint32_t out[kIdWords]) {
     uint32_t state[8] = {0x6a09e667u, 0xbb67ae85u, 0x3c6ef372u, 0xa54ff53au, 0x510e527fu, 0x9b05688cu, 0x1f83d9abu, 0x5be0cd19u};
     const uint64_t nb = m.blocks();
     for (uint64_t b = 0; b < nb; b++) {
@@ -189,14 +184,9 @@ struct Args {
     uint32_t idx_cap;
     pwaf_client_id *out;
 };
-PWAF_CID_HD uint32_t selected(const Args &a) {
-    if (!a.idx) return a.n;
-    if (!a.n_idx) return a.idx_cap;
-    const uint32_t k = *a.n_idx;
-    return k < a.idx_cap ? k : a.idx_cap;
-}
+PWAF_SVC_HD uint32_t selected(const Args &a) { return pwaf::selected(a.idx, a.n_idx, a.idx_cap, a.n); }
 // request i (< a.n) of the batch; lengths in uint32 arithmetic, as every reader of the offsets computes them
-PWAF_CID_HD Message message_of(const Args &a, uint32_t i) {
+PWAF_SVC_HD Message message_of(const Args &a, uint32_t i) {
     const uint32_t u0 = a.ua.offsets[i], h0 = a.host.offsets[i];
     return make_message(a.ip + (size_t)i * 16, a.ip_is_v6[i], a.ua.data + u0, a.ua.offsets[i + 1] - u0, a.host.data + h0, a.host.offsets[i + 1] - h0);
 }
@@ -206,7 +196,7 @@ PWAF_CID_HD Message message_of(const Args &a, uint32_t i) {
 inline bool ids_host(const Args &a, uint32_t *bad) {
     const uint32_t m = selected(a);
     for (uint32_t j = 0; j < m; j++) {
-        const uint32_t i = a.idx ? a.idx[j] : j;
+        const uint32_t i = request_of(a.idx, j);
         if (i >= a.n) continue;
         if (a.ua.offsets[i + 1] < a.ua.offsets[i] || a.host.offsets[i + 1] < a.host.offsets[i]) {
             *bad = j;
@@ -214,7 +204,7 @@ inline bool ids_host(const Args &a, uint32_t *bad) {
         }
     }
     for (uint32_t j = 0; j < m; j++) {
-        const uint32_t i = a.idx ? a.idx[j] : j;
+        const uint32_t i = request_of(a.idx, j);
         uint32_t words[kIdWords] = {0};
         if (i < a.n) client_id_words(message_of(a, i), words);
         memcpy(a.out[j].text, words, sizeof words);

@@ -12,19 +12,13 @@
 #include <string>
 
 #include "clientid.h"
+#include "colscan.h"
 
 namespace pwaf {
 namespace clientid {
 namespace {
 
-// The workgroup is ONE wave (see records.hip): LDS instructions of a wave execute in program order; this keeps the compiler from reordering
-// them across the point where the lanes exchange roles, without __syncthreads' wait for the stores to global memory.
-__device__ __forceinline__ void wave_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
+// (The workgroup is ONE wave: wave_sync, colscan.h, orders its lanes' LDS accesses.)
 __global__ __launch_bounds__(64) void client_id_kernel(Args a) {
     __shared__ uint32_t tile[64 * kIdWords];
     const uint32_t lane = threadIdx.x;
@@ -62,23 +56,17 @@ int launch_client_ids(const Args &a, void *stream) {
 }
 
 }  // namespace clientid
-
-int fail(int code, const std::string &msg);  // engine.cpp: records pwaf_last_error()
 }  // namespace pwaf
 
 extern "C" int pwaf_client_ids(const pwaf_batch *in, const uint32_t *idx, uint32_t idx_cap, const uint32_t *n_idx, pwaf_client_id *out, void *stream) {
     namespace K = pwaf::clientid;
     using pwaf::fail;
     if (!in || !out) return fail(PWAF_E_INVALID_ARG, "pwaf_client_ids: NULL argument");
-    if (in->struct_size != sizeof(pwaf_batch)) return fail(PWAF_E_INVALID_ARG, "pwaf_batch.struct_size mismatch");
-    if (in->memory != PWAF_MEM_HOST && in->memory != PWAF_MEM_DEVICE) return fail(PWAF_E_INVALID_ARG, "pwaf_batch.memory is neither HOST nor DEVICE");
-    if (!idx && (idx_cap || n_idx)) return fail(PWAF_E_INVALID_ARG, "pwaf_client_ids: idx is NULL with idx_cap != 0 or a non-NULL n_idx");
+    if (int rc = pwaf::check_batch_header(in)) return rc;
+    if (int rc = pwaf::check_list("pwaf_client_ids", idx, idx_cap, n_idx)) return rc;
     if ((uintptr_t)out & 3u) return fail(PWAF_E_INVALID_ARG, "pwaf_client_ids: out is not 4-byte aligned");
     const pwaf_strcol &ua = in->field[PWAF_FIELD_USER_AGENT], &host = in->field[PWAF_FIELD_HOST];
-    if (in->n) {
-        if (!in->ip || !in->ip_is_v6) return fail(PWAF_E_INVALID_ARG, "pwaf_batch.ip or ip_is_v6 is NULL");
-        if (!ua.data || !ua.offsets || !host.data || !host.offsets) return fail(PWAF_E_INVALID_ARG, "pwaf_batch User-Agent or host column is NULL");
-    }
+    if (int rc = pwaf::check_client_columns(in)) return rc;
     K::Args a{};
     a.ua = ua, a.host = host, a.ip = in->ip, a.ip_is_v6 = in->ip_is_v6, a.n = in->n;
     a.idx = idx, a.n_idx = n_idx, a.idx_cap = idx_cap, a.out = out;

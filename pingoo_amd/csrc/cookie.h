@@ -24,12 +24,8 @@
 
 #include "clientid.h"
 #include "pwaf.h"
+#include "service.h"
 
-#if defined(__HIPCC__) || defined(__HIP__)
-#define PWAF_CK_HD __host__ __device__ inline
-#else
-#define PWAF_CK_HD inline
-#endif
 #if defined(__HIP_DEVICE_COMPILE__)
 #define PWAF_CK_UNROLL _Pragma("unroll")
 #define PWAF_CK_CONST __constant__ const
@@ -50,7 +46,7 @@ static constexpr uint32_t kSigChars = 86;                             // 64 byte
 typedef unsigned __int128 chunk_t;
 // up to 16 bytes at s: the device reads 16 and may pass the value's end by up to 15 bytes (inside the arena or its PWAF_ARENA_PAD); the
 // host reads exactly `run` bytes
-PWAF_CK_HD chunk_t load_chunk(const uint8_t *s, uint32_t run) {
+PWAF_SVC_HD chunk_t load_chunk(const uint8_t *s, uint32_t run) {
     chunk_t v = 0;
 #if defined(__HIP_DEVICE_COMPILE__)
     memcpy(&v, s, 16);
@@ -63,7 +59,7 @@ PWAF_CK_HD chunk_t load_chunk(const uint8_t *s, uint32_t run) {
 
 // ---- base64url without padding (jwt.rs:205, :228, :236, :244: URL_SAFE_NO_PAD) -----------------------------------------------------------
 // the 6 bits of a character, 64 for a byte outside A-Z a-z 0-9 - _ ('=' included)
-PWAF_CK_HD uint32_t b64_val(uint32_t c) {
+PWAF_SVC_HD uint32_t b64_val(uint32_t c) {
     if (c - 'A' < 26u) return c - 'A';
     if (c - 'a' < 26u) return c - 'a' + 26u;
     if (c - '0' < 10u) return c - '0' + 52u;
@@ -74,12 +70,12 @@ struct B64 {
     const uint8_t *p;
     uint32_t chars, bytes;  // bytes = floor(6 chars / 8)
 };
-PWAF_CK_HD uint32_t b64_byte(const B64 &s, uint32_t j) {  // j < s.bytes, s checked by b64_open
+PWAF_SVC_HD uint32_t b64_byte(const B64 &s, uint32_t j) {  // j < s.bytes, s checked by b64_open
     const uint32_t bit = 8u * j, at = bit / 6u, r = bit % 6u;
     return ((b64_val(s.p[at]) << 6 | b64_val(s.p[at + 1])) >> (4u - r)) & 0xFFu;
 }
 // false: not base64url without padding (a foreign byte, a length of 1 mod 4, non-zero trailing bits)
-PWAF_CK_HD bool b64_open(const uint8_t *p, uint32_t chars, B64 *out) {
+PWAF_SVC_HD bool b64_open(const uint8_t *p, uint32_t chars, B64 *out) {
     if ((chars & 3u) == 1u) return false;
     uint32_t last = 0;
     for (uint32_t i = 0; i < chars; i++) {
@@ -92,7 +88,7 @@ PWAF_CK_HD bool b64_open(const uint8_t *p, uint32_t chars, B64 *out) {
     return true;
 }
 // the signature part: exactly 64 bytes (86 characters, the last with four zero bits) -> R and S as 8 little-endian words each
-PWAF_CK_HD bool decode_signature(const uint8_t *p, uint32_t chars, uint32_t r[8], uint32_t s[8]) {
+PWAF_SVC_HD bool decode_signature(const uint8_t *p, uint32_t chars, uint32_t r[8], uint32_t s[8]) {
     if (chars != kSigChars) return false;
     uint32_t w[16] = {0}, bad = 0;
     PWAF_CK_UNROLL
@@ -118,11 +114,11 @@ PWAF_CK_HD bool decode_signature(const uint8_t *p, uint32_t chars, uint32_t r[8]
 // ---- the Cookie header (http_listener.rs:169-181; cookie 0.18 Cookie::split_parse behind HeaderValue::to_str) -----------------------------
 struct Token {  // where the token's parts lie in the cookie value
     uint32_t at, hdr_len, claims_len;  // header at [at, at + hdr_len), '.', claims, '.', the 86 signature characters
-    PWAF_CK_HD uint32_t signed_len() const { return hdr_len + 1u + claims_len; }
+    PWAF_SVC_HD uint32_t signed_len() const { return hdr_len + 1u + claims_len; }
 };
-PWAF_CK_HD bool is_blank(uint32_t b) { return b == ' ' || b == '\t'; }
+PWAF_SVC_HD bool is_blank(uint32_t b) { return b == ' ' || b == '\t'; }
 // PWAF_COOKIE_ABSENT, PWAF_COOKIE_INVALID or kCandidate with *t, for the first cookie named exactly kName[0 .. kNameLen)
-PWAF_CK_HD uint8_t locate_named(const uint8_t *v, uint32_t len, Token *t, const char *kName, const uint32_t kNameLen) {
+PWAF_SVC_HD uint8_t locate_named(const uint8_t *v, uint32_t len, Token *t, const char *kName, const uint32_t kNameLen) {
     bool bad = false, found = false, in_value = false;
     uint32_t name0 = 0, name1 = 0, val0 = 0, val1 = 0, tok0 = 0, tok1 = 0;  // [first, last + 1) of the bytes that are not blank; 0, 0: none
     for (uint32_t q0 = 0; q0 <= len; q0 += 16) {  // (q == len closes the last segment)
@@ -170,7 +166,7 @@ PWAF_CK_HD uint8_t locate_named(const uint8_t *v, uint32_t len, Token *t, const 
     t->at = tok0, t->hdr_len = dot0 - tok0, t->claims_len = dot1 - dot0 - 1u;
     return kCandidate;
 }
-PWAF_CK_HD uint8_t locate(const uint8_t *v, uint32_t len, Token *t) {
+PWAF_SVC_HD uint8_t locate(const uint8_t *v, uint32_t len, Token *t) {
     const char kName[] = "__pingoo_captcha_verified";
     return locate_named(v, len, t, kName, sizeof kName - 1);
 }
@@ -191,10 +187,10 @@ PWAF_CK_CONST uint64_t kSha512K[80] = {
     0xeada7dd6cde0eb1eull, 0xf57d4f7fee6ed178ull, 0x06f067aa72176fbaull, 0x0a637dc5a2c898a6ull, 0x113f9804bef90daeull, 0x1b710b35131c471bull,
     0x28db77f523047d84ull, 0x32caab7b40c72493ull, 0x3c9ebe0a15c9bebcull, 0x431d67c49c100d4cull, 0x4cc5d4becb3e42b6ull, 0x597f299cfc657e2aull,
     0x5fcb6fab3ad6faecull, 0x6c44198c4a475817ull};
-PWAF_CK_HD uint64_t rotr64(uint64_t x, uint32_t n) { return (x >> n) | (x << (64u - n)); }
+PWAF_SVC_HD uint64_t rotr64(uint64_t x, uint32_t n) { return (x >> n) | (x << (64u - n)); }
 // state += compress(state, w); the rounds in five runs of 16 over a rolling window: w[] keeps literal indices, the round constant is
 // read at a wave-uniform index
-PWAF_CK_HD void sha512_compress(uint64_t st[8], uint64_t w[16]) {
+PWAF_SVC_HD void sha512_compress(uint64_t st[8], uint64_t w[16]) {
     uint64_t a = st[0], b = st[1], c = st[2], d = st[3], e = st[4], f = st[5], g = st[6], h = st[7];
     for (uint32_t t0 = 0; t0 < 80; t0 += 16) {
         PWAF_CK_UNROLL
@@ -212,7 +208,7 @@ PWAF_CK_HD void sha512_compress(uint64_t st[8], uint64_t w[16]) {
 }
 // The 8 bytes of the padded message at message offset q (a multiple of 8), big-endian. The signed message of a token is FOLLOWED in its
 // cookie value by '.' and the 86 signature characters, so the 8-byte load at q <= len stays inside the value, on the host too.
-PWAF_CK_HD uint64_t message_word(const uint8_t *m, uint32_t len, uint32_t q) {
+PWAF_SVC_HD uint64_t message_word(const uint8_t *m, uint32_t len, uint32_t q) {
     if (q > len) return 0;
     uint64_t x;
     memcpy(&x, m + q, 8);
@@ -222,9 +218,9 @@ PWAF_CK_HD uint64_t message_word(const uint8_t *m, uint32_t len, uint32_t q) {
     x = keep ? x & (~0ull << (8u * (8u - keep))) : 0;
     return x | 0x80ull << (8u * (7u - keep));
 }
-PWAF_CK_HD uint64_t be_pair(uint32_t lo_word, uint32_t hi_word) { return (uint64_t)__builtin_bswap32(lo_word) << 32 | __builtin_bswap32(hi_word); }
+PWAF_SVC_HD uint64_t be_pair(uint32_t lo_word, uint32_t hi_word) { return (uint64_t)__builtin_bswap32(lo_word) << 32 | __builtin_bswap32(hi_word); }
 // SHA-512(R || A || m) as the 16 little-endian words of the digest read as one integer (RFC 8032 §5.1.7 step 2)
-PWAF_CK_HD void hash_ram(const uint32_t r[8], const uint32_t a[8], const uint8_t *m, uint32_t len, uint32_t out[16]) {
+PWAF_SVC_HD void hash_ram(const uint32_t r[8], const uint32_t a[8], const uint8_t *m, uint32_t len, uint32_t out[16]) {
     uint64_t st[8] = {0x6a09e667f3bcc908ull, 0xbb67ae8584caa73bull, 0x3c6ef372fe94f82bull, 0xa54ff53a5f1d36f1ull,
                       0x510e527fade682d1ull, 0x9b05688c2b3e6c1full, 0x1f83d9abfb41bd6bull, 0x5be0cd19137e2179ull};
     const uint32_t blocks = (64u + len + 17u + 127u) >> 7;  // the 0x80 byte and the 16-byte length ride in the last one
@@ -254,7 +250,7 @@ struct fe {
     uint32_t v[10];
 };
 static constexpr uint32_t kM26 = 0x3FFFFFFu, kM25 = 0x1FFFFFFu;
-PWAF_CK_HD void fe_carry(fe &h) {  // limbs below 2^31
+PWAF_SVC_HD void fe_carry(fe &h) {  // limbs below 2^31
     PWAF_CK_UNROLL
     for (uint32_t i = 0; i < 9; i++) {
         const uint32_t bits = (i & 1u) ? 25u : 26u;
@@ -266,18 +262,18 @@ PWAF_CK_HD void fe_carry(fe &h) {  // limbs below 2^31
     h.v[1] += h.v[0] >> 26;
     h.v[0] &= kM26;
 }
-PWAF_CK_HD fe fe_small(uint32_t x) {
+PWAF_SVC_HD fe fe_small(uint32_t x) {
     fe h = {{x, 0, 0, 0, 0, 0, 0, 0, 0, 0}};
     return h;
 }
-PWAF_CK_HD fe fe_add(const fe &f, const fe &g) {
+PWAF_SVC_HD fe fe_add(const fe &f, const fe &g) {
     fe h;
     PWAF_CK_UNROLL
     for (uint32_t i = 0; i < 10; i++) h.v[i] = f.v[i] + g.v[i];
     fe_carry(h);
     return h;
 }
-PWAF_CK_HD fe fe_sub(const fe &f, const fe &g) {  // f + 2p - g
+PWAF_SVC_HD fe fe_sub(const fe &f, const fe &g) {  // f + 2p - g
     fe h;
     PWAF_CK_UNROLL
     for (uint32_t i = 0; i < 10; i++) h.v[i] = f.v[i] + (i == 0 ? 0x7FFFFDAu : (i & 1u) ? 0x3FFFFFEu : 0x7FFFFFEu) - g.v[i];
@@ -285,7 +281,7 @@ PWAF_CK_HD fe fe_sub(const fe &f, const fe &g) {  // f + 2p - g
     return h;
 }
 // the term f_i g_j belongs to limb i + j: twice when both i and j are odd (their weights round up), 19 times when i + j >= 10 (2^255 = 19)
-PWAF_CK_HD fe fe_mul(const fe &f, const fe &g) {
+PWAF_SVC_HD fe fe_mul(const fe &f, const fe &g) {
     uint32_t g19[10], f2[10];
     PWAF_CK_UNROLL
     for (uint32_t i = 0; i < 10; i++) g19[i] = 19u * g.v[i], f2[i] = (i & 1u) ? 2u * f.v[i] : f.v[i];
@@ -313,13 +309,13 @@ PWAF_CK_HD fe fe_mul(const fe &f, const fe &g) {
     for (uint32_t i = 0; i < 10; i++) h.v[i] = (uint32_t)t[i];
     return h;
 }
-PWAF_CK_HD fe fe_sq(const fe &f) { return fe_mul(f, f); }
-PWAF_CK_HD fe fe_sq_times(fe f, uint32_t n) {
+PWAF_SVC_HD fe fe_sq(const fe &f) { return fe_mul(f, f); }
+PWAF_SVC_HD fe fe_sq_times(fe f, uint32_t n) {
     for (uint32_t i = 0; i < n; i++) f = fe_sq(f);
     return f;
 }
 // z^(2^250 - 1) and z^11: the common part of the inversion (z^(p - 2)) and of the square root's z^((p - 5) / 8)
-PWAF_CK_HD fe fe_pow_250(const fe &z, fe *z11) {
+PWAF_SVC_HD fe fe_pow_250(const fe &z, fe *z11) {
     const fe z2 = fe_sq(z), z9 = fe_mul(fe_sq_times(z2, 2), z);
     *z11 = fe_mul(z9, z2);
     const fe z5_0 = fe_mul(fe_sq(*z11), z9);  // z^(2^5 - 1)
@@ -331,13 +327,13 @@ PWAF_CK_HD fe fe_pow_250(const fe &z, fe *z11) {
     const fe z200_0 = fe_mul(fe_sq_times(z100_0, 100), z100_0);
     return fe_mul(fe_sq_times(z200_0, 50), z50_0);
 }
-PWAF_CK_HD fe fe_invert(const fe &z) {  // z^(2^255 - 21)
+PWAF_SVC_HD fe fe_invert(const fe &z) {  // z^(2^255 - 21)
     fe z11;
     const fe z250_0 = fe_pow_250(z, &z11);
     return fe_mul(fe_sq_times(z250_0, 5), z11);
 }
 // the canonical value (below p) as 8 little-endian words, bit 255 clear
-PWAF_CK_HD void fe_words(fe h, uint32_t out[8]) {
+PWAF_SVC_HD void fe_words(fe h, uint32_t out[8]) {
     fe_carry(h);
     fe_carry(h);  // the value is now below 2^255 + 2^8
     uint32_t q = (h.v[0] + 19u) >> 26;
@@ -362,7 +358,7 @@ PWAF_CK_HD void fe_words(fe h, uint32_t out[8]) {
     PWAF_CK_UNROLL
     for (uint32_t i = 0; i < 8; i++) out[i] = (uint32_t)acc[i];
 }
-PWAF_CK_HD fe fe_from_words(const uint32_t w[8]) {  // bit 255 is ignored
+PWAF_SVC_HD fe fe_from_words(const uint32_t w[8]) {  // bit 255 is ignored
     fe h;
     PWAF_CK_UNROLL
     for (uint32_t i = 0; i < 10; i++) {
@@ -380,9 +376,9 @@ struct Point {
 struct Precomp {  // an affine point as the addition wants it: 120 bytes
     uint32_t ypx[10], ymx[10], t2d[10];  // y + x, y - x, 2 d x y; {1, 1, 0} is the neutral element
 };
-PWAF_CK_HD Point point_neutral() { return Point{fe_small(0), fe_small(1), fe_small(1), fe_small(0)}; }
+PWAF_SVC_HD Point point_neutral() { return Point{fe_small(0), fe_small(1), fe_small(1), fe_small(0)}; }
 // RFC 8032 §5.1.4, doubling; T of the result only where the next step is an addition
-PWAF_CK_HD Point point_double(const Point &p, bool want_t) {
+PWAF_SVC_HD Point point_double(const Point &p, bool want_t) {
     const fe a = fe_sq(p.x), b = fe_sq(p.y), zz = fe_sq(p.z), c = fe_add(zz, zz), h = fe_add(a, b);
     const fe e = fe_sub(h, fe_sq(fe_add(p.x, p.y))), g = fe_sub(a, b), f = fe_add(c, g);
     Point r;
@@ -391,7 +387,7 @@ PWAF_CK_HD Point point_double(const Point &p, bool want_t) {
     return r;
 }
 // RFC 8032 §5.1.4, addition, with Z2 = 1 and the second point's y - x, y + x and 2 d T2 ready; entry `digit` (0..15) of a 16-entry table
-PWAF_CK_HD Point point_add_table(const Point &p, const Precomp *table, uint32_t digit) {
+PWAF_SVC_HD Point point_add_table(const Point &p, const Precomp *table, uint32_t digit) {
     const uint32_t *w = table[digit].ypx;  // 30 words
     fe ypx, ymx, t2d;
     PWAF_CK_UNROLL
@@ -401,7 +397,7 @@ PWAF_CK_HD Point point_add_table(const Point &p, const Precomp *table, uint32_t 
     return Point{fe_mul(e, f), fe_mul(g, h), fe_mul(f, g), fe_mul(e, h)};
 }
 // the encoding of a point (RFC 8032 §5.1.2) as 8 little-endian words
-PWAF_CK_HD void point_encode(const Point &p, uint32_t out[8]) {
+PWAF_SVC_HD void point_encode(const Point &p, uint32_t out[8]) {
     const fe zi = fe_invert(p.z);
     uint32_t xw[8];
     fe_words(fe_mul(p.x, zi), xw);
@@ -411,7 +407,7 @@ PWAF_CK_HD void point_encode(const Point &p, uint32_t out[8]) {
 
 // ---- scalars: mod L = 2^252 + c (RFC 8032 §5.1) ------------------------------------------------------------------------------------------------
 template <int NA, int NB>
-PWAF_CK_HD void words_mul(const uint32_t (&a)[NA], const uint32_t (&b)[NB], uint32_t (&out)[NA + NB]) {
+PWAF_SVC_HD void words_mul(const uint32_t (&a)[NA], const uint32_t (&b)[NB], uint32_t (&out)[NA + NB]) {
     PWAF_CK_UNROLL
     for (int i = 0; i < NA + NB; i++) out[i] = 0;
     PWAF_CK_UNROLL
@@ -428,14 +424,14 @@ PWAF_CK_HD void words_mul(const uint32_t (&a)[NA], const uint32_t (&b)[NB], uint
 }
 // the low 252 bits of x (8 words) and x >> 252 (NH words), x having NX words
 template <int NX, int NH>
-PWAF_CK_HD void words_split252(const uint32_t (&x)[NX], uint32_t (&lo)[8], uint32_t (&hi)[NH]) {
+PWAF_SVC_HD void words_split252(const uint32_t (&x)[NX], uint32_t (&lo)[8], uint32_t (&hi)[NH]) {
     PWAF_CK_UNROLL
     for (int i = 0; i < 8; i++) lo[i] = i < NX ? x[i] : 0u;
     lo[7] &= 0x0FFFFFFFu;
     PWAF_CK_UNROLL
     for (int i = 0; i < NH; i++) hi[i] = (7 + i < NX ? x[7 + i] >> 28 : 0u) | (8 + i < NX ? x[8 + i] << 4 : 0u);
 }
-PWAF_CK_HD bool words_less(const uint32_t a[8], const uint32_t b[8]) {  // a < b
+PWAF_SVC_HD bool words_less(const uint32_t a[8], const uint32_t b[8]) {  // a < b
     bool less = false, decided = false;
     PWAF_CK_UNROLL
     for (int i = 7; i >= 0; i--) {
@@ -443,13 +439,13 @@ PWAF_CK_HD bool words_less(const uint32_t a[8], const uint32_t b[8]) {  // a < b
     }
     return less;
 }
-PWAF_CK_HD void order_words(uint32_t l[8]) {
+PWAF_SVC_HD void order_words(uint32_t l[8]) {
     l[0] = 0x5CF5D3EDu, l[1] = 0x5812631Au, l[2] = 0xA2F79CD6u, l[3] = 0x14DEF9DEu, l[4] = l[5] = l[6] = 0, l[7] = 0x10000000u;
 }
 // x mod L for a 512-bit x. With x = lo + 2^252 hi and 2^252 = -c (mod L):  x = lo - c hi;  c hi = ylo + 2^252 yhi = ylo - c yhi;
 // c yhi = zlo + 2^252 zhi = zlo - c zhi. So x = lo + zlo - ylo - c zhi, each term below 2^252 (c zhi below 2^131): plus 2 L it is
 // positive and below 4 L, and at most three subtractions of L finish it. No negative number occurs.
-PWAF_CK_HD void scalar_reduce(const uint32_t x[16], uint32_t out[8]) {
+PWAF_SVC_HD void scalar_reduce(const uint32_t x[16], uint32_t out[8]) {
     const uint32_t c[4] = {0x5CF5D3EDu, 0x5812631Au, 0xA2F79CD6u, 0x14DEF9DEu};
     uint32_t xx[16], lo[8], hi[9], y[13], ylo[8], yhi[5], z[9], zlo[8], zhi[1], w[5], l[8];
     PWAF_CK_UNROLL
@@ -506,7 +502,7 @@ struct KeySetData {  // what the verifier reads: one block, in host memory and (
 
 // RFC 8032 §5.1.7 as aws-lc's ED25519_verify does it: S below L; k = SHA-512(R || A || m) mod L; [S]B + [k](-A) encoded and compared byte for
 // byte with R, which is never decompressed. `base`: the 16 multiples of B (the kernel's copy in LDS, or data.base).
-PWAF_CK_HD bool signature_ok(const Precomp *base, const KeyEntry &key, const uint32_t r[8], const uint32_t s_in[8], const uint8_t *m, uint32_t len) {
+PWAF_SVC_HD bool signature_ok(const Precomp *base, const KeyEntry &key, const uint32_t r[8], const uint32_t s_in[8], const uint8_t *m, uint32_t len) {
     uint32_t l[8], s[8], k[8], digest[16];
     order_words(l);
     if (!words_less(s_in, l)) return false;
@@ -546,19 +542,19 @@ struct Names {
     const char *name[kMaxNames];
     uint32_t n;
 };
-PWAF_CK_HD bool text_is(const B64 &s, uint32_t at, uint32_t len, const char *lit) {
+PWAF_SVC_HD bool text_is(const B64 &s, uint32_t at, uint32_t len, const char *lit) {
     uint32_t i = 0;
     for (; i < len && lit[i]; i++)
         if (b64_byte(s, at + i) != (uint8_t)lit[i]) return false;
     return i == len && !lit[i];
 }
-PWAF_CK_HD bool is_json_space(uint32_t b) { return b == ' ' || b == '\t' || b == '\n' || b == '\r'; }
+PWAF_SVC_HD bool is_json_space(uint32_t b) { return b == ' ' || b == '\t' || b == '\n' || b == '\r'; }
 // false: outside the subset (or a known name twice). out[k] is the value of names.name[k]; unknown names are skipped.
 // kNulEscape (the claims of pwaf_verify_pow only): inside a string VALUE the six bytes \u0000 are read as one byte 0x00;
 // the value's [at, at + len) stays the text as it stands, and whoever reads it skips six bytes at a backslash (escape_aware_byte). Every
 // other backslash, and every backslash in a name, stays outside the subset.
 template <bool kNulEscape>
-PWAF_CK_HD bool parse_flat_as(const B64 &s, const Names &names, Value out[kMaxNames]) {
+PWAF_SVC_HD bool parse_flat_as(const B64 &s, const Names &names, Value out[kMaxNames]) {
     PWAF_CK_UNROLL
     for (uint32_t k = 0; k < kMaxNames; k++) out[k] = Value{kAbsent, 0, 0, 0};
     const uint32_t n = s.bytes;
@@ -658,18 +654,18 @@ PWAF_CK_HD bool parse_flat_as(const B64 &s, const Names &names, Value out[kMaxNa
 #undef PWAF_CK_STRING
 #undef PWAF_CK_SKIP_SPACE
 }
-PWAF_CK_HD bool parse_flat(const B64 &s, const Names &names, Value out[kMaxNames]) { return parse_flat_as<false>(s, names, out); }
+PWAF_SVC_HD bool parse_flat(const B64 &s, const Names &names, Value out[kMaxNames]) { return parse_flat_as<false>(s, names, out); }
 // the next byte of a string value that parse_flat_as<true> accepted, *q moving over it: a backslash there begins \u0000
-PWAF_CK_HD uint32_t escape_aware_byte(const B64 &s, uint32_t *q) {
+PWAF_SVC_HD uint32_t escape_aware_byte(const B64 &s, uint32_t *q) {
     const uint32_t b = b64_byte(s, *q);
     *q += b == '\\' ? 6u : 1u;
     return b == '\\' ? 0u : b;
 }
-PWAF_CK_HD bool string_or_absent(const Value &v) { return v.kind == kAbsent || v.kind == kString; }
+PWAF_SVC_HD bool string_or_absent(const Value &v) { return v.kind == kAbsent || v.kind == kString; }
 
 // ---- the decision (captcha.rs:125-156; jwt.rs:213-327) ---------------------------------------------------------------------------------------
 // The header (jwt.rs:36-85): false = the device does not parse it. *key = the key its kid names (kMaxKeys: none), *alg_typ_ok
-PWAF_CK_HD bool read_header(const KeySetData &ks, const uint8_t *p, uint32_t chars, uint32_t *key, bool *alg_typ_ok) {
+PWAF_SVC_HD bool read_header(const KeySetData &ks, const uint8_t *p, uint32_t chars, uint32_t *key, bool *alg_typ_ok) {
     B64 s;
     if (!b64_open(p, chars, &s)) return false;
     const Names names = {{"typ", "alg", "kid", "cty", "jku", "x5u", "x5t", "x5t#S256", "x5c"}, 9};
@@ -693,7 +689,7 @@ PWAF_CK_HD bool read_header(const KeySetData &ks, const uint8_t *p, uint32_t cha
     return true;
 }
 // The claims (captcha.rs:70-75, jwt.rs:89-124) behind a verified signature: VERIFIED, INVALID, or UNDECIDED where the device does not parse them
-PWAF_CK_HD uint8_t judge_claims(const uint8_t *p, uint32_t chars, int64_t now, const uint32_t id[clientid::kIdWords]) {
+PWAF_SVC_HD uint8_t judge_claims(const uint8_t *p, uint32_t chars, int64_t now, const uint32_t id[clientid::kIdWords]) {
     B64 s;
     if (!b64_open(p, chars, &s)) return PWAF_COOKIE_UNDECIDED;
     const Names names = {{"challenge_passed", "iss", "sub", "aud", "exp", "nbf", "iat", "jti", ""}, 8};
@@ -721,7 +717,7 @@ PWAF_CK_HD uint8_t judge_claims(const uint8_t *p, uint32_t chars, int64_t now, c
     return diff ? PWAF_COOKIE_INVALID : PWAF_COOKIE_VERIFIED;
 }
 // A located token of a request whose client id is id[]: the answer to gate C. `v` is the cookie value.
-PWAF_CK_HD uint8_t judge(const KeySetData &ks, const Precomp *base, const uint8_t *v, const Token &t, int64_t now, const uint32_t id[clientid::kIdWords]) {
+PWAF_SVC_HD uint8_t judge(const KeySetData &ks, const Precomp *base, const uint8_t *v, const Token &t, int64_t now, const uint32_t id[clientid::kIdWords]) {
     const uint8_t *m = v + t.at;
     const uint32_t len = t.signed_len();
     uint32_t r[8], s[8], key = kMaxKeys;
@@ -755,15 +751,10 @@ struct Args {
     uint32_t *count;              // DEVICE mode: the candidates' number (zeroed in front of the launches) and the list
     Candidate *cand;
 };
-PWAF_CK_HD uint32_t selected(const Args &a) {
-    if (!a.idx) return a.n;
-    if (!a.n_idx) return a.idx_cap;
-    const uint32_t k = *a.n_idx;
-    return k < a.idx_cap ? k : a.idx_cap;
-}
-PWAF_CK_HD uint32_t request_of(const Args &a, uint32_t e) { return a.idx ? a.idx[e] : e; }
+PWAF_SVC_HD uint32_t selected(const Args &a) { return pwaf::selected(a.idx, a.n_idx, a.idx_cap, a.n); }
+PWAF_SVC_HD uint32_t request_of(const Args &a, uint32_t e) { return pwaf::request_of(a.idx, e); }
 // entry e's first step: ABSENT / INVALID, or kCandidate with *c
-PWAF_CK_HD uint8_t locate_entry(const Args &a, uint32_t e, Candidate *c) {
+PWAF_SVC_HD uint8_t locate_entry(const Args &a, uint32_t e, Candidate *c) {
     const uint32_t i = request_of(a, e);
     if (i >= a.n) return PWAF_COOKIE_ABSENT;
     const uint32_t c0 = a.cookies.offsets[i];
@@ -772,14 +763,14 @@ PWAF_CK_HD uint8_t locate_entry(const Args &a, uint32_t e, Candidate *c) {
     *c = Candidate{e, t.at, t.hdr_len, t.claims_len};
     return st;
 }
-PWAF_CK_HD uint8_t judge_candidate(const Args &a, const Precomp *base, const Candidate &c) {
+PWAF_SVC_HD uint8_t judge_candidate(const Args &a, const Precomp *base, const Candidate &c) {
     const uint32_t i = request_of(a, c.entry);
     const uint32_t u0 = a.ua.offsets[i], h0 = a.host.offsets[i];
     uint32_t id[clientid::kIdWords];
     clientid::client_id_words(clientid::make_message(a.ip + (size_t)i * 16, a.ip_is_v6[i], a.ua.data + u0, a.ua.offsets[i + 1] - u0, a.host.data + h0, a.host.offsets[i + 1] - h0), id);
     return judge(*a.ks, base, a.cookies.data + a.cookies.offsets[i], Token{c.at, c.hdr_len, c.claims_len}, a.now, id);
 }
-PWAF_CK_HD uint8_t flag_of(const Args &a, uint32_t i, uint8_t status) {
+PWAF_SVC_HD uint8_t flag_of(const Args &a, uint32_t i, uint8_t status) {
     const uint8_t f = a.flags ? a.flags[i] : 0;
     return status == PWAF_COOKIE_VERIFIED ? f | PWAF_FLAG_CAPTCHA_VERIFIED : f & (uint8_t)~PWAF_FLAG_CAPTCHA_VERIFIED;
 }

@@ -88,7 +88,6 @@ int launch_verify_cookies(const Args &a, void *stream) {
 
 }  // namespace cookie
 
-int fail(int code, const std::string &msg);  // program_api.cpp: records pwaf_last_error()
 }  // namespace pwaf
 
 extern "C" int pwaf_keyset_create(const pwaf_ed25519_key *keys, uint32_t n, int device, pwaf_keyset **out) {
@@ -148,13 +147,11 @@ extern "C" int pwaf_verify_cookies(const pwaf_keyset *ks, const pwaf_batch *in, 
     namespace K = pwaf::cookie;
     using pwaf::fail;
     if (!ks || !in || !cookies || !status) return fail(PWAF_E_INVALID_ARG, "pwaf_verify_cookies: NULL argument");
-    if (in->struct_size != sizeof(pwaf_batch)) return fail(PWAF_E_INVALID_ARG, "pwaf_batch.struct_size mismatch");
-    if (in->memory != PWAF_MEM_HOST && in->memory != PWAF_MEM_DEVICE) return fail(PWAF_E_INVALID_ARG, "pwaf_batch.memory is neither HOST nor DEVICE");
-    if (!idx && (idx_cap || n_idx)) return fail(PWAF_E_INVALID_ARG, "pwaf_verify_cookies: idx is NULL with idx_cap != 0 or a non-NULL n_idx");
+    if (int rc = pwaf::check_batch_header(in)) return rc;
+    if (int rc = pwaf::check_list("pwaf_verify_cookies", idx, idx_cap, n_idx)) return rc;
     const pwaf_strcol &ua = in->field[PWAF_FIELD_USER_AGENT], &host = in->field[PWAF_FIELD_HOST];
+    if (int rc = pwaf::check_client_columns(in)) return rc;
     if (in->n) {
-        if (!in->ip || !in->ip_is_v6) return fail(PWAF_E_INVALID_ARG, "pwaf_batch.ip or ip_is_v6 is NULL");
-        if (!ua.data || !ua.offsets || !host.data || !host.offsets) return fail(PWAF_E_INVALID_ARG, "pwaf_batch User-Agent or host column is NULL");
         if (!cookies->data || !cookies->offsets) return fail(PWAF_E_INVALID_ARG, "pwaf_verify_cookies: the cookies column is NULL");
     }
     K::Args a{};
@@ -169,8 +166,7 @@ extern "C" int pwaf_verify_cookies(const pwaf_keyset *ks, const pwaf_batch *in, 
     }
     if (!ks->dev) return fail(PWAF_E_DEVICE, "pwaf_verify_cookies: the key set was created for the host only (device < 0)");
     const uint32_t cap = idx ? idx_cap : in->n;
-    if (!scratch || ((uintptr_t)scratch & 15u) || scratch_bytes < pwaf_verify_cookies_scratch_bytes(cap))
-        return fail(PWAF_E_INVALID_ARG, "pwaf_verify_cookies: scratch is NULL, not 16-byte aligned or smaller than pwaf_verify_cookies_scratch_bytes");
+    if (int rc = pwaf::check_scratch("pwaf_verify_cookies", scratch, scratch_bytes, pwaf_verify_cookies_scratch_bytes(cap), "pwaf_verify_cookies_scratch_bytes")) return rc;
     int current = -1;
     if (hipGetDevice(&current) != hipSuccess || current != ks->device) return fail(PWAF_E_DEVICE, "pwaf_verify_cookies: the current device is not the key set's");
     a.ks = ks->dev;

@@ -25,12 +25,7 @@
 #include <string.h>
 
 #include "pwaf.h"
-
-#if defined(__HIPCC__) || defined(__HIP__)
-#define PWAF_DRV_HD __host__ __device__ inline
-#else
-#define PWAF_DRV_HD inline
-#endif
+#include "service.h"
 
 namespace pwaf {
 namespace derive {
@@ -48,7 +43,7 @@ struct Chunk {
     uint64_t lo, hi;  // byte k of the chunk in bits [8k, 8k + 8) of lo (k < 8) / of hi
 };
 // The `run` (1..16) bytes at s; what the other bytes of the chunk hold is unspecified (every user masks with run_bits).
-PWAF_DRV_HD Chunk load16(const uint8_t *s, uint32_t run) {
+PWAF_SVC_HD Chunk load16(const uint8_t *s, uint32_t run) {
     Chunk v{0, 0};
 #if defined(__HIP_DEVICE_COMPILE__)
     (void)run;
@@ -58,14 +53,14 @@ PWAF_DRV_HD Chunk load16(const uint8_t *s, uint32_t run) {
 #endif
     return v;
 }
-PWAF_DRV_HD uint32_t run_bits(uint32_t run) { return run >= 16u ? 0xFFFFu : (1u << run) - 1u; }
+PWAF_SVC_HD uint32_t run_bits(uint32_t run) { return run >= 16u ? 0xFFFFu : (1u << run) - 1u; }
 
 // SWAR byte tests over 8 bytes: 0x80 in every byte of the result for which the test holds, exactly (no carry crosses a byte).
 static constexpr uint64_t kOnes = 0x0101010101010101ull, kLow7 = 0x7F7F7F7F7F7F7F7Full, kHigh = 0x8080808080808080ull;
-PWAF_DRV_HD uint64_t zero_bytes(uint64_t v) { return ~(((v & kLow7) + kLow7) | v | kLow7); }
-PWAF_DRV_HD uint64_t eq_bytes(uint64_t v, uint8_t c) { return zero_bytes(v ^ (kOnes * c)); }
+PWAF_SVC_HD uint64_t zero_bytes(uint64_t v) { return ~(((v & kLow7) + kLow7) | v | kLow7); }
+PWAF_SVC_HD uint64_t eq_bytes(uint64_t v, uint8_t c) { return zero_bytes(v ^ (kOnes * c)); }
 // the 0x80 bits of 8 bytes -> 8 bits, byte k -> bit k (the products' bits are all distinct: nothing carries)
-PWAF_DRV_HD uint32_t gather_bits(uint64_t m) { return (uint32_t)(((m & kHigh) >> 7) * 0x0102040810204080ull >> 56); }
+PWAF_SVC_HD uint32_t gather_bits(uint64_t m) { return (uint32_t)(((m & kHigh) >> 7) * 0x0102040810204080ull >> 56); }
 
 enum ByteClass : uint32_t {
     kSlash,     // '/'
@@ -73,7 +68,7 @@ enum ByteClass : uint32_t {
     kSpace,     // str::trim on uri.host(): char::is_whitespace below 0x80 is 0x09..0x0D and 0x20
     kNotText,   // HeaderValue::to_str refuses it: neither TAB nor 0x20..0x7E
 };
-PWAF_DRV_HD uint64_t class_bytes(uint64_t v, uint32_t cls) {
+PWAF_SVC_HD uint64_t class_bytes(uint64_t v, uint32_t cls) {
     const uint64_t blank = eq_bytes(v, 0x20) | eq_bytes(v, 0x09);
     if (cls == kSlash) return eq_bytes(v, '/');
     if (cls == kBlank) return blank;
@@ -82,17 +77,17 @@ PWAF_DRV_HD uint64_t class_bytes(uint64_t v, uint32_t cls) {
     return (zero_bytes(v & (kOnes * 0xE0u)) & ~eq_bytes(v, 0x09)) | eq_bytes(v, 0x7F) | (v & kHigh);
 }
 // bit k: byte k of the chunk is of the class
-PWAF_DRV_HD uint32_t class_bits(const Chunk &v, uint32_t cls) { return gather_bits(class_bytes(v.lo, cls)) | gather_bits(class_bytes(v.hi, cls)) << 8; }
+PWAF_SVC_HD uint32_t class_bits(const Chunk &v, uint32_t cls) { return gather_bits(class_bytes(v.lo, cls)) | gather_bits(class_bytes(v.hi, cls)) << 8; }
 
-PWAF_DRV_HD uint32_t lowest_bit(uint32_t x) { return (uint32_t)__builtin_ctz(x); }   // x != 0
-PWAF_DRV_HD uint32_t highest_bit(uint32_t x) { return 31u - (uint32_t)__builtin_clz(x); }  // x != 0
+PWAF_SVC_HD uint32_t lowest_bit(uint32_t x) { return (uint32_t)__builtin_ctz(x); }   // x != 0
+PWAF_SVC_HD uint32_t highest_bit(uint32_t x) { return 31u - (uint32_t)__builtin_clz(x); }  // x != 0
 
 // ---- the kept slice of one value -----------------------------------------------------------------------------------------------------
 struct Span {
     uint32_t start, len;  // bytes [start, start + len) of the raw value; start is 0 when len is
 };
 // [b, e) of s without the bytes of class `cls` at its end / at its beginning
-PWAF_DRV_HD uint32_t trim_end(const uint8_t *s, uint32_t b, uint32_t e, uint32_t cls) {
+PWAF_SVC_HD uint32_t trim_end(const uint8_t *s, uint32_t b, uint32_t e, uint32_t cls) {
     while (e > b) {
         const uint32_t at = e - b >= 16u ? e - 16u : b, run = e - at;  // (never a byte in front of b)
         const uint32_t other = ~class_bits(load16(s + at, run), cls) & run_bits(run);
@@ -101,7 +96,7 @@ PWAF_DRV_HD uint32_t trim_end(const uint8_t *s, uint32_t b, uint32_t e, uint32_t
     }
     return e;
 }
-PWAF_DRV_HD uint32_t trim_begin(const uint8_t *s, uint32_t b, uint32_t e, uint32_t cls) {
+PWAF_SVC_HD uint32_t trim_begin(const uint8_t *s, uint32_t b, uint32_t e, uint32_t cls) {
     while (b < e) {
         const uint32_t run = e - b >= 16u ? 16u : e - b;
         const uint32_t other = ~class_bits(load16(s + b, run), cls) & run_bits(run);
@@ -110,23 +105,23 @@ PWAF_DRV_HD uint32_t trim_begin(const uint8_t *s, uint32_t b, uint32_t e, uint32
     }
     return b;
 }
-PWAF_DRV_HD bool any_of(const uint8_t *s, uint32_t b, uint32_t e, uint32_t cls) {
+PWAF_SVC_HD bool any_of(const uint8_t *s, uint32_t b, uint32_t e, uint32_t cls) {
     for (; b < e; b += 16u) {
         const uint32_t run = e - b >= 16u ? 16u : e - b;
         if (class_bits(load16(s + b, run), cls) & run_bits(run)) return true;
     }
     return false;
 }
-PWAF_DRV_HD Span path_span(const uint8_t *s, uint32_t len) { return Span{0, trim_end(s, 0, len, kSlash)}; }
+PWAF_SVC_HD Span path_span(const uint8_t *s, uint32_t len) { return Span{0, trim_end(s, 0, len, kSlash)}; }
 // A header value (Host, User-Agent): "" when a byte is not text, else trimmed of ' ' and TAB, "" when more than 256 bytes remain. A byte
 // that is not text ends both runs, so it is among the kept bytes, and a value with more than 256 of those is "" whatever they are.
-PWAF_DRV_HD Span header_span(const uint8_t *s, uint32_t len) {
+PWAF_SVC_HD Span header_span(const uint8_t *s, uint32_t len) {
     const uint32_t b = trim_begin(s, 0, len, kBlank), e = trim_end(s, b, len, kBlank);
     if (e == b || e - b > kMaxKept || any_of(s, b, e, kNotText)) return Span{0, 0};
     return Span{b, e - b};
 }
 // uri.host(): trimmed of whitespace, "" when more than 256 bytes remain; no byte check (it is a &str already)
-PWAF_DRV_HD Span uri_host_span(const uint8_t *s, uint32_t len) {
+PWAF_SVC_HD Span uri_host_span(const uint8_t *s, uint32_t len) {
     const uint32_t b = trim_begin(s, 0, len, kSpace), e = trim_end(s, b, len, kSpace);
     if (e == b || e - b > kMaxKept) return Span{0, 0};
     return Span{b, e - b};
@@ -149,20 +144,20 @@ struct Args {
 };
 static constexpr uint32_t kDefaultPresent = PWAF_RAW_HAS_HOST_HEADER | PWAF_RAW_HAS_USER_AGENT;
 
-PWAF_DRV_HD uint32_t present_of(const Args &a, uint32_t i) {
+PWAF_SVC_HD uint32_t present_of(const Args &a, uint32_t i) {
     uint32_t p = a.present ? a.present[i] : kDefaultPresent;
     if (!a.uri_host.offsets) p &= ~PWAF_RAW_HAS_URI_HOST;
     return p;
 }
 // which column the host of a request with these present bits is cut from: the URI's host wins, even when it derives to ""
-PWAF_DRV_HD const pwaf_strcol &host_source(const Args &a, uint32_t present) { return (present & PWAF_RAW_HAS_URI_HOST) ? a.uri_host : a.raw[kHost]; }
+PWAF_SVC_HD const pwaf_strcol &host_source(const Args &a, uint32_t present) { return (present & PWAF_RAW_HAS_URI_HOST) ? a.uri_host : a.raw[kHost]; }
 
 // Where the derived value of column c of request i lies: its first byte's position in the source arena, and its length. Lengths in
 // uint32 arithmetic, as every reader of the offsets computes them. The bytes of a value whose present bit is clear are not read.
 struct Kept {
     uint32_t at, len;
 };
-PWAF_DRV_HD Kept kept_of(const Args &a, uint32_t c, uint32_t i, uint32_t present) {
+PWAF_SVC_HD Kept kept_of(const Args &a, uint32_t c, uint32_t i, uint32_t present) {
     if (c == kPath) {
         const uint32_t o = a.raw[kPath].offsets[i];
         return Kept{o, path_span(a.raw[kPath].data + o, a.raw[kPath].offsets[i + 1] - o).len};
@@ -175,21 +170,19 @@ PWAF_DRV_HD Kept kept_of(const Args &a, uint32_t c, uint32_t i, uint32_t present
     return Kept{o + s.start, s.len};
 }
 // the arena the kept bytes of column c are copied from
-PWAF_DRV_HD const uint8_t *source_of(const Args &a, uint32_t c, uint32_t present) { return c == kHost ? host_source(a, present).data : a.raw[c].data; }
+PWAF_SVC_HD const uint8_t *source_of(const Args &a, uint32_t c, uint32_t present) { return c == kHost ? host_source(a, present).data : a.raw[c].data; }
 
 // ---- the scan's arithmetic ---------------------------------------------------------------------------------------------------------------
-PWAF_DRV_HD uint32_t tiles(uint32_t n) { return (uint32_t)(((uint64_t)n + kTile - 1u) / kTile); }
+PWAF_SVC_HD uint32_t tiles(uint32_t n) { return pwaf::tiles(n, kTile); }
 // scratch: the tile array (kColumns x stride 64-bit words, stride = tiles + 1 rounded up to even), then `from` (2 x n words)
-PWAF_DRV_HD uint32_t tile_stride(uint32_t n) { return (tiles(n) + 2u) & ~1u; }
-PWAF_DRV_HD size_t scratch_bytes(uint32_t n) { return ((size_t)kColumns * tile_stride(n) * 8u + (size_t)2u * n * 4u + 15u) & ~(size_t)15u; }
+PWAF_SVC_HD uint32_t tile_stride(uint32_t n) { return pwaf::tile_stride(tiles(n)); }
+PWAF_SVC_HD size_t scratch_bytes(uint32_t n) { return ((size_t)kColumns * tile_stride(n) * 8u + (size_t)2u * n * 4u + 15u) & ~(size_t)15u; }
 inline void scratch_layout(Args &a, void *scratch) {
     a.tile_stride = tile_stride(a.n);
     a.tile = (uint64_t *)scratch;
     a.from = (uint32_t *)(a.tile + (size_t)kColumns * a.tile_stride);
 }
-// the column's bytes were all written and so is its pad
-PWAF_DRV_HD bool fits(uint64_t bytes, uint64_t cap) { return bytes + PWAF_ARENA_PAD <= cap; }
-PWAF_DRV_HD void fill_stats(pwaf_derive_stats *st, const uint64_t total[kColumns], const uint64_t cap[kColumns], uint32_t n) {
+PWAF_SVC_HD void fill_stats(pwaf_derive_stats *st, const uint64_t total[kColumns], const uint64_t cap[kColumns], uint32_t n) {
     uint32_t overflow = 0;
     for (uint32_t c = 0; c < kColumns; c++) {
         st->bytes[c] = total[c];
@@ -197,10 +190,6 @@ PWAF_DRV_HD void fill_stats(pwaf_derive_stats *st, const uint64_t total[kColumns
     }
     st->n = n;
     st->overflow = overflow;
-}
-// the pad: the 16 bytes behind the column's last byte, those that lie below cap
-PWAF_DRV_HD void write_pad_byte(uint8_t *data, uint64_t total, uint64_t cap, uint32_t k) {
-    if (total + k < cap) data[total + k] = 0;
 }
 
 // ---- the three phases as plain loops (tests/derive_host.cpp): what the kernels compute, a tile at a time, in any order of tiles ----------
@@ -241,7 +230,7 @@ inline void copy_tile(const Args &a, uint32_t t) {
         for (uint32_t i = t * kTile; i < end; i++) {
             const uint32_t len = a.off[c][i + 1], p = present_of(a, i);
             const uint32_t from = c == kPath ? a.raw[kPath].offsets[i] : a.from[(size_t)(c == kUserAgent) * a.n + i];
-            if (len && at < a.cap[c]) memcpy(a.data[c] + at, source_of(a, c, p) + from, (size_t)(at + len <= a.cap[c] ? len : a.cap[c] - at));
+            append_clipped(a.data[c], a.cap[c], at, source_of(a, c, p) + from, len);
             at += len;
             a.off[c][i + 1] = (uint32_t)at;
         }
@@ -278,7 +267,7 @@ inline bool derive_host(const Args &a, uint32_t *bad_request, uint32_t *bad_colu
         const uint32_t p = present_of(a, i);
         for (uint32_t c = 0; c < kColumns; c++) {
             const Kept k = kept_of(a, c, i, p);
-            if (k.len && at[c] < a.cap[c]) memcpy(a.data[c] + at[c], source_of(a, c, p) + k.at, (size_t)(at[c] + k.len <= a.cap[c] ? k.len : a.cap[c] - at[c]));
+            append_clipped(a.data[c], a.cap[c], at[c], source_of(a, c, p) + k.at, k.len);
             at[c] += k.len;
             a.off[c][i + 1] = (uint32_t)at[c];
         }

@@ -1,7 +1,9 @@
 // derive.hip — pwaf_derive_batch (include/pwaf.h): the derived host, path and User-Agent columns of a raw batch, with its three kernels for
 // a batch in device memory. csrc/derive.h holds what a request costs (the kept slice of a value), the scan's arithmetic and the HOST mode.
 //
-// Three launches, reduce-then-scan over tiles of kTile requests, as records_scan.hip. No workgroup waits for another: no spin, no
+// Three launches, reduce-then-scan over tiles of kTile requests, as records_scan.hip. The base and the copy kernel keep their own step loop
+// and copy loop, which colscan.h has as scan_tile_bases and copy_wave_range (powbody.hip uses those): written on them the three launches
+// measured 1.1 % slower on the MI355X. No workgroup waits for another: no spin, no
 // look-back, no cooperative launch; what one phase needs of all workgroups of the phase before crosses a launch boundary.
 //   derive_span_kernel  one request per lane: the kept slice of its three values (16-byte loads over the whitespace runs and the trailing
 //                       slashes, then the at most 256 kept bytes of a header value). Reads the raw columns, the URI hosts and the present
@@ -11,14 +13,15 @@
 //   derive_copy_kernel  one workgroup per tile. Per column a wave rescans its 64 lengths from the tile's base, in place, and copies: its
 //                       requests' kept bytes are ONE contiguous range of the output, which the lanes take 16 aligned output bytes at a time.
 //                       A lane finds the request holding its chunk's first byte by a search in the wave's offsets (LDS), gathers the chunk
-//                       from the runs it crosses (one 16-byte load per run at the run's own alignment, cut and shifted into place, as
-//                       pack_records_kernel) and stores it: one aligned 16-byte store when the whole chunk is the wave's and lies below
+//                       from the runs it crosses (one 16-byte load per run at the run's own alignment, cut and shifted into place) and
+//                       stores it: one aligned 16-byte store when the whole chunk is the wave's and lies below
 //                       cap, else byte by byte — a neighbouring wave owns the rest of a boundary chunk. The last tile writes the pads,
 //                       the first offsets[0] and stats. Nothing is stored at or beyond cap.
 #include <hip/hip_runtime.h>
 
 #include <string>
 
+#include "colscan.h"
 #include "derive.h"
 
 namespace pwaf {
@@ -26,27 +29,6 @@ namespace derive {
 namespace {
 
 static_assert(kTile % 64 == 0 && kStep % 64 == 0 && kTile <= 1024 && kStep <= 1024 && kCopyGroup == kTile, "whole waves, one workgroup per tile");
-
-__device__ __forceinline__ uint64_t wave_sum(uint64_t x) {
-    for (uint32_t d = 32; d; d >>= 1) x += __shfl_xor(x, d, 64);
-    return x;
-}
-// inclusive prefix inside the wave
-template <class T>
-__device__ __forceinline__ T wave_scan(T x, uint32_t lane) {
-    for (uint32_t d = 1; d < 64; d <<= 1) {
-        const T y = __shfl_up(x, d, 64);
-        if (lane >= d) x += y;
-    }
-    return x;
-}
-// A wave's LDS instructions execute in program order; this keeps the compiler from reordering them across the point where the lanes
-// exchange roles (see records.hip).
-__device__ __forceinline__ void wave_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
 
 // Phase 1. One workgroup per tile, one request per lane.
 __global__ __launch_bounds__(kTile) void derive_span_kernel(Args a) {
@@ -198,26 +180,17 @@ __global__ __launch_bounds__(kCopyGroup) void derive_copy_kernel(Args a) {
 
 }  // namespace
 
-// The launch's own status (hipLaunchKernel returns it): an earlier error that still sticks to the thread is neither read nor cleared here.
-static int launch(void (*kernel)(Args), uint32_t grid, uint32_t block, const Args &a, hipStream_t s) {
-    Args copy = a;
-    void *args[] = {&copy};
-    return hipLaunchKernel(reinterpret_cast<const void *>(kernel), dim3(grid), dim3(block), args, 0, s) == hipSuccess ? 0 : -1;
-}
-
 int launch_derive(int phase, const Args &a, void *stream) {
     if (a.n > kMaxRequests || a.tile_stride <= tiles(a.n) || !a.tile || !a.from) return -1;
     const hipStream_t s = (hipStream_t)stream;
     const uint32_t nt = tiles(a.n);
-    if (phase == 1) return nt ? launch(derive_span_kernel, nt, kTile, a, s) : 0;
-    if (phase == 2) return launch(derive_base_kernel, kColumns, kStep, a, s);
-    if (phase == 3) return launch(derive_copy_kernel, nt ? nt : 1u, kCopyGroup, a, s);
+    if (phase == 1) return nt ? launch_args(derive_span_kernel, nt, kTile, a, s) : 0;
+    if (phase == 2) return launch_args(derive_base_kernel, kColumns, kStep, a, s);
+    if (phase == 3) return launch_args(derive_copy_kernel, nt ? nt : 1u, kCopyGroup, a, s);
     return -1;
 }
 
 }  // namespace derive
-
-int fail(int code, const std::string &msg);  // program_api.cpp: records pwaf_last_error() (declared per unit, as in records.hip and clientid.hip)
 }  // namespace pwaf
 
 extern "C" size_t pwaf_derive_scratch_bytes(uint32_t n) { return pwaf::derive::scratch_bytes(n); }
@@ -229,8 +202,7 @@ extern "C" int pwaf_derive_batch(const pwaf_batch *raw, const pwaf_raw_columns *
     static const char *const kName[4] = {"host", "path", "User-Agent", "URI host"};
     static const uint32_t kField[D::kColumns] = {PWAF_FIELD_HOST, PWAF_FIELD_PATH, PWAF_FIELD_USER_AGENT};
     if (!raw || !out || !stats) return fail(PWAF_E_INVALID_ARG, "pwaf_derive_batch: NULL argument");
-    if (raw->struct_size != sizeof(pwaf_batch)) return fail(PWAF_E_INVALID_ARG, "pwaf_batch.struct_size mismatch");
-    if (raw->memory != PWAF_MEM_HOST && raw->memory != PWAF_MEM_DEVICE) return fail(PWAF_E_INVALID_ARG, "pwaf_batch.memory is neither HOST nor DEVICE");
+    if (int rc = pwaf::check_batch_header(raw)) return rc;
     if (extra && extra->struct_size != sizeof(pwaf_raw_columns)) return fail(PWAF_E_INVALID_ARG, "pwaf_raw_columns.struct_size mismatch");
     if (raw->n > D::kMaxRequests) return fail(PWAF_E_INVALID_ARG, "pwaf_derive_batch: more than 0xFFFFFFF0 / 256 requests (a derived column could pass 32 bits): split the batch");
     if ((uintptr_t)stats & 7u) return fail(PWAF_E_INVALID_ARG, "pwaf_derive_batch: stats is not 8-byte aligned");
@@ -240,10 +212,7 @@ extern "C" int pwaf_derive_batch(const pwaf_batch *raw, const pwaf_raw_columns *
         const std::string col = std::string("pwaf_derive_batch: ") + kName[c];
         a.raw[c] = raw->field[kField[c]];
         if (a.n && (!a.raw[c].data || !a.raw[c].offsets)) return fail(PWAF_E_INVALID_ARG, col + " column of the raw batch is NULL");
-        if (a.n && !out[c].offsets) return fail(PWAF_E_INVALID_ARG, col + ": out offsets is NULL");
-        if (!out[c].data && out[c].cap) return fail(PWAF_E_INVALID_ARG, col + ": out data is NULL with cap != 0");
-        if ((uintptr_t)out[c].data & 15u) return fail(PWAF_E_INVALID_ARG, col + ": out data is not 16-byte aligned");
-        if ((uintptr_t)out[c].offsets & 3u) return fail(PWAF_E_INVALID_ARG, col + ": out offsets is not 4-byte aligned");
+        if (int rc = pwaf::check_derived_col(col + ": out", a.n, out[c])) return rc;
         a.data[c] = out[c].data, a.off[c] = out[c].offsets, a.cap[c] = out[c].cap;
     }
     if (extra) {
@@ -256,8 +225,7 @@ extern "C" int pwaf_derive_batch(const pwaf_batch *raw, const pwaf_raw_columns *
         if (!D::derive_host(a, &bad, &col)) return fail(PWAF_E_BATCH, "pwaf_derive_batch: request " + std::to_string(bad) + ": offsets decrease in the " + kName[col] + " column");
         return PWAF_OK;
     }
-    if (!scratch || ((uintptr_t)scratch & 15u) || scratch_bytes < D::scratch_bytes(a.n))
-        return fail(PWAF_E_INVALID_ARG, "pwaf_derive_batch: scratch is NULL, not 16-byte aligned or smaller than pwaf_derive_scratch_bytes(n)");
+    if (int rc = pwaf::check_scratch("pwaf_derive_batch", scratch, scratch_bytes, D::scratch_bytes(a.n), "pwaf_derive_scratch_bytes(n)")) return rc;
     static_assert(sizeof(D::Args) <= 4096, "Args travels in the kernel argument block");
     D::scratch_layout(a, scratch);
     for (int phase = 1; phase <= 3; phase++)

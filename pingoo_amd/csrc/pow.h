@@ -32,21 +32,21 @@ static_assert(PWAF_POW_ABSENT == PWAF_COOKIE_ABSENT && PWAF_POW_FAILED == PWAF_C
 
 // ---- the cookie (captcha.rs:247-253) ---------------------------------------------------------------------------------------------------
 // PWAF_POW_ABSENT, PWAF_POW_FAILED or kCandidate with *t
-PWAF_CK_HD uint8_t locate_pow(const uint8_t *v, uint32_t len, Token *t) {
+PWAF_SVC_HD uint8_t locate_pow(const uint8_t *v, uint32_t len, Token *t) {
     const char kName[] = "__pingoo_captcha";
     return cookie::locate_named(v, len, t, kName, sizeof kName - 1);
 }
 
 // ---- the proof of work (captcha.rs:311-333) --------------------------------------------------------------------------------------------
 // hash[32] as 8 big-endian words: word 0 holds the first two hex digits in its top byte
-PWAF_CK_HD void hash_words(const uint8_t *hash, uint32_t hw[8]) {
+PWAF_SVC_HD void hash_words(const uint8_t *hash, uint32_t hw[8]) {
     uint32_t raw[8];
     memcpy(raw, hash, 32);
     PWAF_CK_UNROLL
     for (uint32_t k = 0; k < 8; k++) hw[k] = __builtin_bswap32(raw[k]);
 }
 // the leading '0' characters of the hash's hex form: zero nibbles, the high nibble of byte 0 first
-PWAF_CK_HD uint32_t leading_zero_nibbles(const uint32_t hw[8]) {
+PWAF_SVC_HD uint32_t leading_zero_nibbles(const uint32_t hw[8]) {
     uint32_t zeros = 0;
     bool run = true;
     PWAF_CK_UNROLL
@@ -69,12 +69,12 @@ struct Work {
     const uint8_t *nonce;
     uint32_t nonce_at, nonce_len;
 };
-PWAF_CK_HD uint32_t work_byte(Work &w) {  // called total_bytes times at most
+PWAF_SVC_HD uint32_t work_byte(Work &w) {  // called total_bytes times at most
     if (w.q < w.q_end) return cookie::escape_aware_byte(w.claims, &w.q);
     return w.nonce[w.nonce_at++];
 }
 // SHA-256(challenge || nonce) == hash?  `challenge`: a kString value that parse_flat_as<true> accepted
-PWAF_CK_HD bool work_matches(const B64 &claims, const Value &challenge, const uint8_t *nonce, uint32_t nonce_len, const uint32_t hw[8]) {
+PWAF_SVC_HD bool work_matches(const B64 &claims, const Value &challenge, const uint8_t *nonce, uint32_t nonce_len, const uint32_t hw[8]) {
     uint32_t decoded = 0;
     for (uint32_t q = challenge.at; q < challenge.at + challenge.len; decoded++) (void)cookie::escape_aware_byte(claims, &q);
     Work w{claims, challenge.at, challenge.at + challenge.len, nonce, 0, nonce_len};
@@ -106,7 +106,7 @@ PWAF_CK_HD bool work_matches(const B64 &claims, const Value &challenge, const ui
     return diff == 0;
 }
 // the decoded bytes of a string value are exactly the 44 bytes of the client id (43 characters and the NUL: the reference's string)
-PWAF_CK_HD bool is_client_id(const B64 &claims, const Value &sub, const uint32_t id[clientid::kIdWords]) {
+PWAF_SVC_HD bool is_client_id(const B64 &claims, const Value &sub, const uint32_t id[clientid::kIdWords]) {
     uint32_t q = sub.at, count = 0, diff = 0;
     const uint32_t end = sub.at + sub.len;
     PWAF_CK_UNROLL
@@ -130,7 +130,7 @@ struct Stage {  // what the signature stage is asked: under key `key` (kMaxKeys:
     uint32_t key, good;
 };
 // Rules 3 to 5 for a located token (`v` is the cookie value): PWAF_POW_FAILED, or kCandidate with *stage
-PWAF_CK_HD uint8_t check(const KeySetData &ks, const uint8_t *v, const Token &t, int64_t now, const Request &r, Stage *stage) {
+PWAF_SVC_HD uint8_t check(const KeySetData &ks, const uint8_t *v, const Token &t, int64_t now, const Request &r, Stage *stage) {
     const uint8_t *m = v + t.at;
     uint32_t key = kMaxKeys;
     bool alg_typ_ok = false;
@@ -164,7 +164,7 @@ PWAF_CK_HD uint8_t check(const KeySetData &ks, const uint8_t *v, const Token &t,
     return kCandidate;
 }
 // Rules 3, 4 and 6 where they need the curve: stage.good behind a good signature, PWAF_POW_FAILED behind a bad one
-PWAF_CK_HD uint8_t verify(const KeySetData &ks, const Precomp *base, const uint8_t *v, const Token &t, const Stage &stage) {
+PWAF_SVC_HD uint8_t verify(const KeySetData &ks, const Precomp *base, const uint8_t *v, const Token &t, const Stage &stage) {
     const uint8_t *m = v + t.at;
     const uint32_t len = t.signed_len();
     uint32_t r[8], s[8];
@@ -203,20 +203,15 @@ struct Args {
     uint32_t *count;  // DEVICE mode: the candidates' number (zeroed in front of the launches; scratch word 0) and the list
     Candidate *cand;
 };
-PWAF_CK_HD uint32_t selected(const Args &a) {
-    if (!a.idx) return a.n;
-    if (!a.n_idx) return a.idx_cap;
-    const uint32_t k = *a.n_idx;
-    return k < a.idx_cap ? k : a.idx_cap;
-}
-PWAF_CK_HD uint32_t request_of(const Args &a, uint32_t e) { return a.idx ? a.idx[e] : e; }
-PWAF_CK_HD Request request_at(const Args &a, uint32_t i) {  // i < a.n
+PWAF_SVC_HD uint32_t selected(const Args &a) { return pwaf::selected(a.idx, a.n_idx, a.idx_cap, a.n); }
+PWAF_SVC_HD uint32_t request_of(const Args &a, uint32_t e) { return pwaf::request_of(a.idx, e); }
+PWAF_SVC_HD Request request_at(const Args &a, uint32_t i) {  // i < a.n
     const uint32_t u0 = a.ua.offsets[i], h0 = a.host.offsets[i], n0 = a.nonce.offsets[i];
     return Request{a.ip + (size_t)i * 16, a.ip_is_v6[i], a.ua.data + u0, a.host.data + h0, a.hash + (size_t)i * 32, a.nonce.data + n0,
                    a.ua.offsets[i + 1] - u0,    a.host.offsets[i + 1] - h0, a.nonce.offsets[i + 1] - n0};
 }
 // entry e's first step (rules 1 to 5): ABSENT / FAILED, or kCandidate with *c
-PWAF_CK_HD uint8_t check_entry(const Args &a, uint32_t e, Candidate *c) {
+PWAF_SVC_HD uint8_t check_entry(const Args &a, uint32_t e, Candidate *c) {
     const uint32_t i = request_of(a, e);
     if (i >= a.n) return PWAF_POW_ABSENT;
     const uint32_t c0 = a.cookies.offsets[i];
@@ -229,7 +224,7 @@ PWAF_CK_HD uint8_t check_entry(const Args &a, uint32_t e, Candidate *c) {
     *c = Candidate{e, t.at, t.hdr_len, t.claims_len, stage.key, stage.good};
     return st;
 }
-PWAF_CK_HD uint8_t verify_candidate(const Args &a, const Precomp *base, const Candidate &c) {
+PWAF_SVC_HD uint8_t verify_candidate(const Args &a, const Precomp *base, const Candidate &c) {
     const uint32_t i = request_of(a, c.entry);
     return verify(*a.ks, base, a.cookies.data + a.cookies.offsets[i], Token{c.at, c.hdr_len, c.claims_len}, Stage{c.key, c.good});
 }

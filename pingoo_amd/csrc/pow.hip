@@ -82,7 +82,6 @@ int launch_verify_pow(const Args &a, void *stream) {
 
 }  // namespace pow
 
-int fail(int code, const std::string &msg);  // program_api.cpp: records pwaf_last_error()
 }  // namespace pwaf
 
 extern "C" size_t pwaf_verify_pow_scratch_bytes(uint32_t n) { return 16 + sizeof(pwaf::pow::Candidate) * (size_t)n; }
@@ -92,13 +91,11 @@ extern "C" int pwaf_verify_pow(const pwaf_keyset *ks, const pwaf_batch *in, cons
     namespace K = pwaf::pow;
     using pwaf::fail;
     if (!ks || !in || !cookies || !status || !hash || !nonce) return fail(PWAF_E_INVALID_ARG, "pwaf_verify_pow: NULL argument");
-    if (in->struct_size != sizeof(pwaf_batch)) return fail(PWAF_E_INVALID_ARG, "pwaf_batch.struct_size mismatch");
-    if (in->memory != PWAF_MEM_HOST && in->memory != PWAF_MEM_DEVICE) return fail(PWAF_E_INVALID_ARG, "pwaf_batch.memory is neither HOST nor DEVICE");
-    if (!idx && (idx_cap || n_idx)) return fail(PWAF_E_INVALID_ARG, "pwaf_verify_pow: idx is NULL with idx_cap != 0 or a non-NULL n_idx");
+    if (int rc = pwaf::check_batch_header(in)) return rc;
+    if (int rc = pwaf::check_list("pwaf_verify_pow", idx, idx_cap, n_idx)) return rc;
     const pwaf_strcol &ua = in->field[PWAF_FIELD_USER_AGENT], &host = in->field[PWAF_FIELD_HOST];
+    if (int rc = pwaf::check_client_columns(in)) return rc;
     if (in->n) {
-        if (!in->ip || !in->ip_is_v6) return fail(PWAF_E_INVALID_ARG, "pwaf_batch.ip or ip_is_v6 is NULL");
-        if (!ua.data || !ua.offsets || !host.data || !host.offsets) return fail(PWAF_E_INVALID_ARG, "pwaf_batch User-Agent or host column is NULL");
         if (!cookies->data || !cookies->offsets) return fail(PWAF_E_INVALID_ARG, "pwaf_verify_pow: the cookies column is NULL");
         if (!nonce->data || !nonce->offsets) return fail(PWAF_E_INVALID_ARG, "pwaf_verify_pow: the nonce column is NULL");
     }
@@ -114,8 +111,7 @@ extern "C" int pwaf_verify_pow(const pwaf_keyset *ks, const pwaf_batch *in, cons
     }
     if (!ks->dev) return fail(PWAF_E_DEVICE, "pwaf_verify_pow: the key set was created for the host only (device < 0)");
     const uint32_t cap = idx ? idx_cap : in->n;
-    if (!scratch || ((uintptr_t)scratch & 15u) || scratch_bytes < pwaf_verify_pow_scratch_bytes(cap))
-        return fail(PWAF_E_INVALID_ARG, "pwaf_verify_pow: scratch is NULL, not 16-byte aligned or smaller than pwaf_verify_pow_scratch_bytes");
+    if (int rc = pwaf::check_scratch("pwaf_verify_pow", scratch, scratch_bytes, pwaf_verify_pow_scratch_bytes(cap), "pwaf_verify_pow_scratch_bytes")) return rc;
     int current = -1;
     if (hipGetDevice(&current) != hipSuccess || current != ks->device) return fail(PWAF_E_DEVICE, "pwaf_verify_pow: the current device is not the key set's");
     a.ks = ks->dev;

@@ -23,12 +23,7 @@
 #include <string.h>
 
 #include "pwaf.h"
-
-#if defined(__HIPCC__) || defined(__HIP__)
-#define PWAF_PB_HD __host__ __device__ inline
-#else
-#define PWAF_PB_HD inline
-#endif
+#include "service.h"
 
 namespace pwaf {
 namespace powbody {
@@ -46,7 +41,7 @@ struct Chunk {
 };
 struct Padded {  // DEVICE: one 16-byte load at the body's own alignment; it may pass the body's end by up to 15 bytes
     const uint8_t *s;
-    PWAF_PB_HD Chunk load(uint32_t at, uint32_t run) const {
+    PWAF_SVC_HD Chunk load(uint32_t at, uint32_t run) const {
         (void)run;
         Chunk v;
         memcpy(&v, s + at, 16);
@@ -55,7 +50,7 @@ struct Padded {  // DEVICE: one 16-byte load at the body's own alignment; it may
 };
 struct Exact {  // HOST: not a byte outside the body
     const uint8_t *s;
-    PWAF_PB_HD Chunk load(uint32_t at, uint32_t run) const {
+    PWAF_SVC_HD Chunk load(uint32_t at, uint32_t run) const {
         Chunk v{0, 0};
         memcpy(&v, s + at, run);
         return v;
@@ -68,7 +63,7 @@ struct Cursor {
     Src src;
     uint32_t len, at;
     uint64_t lo, hi;
-    PWAF_PB_HD uint32_t byte(uint32_t p) {  // p < len
+    PWAF_SVC_HD uint32_t byte(uint32_t p) {  // p < len
         if ((p & ~15u) != at) {
             at = p & ~15u;
             const Chunk c = src.load(at, len - at >= 16u ? 16u : len - at);
@@ -85,9 +80,9 @@ struct Body {
     uint32_t nonce_len;
     uint32_t hash[8];   // OK: the 32 bytes, byte k in bits [8(k & 3), +8) of word k / 4 (memory order on a little-endian machine); else 0
 };
-PWAF_PB_HD bool is_ws(uint32_t b) { return b == 0x20u || b == 0x09u || b == 0x0Au || b == 0x0Du; }
+PWAF_SVC_HD bool is_ws(uint32_t b) { return b == 0x20u || b == 0x09u || b == 0x0Au || b == 0x0Du; }
 // 0..15, or 16 for a byte that is no hexadecimal digit
-PWAF_PB_HD uint32_t hex_value(uint32_t b) {
+PWAF_SVC_HD uint32_t hex_value(uint32_t b) {
     const uint32_t d = b - '0', l = (b | 0x20u) - 'a';
     return d < 10u ? d : l < 6u ? l + 10u : 16u;
 }
@@ -102,7 +97,7 @@ enum : uint32_t { kCtl = 1u, kEscape = 2u, kHigh = 4u, kNotHex = 8u };
 static constexpr uint64_t kKeyHash = 0x68736168ull;     // "hash"
 static constexpr uint64_t kKeyNonce = 0x65636E6F6Eull;  // "nonce"
 template <class Src>
-PWAF_PB_HD Text read_text(Cursor<Src> &c, uint32_t p) {
+PWAF_SVC_HD Text read_text(Cursor<Src> &c, uint32_t p) {
     Text t{c.len, 0, 0, {0, 0, 0, 0, 0, 0, 0, 0}};
     uint32_t acc = 0;
     for (uint32_t k = 0; p < c.len; p++, k++) {
@@ -127,7 +122,7 @@ PWAF_PB_HD Text read_text(Cursor<Src> &c, uint32_t p) {
 }
 // D-B1 to D-B10. The FIRST deciding event wins.
 template <class Src>
-PWAF_PB_HD Body read_body(const Src &src, uint32_t len) {
+PWAF_SVC_HD Body read_body(const Src &src, uint32_t len) {
     Body r{PWAF_BODY_MALFORMED, 0, 0, {0, 0, 0, 0, 0, 0, 0, 0}};
     const Body malformed = r;
     Body undecided = r;
@@ -205,16 +200,11 @@ struct Args {
     uint32_t *count;  // scratch: [groups][4] OK / MALFORMED / UNDECIDED / entries of each parse workgroup
     uint32_t *from;   // scratch: [n] where the nonce of a request begins in the body arena
 };
-PWAF_PB_HD uint32_t selected(const Args &a) {
-    if (!a.idx) return a.n;
-    if (!a.n_idx) return a.idx_cap;
-    const uint32_t k = *a.n_idx;
-    return k < a.idx_cap ? k : a.idx_cap;
-}
-PWAF_PB_HD uint32_t request_of(const Args &a, uint32_t e) { return a.idx ? a.idx[e] : e; }
+PWAF_SVC_HD uint32_t selected(const Args &a) { return pwaf::selected(a.idx, a.n_idx, a.idx_cap, a.n); }
+PWAF_SVC_HD uint32_t request_of(const Args &a, uint32_t e) { return pwaf::request_of(a.idx, e); }
 // Entry e, of request i < n: the status, and where selected by request the hash row, the nonce's length one slot up and its start.
 template <class Src>
-PWAF_PB_HD Body parse_entry(const Args &a, uint32_t e, uint32_t i) {
+PWAF_SVC_HD Body parse_entry(const Args &a, uint32_t e, uint32_t i) {
     const uint32_t o = a.bodies.offsets[i];
     const Body b = read_body(Src{a.bodies.data + o}, a.bodies.offsets[i + 1] - o);
     a.status[e] = (uint8_t)b.status;
@@ -224,32 +214,27 @@ PWAF_PB_HD Body parse_entry(const Args &a, uint32_t e, uint32_t i) {
 }
 
 // ---- the scan's arithmetic -----------------------------------------------------------------------------------------------------------------
-PWAF_PB_HD uint32_t tiles(uint32_t n) { return (uint32_t)(((uint64_t)n + kTile - 1u) / kTile); }
+PWAF_SVC_HD uint32_t tiles(uint32_t n) { return pwaf::tiles(n, kTile); }
 // the parse launch: one workgroup per tile of entries; with a list a bounded number of them, each striding over the tiles
-PWAF_PB_HD uint32_t parse_groups(uint32_t n, bool list, uint32_t idx_cap) {
+PWAF_SVC_HD uint32_t parse_groups(uint32_t n, bool list, uint32_t idx_cap) {
     if (!list) return tiles(n);
     const uint32_t most = tiles(n) > kMinGroups ? tiles(n) : kMinGroups;
     return tiles(idx_cap) < most ? tiles(idx_cap) : most;
 }
 // scratch: the tile array (tiles + 1 64-bit words, rounded up to even), the count slots (16 bytes each), `from` (n words)
-PWAF_PB_HD uint32_t tile_stride(uint32_t n) { return (tiles(n) + 2u) & ~1u; }
-PWAF_PB_HD uint32_t count_slots(uint32_t n) { return tiles(n) > kMinGroups ? tiles(n) : kMinGroups; }
-PWAF_PB_HD size_t scratch_bytes(uint32_t n) { return ((size_t)tile_stride(n) * 8u + (size_t)count_slots(n) * 16u + (size_t)n * 4u + 15u) & ~(size_t)15u; }
+PWAF_SVC_HD uint32_t tile_stride(uint32_t n) { return pwaf::tile_stride(tiles(n)); }
+PWAF_SVC_HD uint32_t count_slots(uint32_t n) { return tiles(n) > kMinGroups ? tiles(n) : kMinGroups; }
+PWAF_SVC_HD size_t scratch_bytes(uint32_t n) { return ((size_t)tile_stride(n) * 8u + (size_t)count_slots(n) * 16u + (size_t)n * 4u + 15u) & ~(size_t)15u; }
 inline void scratch_layout(Args &a, void *scratch) {
     a.tile = (uint64_t *)scratch;
     a.count = (uint32_t *)(a.tile + tile_stride(a.n));
     a.from = a.count + (size_t)count_slots(a.n) * 4u;
 }
-PWAF_PB_HD bool fits(uint64_t bytes, uint64_t cap) { return bytes + PWAF_ARENA_PAD <= cap; }
-PWAF_PB_HD void fill_stats(pwaf_body_stats *st, uint64_t total, uint64_t cap, const uint32_t count[4]) {
+PWAF_SVC_HD void fill_stats(pwaf_body_stats *st, uint64_t total, uint64_t cap, const uint32_t count[4]) {
     st->nonce_bytes = total;
     st->n = count[3], st->n_ok = count[0], st->n_malformed = count[1], st->n_undecided = count[2];
     st->overflow = fits(total, cap) ? 0u : 1u;
     st->reserved = 0;
-}
-// the pad: the 16 bytes behind the column's last byte, those that lie below cap
-PWAF_PB_HD void write_pad_byte(uint8_t *data, uint64_t total, uint64_t cap, uint32_t k) {
-    if (total + k < cap) data[total + k] = 0;
 }
 
 // ---- the HOST mode -------------------------------------------------------------------------------------------------------------------------
@@ -280,7 +265,7 @@ inline bool parse_host(const Args &a, uint32_t *from, uint32_t *bad) {
     if (a.off) a.off[0] = 0;  // (n == 0: the offsets may be NULL)
     for (uint32_t i = 0; i < a.n; i++) {
         const uint32_t len = a.off[(size_t)i + 1];
-        if (len && at < a.cap) memcpy(a.data + at, a.bodies.data + from[i], (size_t)(at + len <= a.cap ? len : a.cap - at));
+        if (len) append_clipped(a.data, a.cap, at, a.bodies.data + from[i], len);  // (from[i] is written only for a request the list names)
         at += len;
         a.off[(size_t)i + 1] = (uint32_t)at;
     }

@@ -12,7 +12,7 @@
 //                         length and the base launch sums the tiles. Each workgroup writes its status counts to a slot of its own.
 //   powbody_base_kernel   one workgroup: (with a list) each tile's sum, a wave a tile; tile sums -> exclusive bases, kStep tiles a step;
 //                         slot tiles(n): the total. Sums the workgroups' status counts.
-//   powbody_copy_kernel   one workgroup per tile: derive_copy_kernel for one column. A wave rescans its 64 lengths from the tile's base, in
+//   powbody_copy_kernel   one workgroup per tile: copy_wave_range (colscan.h) for one column, as derive_copy_kernel for three. A wave rescans its 64 lengths from the tile's base, in
 //                         place, and copies its requests' nonces, ONE contiguous range of the output, 16 aligned output bytes at a time. The
 //                         last tile writes the pad, the first offsets[0] and stats. Nothing is stored at or beyond cap.
 #include <hip/hip_runtime.h>
@@ -20,6 +20,7 @@
 #include <new>
 #include <string>
 
+#include "colscan.h"
 #include "powbody.h"
 
 namespace pwaf {
@@ -27,27 +28,6 @@ namespace powbody {
 namespace {
 
 static_assert(kTile % 64 == 0 && kStep % 64 == 0 && kTile <= 1024 && kStep <= 1024 && kCopyGroup == kTile, "whole waves, one workgroup per tile");
-
-__device__ __forceinline__ uint64_t wave_sum(uint64_t x) {
-    for (uint32_t d = 32; d; d >>= 1) x += __shfl_xor(x, d, 64);
-    return x;
-}
-// inclusive prefix inside the wave
-template <class T>
-__device__ __forceinline__ T wave_scan(T x, uint32_t lane) {
-    for (uint32_t d = 1; d < 64; d <<= 1) {
-        const T y = __shfl_up(x, d, 64);
-        if (lane >= d) x += y;
-    }
-    return x;
-}
-// A wave's LDS instructions execute in program order; this keeps the compiler from reordering them across the point where the lanes
-// exchange roles (see records.hip).
-__device__ __forceinline__ void wave_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
 
 // Phase 1. One entry per lane; workgroup g takes the tiles g, g + gridDim.x, ... of the entries (without a list: tile g alone).
 __global__ __launch_bounds__(kTile) void powbody_parse_kernel(Args a) {
@@ -120,25 +100,8 @@ __global__ __launch_bounds__(kStep) void powbody_base_kernel(Args a) {
         }
         __syncthreads();  // (the workgroup's own global writes are visible to it behind the barrier)
     }
-    uint64_t carry = 0;
-    for (uint32_t t0 = 0; t0 < nt; t0 += kStep) {
-        const uint32_t t = t0 + tid;  // (nt is at most 2^12: no wrap)
-        const uint64_t x = t < nt ? tile[t] : 0u;
-        uint64_t incl = wave_scan(x, lane);
-        if (lane == 63) wsum[wave] = incl;
-        __syncthreads();
-        uint64_t all = 0;
-#pragma unroll
-        for (uint32_t w = 0; w < W; w++) {
-            const uint64_t s = wsum[w];
-            if (w < wave) incl += s;
-            all += s;
-        }
-        if (t < nt) tile[t] = carry + incl - x;
-        carry += all;
-        __syncthreads();  // (wsum is rewritten by the next step)
-    }
-    if (tid == 0) tile[nt] = carry;
+    const uint64_t total = scan_tile_bases<W>(tile, nt, wsum);
+    if (tid == 0) tile[nt] = total;
     // the status counts of the parse launch's workgroups -> slot 0
     uint32_t c[3] = {0, 0, 0};
     for (uint32_t g = tid; g < a.groups; g += kStep) {
@@ -188,56 +151,13 @@ __global__ __launch_bounds__(kCopyGroup) void powbody_copy_kernel(Args a) {
         if (lane == 63) woff[wave][64] = range;
         wsrc[wave][lane] = len ? a.bodies.data + a.from[i] : nullptr;
         wave_sync();
-        // the aligned 16-byte chunks of the output that hold a byte of [base, base + range)
-        const uint64_t end = base + range;
-        for (uint64_t ck = (base >> 4) + lane; ck * 16u < end; ck += 64) {
-            const uint64_t p0 = ck * 16u, lo64 = p0 > base ? p0 : base, hi64 = p0 + 16u < end ? p0 + 16u : end;
-            const uint32_t lo = (uint32_t)(lo64 - base), hi = (uint32_t)(hi64 - base), shift = (uint32_t)(lo64 - p0);  // inside the range; the chunk's first own byte
-            uint32_t l = 0, h = 64;  // woff[l] <= lo < woff[h]: request l holds byte lo (and is not empty)
-            while (h - l > 1) {
-                const uint32_t mid = (l + h) >> 1;
-                if (woff[wave][mid] <= lo) l = mid;
-                else h = mid;
-            }
-            uint32_t k = l, first = woff[wave][k], next = woff[wave][k + 1];
-            const uint8_t *src = wsrc[wave][k];  // byte `first` of the range is src[0]
-            unsigned __int128 acc = 0;
-            for (uint32_t p = lo; p < hi;) {
-                while (p >= next) {  // (p < hi <= range == woff[64]: k stays below 64)
-                    k++;
-                    first = next;
-                    next = woff[wave][k + 1];
-                    src = wsrc[wave][k];
-                }
-                const uint32_t run = (next < hi ? next : hi) - p;
-                unsigned __int128 v;
-                memcpy(&v, src + (p - first), 16);  // may pass the nonce's end by fewer than 16 bytes: inside its body's arena or the pad
-                if (run < 16u) v &= ((unsigned __int128)1 << (8u * run)) - 1u;
-                acc |= v << (8u * (p - lo + shift));
-                p += run;
-            }
-            if (hi - lo == 16u && p0 + 16u <= cap) {
-                uint4 q;
-                memcpy(&q, &acc, 16);
-                *reinterpret_cast<uint4 *>(data + p0) = q;
-            } else {
-                for (uint32_t b = shift; b < shift + (hi - lo); b++)
-                    if (p0 + b < cap) data[p0 + b] = (uint8_t)(acc >> (8u * b));
-            }
-        }
+        copy_wave_range(data, cap, base, range, woff[wave], wsrc[wave], lane);
     }
     if (blockIdx.x + 1 == gridDim.x && tid < PWAF_ARENA_PAD) write_pad_byte(data, total, cap, tid);
     if (blockIdx.x == 0 && tid == 0) {
         const uint32_t count[4] = {a.count[0], a.count[1], a.count[2], a.count[3]};
         fill_stats(a.stats, total, cap, count);
     }
-}
-
-// The launch's own status (hipLaunchKernel returns it): an earlier error that still sticks to the thread is neither read nor cleared here.
-int launch(void (*kernel)(Args), uint32_t grid, uint32_t block, const Args &a, hipStream_t s) {
-    Args copy = a;
-    void *args[] = {&copy};
-    return hipLaunchKernel(reinterpret_cast<const void *>(kernel), dim3(grid), dim3(block), args, 0, s) == hipSuccess ? 0 : -1;
 }
 
 }  // namespace
@@ -248,14 +168,12 @@ int launch_parse_pow(const Args &a, void *stream) {
     const uint32_t nt = tiles(a.n);
     // with a list: the length of every request the list does not name (the parse launch overwrites those it names)
     if (a.idx && a.n && hipMemsetAsync(a.off, 0, ((size_t)a.n + 1u) * 4u, s) != hipSuccess) return -1;
-    if (a.groups && launch(powbody_parse_kernel, a.groups, kTile, a, s)) return -1;
-    if (launch(powbody_base_kernel, 1, kStep, a, s)) return -1;
-    return launch(powbody_copy_kernel, nt ? nt : 1u, kCopyGroup, a, s);
+    if (a.groups && launch_args(powbody_parse_kernel, a.groups, kTile, a, s)) return -1;
+    if (launch_args(powbody_base_kernel, 1, kStep, a, s)) return -1;
+    return launch_args(powbody_copy_kernel, nt ? nt : 1u, kCopyGroup, a, s);
 }
 
 }  // namespace powbody
-
-int fail(int code, const std::string &msg);  // program_api.cpp: records pwaf_last_error()
 }  // namespace pwaf
 
 extern "C" size_t pwaf_parse_pow_bodies_scratch_bytes(uint32_t n) { return pwaf::powbody::scratch_bytes(n); }
@@ -266,15 +184,12 @@ extern "C" int pwaf_parse_pow_bodies(const pwaf_strcol *bodies, uint32_t n, uint
     using pwaf::fail;
     if (!bodies || !status || !hash || !nonce || !stats) return fail(PWAF_E_INVALID_ARG, "pwaf_parse_pow_bodies: NULL argument");
     if (memory != PWAF_MEM_HOST && memory != PWAF_MEM_DEVICE) return fail(PWAF_E_INVALID_ARG, "pwaf_parse_pow_bodies: memory is neither HOST nor DEVICE");
-    if (!idx && (idx_cap || n_idx)) return fail(PWAF_E_INVALID_ARG, "pwaf_parse_pow_bodies: idx is NULL with idx_cap != 0 or a non-NULL n_idx");
+    if (int rc = pwaf::check_list("pwaf_parse_pow_bodies", idx, idx_cap, n_idx)) return rc;
     if (n > B::kMaxRequests)
         return fail(PWAF_E_INVALID_ARG, "pwaf_parse_pow_bodies: more than 0xFFFFFFF0 / PWAF_POW_BODY_MAX_BYTES requests (the nonce column could pass 32 bits): split the batch");
     if ((uintptr_t)stats & 7u) return fail(PWAF_E_INVALID_ARG, "pwaf_parse_pow_bodies: stats is not 8-byte aligned");
     if (n && (!bodies->data || !bodies->offsets)) return fail(PWAF_E_INVALID_ARG, "pwaf_parse_pow_bodies: the bodies column is NULL");
-    if (n && !nonce->offsets) return fail(PWAF_E_INVALID_ARG, "pwaf_parse_pow_bodies: nonce offsets is NULL");
-    if (!nonce->data && nonce->cap) return fail(PWAF_E_INVALID_ARG, "pwaf_parse_pow_bodies: nonce data is NULL with cap != 0");
-    if ((uintptr_t)nonce->data & 15u) return fail(PWAF_E_INVALID_ARG, "pwaf_parse_pow_bodies: nonce data is not 16-byte aligned");
-    if ((uintptr_t)nonce->offsets & 3u) return fail(PWAF_E_INVALID_ARG, "pwaf_parse_pow_bodies: nonce offsets is not 4-byte aligned");
+    if (int rc = pwaf::check_derived_col("pwaf_parse_pow_bodies: nonce", n, *nonce)) return rc;
     B::Args a{};
     a.bodies = *bodies, a.n = n, a.idx = idx, a.n_idx = n_idx, a.idx_cap = idx_cap, a.status = status, a.hash = hash;
     a.data = nonce->data, a.off = nonce->offsets, a.cap = nonce->cap, a.stats = stats;
@@ -288,8 +203,7 @@ extern "C" int pwaf_parse_pow_bodies(const pwaf_strcol *bodies, uint32_t n, uint
         if (!ok) return fail(PWAF_E_BATCH, "pwaf_parse_pow_bodies: entry " + std::to_string(bad) + " (request " + std::to_string(bad_request) + "): body offsets decrease");
         return PWAF_OK;
     }
-    if (!scratch || ((uintptr_t)scratch & 15u) || scratch_bytes < B::scratch_bytes(n))
-        return fail(PWAF_E_INVALID_ARG, "pwaf_parse_pow_bodies: scratch is NULL, not 16-byte aligned or smaller than pwaf_parse_pow_bodies_scratch_bytes(n)");
+    if (int rc = pwaf::check_scratch("pwaf_parse_pow_bodies", scratch, scratch_bytes, B::scratch_bytes(n), "pwaf_parse_pow_bodies_scratch_bytes(n)")) return rc;
     static_assert(sizeof(B::Args) <= 4096, "Args travels in the kernel argument block");
     B::scratch_layout(a, scratch);
     a.groups = B::parse_groups(n, idx != nullptr, idx_cap);

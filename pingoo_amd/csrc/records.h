@@ -11,12 +11,7 @@
 #include <string.h>
 
 #include "pwaf.h"
-
-#if defined(__HIPCC__) || defined(__HIP__)
-#define PWAF_RECORD_HD __host__ __device__ inline
-#else
-#define PWAF_RECORD_HD inline
-#endif
+#include "service.h"
 
 namespace pwaf {
 namespace records {
@@ -29,12 +24,12 @@ static constexpr uint64_t kMaxColumn = 0xFFFFFFF0ull;         // a column's byte
 static_assert(sizeof(pwaf_record_head) == 36, "pwaf_record_head layout");
 
 // where the values of a record with n_values lengths begin (16-byte aligned inside the record) and the record's size
-PWAF_RECORD_HD uint32_t values_offset(uint32_t n_values) { return (kHead + 4u * n_values + 15u) & ~15u; }
-PWAF_RECORD_HD uint64_t record_size(uint32_t n_values, uint64_t value_bytes) { return ((uint64_t)values_offset(n_values) + value_bytes + 15u) & ~(uint64_t)15u; }
+PWAF_SVC_HD uint32_t values_offset(uint32_t n_values) { return (kHead + 4u * n_values + 15u) & ~15u; }
+PWAF_SVC_HD uint64_t record_size(uint32_t n_values, uint64_t value_bytes) { return ((uint64_t)values_offset(n_values) + value_bytes + 15u) & ~(uint64_t)15u; }
 
 // (memcpy: a host buffer is only byte-aligned as far as the C ABI knows)
-PWAF_RECORD_HD void load_head(const uint8_t *rec, pwaf_record_head *h) { memcpy(h, rec, kHead); }
-PWAF_RECORD_HD uint32_t load_len(const uint8_t *rec, uint32_t k) {
+PWAF_SVC_HD void load_head(const uint8_t *rec, pwaf_record_head *h) { memcpy(h, rec, kHead); }
+PWAF_SVC_HD uint32_t load_len(const uint8_t *rec, uint32_t k) {
     uint32_t v;
     memcpy(&v, rec + kHead + 4u * k, 4);
     return v;
@@ -70,7 +65,7 @@ inline const char *check_message(int c) {
 
 // One record at byte offset `off` of a buffer of buf_bytes bytes: kOk or what is wrong with it. Reads nothing outside the buffer.
 // *value_bytes = the sum of its lengths.
-PWAF_RECORD_HD int check_record(const uint8_t *buf, uint64_t buf_bytes, uint64_t off, uint32_t max_values, uint64_t *value_bytes) {
+PWAF_SVC_HD int check_record(const uint8_t *buf, uint64_t buf_bytes, uint64_t off, uint32_t max_values, uint64_t *value_bytes) {
     if (off & 15u) return kMisaligned;
     if (off > buf_bytes || buf_bytes - off < kHead) return kPastEnd;
     pwaf_record_head h;
@@ -164,29 +159,29 @@ static constexpr uint32_t kScanStep = 256;  // tiles one step of phase 2 takes: 
 static constexpr uint64_t kNoFailure = ~0ull;
 
 // the failure key: ordered by (index, check), so that the minimum names what validate()'s loop meets first
-PWAF_RECORD_HD uint64_t fail_key(uint32_t i, int check) { return ((uint64_t)i << 32) | (uint32_t)check; }
-PWAF_RECORD_HD uint32_t key_index(uint64_t key) { return (uint32_t)(key >> 32); }
-PWAF_RECORD_HD int key_check(uint64_t key) { return (int)(uint32_t)key; }
+PWAF_SVC_HD uint64_t fail_key(uint32_t i, int check) { return ((uint64_t)i << 32) | (uint32_t)check; }
+PWAF_SVC_HD uint32_t key_index(uint64_t key) { return (uint32_t)(key >> 32); }
+PWAF_SVC_HD int key_check(uint64_t key) { return (int)(uint32_t)key; }
 
 // the records a call looks at: min(*n_rec, n), or n without a count
-PWAF_RECORD_HD uint32_t records_in_call(const uint32_t *n_rec, uint32_t n) {
+PWAF_SVC_HD uint32_t records_in_call(const uint32_t *n_rec, uint32_t n) {
     if (!n_rec) return n;
     const uint32_t k = *n_rec;
     return k < n ? k : n;
 }
-PWAF_RECORD_HD uint32_t scan_tiles(uint32_t m) { return m / kScanTile + (m % kScanTile ? 1u : 0u); }
+PWAF_SVC_HD uint32_t scan_tiles(uint32_t m) { return m / kScanTile + (m % kScanTile ? 1u : 0u); }
 // a column's n + 1 offsets, on a 256-byte grid (evaluate_records_impl's stride)
-PWAF_RECORD_HD size_t offsets_stride(uint32_t n) { return ((size_t)n + 1 + 63) & ~(size_t)63; }
+PWAF_SVC_HD size_t offsets_stride(uint32_t n) { return ((size_t)n + 1 + 63) & ~(size_t)63; }
 
 // has_geoip of the call's first record where its head can be read, else a value no record has (the record then fails at index 0, and
 // no kMixedGeo behind it is ever reported)
-PWAF_RECORD_HD uint32_t first_geo(const uint8_t *buf, uint64_t buf_bytes, uint32_t off0) {
+PWAF_SVC_HD uint32_t first_geo(const uint8_t *buf, uint64_t buf_bytes, uint32_t off0) {
     if ((off0 & 15u) || off0 > buf_bytes || buf_bytes - off0 < kHead) return 0xFFFFFFFFu;
     return buf[(size_t)off0 + offsetof(pwaf_record_head, has_geoip)];
 }
 // One record of the call, as validate() judges it apart from the column totals: check_record, then has_geoip against the first record's.
 // *n_values = the lengths it carries (0 unless kOk).
-PWAF_RECORD_HD int scan_check(const uint8_t *buf, uint64_t buf_bytes, uint32_t off, uint32_t n_cols, uint32_t geo0, uint32_t *n_values) {
+PWAF_SVC_HD int scan_check(const uint8_t *buf, uint64_t buf_bytes, uint32_t off, uint32_t n_cols, uint32_t geo0, uint32_t *n_values) {
     *n_values = 0;
     uint64_t vb = 0;
     const int c = check_record(buf, buf_bytes, off, n_cols, &vb);
@@ -199,12 +194,12 @@ PWAF_RECORD_HD int scan_check(const uint8_t *buf, uint64_t buf_bytes, uint32_t o
     return kOk;
 }
 // the length a record with n_values lengths contributes to column f
-PWAF_RECORD_HD uint32_t scan_len(const uint8_t *rec, uint32_t n_values, uint32_t f) { return f < n_values ? load_len(rec, f) : 0u; }
+PWAF_SVC_HD uint32_t scan_len(const uint8_t *rec, uint32_t n_values, uint32_t f) { return f < n_values ? load_len(rec, f) : 0u; }
 // a column's running total, inclusive of a record: validate()'s kColumnTooBig
-PWAF_RECORD_HD bool column_too_big(uint64_t inclusive_total) { return inclusive_total > kMaxColumn; }
+PWAF_SVC_HD bool column_too_big(uint64_t inclusive_total) { return inclusive_total > kMaxColumn; }
 // Where the columns go in the unpacked batch: each total plus PWAF_ARENA_PAD, on the 256-byte grid of staging.h's Layout::take.
 // Returns the bytes the columns occupy together (where the fixed columns begin).
-PWAF_RECORD_HD uint64_t place_columns(const uint64_t *totals, uint32_t n_cols, uint64_t *col_at) {
+PWAF_SVC_HD uint64_t place_columns(const uint64_t *totals, uint32_t n_cols, uint64_t *col_at) {
     uint64_t used = 0;
     for (uint32_t f = 0; f < n_cols; f++) {
         col_at[f] = used;
@@ -220,7 +215,7 @@ struct ScanSummary {
     uint32_t bad_off, m, has_geoip, reserved;
     uint64_t totals[kMaxValues];
 };
-PWAF_RECORD_HD size_t summary_bytes(uint32_t n_cols) { return offsetof(ScanSummary, totals) + 8u * (size_t)n_cols; }
+PWAF_SVC_HD size_t summary_bytes(uint32_t n_cols) { return offsetof(ScanSummary, totals) + 8u * (size_t)n_cols; }
 
 // The three launches' arguments. off / col_at are what UnpackArgs then takes; nothing here is the caller's memory but buf, rec_off, n_rec.
 struct ScanArgs {
@@ -262,34 +257,30 @@ struct PackArgs {
     pwaf_export_stats *stats;
 };
 
-PWAF_RECORD_HD uint32_t selected(const PackArgs &a) {
-    if (!a.n_idx) return a.idx_cap;
-    const uint32_t k = *a.n_idx;
-    return k < a.idx_cap ? k : a.idx_cap;
-}
+PWAF_SVC_HD uint32_t selected(const PackArgs &a) { return list_length(a.n_idx, a.idx_cap); }  // (there is always a list: idx NULL only with idx_cap == 0)
 // length of column k's value of request i (uint32 arithmetic, as every reader of the offsets does; monotone offsets are export_host's check)
-PWAF_RECORD_HD uint32_t col_len(const pwaf_strcol &c, uint32_t i) { return c.data && c.offsets ? c.offsets[i + 1] - c.offsets[i] : 0u; }
+PWAF_SVC_HD uint32_t col_len(const pwaf_strcol &c, uint32_t i) { return c.data && c.offsets ? c.offsets[i + 1] - c.offsets[i] : 0u; }
 
 // What a request's record looks like, from its column lengths: add() them in column order.
 struct ExportShape {
     uint32_t n_values = PWAF_N_FIELDS;  // ends after the last non-empty header value
     uint64_t value_bytes = 0;
-    PWAF_RECORD_HD void add(uint32_t k, uint32_t len) {
+    PWAF_SVC_HD void add(uint32_t k, uint32_t len) {
         value_bytes += len;
         if (len && k >= PWAF_N_FIELDS) n_values = k + 1;
     }
-    PWAF_RECORD_HD uint64_t size() const { return record_size(n_values, value_bytes); }
+    PWAF_SVC_HD uint64_t size() const { return record_size(n_values, value_bytes); }
     // a record that cannot be described in 32 bits is not exported (PWAF_RECORD_NONE, not counted)
-    PWAF_RECORD_HD uint32_t size32() const { return size() > kMaxRecord ? 0u : (uint32_t)size(); }
+    PWAF_SVC_HD uint32_t size32() const { return size() > kMaxRecord ? 0u : (uint32_t)size(); }
 };
-PWAF_RECORD_HD ExportShape export_shape(const PackArgs &a, uint32_t i) {
+PWAF_SVC_HD ExportShape export_shape(const PackArgs &a, uint32_t i) {
     ExportShape s;
     for (uint32_t k = 0; k < a.n_cols; k++) s.add(k, col_len(a.col[k], i));
     return s;
 }
 
 // the head of request i's record (every byte of *h is written: reserved and the GeoIP fields of a batch without GeoIP are 0)
-PWAF_RECORD_HD void fill_head(const PackArgs &a, uint32_t i, uint32_t n_values, uint32_t size, pwaf_record_head *h) {
+PWAF_SVC_HD void fill_head(const PackArgs &a, uint32_t i, uint32_t n_values, uint32_t size, pwaf_record_head *h) {
     memset(h, 0, kHead);
     h->size = size;
     h->n_values = (uint16_t)n_values;
@@ -305,7 +296,7 @@ PWAF_RECORD_HD void fill_head(const PackArgs &a, uint32_t i, uint32_t n_values, 
 }
 
 // One record, written by one thread: request i with shape s (s.size32() != 0) to dst, s.size() bytes, every one of them written.
-PWAF_RECORD_HD void pack_record(const PackArgs &a, uint32_t i, const ExportShape &s, uint8_t *dst) {
+PWAF_SVC_HD void pack_record(const PackArgs &a, uint32_t i, const ExportShape &s, uint8_t *dst) {
     const uint32_t size = s.size32(), vo = values_offset(s.n_values);
     pwaf_record_head h;
     fill_head(a, i, s.n_values, size, &h);

@@ -13,6 +13,7 @@
 
 #include <string>
 
+#include "colscan.h"
 #include "records.h"
 
 namespace pwaf {
@@ -107,15 +108,11 @@ __global__ __launch_bounds__(64) void unpack_records_kernel(UnpackArgs a) {
 //                16-byte store. Bytes past the last value are 0: the record's tail padding falls out of the last chunk.
 // The column descriptors are read from the kernel argument block (PackArgs::col) by a wave-uniform index while sizing; the prefix loop
 // indexes them per lane, from a copy in LDS made once per workgroup.
-// The workgroup is ONE wave, and a wave's LDS instructions execute in program order: what orders its lanes' LDS writes against its other
-// lanes' LDS reads is that the compiler keeps them in program order, not a barrier. (__syncthreads would also wait for every store to global
-// memory to be acknowledged: a round trip per record that nothing needs.)
-__device__ __forceinline__ void wave_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
+// The workgroup is ONE wave: its lanes' LDS writes and reads are ordered by wave_sync (colscan.h), not by __syncthreads, which would cost a
+// round trip to global memory per record.
+// Both kernels keep their own prefix loops, search and gather, which colscan.h also has (wave_scan, copy_wave_range): written on shared
+// functions, pack_records_kernel measured 3.6 % to 7 % slower on the MI355X and unpack_records_kernel compiled to another schedule
+// (DESIGN.md §0.6).
 __global__ __launch_bounds__(64) void pack_records_kernel(PackArgs a) {
     __shared__ uint32_t start[kMaxValues + 1];          // as in unpack_records_kernel
     __shared__ const uint8_t *src[kMaxValues];          // src[k] = the first byte of value k in its arena
@@ -245,8 +242,6 @@ int launch_pack_records(const PackArgs &a, void *stream) {
 }
 
 }  // namespace records
-
-int fail(int code, const std::string &msg);  // engine.cpp: records pwaf_last_error()
 }  // namespace pwaf
 
 extern "C" int pwaf_export_records(const pwaf_batch *in, const uint32_t *idx, uint32_t idx_cap, const uint32_t *n_idx, uint8_t *buf, size_t buf_cap,
@@ -254,8 +249,7 @@ extern "C" int pwaf_export_records(const pwaf_batch *in, const uint32_t *idx, ui
     namespace R = pwaf::records;
     using pwaf::fail;
     if (!in || !rec_off || !stats || (idx_cap && !idx)) return fail(PWAF_E_INVALID_ARG, "pwaf_export_records: NULL argument");
-    if (in->struct_size != sizeof(pwaf_batch)) return fail(PWAF_E_INVALID_ARG, "pwaf_batch.struct_size mismatch");
-    if (in->memory != PWAF_MEM_HOST && in->memory != PWAF_MEM_DEVICE) return fail(PWAF_E_INVALID_ARG, "pwaf_batch.memory is neither HOST nor DEVICE");
+    if (int rc = pwaf::check_batch_header(in)) return rc;
     if (in->n_headers > R::kMaxValues - PWAF_N_FIELDS) return fail(PWAF_E_INVALID_ARG, "pwaf_export_records: more header columns than a record can carry");
     if (in->n_headers && !in->headers) return fail(PWAF_E_INVALID_ARG, "pwaf_batch.headers is NULL");
     if ((uintptr_t)stats & 7u) return fail(PWAF_E_INVALID_ARG, "pwaf_export_records: stats is not 8-byte aligned");

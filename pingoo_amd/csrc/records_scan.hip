@@ -11,6 +11,7 @@
 // is read through it. Everything written is the engine's own (ScanArgs::off, tile, col_at, sum).
 #include <hip/hip_runtime.h>
 
+#include "colscan.h"
 #include "records.h"
 
 namespace pwaf {
@@ -21,45 +22,6 @@ const char *const kScanKernelNames[3] = {"records_check_kernel", "records_bases_
 namespace {
 
 static_assert(kScanTile % 64 == 0 && kScanStep % 64 == 0 && kScanTile <= 1024 && kScanStep <= 1024, "whole waves, one workgroup");
-
-__device__ __forceinline__ uint64_t wave_sum(uint64_t x) {
-    for (uint32_t d = 32; d; d >>= 1) x += __shfl_xor(x, d, 64);
-    return x;
-}
-__device__ __forceinline__ uint64_t wave_min(uint64_t x) {
-    for (uint32_t d = 32; d; d >>= 1) {
-        const uint64_t y = __shfl_xor(x, d, 64);
-        x = y < x ? y : x;
-    }
-    return x;
-}
-// inclusive prefix inside the wave
-template <class T>
-__device__ __forceinline__ T wave_scan(T x, uint32_t lane) {
-    for (uint32_t d = 1; d < 64; d <<= 1) {
-        const T y = __shfl_up(x, d, 64);
-        if (lane >= d) x += y;
-    }
-    return x;
-}
-// inclusive prefix over the workgroup (W waves; every thread calls it); *total = the workgroup's sum. wsum: W words of LDS.
-template <uint32_t W>
-__device__ __forceinline__ uint64_t block_scan(uint64_t x, uint64_t *wsum, uint64_t *total) {
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    uint64_t incl = wave_scan(x, lane);
-    if (lane == 63) wsum[wave] = incl;
-    __syncthreads();
-    uint64_t all = 0;
-#pragma unroll
-    for (uint32_t w = 0; w < W; w++) {
-        const uint64_t s = wsum[w];
-        if (w < wave) incl += s;
-        all += s;
-    }
-    *total = all;
-    __syncthreads();  // (wsum is rewritten by the next call)
-    return incl;
-}
 
 // Phase 1. One workgroup per tile, one record per lane.
 __global__ __launch_bounds__(kScanTile) void records_check_kernel(ScanArgs a) {

@@ -9,10 +9,8 @@
 #include <string>
 
 #include "records.h"
+#include "service.h"  // (fail)
 
-namespace pwaf {
-int fail(int code, const std::string &msg);  // program_api.cpp: records pwaf_last_error()
-}
 #pragma GCC visibility push(hidden)  // (internal to libpwaf.so, like everything of the engine's that several units share: engine_impl.h)
 namespace pwaf {
 

@@ -235,6 +235,12 @@ def _raise(code: int, message: str, rule_index: Optional[int] = None):
     raise cls(code, message, rule_index)
 
 
+def _check(rc: int, message: str = "", rule_index: Optional[int] = None) -> None:
+    """The status of a C ABI call: 0, or the error to raise with `message` or else what the library recorded for it."""
+    if rc != 0:
+        _raise(rc, message or lib().pwaf_last_error().decode(errors="replace"), rule_index)
+
+
 class Action(enum.IntEnum):
     """rules::Action (rules/rules.rs:30-35). Values are the PWAF_RULE_ACTION_* codes."""
 
@@ -321,9 +327,7 @@ def generate_captcha_client_id(ip, user_agent, host) -> str:
     C.memmove(st.ip, raw, 16)
     st.ip_is_v6 = int(v6)
     out = _abi.ClientId()
-    rc = lib().pwaf_client_id_one(C.byref(st), C.addressof(out))
-    if rc != 0:
-        _raise(rc, lib().pwaf_last_error().decode(errors="replace"))
+    _check(lib().pwaf_client_id_one(C.byref(st), C.addressof(out)))
     return out.text.decode("ascii")
 
 
@@ -394,9 +398,7 @@ class CompiledProgram:
         device compiles (csrc/confirm.h). Returns (local atoms of the confirmed literal predicates, flagged, walk)."""
         atoms = (C.c_uint16 * 4096)()
         n, fl, wk = C.c_size_t(), C.c_int(), C.c_int()
-        rc = lib().pwaf_program_confirm_field(self._h, group, data, len(data), arena_offset, atoms, 4096, C.byref(n), C.byref(fl), C.byref(wk))
-        if rc != 0:
-            _raise(rc, lib().pwaf_last_error().decode(errors="replace"))
+        _check(lib().pwaf_program_confirm_field(self._h, group, data, len(data), arena_offset, atoms, 4096, C.byref(n), C.byref(fl), C.byref(wk)))
         return sorted(set(atoms[k] for k in range(n.value))), bool(fl.value), bool(wk.value)
 
     def confirm_shape(self, group: int) -> dict:
@@ -404,9 +406,7 @@ class CompiledProgram:
         entries, pool bytes, class words, in_lds (confirm_kernel compares from its LDS copy), longest factor, highest class position,
         largest bin, has_walk. Raises for a pass without a confirm tier."""
         out = (C.c_uint32 * len(_abi.CONFIRM_SHAPE_FIELDS))()
-        rc = lib().pwaf_program_confirm_shape(self._h, group, out)
-        if rc != 0:
-            _raise(rc, lib().pwaf_last_error().decode(errors="replace"))
+        _check(lib().pwaf_program_confirm_shape(self._h, group, out))
         return dict(zip(_abi.CONFIRM_SHAPE_FIELDS, (int(x) for x in out)))
 
     def flat_image(self, group: int, tier: int = 0) -> bytes:
@@ -415,7 +415,7 @@ class CompiledProgram:
         and end lists. After tune() the table rebuilt for the sample. Raises for a pass without that tier."""
         n = lib().pwaf_program_flat_image(self._h, group, tier, None, 0)
         if n == 0:
-            _raise(_abi.E_INVALID_ARG, lib().pwaf_last_error().decode(errors="replace"))
+            _check(_abi.E_INVALID_ARG)
         buf = C.create_string_buffer(n)
         lib().pwaf_program_flat_image(self._h, group, tier, buf, n)
         return buf.raw
@@ -429,8 +429,7 @@ class CompiledProgram:
         if rc == 0 and n.value:
             out = (C.c_uint32 * (W * n.value))()
             rc = lib().pwaf_program_list_scans(self._h, out, n.value, C.byref(n))
-        if rc != 0:
-            _raise(rc, lib().pwaf_last_error().decode(errors="replace"))
+        _check(rc)
         res = [dict(zip(_abi.LIST_SCAN_FIELDS, (int(x) for x in out[k * W:(k + 1) * W]))) for k in range(n.value)]
         for d in res:
             d["share_owner"] = -1 if d["share_owner"] == 0xFFFFFFFF else d["share_owner"]
@@ -441,9 +440,7 @@ class CompiledProgram:
         by the names of _abi.VERDICT_SHAPE_FIELDS — mode, capacity per wave, waves per workgroup (0: engine creation refuses the program),
         workgroups per CU, tables in LDS, LDS bytes, the pass count it was computed for and the bitmap registers that count selects."""
         out = (C.c_uint32 * len(_abi.VERDICT_SHAPE_FIELDS))()
-        rc = lib().pwaf_program_verdict_shape(self._h, out)
-        if rc != 0:
-            _raise(rc, lib().pwaf_last_error().decode(errors="replace"))
+        _check(lib().pwaf_program_verdict_shape(self._h, out))
         return dict(zip(_abi.VERDICT_SHAPE_FIELDS, (int(x) for x in out)))
 
     def residual_source(self, kind: int = 1) -> str:
@@ -476,9 +473,7 @@ class CompiledProgram:
     def tune(self, sample: RequestBatch) -> None:
         """The host half of RuleEngine.tune on this program alone (no device): the prefilters in the dump become the tuned ones."""
         st = sample.as_struct(self.header_names)
-        rc = lib().pwaf_program_tune(self._h, C.byref(st))
-        if rc != 0:
-            _raise(rc, lib().pwaf_last_error().decode(errors="replace"))
+        _check(lib().pwaf_program_tune(self._h, C.byref(st)))
 
     def warnings(self) -> List[str]:
         return [lib().pwaf_program_warning(self._h, i).decode(errors="replace") for i in range(lib().pwaf_program_warning_count(self._h))]
@@ -553,18 +548,14 @@ class RuleEngine:
         """TEST HOOK (pwaf_engine_address_tables): the shape of this engine's IPv4 lookup structures, by the names of
         _abi.ADDRESS_TABLE_FIELDS — escapes, run-table length, summary present / granularity / common entry, packed, classes, sets."""
         out = (C.c_uint32 * len(_abi.ADDRESS_TABLE_FIELDS))()
-        rc = lib().pwaf_engine_address_tables(self._h, out)
-        if rc != 0:
-            _raise(rc, lib().pwaf_last_error().decode(errors="replace"))
+        _check(lib().pwaf_engine_address_tables(self._h, out))
         return dict(zip(_abi.ADDRESS_TABLE_FIELDS, (int(x) for x in out)))
 
     def coarse_tables(self) -> dict:
         """TEST HOOK (pwaf_engine_coarse_tables): the coarse bitmap in front of the summary — present, shift, bytes, blocks set, the
         summary's blocks set, the lookup kernel's launch shape — by the names of _abi.COARSE_TABLE_FIELDS."""
         out = (C.c_uint32 * len(_abi.COARSE_TABLE_FIELDS))()
-        rc = lib().pwaf_engine_coarse_tables(self._h, out)
-        if rc != 0:
-            _raise(rc, lib().pwaf_last_error().decode(errors="replace"))
+        _check(lib().pwaf_engine_coarse_tables(self._h, out))
         return dict(zip(_abi.COARSE_TABLE_FIELDS, (int(x) for x in out)))
 
     def filter_flags(self, group: int) -> dict:
@@ -574,18 +565,14 @@ class RuleEngine:
         (where each slab's pairs begin) and pair_count (both None for a pass without a pair list)."""
         L = lib()
         info = (C.c_uint32 * len(_abi.FILTER_FLAGS_FIELDS))()
-        rc = L.pwaf_engine_filter_flags(self._h, group, info, None, 0, None, None, 0)
-        if rc != 0:
-            _raise(rc, L.pwaf_last_error().decode(errors="replace"))
+        _check(L.pwaf_engine_filter_flags(self._h, group, info, None, 0, None, None, 0))
         d = dict(zip(_abi.FILTER_FLAGS_FIELDS, (int(x) for x in info)))
         assert d["slab_rows"] == _abi.FILTER_SLAB_ROWS
         slabs = d["slabs"]
         rows = np.zeros(slabs * _abi.FILTER_SLAB_ROWS, dtype="<u8")
         per_slab, pair_base = np.zeros(slabs, dtype=np.uint32), np.zeros(slabs, dtype=np.uint32)
         if slabs:
-            rc = L.pwaf_engine_filter_flags(self._h, group, info, rows.ctypes.data, len(rows), per_slab.ctypes.data, pair_base.ctypes.data, slabs)
-            if rc != 0:
-                _raise(rc, L.pwaf_last_error().decode(errors="replace"))
+            _check(L.pwaf_engine_filter_flags(self._h, group, info, rows.ctypes.data, len(rows), per_slab.ctypes.data, pair_base.ctypes.data, slabs))
         has_pairs = bool(d["has_pairs"])
         return dict(slab0=d["slab0"], slabs=slabs, stride=d["stride"], chunks=np.unpackbits(rows.view(np.uint8), bitorder="little").astype(bool), per_slab=per_slab,
                     pair_base=pair_base if has_pairs else None, pair_count=d["pair_count"] if has_pairs else None)
@@ -594,9 +581,7 @@ class RuleEngine:
         """TEST HOOK (pwaf_engine_geo_answer_tables; OPT_GEO_ANSWERS engines): the shape of the record tables, by the names of
         _abi.GEO_ANSWER_TABLE_FIELDS."""
         out = (C.c_uint32 * len(_abi.GEO_ANSWER_TABLE_FIELDS))()
-        rc = lib().pwaf_engine_geo_answer_tables(self._h, out)
-        if rc != 0:
-            _raise(rc, lib().pwaf_last_error().decode(errors="replace"))
+        _check(lib().pwaf_engine_geo_answer_tables(self._h, out))
         return dict(zip(_abi.GEO_ANSWER_TABLE_FIELDS, (int(x) for x in out)))
 
     def lookup_geoip(self, ip16, v6) -> np.ndarray:
@@ -606,18 +591,14 @@ class RuleEngine:
         v6 = np.ascontiguousarray(v6, dtype=np.uint8).reshape(-1)
         assert len(ip16) == len(v6)
         out = np.zeros(len(v6), dtype=GEO_DTYPE)
-        rc = lib().pwaf_geoip_lookup(self._h, ip16.ctypes.data, v6.ctypes.data, len(v6), _abi.MEM_HOST, out.ctypes.data, None)
-        if rc != 0:
-            _raise(rc, lib().pwaf_last_error().decode(errors="replace"))
+        _check(lib().pwaf_geoip_lookup(self._h, ip16.ctypes.data, v6.ctypes.data, len(v6), _abi.MEM_HOST, out.ctypes.data, None))
         return out
 
     def rule_errors(self, n_rules: int) -> List[int]:
         """Per caller rule: requests (over every batch so far) for which the rule's evaluation ended in an execution error — what the
         reference logs per occurrence (pingoo/rules.rs:41-45). Static errors are creation-time warnings instead."""
         arr = (C.c_uint64 * n_rules)()
-        rc = lib().pwaf_engine_rule_errors(self._h, arr, n_rules)
-        if rc != 0:
-            _raise(rc, lib().pwaf_last_error().decode(errors="replace"))
+        _check(lib().pwaf_engine_rule_errors(self._h, arr, n_rules))
         return list(arr)
 
     def stats(self) -> dict:
@@ -640,8 +621,7 @@ class RuleEngine:
             rc = lib().pwaf_evaluate_batch_geo(self._h, C.byref(st), out.ctypes.data, C.addressof(counts), geo.ctypes.data)
         else:
             rc = lib().pwaf_evaluate_batch(self._h, C.byref(st), out.ctypes.data, C.addressof(counts))
-        if rc != 0:
-            _raise(rc, lib().pwaf_last_error().decode(errors="replace"))
+        _check(rc)
         res = (out, np.array(list(counts.by_action), dtype=np.uint64)) if with_counts else (out,)
         res += (geo,) if with_geo else ()
         return res if len(res) > 1 else res[0]
@@ -654,9 +634,7 @@ class RuleEngine:
         route = np.full(max(1, batch.n), _abi.ROUTE_NONE, dtype=np.uint32)
         counts = _abi.Counts()
         st = batch.as_struct(self.header_names)
-        rc = lib().pwaf_evaluate_batch_routes(self._h, C.byref(st), out.ctypes.data, C.addressof(counts), route.ctypes.data)
-        if rc != 0:
-            _raise(rc, lib().pwaf_last_error().decode(errors="replace"))
+        _check(lib().pwaf_evaluate_batch_routes(self._h, C.byref(st), out.ctypes.data, C.addressof(counts), route.ctypes.data))
         res = (out, route[:batch.n].view(np.int32))
         return res + (np.array(list(counts.by_action), dtype=np.uint64),) if with_counts else res
 
@@ -665,9 +643,7 @@ class RuleEngine:
         st, _keep = _request_struct(request, self.header_names)
         out = _abi.Verdict()
         route = C.c_uint32(_abi.ROUTE_NONE)
-        rc = lib().pwaf_evaluate_one_route(self._h, C.byref(st), C.byref(out), C.byref(route))
-        if rc != 0:
-            _raise(rc, lib().pwaf_last_error().decode(errors="replace"))
+        _check(lib().pwaf_evaluate_one_route(self._h, C.byref(st), C.byref(out), C.byref(route)))
         return verdict_from_record({"action": out.action, "rule_idx": out.rule_idx}), (-1 if route.value == _abi.ROUTE_NONE else int(route.value))
 
     def evaluate_batch_hits_into(self, batch: RequestBatch, hits: Optional[np.ndarray], cap: int = 0, with_rule_hits: bool = True):
@@ -682,8 +658,7 @@ class RuleEngine:
         st = batch.as_struct(self.header_names)
         rc = lib().pwaf_evaluate_batch_hits(self._h, C.byref(st), out.ctypes.data, C.addressof(counts), None if hits is None else max(hits.ctypes.data, 1), cap,
                                             None if hits is None else C.addressof(n_hits), None if rule_hits is None else rule_hits.ctypes.data)
-        if rc != 0:
-            _raise(rc, lib().pwaf_last_error().decode(errors="replace"))
+        _check(rc)
         return (out, np.array(list(counts.by_action), dtype=np.uint64), None if hits is None else int(n_hits.value),
                 None if rule_hits is None else rule_hits[:len(self.rules)])
 
@@ -716,8 +691,7 @@ class RuleEngine:
             rc = lib().pwaf_evaluate_records_geo(self._h, buf.ctypes.data, buf.nbytes, rec_off.ctypes.data, len(rec_off), out.ctypes.data, C.addressof(counts), geo.ctypes.data)
         else:
             rc = lib().pwaf_evaluate_records(self._h, buf.ctypes.data, buf.nbytes, rec_off.ctypes.data, len(rec_off), out.ctypes.data, C.addressof(counts))
-        if rc != 0:
-            _raise(rc, lib().pwaf_last_error().decode(errors="replace"))
+        _check(rc)
         res = (out, np.array(list(counts.by_action), dtype=np.uint64)) if with_counts else (out,)
         res += (geo,) if with_geo else ()
         return res if len(res) > 1 else res[0]
@@ -747,8 +721,7 @@ class RuleEngine:
                                                 None if n_rec is None else n_rec.data_ptr(), out.data_ptr(), None if counts is None else counts.data_ptr(),
                                                 None if match_idx is None else match_idx.data_ptr(), None if n_matches is None else n_matches.data_ptr(),
                                                 C.c_void_p(stream))
-        if rc != 0:
-            _raise(rc, lib().pwaf_last_error().decode(errors="replace"))
+        _check(rc)
         return out
 
     def client_ids(self, batch, idx=None, n_idx=None, stream=None):
@@ -793,8 +766,7 @@ class RuleEngine:
             rc = lib().pwaf_evaluate_one_geo(self._h, C.byref(st), C.byref(out), C.byref(geo))
         else:
             rc = lib().pwaf_evaluate_one(self._h, C.byref(st), C.byref(out))
-        if rc != 0:
-            _raise(rc, lib().pwaf_last_error().decode(errors="replace"))
+        _check(rc)
         v = verdict_from_record({"action": out.action, "rule_idx": out.rule_idx})
         return (v, (int(geo.asn), bytes(geo.country).decode("latin-1"))) if with_geo else v
 
@@ -833,22 +805,17 @@ class RuleEngine:
             rc = lib().pwaf_evaluate_device_geo(*args, geo.data_ptr(), C.c_void_p(stream))
         else:
             rc = lib().pwaf_evaluate_device(*args, C.c_void_p(stream))
-        if rc != 0:
-            _raise(rc, lib().pwaf_last_error().decode(errors="replace"))
+        _check(rc)
         return out
 
     def device_status(self) -> None:
         """Synchronises and raises if the last device-resident batch ran out of scan scratch."""
-        rc = lib().pwaf_engine_device_status(self._h)
-        if rc != 0:
-            _raise(rc, lib().pwaf_last_error().decode(errors="replace"))
+        _check(lib().pwaf_engine_device_status(self._h))
 
     def tune(self, sample: RequestBatch) -> None:
         """Re-selects the LDS-resident DFA rows from a host traffic sample (speed only; verdicts never change)."""
         st = sample.as_struct(self.header_names)
-        rc = lib().pwaf_engine_tune(self._h, C.byref(st))
-        if rc != 0:
-            _raise(rc, lib().pwaf_last_error().decode(errors="replace"))
+        _check(lib().pwaf_engine_tune(self._h, C.byref(st)))
 
     def set_profiling(self, on):
         """False / 0: off; True / 1: HIP events around every kernel; 2: only around the launches that stream the request bytes."""
@@ -858,7 +825,7 @@ class RuleEngine:
         arr = (_abi.KernelTime * 8192)()
         n = lib().pwaf_engine_kernel_times(self._h, arr, 8192)
         if n < 0:
-            _raise(n, lib().pwaf_last_error().decode(errors="replace"))
+            _check(n)
         return [(arr[i].name.decode(), float(arr[i].ms), int(arr[i].alg_bytes)) for i in range(n)]
 
 
@@ -878,7 +845,7 @@ class NodeEngine:
         devs = (C.c_int * len(devices))(*devices)
         rc = L.pwaf_node_create(r, nr, l, nl, g, C.byref(o), devs, len(devices), C.byref(h), C.byref(err))
         if rc < 0:
-            _raise(rc, err.message.decode(errors="replace") or L.pwaf_last_error().decode(errors="replace"), None if err.rule_index == 0xFFFFFFFF else err.rule_index)
+            _check(rc, err.message.decode(errors="replace"), None if err.rule_index == 0xFFFFFFFF else err.rule_index)
         self.partial = rc == _abi.W_PARTIAL  # PWAF_OPT_LENIENT dropped a rule (see the program's rule status / warnings)
         self._h = h
         e0 = L.pwaf_node_engine(h, 0)
@@ -889,9 +856,7 @@ class NodeEngine:
         out = np.zeros(batch.n, dtype=VERDICT_DTYPE)
         counts = _abi.Counts()
         st = batch.as_struct(self.header_names)
-        rc = lib().pwaf_node_evaluate_batch(self._h, C.byref(st), out.ctypes.data, C.addressof(counts))
-        if rc != 0:
-            _raise(rc, lib().pwaf_last_error().decode(errors="replace"))
+        _check(lib().pwaf_node_evaluate_batch(self._h, C.byref(st), out.ctypes.data, C.addressof(counts)))
         return (out, np.array(list(counts.by_action), dtype=np.uint64)) if with_counts else out
 
     def evaluate_device(self, dbatches, outs, counts=None, streams=None) -> None:
@@ -904,9 +869,7 @@ class NodeEngine:
         o = (C.c_void_p * k)(*[t.data_ptr() for t in outs])
         c = (C.c_void_p * k)(*[t.data_ptr() for t in counts]) if counts is not None else None
         st = (C.c_void_p * k)(*[int(x) for x in streams]) if streams is not None else None
-        rc = lib().pwaf_node_evaluate_device(self._h, arr, o, c, st)
-        if rc != 0:
-            _raise(rc, lib().pwaf_last_error().decode(errors="replace"))
+        _check(lib().pwaf_node_evaluate_device(self._h, arr, o, c, st))
 
     def allreduce_counts(self, comms, counts, streams=None) -> None:
         """pwaf_node_allreduce_counts: the per-device int64[4] counter tensors summed in place over RCCL; `comms` = one ncclComm_t
@@ -915,20 +878,14 @@ class NodeEngine:
         cm = (C.c_void_p * k)(*[int(x) for x in comms])
         c = (C.c_void_p * k)(*[t.data_ptr() for t in counts])
         st = (C.c_void_p * k)(*[int(x) for x in streams]) if streams is not None else None
-        rc = lib().pwaf_node_allreduce_counts(self._h, cm, c, st)
-        if rc != 0:
-            _raise(rc, lib().pwaf_last_error().decode(errors="replace"))
+        _check(lib().pwaf_node_allreduce_counts(self._h, cm, c, st))
 
     def synchronize(self) -> None:
-        rc = lib().pwaf_node_synchronize(self._h)
-        if rc != 0:
-            _raise(rc, lib().pwaf_last_error().decode(errors="replace"))
+        _check(lib().pwaf_node_synchronize(self._h))
 
     def tune(self, sample: RequestBatch) -> None:
         st = sample.as_struct(self.header_names)
-        rc = lib().pwaf_node_tune(self._h, C.byref(st))
-        if rc != 0:
-            _raise(rc, lib().pwaf_last_error().decode(errors="replace"))
+        _check(lib().pwaf_node_tune(self._h, C.byref(st)))
 
     def close(self):
         if getattr(self, "_h", None):
@@ -946,9 +903,7 @@ class PinnedVerdicts:
     def __init__(self, n: int):
         p = C.c_void_p()
         nbytes = max(1, n) * VERDICT_DTYPE.itemsize
-        rc = lib().pwaf_host_alloc(nbytes, C.byref(p))
-        if rc != 0:
-            _raise(rc, lib().pwaf_last_error().decode(errors="replace"))
+        _check(lib().pwaf_host_alloc(nbytes, C.byref(p)))
         self._p = p
         self.array = np.frombuffer((C.c_uint8 * nbytes).from_address(p.value), dtype=VERDICT_DTYPE, count=n)
 
@@ -1032,17 +987,13 @@ class MicroBatcher:
     def __init__(self, engine: "RuleEngine", max_batch: int = 4096, max_delay_us: int = 200):
         self._engine = engine  # keeps the engine alive
         h = C.c_void_p()
-        rc = lib().pwaf_batcher_create(engine._h, max_batch, max_delay_us, C.byref(h))
-        if rc != 0:
-            _raise(rc, lib().pwaf_last_error().decode(errors="replace"))
+        _check(lib().pwaf_batcher_create(engine._h, max_batch, max_delay_us, C.byref(h)))
         self._h = h
 
     def evaluate(self, request: Request) -> Verdict:
         st, _keep = _request_struct(request, self._engine.header_names)
         out = _abi.Verdict()
-        rc = lib().pwaf_batcher_evaluate(self._h, C.byref(st), C.byref(out))
-        if rc != 0:
-            _raise(rc, lib().pwaf_last_error().decode(errors="replace"))
+        _check(lib().pwaf_batcher_evaluate(self._h, C.byref(st), C.byref(out)))
         return verdict_from_record({"action": out.action, "rule_idx": out.rule_idx})
 
     def stats(self) -> Tuple[int, int]:
@@ -1105,9 +1056,7 @@ class AsyncBatcher:
         self._engine = engine  # keeps the engine alive
         self._geo = geo  # pwaf_async_create_geo (OPT_GEO_ANSWERS engines): completions carry the request's GeoIP record
         h = C.c_void_p()
-        rc = (lib().pwaf_async_create_geo if geo else lib().pwaf_async_create)(engine._h, max_batch, max_delay_us, max_in_flight, C.byref(h))
-        if rc != 0:
-            _raise(rc, lib().pwaf_last_error().decode(errors="replace"))
+        _check((lib().pwaf_async_create_geo if geo else lib().pwaf_async_create)(engine._h, max_batch, max_delay_us, max_in_flight, C.byref(h)))
         self._h = h
 
     def submit(self, request: Request, tag: int) -> bool:
@@ -1115,8 +1064,7 @@ class AsyncBatcher:
         rc = lib().pwaf_async_submit(self._h, C.byref(st), tag)
         if rc == _abi.E_BUSY:
             return False
-        if rc != 0:
-            _raise(rc, lib().pwaf_last_error().decode(errors="replace"))
+        _check(rc)
         return True
 
     def poll(self, cap: int = 4096, with_geo: bool = False):
@@ -1126,7 +1074,7 @@ class AsyncBatcher:
             garr = (_abi.Geo * cap)()
             k = lib().pwaf_async_poll_geo(self._h, arr, garr, cap)
             if k == 0 and not self._geo:
-                _raise(_abi.E_UNSUPPORTED, lib().pwaf_last_error().decode(errors="replace"))
+                _check(_abi.E_UNSUPPORTED)
             return [(arr[i].tag, verdict_from_record({"action": arr[i].verdict.action, "rule_idx": arr[i].verdict.rule_idx}), arr[i].status,
                      (int(garr[i].asn), bytes(garr[i].country).decode("latin-1"))) for i in range(k)]
         k = lib().pwaf_async_poll(self._h, arr, cap)
@@ -1223,9 +1171,7 @@ def geoip_from_mmdb(content: bytes, path: str = "geoip.mmdb") -> np.ndarray:
     from .batch import GEOIP_DTYPE
 
     ptr, n = C.POINTER(_abi.GeoipEntry)(), C.c_size_t(0)
-    rc = lib().pwaf_geoip_from_file_image(path.encode(), content, len(content), C.byref(ptr), C.byref(n))
-    if rc != 0:
-        _raise(rc, lib().pwaf_last_error().decode(errors="replace"))
+    _check(lib().pwaf_geoip_from_file_image(path.encode(), content, len(content), C.byref(ptr), C.byref(n)))
     try:
         out = np.zeros(n.value, dtype=GEOIP_DTYPE)
         if n.value:
@@ -1237,9 +1183,7 @@ def geoip_from_mmdb(content: bytes, path: str = "geoip.mmdb") -> np.ndarray:
 
 def zstd_decompress(data: bytes) -> bytes:
     out, n = C.c_void_p(), C.c_size_t(0)
-    rc = lib().pwaf_zstd_decompress(data, len(data), C.byref(out), C.byref(n))
-    if rc != 0:
-        _raise(rc, lib().pwaf_last_error().decode(errors="replace"))
+    _check(lib().pwaf_zstd_decompress(data, len(data), C.byref(out), C.byref(n)))
     try:
         return C.string_at(out, n.value)
     finally:
@@ -1250,9 +1194,7 @@ def parse_list_csv(text) -> List[str]:
     """List file content -> items (pingoo/lists.rs:62-117: CSV, no header, 1-2 columns, first column trimmed)."""
     raw = text.encode() if isinstance(text, str) else bytes(text)
     items, n = C.POINTER(C.c_char_p)(), C.c_size_t(0)
-    rc = lib().pwaf_list_parse_csv(raw, len(raw), C.byref(items), C.byref(n))
-    if rc != 0:
-        _raise(rc, lib().pwaf_last_error().decode(errors="replace"))
+    _check(lib().pwaf_list_parse_csv(raw, len(raw), C.byref(items), C.byref(n)))
     try:
         return [items[k].decode(errors="surrogateescape") for k in range(n.value)]
     finally:
@@ -1273,6 +1215,56 @@ def _aligned_bytes(nbytes: int) -> np.ndarray:
     return raw[at:at + nbytes]
 
 
+def _host_list(n: int, idx, n_idx):
+    """The list arguments of a HOST-mode call over n requests -> (idx_ptr, idx_len, n_idx_ptr, m, keep). idx None: every request, a NULL
+    idx and m = n. Else idx_len entries, of which m = min(idx_len, n_idx) count (n_idx clamps m here only: the library reads it itself);
+    an empty list is not NULL, which would mean every request. `keep` owns what the pointers point at."""
+    if idx is None:
+        assert n_idx is None
+        return None, 0, None, n, ()
+    idx = np.ascontiguousarray(idx, dtype=np.uint32).reshape(-1)
+    n_ref = None if n_idx is None else np.array([int(np.asarray(n_idx).reshape(-1)[0])], dtype=np.uint32)
+    keep = idx if len(idx) else np.zeros(1, dtype=np.uint32)
+    return keep.ctypes.data, len(idx), None if n_ref is None else n_ref.ctypes.data, len(idx) if n_ref is None else min(len(idx), int(n_ref[0])), (keep, n_ref)
+
+
+def _device_list(n: int, idx, n_idx):
+    """_host_list for device tensors: idx and n_idx (one element) are 32 bits wide and stay on the device, so m = idx_len."""
+    if idx is None:
+        assert n_idx is None
+        return None, 0, None, n, ()
+    import torch
+
+    assert idx.is_contiguous() and idx.element_size() == 4 and (n_idx is None or n_idx.element_size() == 4)
+    m = idx.numel()
+    keep = idx if m else torch.zeros(1, dtype=torch.int32, device=idx.device)
+    return keep.data_ptr(), m, None if n_idx is None else n_idx.data_ptr(), m, (keep, n_idx)
+
+
+def _strcol(values, device=None):
+    """A list of bytes | str | None, or a (data, offsets) pair -> (an _abi.StrCol, the (data, offsets) it points at) in host memory, or on
+    `device` (a list is uploaded)."""
+    col = _abi.StrCol()
+    data, off = values if isinstance(values, tuple) else cookie_column(values)
+    if device is None:
+        data, off = np.ascontiguousarray(data, dtype=np.uint8), np.ascontiguousarray(off, dtype=np.uint32)
+        col.data, col.offsets = data.ctypes.data, off.ctypes.data
+        return col, (data, off)
+    import torch
+
+    if not torch.is_tensor(off):
+        data, off = torch.from_numpy(data).to(device), torch.from_numpy(off.view(np.int32)).to(device)
+    assert data.is_contiguous() and off.is_contiguous() and off.element_size() == 4
+    col.data, col.offsets = data.data_ptr(), off.data_ptr()
+    return col, (data, off)
+
+
+def _scan_shape(fn, fields) -> dict:
+    out = (C.c_uint32 * 4)()
+    _check(fn(out))
+    return dict(zip(fields, (int(x) for x in out)))
+
+
 def export_records(batch, idx, n_idx=None, cap=None, stream=None, header_names: Optional[Sequence[str]] = None):
     """The requests of `batch` that the list `idx` names, as request records (pwaf_export_records; include/pwaf.h) -> (buf, rec_off, stats):
     the record of request idx[j] starts at buf[rec_off[j]], or rec_off[j] == _abi.RECORD_NONE when it has none (it did not fit `cap`
@@ -1288,16 +1280,12 @@ def export_records(batch, idx, n_idx=None, cap=None, stream=None, header_names: 
     names = list(batch.headers) if header_names is None else list(header_names)
     st = batch.as_struct(names)
     if isinstance(batch, RequestBatch):
-        idx = np.ascontiguousarray(idx, dtype=np.uint32).reshape(-1)
-        n_ref = None if n_idx is None else np.array([int(np.asarray(n_idx).reshape(-1)[0])], dtype=np.uint32)
-        rec_off = np.full(max(1, len(idx)), _abi.RECORD_NONE, dtype=np.uint32)
+        idx_ptr, n_list, n_ptr, _, keep = _host_list(batch.n, np.asarray(idx), n_idx)
+        rec_off = np.full(max(1, n_list), _abi.RECORD_NONE, dtype=np.uint32)
         stats = _abi.ExportStats()
 
         def call(buf, nbytes):
-            rc = lib().pwaf_export_records(C.byref(st), idx.ctypes.data if len(idx) else None, len(idx), None if n_ref is None else n_ref.ctypes.data,
-                                           None if buf is None else buf.ctypes.data, nbytes, rec_off.ctypes.data, C.addressof(stats), None)
-            if rc != 0:
-                _raise(rc, lib().pwaf_last_error().decode(errors="replace"))
+            _check(lib().pwaf_export_records(C.byref(st), idx_ptr, n_list, n_ptr, None if buf is None else buf.ctypes.data, nbytes, rec_off.ctypes.data, C.addressof(stats), None))
 
         if cap is None:
             call(None, 0)
@@ -1305,7 +1293,8 @@ def export_records(batch, idx, n_idx=None, cap=None, stream=None, header_names: 
         buf = _aligned_bytes(int(cap))
         call(buf, int(cap))
         res = {"bytes_needed": int(stats.bytes_needed), "n_selected": int(stats.n_selected), "n_written": int(stats.n_written)}
-        return buf[:min(int(cap), res["bytes_needed"])], rec_off[:len(idx)], res
+        del keep
+        return buf[:min(int(cap), res["bytes_needed"])], rec_off[:n_list], res
     import torch
 
     assert idx.is_contiguous() and idx.element_size() == 4 and (n_idx is None or n_idx.element_size() == 4)
@@ -1321,8 +1310,7 @@ def export_records(batch, idx, n_idx=None, cap=None, stream=None, header_names: 
     stats = torch.empty(16, dtype=torch.uint8, device=batch.device)
     rc = lib().pwaf_export_records(C.byref(st), idx.data_ptr() if n_list else None, n_list, None if n_idx is None else n_idx.data_ptr(), buf.data_ptr(), int(cap),
                                    rec_off.data_ptr(), stats.data_ptr(), C.c_void_p(stream))
-    if rc != 0:
-        _raise(rc, lib().pwaf_last_error().decode(errors="replace"))
+    _check(rc)
     return buf[:int(cap)], rec_off[:n_list], stats
 
 
@@ -1337,38 +1325,22 @@ def client_ids(batch, idx=None, n_idx=None, stream=None):
     batch's requests) to be read after the stream is synchronised; rows at or past n_idx are not written."""
     st = batch.as_struct()
     if isinstance(batch, RequestBatch):
-        if idx is None:
-            assert n_idx is None
-            m = batch.n
-        else:
-            idx = np.ascontiguousarray(idx, dtype=np.uint32).reshape(-1)
-            m = len(idx) if n_idx is None else min(len(idx), int(np.asarray(n_idx).reshape(-1)[0]))
-            if not len(idx):
-                return []  # (a NULL idx would mean every request)
-        n_ref = None if n_idx is None else np.array([int(np.asarray(n_idx).reshape(-1)[0])], dtype=np.uint32)
+        idx_ptr, n_list, n_ptr, m, keep = _host_list(batch.n, idx, n_idx)
+        if idx is not None and not n_list:
+            return []
         out = np.zeros((max(1, m), 44), dtype=np.uint8)
-        rc = lib().pwaf_client_ids(C.byref(st), None if idx is None else idx.ctypes.data, 0 if idx is None else len(idx),
-                                   None if n_ref is None else n_ref.ctypes.data, out.ctypes.data, None)
-        if rc != 0:
-            _raise(rc, lib().pwaf_last_error().decode(errors="replace"))
+        _check(lib().pwaf_client_ids(C.byref(st), idx_ptr, n_list, n_ptr, out.ctypes.data, None))
+        del keep
         return [row.tobytes().split(b"\0", 1)[0].decode("ascii") for row in out[:m]]
     import torch
 
-    if idx is None:
-        assert n_idx is None
-        m = batch.n
-    else:
-        assert idx.is_contiguous() and idx.element_size() == 4 and (n_idx is None or n_idx.element_size() == 4)
-        m = idx.numel()
+    idx_ptr, n_list, n_ptr, m, _ = _device_list(batch.n, idx, n_idx)
     if stream is None:
         stream = torch.cuda.current_stream(batch.device).cuda_stream
     out = torch.empty((max(1, m), 44), dtype=torch.uint8, device=batch.device)
     if idx is not None and not m:
-        return out[:0]  # (a NULL idx would mean every request)
-    rc = lib().pwaf_client_ids(C.byref(st), None if idx is None else idx.data_ptr(), 0 if idx is None else m,
-                               None if n_idx is None else n_idx.data_ptr(), out.data_ptr(), C.c_void_p(stream))
-    if rc != 0:
-        _raise(rc, lib().pwaf_last_error().decode(errors="replace"))
+        return out[:0]
+    _check(lib().pwaf_client_ids(C.byref(st), idx_ptr, n_list, n_ptr, out.data_ptr(), C.c_void_p(stream)))
     return out[:m]
 
 
@@ -1399,9 +1371,7 @@ class KeySet:
             arr[k].kid = kid
             C.memmove(arr[k].x, x, 32)
         h = C.c_void_p()
-        rc = lib().pwaf_keyset_create(arr, len(keys), ordinal, C.byref(h))
-        if rc != 0:
-            _raise(rc, lib().pwaf_last_error().decode(errors="replace"))
+        _check(lib().pwaf_keyset_create(arr, len(keys), ordinal, C.byref(h)))
         self._h, self.device, self.kids = h, ordinal, [kid.decode(errors="replace") for kid, _ in keys]
 
     def close(self):
@@ -1438,57 +1408,35 @@ def verify_cookies(keyset, batch, cookies, now, idx=None, n_idx=None, flags_out=
     the call returns -> a uint8 tensor to be read after the stream is synchronised; entries at or past n_idx are not written. With
     flags_out = batch.flags an evaluate_device on the same stream follows without a synchronisation by the caller."""
     st = batch.as_struct()
-    col = _abi.StrCol()
     if isinstance(batch, RequestBatch):
-        data, off = cookies if isinstance(cookies, tuple) else cookie_column(cookies)
-        data, off = np.ascontiguousarray(data, dtype=np.uint8), np.ascontiguousarray(off, dtype=np.uint32)
-        assert len(off) == batch.n + 1
-        col.data, col.offsets = data.ctypes.data, off.ctypes.data
-        if idx is None:
-            assert n_idx is None
-            m = batch.n
-        else:
-            idx = np.ascontiguousarray(idx, dtype=np.uint32).reshape(-1)
-            m = len(idx) if n_idx is None else min(len(idx), int(np.asarray(n_idx).reshape(-1)[0]))
-            if not len(idx):
-                return np.zeros(0, dtype=np.uint8)  # (a NULL idx would mean every request)
-        n_ref = None if n_idx is None else np.array([int(np.asarray(n_idx).reshape(-1)[0])], dtype=np.uint32)
+        col, cmem = _strcol(cookies)  # (cmem, like keep below, owns what the call reads)
+        assert len(cmem[1]) == batch.n + 1
+        idx_ptr, n_list, n_ptr, m, keep = _host_list(batch.n, idx, n_idx)
+        if idx is not None and not n_list:
+            return np.zeros(0, dtype=np.uint8)
         if flags_out is not None:
             assert isinstance(flags_out, np.ndarray) and flags_out.dtype == np.uint8 and flags_out.flags.c_contiguous and flags_out.size == batch.n
         out = np.zeros(max(1, m), dtype=np.uint8)
-        rc = lib().pwaf_verify_cookies(keyset._h, C.byref(st), C.byref(col), int(now), None if idx is None else idx.ctypes.data, 0 if idx is None else len(idx),
-                                       None if n_ref is None else n_ref.ctypes.data, out.ctypes.data, None if flags_out is None else flags_out.ctypes.data, None, 0, None)
-        if rc != 0:
-            _raise(rc, lib().pwaf_last_error().decode(errors="replace"))
+        _check(lib().pwaf_verify_cookies(keyset._h, C.byref(st), C.byref(col), int(now), idx_ptr, n_list, n_ptr, out.ctypes.data,
+                                         None if flags_out is None else flags_out.ctypes.data, None, 0, None))
+        del keep, cmem
         return out[:m]
     import torch
 
-    if not isinstance(cookies, tuple):
-        data, off = cookie_column(cookies)
-        cookies = (torch.from_numpy(data).to(batch.device), torch.from_numpy(off.view(np.int32)).to(batch.device))
-    data, off = cookies
-    assert data.is_contiguous() and off.is_contiguous() and off.element_size() == 4 and off.numel() == batch.n + 1
-    col.data, col.offsets = data.data_ptr(), off.data_ptr()
-    if idx is None:
-        assert n_idx is None
-        m = batch.n
-    else:
-        assert idx.is_contiguous() and idx.element_size() == 4 and (n_idx is None or n_idx.element_size() == 4)
-        m = idx.numel()
+    col, cmem = _strcol(cookies, batch.device)
+    assert len(cmem[1]) == batch.n + 1
+    idx_ptr, n_list, n_ptr, m, _ = _device_list(batch.n, idx, n_idx)
     if flags_out is not None:
         assert flags_out.is_contiguous() and flags_out.element_size() == 1 and flags_out.numel() == batch.n
     if stream is None:
         stream = torch.cuda.current_stream(batch.device).cuda_stream
     out = torch.empty(max(1, m), dtype=torch.uint8, device=batch.device)
     if not m:
-        return out[:0]  # (a NULL idx would mean every request)
+        return out[:0]
     need = int(lib().pwaf_verify_cookies_scratch_bytes(m))
     scratch = torch.empty(need, dtype=torch.uint8, device=batch.device)
-    rc = lib().pwaf_verify_cookies(keyset._h, C.byref(st), C.byref(col), int(now), None if idx is None else idx.data_ptr(), 0 if idx is None else m,
-                                   None if n_idx is None else n_idx.data_ptr(), out.data_ptr(), None if flags_out is None else flags_out.data_ptr(),
-                                   scratch.data_ptr(), need, C.c_void_p(stream))
-    if rc != 0:
-        _raise(rc, lib().pwaf_last_error().decode(errors="replace"))
+    _check(lib().pwaf_verify_cookies(keyset._h, C.byref(st), C.byref(col), int(now), idx_ptr, n_list, n_ptr, out.data_ptr(), None if flags_out is None else flags_out.data_ptr(),
+                                     scratch.data_ptr(), need, C.c_void_p(stream)))
     return out[:m]
 
 
@@ -1500,8 +1448,7 @@ def verify_cookie(keyset, request, cookie, now) -> int:
     out = C.c_uint8(0xEE)
     rc = lib().pwaf_verify_cookie_one(keyset._h, C.byref(st), c, 0 if c is None else len(c), int(now), C.byref(out))
     del keep
-    if rc != 0:
-        _raise(rc, lib().pwaf_last_error().decode(errors="replace"))
+    _check(rc)
     return int(out.value)
 
 
@@ -1538,63 +1485,35 @@ def verify_pow(keyset, batch, cookies, hashes, nonces, now, idx=None, n_idx=None
     synchronised (entries at or past n_idx are not written); it keeps the call's scratch reachable as `.pow_scratch`, whose word 0
     pow_handed(status) reads: the diagnostic."""
     st = batch.as_struct()
-    col, ncol = _abi.StrCol(), _abi.StrCol()
     if isinstance(batch, RequestBatch):
-        data, off = cookies if isinstance(cookies, tuple) else cookie_column(cookies)
-        data, off = np.ascontiguousarray(data, dtype=np.uint8), np.ascontiguousarray(off, dtype=np.uint32)
-        ndata, noff = nonces if isinstance(nonces, tuple) else cookie_column(nonces)
-        ndata, noff = np.ascontiguousarray(ndata, dtype=np.uint8), np.ascontiguousarray(noff, dtype=np.uint32)
-        assert len(off) == batch.n + 1 and len(noff) == batch.n + 1
-        col.data, col.offsets, ncol.data, ncol.offsets = data.ctypes.data, off.ctypes.data, ndata.ctypes.data, noff.ctypes.data
+        (col, cmem), (ncol, nmem) = _strcol(cookies), _strcol(nonces)
+        assert len(cmem[1]) == batch.n + 1 and len(nmem[1]) == batch.n + 1
         rows = _hash_rows(hashes, batch.n)
         hbuf = rows if batch.n else np.zeros((1, 32), dtype=np.uint8)
-        if idx is None:
-            assert n_idx is None
-            m = batch.n
-        else:
-            idx = np.ascontiguousarray(idx, dtype=np.uint32).reshape(-1)
-            m = len(idx) if n_idx is None else min(len(idx), int(np.asarray(n_idx).reshape(-1)[0]))
-            if not len(idx):
-                return np.zeros(0, dtype=np.uint8)  # (a NULL idx would mean every request)
-        n_ref = None if n_idx is None else np.array([int(np.asarray(n_idx).reshape(-1)[0])], dtype=np.uint32)
+        idx_ptr, n_list, n_ptr, m, keep = _host_list(batch.n, idx, n_idx)
+        if idx is not None and not n_list:
+            return np.zeros(0, dtype=np.uint8)
         out = np.zeros(max(1, m), dtype=np.uint8)
-        rc = lib().pwaf_verify_pow(keyset._h, C.byref(st), C.byref(col), hbuf.ctypes.data, C.byref(ncol), int(now), None if idx is None else idx.ctypes.data,
-                                   0 if idx is None else len(idx), None if n_ref is None else n_ref.ctypes.data, out.ctypes.data, None, 0, None)
-        if rc != 0:
-            _raise(rc, lib().pwaf_last_error().decode(errors="replace"))
+        _check(lib().pwaf_verify_pow(keyset._h, C.byref(st), C.byref(col), hbuf.ctypes.data, C.byref(ncol), int(now), idx_ptr, n_list, n_ptr, out.ctypes.data, None, 0, None))
+        del keep, cmem, nmem
         return out[:m]
     import torch
 
-    def column(values):
-        if isinstance(values, tuple):
-            return values
-        d, o = cookie_column(values)
-        return torch.from_numpy(d).to(batch.device), torch.from_numpy(o.view(np.int32)).to(batch.device)
-
-    (data, off), (ndata, noff) = column(cookies), column(nonces)
-    for d, o in ((data, off), (ndata, noff)):
-        assert d.is_contiguous() and o.is_contiguous() and o.element_size() == 4 and o.numel() == batch.n + 1
-    col.data, col.offsets, ncol.data, ncol.offsets = data.data_ptr(), off.data_ptr(), ndata.data_ptr(), noff.data_ptr()
+    (col, cmem), (ncol, nmem) = _strcol(cookies, batch.device), _strcol(nonces, batch.device)
+    assert len(cmem[1]) == batch.n + 1 and len(nmem[1]) == batch.n + 1
     if not torch.is_tensor(hashes):
         hashes = torch.from_numpy(_hash_rows(hashes, batch.n)).to(batch.device)
     assert hashes.is_contiguous() and hashes.element_size() == 1 and hashes.numel() == 32 * batch.n
-    if idx is None:
-        assert n_idx is None
-        m = batch.n
-    else:
-        assert idx.is_contiguous() and idx.element_size() == 4 and (n_idx is None or n_idx.element_size() == 4)
-        m = idx.numel()
+    idx_ptr, n_list, n_ptr, m, _ = _device_list(batch.n, idx, n_idx)
     if stream is None:
         stream = torch.cuda.current_stream(batch.device).cuda_stream
     out = torch.empty(max(1, m), dtype=torch.uint8, device=batch.device)
     if not m:
-        return out[:0]  # (a NULL idx would mean every request)
+        return out[:0]
     need = int(lib().pwaf_verify_pow_scratch_bytes(m))
     scratch = torch.empty(need, dtype=torch.uint8, device=batch.device)
-    rc = lib().pwaf_verify_pow(keyset._h, C.byref(st), C.byref(col), hashes.data_ptr(), C.byref(ncol), int(now), None if idx is None else idx.data_ptr(),
-                               0 if idx is None else m, None if n_idx is None else n_idx.data_ptr(), out.data_ptr(), scratch.data_ptr(), need, C.c_void_p(stream))
-    if rc != 0:
-        _raise(rc, lib().pwaf_last_error().decode(errors="replace"))
+    _check(lib().pwaf_verify_pow(keyset._h, C.byref(st), C.byref(col), hashes.data_ptr(), C.byref(ncol), int(now), idx_ptr, n_list, n_ptr, out.data_ptr(), scratch.data_ptr(), need,
+                                 C.c_void_p(stream)))
     status = out[:m]
     status.pow_scratch = scratch
     return status
@@ -1612,8 +1531,7 @@ def verify_pow_one(keyset, request, cookie, hash, nonce, now) -> int:
     out = C.c_uint8(0xEE)
     rc = lib().pwaf_verify_pow_one(keyset._h, C.byref(st), c, 0 if c is None else len(c), h, nv, len(nv), int(now), C.byref(out))
     del keep
-    if rc != 0:
-        _raise(rc, lib().pwaf_last_error().decode(errors="replace"))
+    _check(rc)
     return int(out.value)
 
 
@@ -1633,11 +1551,7 @@ def body_stats(stats) -> dict:
 
 def parse_pow_scan_shape() -> dict:
     """TEST HOOK (pwaf_parse_pow_scan_shape): the shape of parse_pow_bodies' scan, by the names of _abi.PARSE_POW_SCAN_SHAPE_FIELDS."""
-    out = (C.c_uint32 * 4)()
-    rc = lib().pwaf_parse_pow_scan_shape(out)
-    if rc != 0:
-        _raise(rc, lib().pwaf_last_error().decode(errors="replace"))
-    return dict(zip(_abi.PARSE_POW_SCAN_SHAPE_FIELDS, (int(x) for x in out)))
+    return _scan_shape(lib().pwaf_parse_pow_scan_shape, _abi.PARSE_POW_SCAN_SHAPE_FIELDS)
 
 
 def parse_pow_bodies(bodies, n=None, idx=None, n_idx=None, stream=None, cap=None):
@@ -1658,20 +1572,13 @@ def parse_pow_bodies(bodies, n=None, idx=None, n_idx=None, stream=None, cap=None
         bodies = body_column(bodies)
     data, off = bodies
     host_mode = isinstance(off, np.ndarray)
-    col, ncol = _abi.StrCol(), _abi.DerivedCol()
+    col, (data, off) = _strcol(bodies, None if host_mode else off.device)
+    ncol = _abi.DerivedCol()
+    if n is None:
+        n = len(off) - 1
+    assert len(off) >= n + 1
     if host_mode:
-        data, off = np.ascontiguousarray(data, dtype=np.uint8), np.ascontiguousarray(off, dtype=np.uint32)
-        if n is None:
-            n = len(off) - 1
-        assert len(off) >= n + 1
-        col.data, col.offsets = data.ctypes.data, off.ctypes.data
-        if idx is None:
-            assert n_idx is None
-            m = n
-        else:
-            idx = np.ascontiguousarray(idx, dtype=np.uint32).reshape(-1)
-            m = len(idx) if n_idx is None else min(len(idx), int(np.asarray(n_idx).reshape(-1)[0]))
-        n_ref = None if n_idx is None else np.array([int(np.asarray(n_idx).reshape(-1)[0])], dtype=np.uint32)
+        idx_ptr, n_list, n_ptr, m, keep = _host_list(n, idx, n_idx)
         if cap is None:
             cap = (int(off[n]) - int(off[0]) if n else 0) + _abi.ARENA_PAD
         status = np.zeros(max(1, m), dtype=np.uint8)
@@ -1679,27 +1586,13 @@ def parse_pow_bodies(bodies, n=None, idx=None, n_idx=None, stream=None, cap=None
         ndata, noff = _aligned_bytes(cap), np.zeros(n + 1, dtype=np.uint32)
         stats = np.zeros(C.sizeof(_abi.BodyStats) // 8, dtype=np.uint64)
         ncol.data, ncol.offsets, ncol.cap = ndata.ctypes.data, noff.ctypes.data, cap
-        # (an empty list is not a NULL idx, which would mean every request)
-        keep_idx = idx if idx is None or len(idx) else np.zeros(1, dtype=np.uint32)
-        rc = lib().pwaf_parse_pow_bodies(C.byref(col), n, _abi.MEM_HOST, None if idx is None else keep_idx.ctypes.data, 0 if idx is None else len(idx),
-                                         None if n_ref is None else n_ref.ctypes.data, status.ctypes.data, hashes.ctypes.data, C.byref(ncol), stats.ctypes.data, None, 0, None)
-        if rc != 0:
-            _raise(rc, lib().pwaf_last_error().decode(errors="replace"))
+        _check(lib().pwaf_parse_pow_bodies(C.byref(col), n, _abi.MEM_HOST, idx_ptr, n_list, n_ptr, status.ctypes.data, hashes.ctypes.data, C.byref(ncol), stats.ctypes.data, None, 0, None))
+        del keep
         return status[:m], hashes[:n], (ndata, noff), stats.view(np.uint8)
     import torch
 
-    assert data.is_contiguous() and off.is_contiguous() and off.element_size() == 4
-    if n is None:
-        n = off.numel() - 1
-    assert off.numel() >= n + 1
     device = off.device
-    col.data, col.offsets = data.data_ptr(), off.data_ptr()
-    if idx is None:
-        assert n_idx is None
-        m = n
-    else:
-        assert idx.is_contiguous() and idx.element_size() == 4 and (n_idx is None or n_idx.element_size() == 4)
-        m = idx.numel()
+    idx_ptr, n_list, n_ptr, m, keep = _device_list(n, idx, n_idx)
     if stream is None:
         stream = torch.cuda.current_stream(device).cuda_stream
     if cap is None:
@@ -1711,15 +1604,11 @@ def parse_pow_bodies(bodies, n=None, idx=None, n_idx=None, stream=None, cap=None
     stats = torch.empty(C.sizeof(_abi.BodyStats), dtype=torch.uint8, device=device)
     need = int(lib().pwaf_parse_pow_bodies_scratch_bytes(n))
     scratch = torch.empty(need, dtype=torch.uint8, device=device)
-    keep_idx = idx if idx is None or m else torch.zeros(1, dtype=torch.int32, device=device)
     ncol.data, ncol.offsets, ncol.cap = ndata.data_ptr(), noff.data_ptr(), cap
-    rc = lib().pwaf_parse_pow_bodies(C.byref(col), n, _abi.MEM_DEVICE, None if idx is None else keep_idx.data_ptr(), 0 if idx is None else m,
-                                     None if n_idx is None else n_idx.data_ptr(), status.data_ptr(), hashes.data_ptr(), C.byref(ncol), stats.data_ptr(), scratch.data_ptr(), need,
-                                     C.c_void_p(stream))
-    if rc != 0:
-        _raise(rc, lib().pwaf_last_error().decode(errors="replace"))
+    _check(lib().pwaf_parse_pow_bodies(C.byref(col), n, _abi.MEM_DEVICE, idx_ptr, n_list, n_ptr, status.data_ptr(), hashes.data_ptr(), C.byref(ncol), stats.data_ptr(), scratch.data_ptr(), need,
+                                       C.c_void_p(stream)))
     status = status[:m]
-    status.body_scratch = (scratch, keep_idx, bodies)
+    status.body_scratch = (scratch, keep, bodies)
     return status, hashes[:n], (ndata, noff), stats
 
 
@@ -1729,9 +1618,7 @@ def parse_pow_body_one(body):
     b = body.encode() if isinstance(body, str) else bytes(body)
     buf = (C.c_uint8 * max(1, len(b))).from_buffer_copy(b or b"\0")
     st, h, at, ln = C.c_uint8(0xEE), (C.c_uint8 * 32)(), C.c_uint32(0), C.c_uint32(0)
-    rc = lib().pwaf_parse_pow_body_one(C.addressof(buf), len(b), C.byref(st), C.addressof(h), C.byref(at), C.byref(ln))
-    if rc != 0:
-        _raise(rc, lib().pwaf_last_error().decode(errors="replace"))
+    _check(lib().pwaf_parse_pow_body_one(C.addressof(buf), len(b), C.byref(st), C.addressof(h), C.byref(at), C.byref(ln)))
     return int(st.value), bytes(h), b[at.value:at.value + ln.value]
 
 
@@ -1748,11 +1635,7 @@ def derive_stats(stats) -> dict:
 
 def derive_scan_shape() -> dict:
     """TEST HOOK (pwaf_derive_scan_shape): the shape of derive_batch's scan, by the names of _abi.DERIVE_SCAN_SHAPE_FIELDS."""
-    out = (C.c_uint32 * 4)()
-    rc = lib().pwaf_derive_scan_shape(out)
-    if rc != 0:
-        _raise(rc, lib().pwaf_last_error().decode(errors="replace"))
-    return dict(zip(_abi.DERIVE_SCAN_SHAPE_FIELDS, (int(x) for x in out)))
+    return _scan_shape(lib().pwaf_derive_scan_shape, _abi.DERIVE_SCAN_SHAPE_FIELDS)
 
 
 def derive_batch(batch, uri_host=None, present=None, stream=None):
@@ -1781,14 +1664,10 @@ def derive_batch(batch, uri_host=None, present=None, stream=None):
             assert len(present) == n
         if isinstance(uri_host, (list, tuple)) and not (len(uri_host) == 2 and isinstance(uri_host[0], np.ndarray)):
             assert len(uri_host) == n
-            vals = [b"" if v is None else (v.encode() if isinstance(v, str) else bytes(v)) for v in uri_host]
             has = np.array([_abi.RAW_HAS_URI_HOST if v is not None else 0 for v in uri_host], dtype=np.uint8).reshape(-1)
             rest = np.full(n, _abi.RAW_HAS_HOST_HEADER | _abi.RAW_HAS_USER_AGENT, dtype=np.uint8) if present is None else present & ~np.uint8(_abi.RAW_HAS_URI_HOST)
             present = (rest | has).astype(np.uint8)
-            uo = np.zeros(n + 1, dtype=np.uint32)
-            if n:
-                uo[1:] = np.cumsum([len(v) for v in vals], dtype=np.uint64).astype(np.uint32)
-            uri_host = (np.frombuffer(b"".join(vals) + b"\0" * _abi.ARENA_PAD, dtype=np.uint8).copy(), uo)
+            uri_host = cookie_column(uri_host)
         elif uri_host is not None:
             if present is None:
                 raise ValueError("derive_batch: a uri_host column needs `present` to say which requests have a URI host")
@@ -1840,8 +1719,7 @@ def derive_batch(batch, uri_host=None, present=None, stream=None):
         out[c].data, out[c].offsets, out[c].cap = ptr(data[c]), ptr(offs[c]), caps[c]
     rc = lib().pwaf_derive_batch(C.byref(st), None if extra is None else C.byref(extra), out, ptr(stats), None if scratch is None else ptr(scratch), scratch_bytes,
                                  None if host_mode else C.c_void_p(stream))
-    if rc != 0:
-        _raise(rc, lib().pwaf_last_error().decode(errors="replace"))
+    _check(rc)
     if host_mode:
         if derive_stats(stats)["overflow"]:  # (cannot happen with the caps above: a column's bytes would be incomplete)
             raise PwafError(_abi.E_BATCH, f"derive_batch: a derived column did not fit its room: {derive_stats(stats)}")
@@ -1856,11 +1734,7 @@ def derive_batch(batch, uri_host=None, present=None, stream=None):
 
 def records_scan_shape() -> dict:
     """TEST HOOK (pwaf_records_scan_shape): the shape of evaluate_records_device's scan, by the names of _abi.RECORDS_SCAN_SHAPE_FIELDS."""
-    out = (C.c_uint32 * 4)()
-    rc = lib().pwaf_records_scan_shape(out)
-    if rc != 0:
-        _raise(rc, lib().pwaf_last_error().decode(errors="replace"))
-    return dict(zip(_abi.RECORDS_SCAN_SHAPE_FIELDS, (int(x) for x in out)))
+    return _scan_shape(lib().pwaf_records_scan_shape, _abi.RECORDS_SCAN_SHAPE_FIELDS)
 
 
 def verdict_from_record(v) -> Verdict:

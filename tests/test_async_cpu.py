@@ -14,7 +14,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 BUILD = os.path.join(HERE, "_build")
 SRCS = [os.path.join(HERE, "async_stub.cpp"), os.path.join(ROOT, "pingoo_amd", "csrc", "async.cpp")]
-DEPS = SRCS + [os.path.join(ROOT, "pingoo_amd", "csrc", "records.h"), os.path.join(ROOT, "include", "pwaf.h")]
+DEPS = SRCS + [os.path.join(ROOT, "pingoo_amd", "csrc", "records.h"), os.path.join(ROOT, "pingoo_amd", "csrc", "service.h"), os.path.join(ROOT, "include", "pwaf.h")]
 
 
 def build(name, *flags):

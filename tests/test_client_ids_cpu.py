@@ -21,7 +21,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 BUILD = os.path.join(HERE, "_build")
 SRC = os.path.join(HERE, "client_id_host.cpp")
-DEPS = [SRC, os.path.join(ROOT, "pingoo_amd", "csrc", "clientid.h"), os.path.join(ROOT, "include", "pwaf.h")]
+DEPS = [SRC, os.path.join(ROOT, "pingoo_amd", "csrc", "clientid.h"), os.path.join(ROOT, "pingoo_amd", "csrc", "service.h"), os.path.join(ROOT, "include", "pwaf.h")]
 UA, HOST = 4, 0  # PWAF_FIELD_USER_AGENT, PWAF_FIELD_HOST
 
 VECTORS = [("97.98.99.100", b"", b"", "iNQmb9TmM40TuEX88olXnSCciXgjuSF9o-Fhk28DFYk"),

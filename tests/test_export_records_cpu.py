@@ -20,7 +20,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 BUILD = os.path.join(HERE, "_build")
 SRC = os.path.join(HERE, "records_pack_host.cpp")
-DEPS = [SRC, os.path.join(ROOT, "pingoo_amd", "csrc", "records.h"), os.path.join(ROOT, "include", "pwaf.h")]
+DEPS = [SRC, os.path.join(ROOT, "pingoo_amd", "csrc", "records.h"), os.path.join(ROOT, "pingoo_amd", "csrc", "service.h"), os.path.join(ROOT, "include", "pwaf.h")]
 NONE = _abi.RECORD_NONE
 
 

@@ -19,7 +19,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 BUILD = os.path.join(HERE, "_build")
 SRC = os.path.join(ROOT, "tools", "powbody_host.cpp")
-DEPS = [SRC, os.path.join(ROOT, "pingoo_amd", "csrc", "powbody.h"), os.path.join(ROOT, "include", "pwaf.h")]
+DEPS = [SRC, os.path.join(ROOT, "pingoo_amd", "csrc", "powbody.h"), os.path.join(ROOT, "pingoo_amd", "csrc", "service.h"), os.path.join(ROOT, "include", "pwaf.h")]
 N, K, M, U = O.NONE, O.OK, O.MALFORMED, O.UNDECIDED
 NAMES = {N: "NONE", K: "OK", M: "MALFORMED", U: "UNDECIDED"}
 

@@ -12,7 +12,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 BUILD = os.path.join(HERE, "_build")
 SRC = os.path.join(HERE, "staging_host.cpp")
-DEPS = [SRC] + [os.path.join(ROOT, "pingoo_amd", "csrc", h) for h in ("staging.h", "records.h")] + [os.path.join(ROOT, "include", "pwaf.h")]
+DEPS = [SRC] + [os.path.join(ROOT, "pingoo_amd", "csrc", h) for h in ("staging.h", "records.h")] + [os.path.join(ROOT, "pingoo_amd", "csrc", "service.h"), os.path.join(ROOT, "include", "pwaf.h")]
 FLAGS = {"plain": ["-O2"], "sanitized": ["-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined"]}
 PACK_MAX = 1 << 20  # csrc/staging.h: kPackMax
 E_BATCH = -6        # include/pwaf.h: PWAF_E_BATCH

@@ -25,7 +25,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 BUILD = os.path.join(HERE, "_build")
 SRC = os.path.join(HERE, "pow_host.cpp")
-DEPS = [SRC] + [os.path.join(ROOT, "pingoo_amd", "csrc", h) for h in ("pow.h", "cookie.h", "clientid.h")] + [os.path.join(ROOT, "include", "pwaf.h")]
+DEPS = [SRC] + [os.path.join(ROOT, "pingoo_amd", "csrc", h) for h in ("pow.h", "cookie.h", "clientid.h")] + [os.path.join(ROOT, "pingoo_amd", "csrc", "service.h"), os.path.join(ROOT, "include", "pwaf.h")]
 A, P, F, U = O.ABSENT, O.PASSED, O.FAILED, O.UNDECIDED
 NOW = 1_800_000_000
 NAME = b"__pingoo_captcha"
