@@ -27,6 +27,8 @@
  *                                                              pwaf_verify_pow_one / pwaf_verify_pow (pwaf_keyset)
  *   serde_json::from_reader -> CaptchaVerifyRequestBody      pingoo/captcha.rs:50-57,291
  *                                                              pwaf_parse_pow_body_one / pwaf_parse_pow_bodies
+ *   which response a request gets    http_listener.rs:196-272; pingoo/captcha.rs:158-174
+ *                                                              pwaf_respond_one / pwaf_respond
  *
  * Plain pointers and sizes only; no C++/torch types. Never aborts across the ABI:
  * every failure is an int status (<0) plus pwaf_last_error().
@@ -742,6 +744,84 @@ int pwaf_parse_pow_body_one(const uint8_t *body, uint32_t len, uint8_t *status, 
 /* TEST HOOK, CPU: [0] entries per tile, [1] tiles per step of the base launch, [2] requests per workgroup of the copy launch, [3] the
  * least bound on the parse launch's workgroups with a list */
 int pwaf_parse_pow_scan_shape(uint32_t out[4]);
+
+/* ---- the listener's response decision (ABI 4, additive) ------------------------------------------------------
+ * What the reference's listener produces per request (http_listener.rs:196-272, serve_captcha_request: pingoo/captcha.rs:158-174): WHICH
+ * response the request gets, from what the earlier calls wrote where they wrote it — the verdict (pwaf_evaluate_*), the verified-cookie
+ * status (pwaf_verify_cookies), the route (pwaf_evaluate_*_routes) and the batch's PWAF_FIELD_PATH column (get_path's value, which both
+ * http_listener.rs:141 and captcha.rs:164 use) — plus ordered lists of request indices, by kind of response, that the follow-up calls take
+ * as they stand. It takes no engine and no key set. DESIGN.md §5.1.9 states it row by row; the FIRST row that applies decides:
+ *   1  rule_idx == PWAF_RULE_UA_GATE      BLOCKED, arg PWAF_RULE_UA_GATE (gate A, :196-198)
+ *   2  action == PWAF_ACTION_BYPASS       by the path, in captcha.rs:165-173's order: starts with /__pingoo/captcha/assets: CAPTCHA_ASSET;
+ *                                         equals /__pingoo/captcha/api/init: CAPTCHA_INIT; equals /__pingoo/captcha/api/verify:
+ *                                         CAPTCHA_VERIFY; anything else: CAPTCHA_NOT_FOUND. arg PWAF_RULE_CAPTCHA_ENDPOINT (gate B, :200-204)
+ *   3  cookie status INVALID              CAPTCHA_PAGE, arg PWAF_RULE_COOKIE (gate C, :233-235)
+ *   4  cookie status UNDECIDED            HOST_DECIDES, arg the verdict's rule_idx (the host validates the cookie with its own library and
+ *                                         then takes row 3, or reads the verdict as evaluated)
+ *   5  action BLOCK / CAPTCHA             BLOCKED / CAPTCHA_PAGE, arg rule_idx (:255, :258)
+ *   6  otherwise (ALLOW)                  route == NULL: FORWARD, arg PWAF_ROUTE_NONE; else FORWARD, arg route[i] (:266-270), or NOT_FOUND
+ *                                         when route[i] == PWAF_ROUTE_NONE (:272)
+ * An invalid cookie therefore does NOT turn a request with an empty User-Agent or one on a captcha endpoint into a captcha page: :196 and
+ * :200 run before :222. cookie_status == NULL: every request is ABSENT. Rows 1 and 2 follow the verdict's sentinels, so an engine created
+ * with PWAF_OPT_NO_UA_GATE / PWAF_OPT_NO_CAPTCHA_BYPASS needs no special case. pwaf_respond_one, the HOST and the DEVICE mode answer the same.
+ * Output: out[i] for every request; counts (nullable, PWAF_RESP_KINDS words, WRITTEN): the requests of each kind; and up to
+ * PWAF_RESP_MAX_LISTS lists: list l holds, in ASCENDING request order, the indices of the requests whose kind has its bit set in
+ * lists[l].kinds. *lists[l].n is WRITTEN with how many there are, which may exceed cap; only the first min(*n, cap) entries of idx are
+ * written, nothing at or beyond idx + cap. Masks may overlap and may be 0 (an empty list, *n == 0); idx may be NULL with cap 0 (count
+ * only). A list is exactly what pwaf_client_ids, pwaf_verify_cookies, pwaf_verify_pow, pwaf_parse_pow_bodies and pwaf_export_records take
+ * as idx / idx_cap / n_idx. n == 0 writes *n = 0 for every list and zero counts.
+ * Memory and streams: in->memory says where EVERY pointer lives: the path column, verdicts, cookie_status, route, out, counts and the idx
+ * and n of every list (the `lists` array itself is host memory). Of the batch only n and field[PWAF_FIELD_PATH] are looked at.
+ *   PWAF_MEM_DEVICE  at most one 64-byte memset and three launches (respond_classify_kernel, respond_base_kernel, respond_scatter_kernel)
+ *                    are enqueued on `stream` (hipStream_t; NULL = HIP's default stream) of the current device and the call returns at
+ *                    once. Nothing is allocated, nothing is copied. The call may follow pwaf_verify_cookies and
+ *                    pwaf_evaluate_device_routes, and be followed by the list consumers, on one stream without a synchronisation.
+ *                    scratch: pwaf_respond_scratch_bytes(n) bytes of device memory, 16-byte aligned, the call's own until the launches
+ *                    have run. The inputs are trusted as pwaf_evaluate_device trusts its batch (an action or status above 3 is not
+ *                    refused). Only requests whose action is BYPASS and whose path has at least 24 bytes (the shortest literal) have their
+ *                    path read: two 16-byte loads at the path's own alignment; they may pass the path's end by fewer than 16 bytes
+ *                    (PWAF_ARENA_PAD) and never begin before it.
+ *   PWAF_MEM_HOST    synchronous, plain C++, no HIP call; reads no byte outside a path; scratch and stream are ignored. An action or a
+ *                    cookie status above 3, or path offsets that decrease, refuse the call with PWAF_E_BATCH (naming the request)
+ *                    before anything is written.
+ * PWAF_E_INVALID_ARG, before anything runs: NULL in, verdicts or out; a bad struct_size or memory; with n > 0 a NULL path column;
+ * n_lists > PWAF_RESP_MAX_LISTS; lists == NULL with n_lists != 0; a list with idx == NULL and cap != 0, or with n == NULL; a mask with a
+ * bit at or above PWAF_RESP_KINDS; in DEVICE mode scratch NULL, not 16-byte aligned or smaller than pwaf_respond_scratch_bytes(n).
+ * pwaf_respond_one: the same decision for one request on the host (no GPU): what a per-request closure calls behind
+ * pwaf_verify_cookie_one and pwaf_evaluate_one_route. has_route == 0 stands for route == NULL. PWAF_E_INVALID_ARG for a NULL verdict or
+ * out, or a NULL path with path_len != 0; PWAF_E_BATCH for an action or status above 3. */
+#define PWAF_RESP_FORWARD 0u           /* a service handles it (:266-270); arg = route, or PWAF_ROUTE_NONE when no route column was given */
+#define PWAF_RESP_NOT_FOUND 1u         /* a route column was given and no route matches (:272); arg = PWAF_ROUTE_NONE */
+#define PWAF_RESP_BLOCKED 2u           /* new_blocked_response (:197, :255); arg = rule_idx (PWAF_RULE_UA_GATE for gate A) */
+#define PWAF_RESP_CAPTCHA_PAGE 3u      /* serve_captcha (:234, :258); arg = rule_idx, or PWAF_RULE_COOKIE for an invalid cookie */
+#define PWAF_RESP_CAPTCHA_ASSET 4u     /* captcha.rs:165 */
+#define PWAF_RESP_CAPTCHA_INIT 5u      /* captcha.rs:167 */
+#define PWAF_RESP_CAPTCHA_VERIFY 6u    /* captcha.rs:169 */
+#define PWAF_RESP_CAPTCHA_NOT_FOUND 7u /* captcha.rs:173 */
+#define PWAF_RESP_HOST_DECIDES 8u      /* the cookie is PWAF_COOKIE_UNDECIDED and neither gate A nor B answered; arg = rule_idx of the verdict as evaluated */
+#define PWAF_RESP_KINDS 9u
+#define PWAF_RESP_MAX_LISTS 4u
+#define PWAF_RULE_COOKIE 0xFFFFFFFCu   /* gate C: a present but invalid verified cookie (:233-235) */
+typedef struct pwaf_response {
+    uint8_t kind; /* PWAF_RESP_* */
+    uint8_t pad[3]; /* 0 */
+    uint32_t arg;
+} pwaf_response; /* 8 bytes */
+typedef struct pwaf_resp_list {
+    uint32_t kinds; /* bit k set: requests whose kind is k belong to the list */
+    uint32_t cap;   /* entries of idx */
+    uint32_t *idx;  /* nullable with cap 0: count only */
+    uint32_t *n;    /* WRITTEN (not accumulated): how many requests belong, which may exceed cap */
+} pwaf_resp_list;
+size_t pwaf_respond_scratch_bytes(uint32_t n); /* DEVICE mode scratch for a batch of n; HOST mode needs none */
+int pwaf_respond(const pwaf_batch *in, const pwaf_verdict *verdicts, const uint8_t *cookie_status /* nullable */, const uint32_t *route /* nullable */,
+                 pwaf_response *out, uint64_t *counts /* PWAF_RESP_KINDS, nullable, WRITTEN */, const pwaf_resp_list *lists, uint32_t n_lists,
+                 void *scratch, size_t scratch_bytes, void *stream);
+int pwaf_respond_one(const pwaf_verdict *verdict, uint8_t cookie_status, int has_route, uint32_t route, const char *path, uint32_t path_len,
+                     pwaf_response *out);
+/* TEST HOOK, CPU: [0] requests per tile (and per workgroup of the classify and scatter launches), [1] tiles per step of the base launch,
+ * [2] PWAF_RESP_MAX_LISTS, [3] PWAF_RESP_KINDS */
+int pwaf_respond_scan_shape(uint32_t out[4]);
 
 /* ---- records in device memory (ABI 4, additive) ----------------------------------------------------------
  * pwaf_evaluate_records for records that already lie in DEVICE memory — what pwaf_export_records wrote, or a replay file copied to the

@@ -41,6 +41,11 @@ POW_ABSENT, POW_PASSED, POW_FAILED, POW_UNDECIDED = 0, 1, 2, 3
 # pwaf_parse_pow_bodies / pwaf_parse_pow_body_one: one status per proof-of-work request body (CaptchaVerifyRequestBody, captcha.rs:50-57, :291)
 BODY_NONE, BODY_OK, BODY_MALFORMED, BODY_UNDECIDED = 0, 1, 2, 3
 POW_BODY_MAX_BYTES = 4096
+# pwaf_respond / pwaf_respond_one: which response a request gets (http_listener.rs:196-272; serve_captcha_request, captcha.rs:158-174)
+RESP_FORWARD, RESP_NOT_FOUND, RESP_BLOCKED, RESP_CAPTCHA_PAGE, RESP_CAPTCHA_ASSET, RESP_CAPTCHA_INIT, RESP_CAPTCHA_VERIFY, RESP_CAPTCHA_NOT_FOUND, RESP_HOST_DECIDES = range(9)
+RESP_KINDS, RESP_MAX_LISTS = 9, 4
+RESP_KIND_NAMES = ("forward", "not_found", "blocked", "captcha_page", "captcha_asset", "captcha_init", "captcha_verify", "captcha_not_found", "host_decides")
+RULE_COOKIE = 0xFFFFFFFC  # PWAF_RULE_COOKIE: gate C, a present but invalid verified cookie (pwaf_response.arg)
 N_FIELDS = 5
 FIELD_NAMES = ("host", "url", "path", "method", "user_agent")
 ARENA_PAD = 16
@@ -56,6 +61,9 @@ DERIVE_SCAN_SHAPE_FIELDS = ("tile", "step", "copy_group", "zero3")
 # pwaf_parse_pow_scan_shape (test hook): the meaning of out[0..3] (pwaf_parse_pow_bodies' scan: entries per tile, tiles per step of the base
 # launch, requests per workgroup of the copy launch, the least bound on the parse launch's workgroups with a list)
 PARSE_POW_SCAN_SHAPE_FIELDS = ("tile", "step", "copy_group", "min_groups")
+# pwaf_respond_scan_shape (test hook): the meaning of out[0..3] (pwaf_respond's scan: requests per tile, tiles per step of the base launch,
+# PWAF_RESP_MAX_LISTS, PWAF_RESP_KINDS)
+RESPOND_SCAN_SHAPE_FIELDS = ("tile", "step", "max_lists", "kinds")
 # pwaf_raw_columns.present: which of its sources a raw request has (pwaf_derive_batch)
 RAW_HAS_URI_HOST, RAW_HAS_HOST_HEADER, RAW_HAS_USER_AGENT = 1, 2, 4
 # pwaf_program_list_scans (test hook): the meaning of a descriptor's PWAF_LIST_SCAN_WORDS words (share_owner 0xFFFFFFFF: none)
@@ -237,6 +245,18 @@ class BodyStats(C.Structure):
 
     _fields_ = [("nonce_bytes", C.c_uint64), ("n", C.c_uint32), ("n_ok", C.c_uint32), ("n_malformed", C.c_uint32), ("n_undecided", C.c_uint32),
                 ("overflow", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class Response(C.Structure):
+    """pwaf_response: which response a request gets (pwaf_respond) — a RESP_* kind and its argument (a rule, a route or a RULE_* sentinel)."""
+
+    _fields_ = [("kind", C.c_uint8), ("pad", C.c_uint8 * 3), ("arg", C.c_uint32)]
+
+
+class RespList(C.Structure):
+    """pwaf_resp_list: one output list of pwaf_respond — the mask of kinds that belong, the room of idx, idx and the written count."""
+
+    _fields_ = [("kinds", C.c_uint32), ("cap", C.c_uint32), ("idx", C.c_void_p), ("n", C.c_void_p)]
 
 
 class Geo(C.Structure):

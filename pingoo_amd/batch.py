@@ -22,6 +22,9 @@ GEOIP_DTYPE = np.dtype(
 )
 VERDICT_DTYPE = np.dtype([("action", np.uint8), ("pad", np.uint8, (3,)), ("rule_idx", np.uint32)])
 assert GEOIP_DTYPE.itemsize == 24 and VERDICT_DTYPE.itemsize == 8
+# pwaf_response: which response a request gets (pwaf_respond)
+RESPONSE_DTYPE = np.dtype([("kind", np.uint8), ("pad", np.uint8, (3,)), ("arg", np.uint32)])
+assert RESPONSE_DTYPE.itemsize == 8
 # pwaf_geo: one GeoIP answer (engines created with OPT_GEO_ANSWERS)
 GEO_DTYPE = np.dtype([("asn", "<u4"), ("country", "S2"), ("reserved", "<u2")])
 assert GEO_DTYPE.itemsize == 8

@@ -13,8 +13,8 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libpwaf.so")
-SOURCES = ["frontend.cpp", "pattern.cpp", "dfa.cpp", "iptrie.cpp", "filter.cpp", "residual.cpp", "residual_jit.cpp", "rtc.cpp", "compile.cpp", "tableplan.cpp", "scanplan.cpp", "loaders.cpp", "batcher.cpp", "async.cpp", "node.cpp", "program_api.cpp", "engine.cpp", "pipeline.cpp", "evaluate.cpp", "evaluate_records.cpp", "kernels.hip", "scan.hip", "filter.hip", "confirm.hip", "verdict.hip", "attr.hip", "records.hip", "records_scan.hip", "clientid.hip", "derive.hip", "cookie.hip", "pow.hip", "powbody.hip"]
-HEADERS = ["frontend.h", "program.h", "program_handle.h", "engine_impl.h", "staging.h", "kernels.h", "wave.h", "hitrec.h", "colscan.h", "service.h", "residual.h", "confirm.h", "records.h", "clientid.h", "derive.h", "cookie.h", "pow.h", "powbody.h", "lscan_split.h", "dirtable.h", "georec.h", "tableplan.h", "scanplan.h", "verdictplan.h", "unicode_data.inc", os.path.join("..", "..", "include", "pwaf.h")]
+SOURCES = ["frontend.cpp", "pattern.cpp", "dfa.cpp", "iptrie.cpp", "filter.cpp", "residual.cpp", "residual_jit.cpp", "rtc.cpp", "compile.cpp", "tableplan.cpp", "scanplan.cpp", "loaders.cpp", "batcher.cpp", "async.cpp", "node.cpp", "program_api.cpp", "engine.cpp", "pipeline.cpp", "evaluate.cpp", "evaluate_records.cpp", "kernels.hip", "scan.hip", "filter.hip", "confirm.hip", "verdict.hip", "attr.hip", "records.hip", "records_scan.hip", "clientid.hip", "derive.hip", "cookie.hip", "pow.hip", "powbody.hip", "respond.hip"]
+HEADERS = ["frontend.h", "program.h", "program_handle.h", "engine_impl.h", "staging.h", "kernels.h", "wave.h", "hitrec.h", "colscan.h", "service.h", "residual.h", "confirm.h", "records.h", "clientid.h", "derive.h", "cookie.h", "pow.h", "powbody.h", "respond.h", "lscan_split.h", "dirtable.h", "georec.h", "tableplan.h", "scanplan.h", "verdictplan.h", "unicode_data.inc", os.path.join("..", "..", "include", "pwaf.h")]
 # host code that calls the HIP runtime (engine_impl.h): compiled as HIP like the kernels; every other .cpp is plain C++
 HIP_HOST_UNITS = ("engine.cpp", "pipeline.cpp", "evaluate.cpp", "evaluate_records.cpp", "rtc.cpp")
 

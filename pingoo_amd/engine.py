@@ -24,7 +24,7 @@ from typing import Dict, Iterable, List, Optional, Sequence, Tuple
 import numpy as np
 
 from . import _abi
-from .batch import GEO_DTYPE, RULE_HIT_DTYPE, VERDICT_DTYPE, Request, RequestBatch
+from .batch import GEO_DTYPE, RESPONSE_DTYPE, RULE_HIT_DTYPE, VERDICT_DTYPE, Request, RequestBatch
 
 _LIB = None
 # PWAF_LIB_VARIANT=prof loads libpwaf_prof.so, the -DPWAF_PROFILING build with the timing-experiment switches (tools/ only: results may
@@ -170,6 +170,11 @@ def lib():
     L.pwaf_parse_pow_bodies.argtypes = [C.POINTER(_abi.StrCol), C.c_uint32, C.c_uint32, vp, C.c_uint32, vp, vp, vp, C.POINTER(_abi.DerivedCol), vp, vp, C.c_size_t, vp]
     L.pwaf_parse_pow_body_one.argtypes = [vp, C.c_uint32, C.POINTER(C.c_uint8), vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
     L.pwaf_parse_pow_scan_shape.argtypes = [C.POINTER(C.c_uint32)]
+    L.pwaf_respond_scratch_bytes.argtypes = [C.c_uint32]
+    L.pwaf_respond_scratch_bytes.restype = C.c_size_t
+    L.pwaf_respond.argtypes = [C.POINTER(_abi.Batch), vp, vp, vp, vp, vp, C.POINTER(_abi.RespList), C.c_uint32, vp, C.c_size_t, vp]
+    L.pwaf_respond_one.argtypes = [C.POINTER(_abi.Verdict), C.c_uint8, C.c_int, C.c_uint32, vp, C.c_uint32, C.POINTER(_abi.Response)]
+    L.pwaf_respond_scan_shape.argtypes = [C.POINTER(C.c_uint32)]
     L.pwaf_derive_scratch_bytes.argtypes = [C.c_uint32]
     L.pwaf_derive_scratch_bytes.restype = C.c_size_t
     L.pwaf_derive_batch.argtypes = [C.POINTER(_abi.Batch), C.POINTER(_abi.RawColumns), C.POINTER(_abi.DerivedCol), vp, vp, C.c_size_t, vp]
@@ -751,6 +756,10 @@ class RuleEngine:
     def parse_pow_body_one(self, body):
         """parse_pow_body_one (below): one proof-of-work request body, on the host; needs nothing of the engine."""
         return parse_pow_body_one(body)
+
+    def respond(self, batch, verdicts, cookie_status=None, route=None, lists=(), caps=None, stream=None):
+        """respond (below): which response each request of a batch gets, and the lists the follow-up calls take; needs nothing of the engine."""
+        return respond(batch, verdicts, cookie_status=cookie_status, route=route, lists=lists, caps=caps, stream=stream)
 
     def derive_batch(self, batch, uri_host=None, present=None, stream=None):
         """derive_batch (below): the derived host, path and user_agent columns of a raw batch; needs nothing of the engine."""
@@ -1620,6 +1629,98 @@ def parse_pow_body_one(body):
     st, h, at, ln = C.c_uint8(0xEE), (C.c_uint8 * 32)(), C.c_uint32(0), C.c_uint32(0)
     _check(lib().pwaf_parse_pow_body_one(C.addressof(buf), len(b), C.byref(st), C.addressof(h), C.byref(at), C.byref(ln)))
     return int(st.value), bytes(h), b[at.value:at.value + ln.value]
+
+
+def respond_scan_shape() -> dict:
+    """TEST HOOK (pwaf_respond_scan_shape): the shape of respond's scan, by the names of _abi.RESPOND_SCAN_SHAPE_FIELDS."""
+    return _scan_shape(lib().pwaf_respond_scan_shape, _abi.RESPOND_SCAN_SHAPE_FIELDS)
+
+
+def _resp_mask(kinds) -> int:
+    """A tuple of _abi.RESP_* kinds (or a mask as an int) -> the mask of a pwaf_resp_list"""
+    if isinstance(kinds, (int, np.integer)):
+        return int(kinds)
+    mask = 0
+    for k in kinds:
+        mask |= 1 << int(k)
+    return mask
+
+
+def respond(batch, verdicts, cookie_status=None, route=None, lists=(), caps=None, stream=None):
+    """Which response each request of `batch` gets (pwaf_respond; include/pwaf.h): the reference's order of precedence
+    (http_listener.rs:196-272: gate A, gate B with serve_captcha_request's dispatch, gate C, the rules, the routes, 404) over what the
+    earlier calls wrote — verdicts (evaluate_*), cookie_status (verify_cookies; None: every request ABSENT) and route (evaluate_*_routes;
+    None: no route column) — and the batch's path column. -> (responses, counts, [(idx, n), ...]): one response per request (kind: an
+    _abi.RESP_*, arg: the rule, the route or a sentinel), the RESP_KINDS counters, and per entry of `lists` (each a tuple of RESP_* kinds;
+    at most RESP_MAX_LISTS) the ASCENDING indices of the requests whose kind is among them with their number n — what client_ids,
+    verify_cookies, verify_pow, parse_pow_bodies and export_records take as idx / n_idx. caps: the room of each list (default: the batch's
+    n, which no list exceeds; 0: count only); n may exceed it, the first min(n, cap) entries are written. Takes no engine.
+    RequestBatch: verdicts a VERDICT_DTYPE array, cookie_status uint8, route 32 bits wide (-1 / ROUTE_NONE: none); synchronous, on the CPU
+    -> a RESPONSE_DTYPE array, a uint64 array, [(uint32 array of min(n, cap) entries, int)].
+    DeviceBatch: device tensors (verdicts as evaluate_device returns them); one small memset and at most three launches are enqueued on
+    `stream` (default: torch's current stream, which must be the stream torch allocates on when the call is made: outputs and scratch come
+    from its caching allocator) and the call returns -> an (n, 2) int32 tensor (word 0: the kind, word 1: the arg), an int64 tensor of
+    RESP_KINDS counters, [(int32 tensor of cap entries, one-element int32 tensor)] to be read after the stream is synchronised; a
+    consumer on the same stream takes (idx, n) as they are. The scratch stays reachable as `responses.respond_scratch`."""
+    lists = [_resp_mask(k) for k in lists]
+    n = batch.n
+    caps = [n] * len(lists) if caps is None else [int(c) for c in caps]
+    assert len(caps) == len(lists)
+    st = batch.as_struct()
+    arr = (_abi.RespList * max(1, len(lists)))()
+    if isinstance(batch, RequestBatch):
+        verdicts = np.ascontiguousarray(verdicts, dtype=VERDICT_DTYPE)
+        assert len(verdicts) >= n
+        status = None if cookie_status is None else np.ascontiguousarray(cookie_status, dtype=np.uint8)
+        rt = None if route is None else np.ascontiguousarray(np.asarray(route).astype(np.int64) & 0xFFFFFFFF, dtype=np.uint32)
+        assert (status is None or len(status) >= n) and (rt is None or len(rt) >= n)
+        out = np.zeros(max(1, n), dtype=RESPONSE_DTYPE)
+        counts = np.zeros(_abi.RESP_KINDS, dtype=np.uint64)
+        res = []
+        for l, (mask, cap) in enumerate(zip(lists, caps)):
+            idx, cnt = np.zeros(max(1, cap), dtype=np.uint32), np.zeros(1, dtype=np.uint32)
+            arr[l].kinds, arr[l].cap, arr[l].idx, arr[l].n = mask, cap, idx.ctypes.data if cap else None, cnt.ctypes.data
+            res.append((idx, cnt))
+        _check(lib().pwaf_respond(C.byref(st), verdicts.ctypes.data, None if status is None else status.ctypes.data, None if rt is None else rt.ctypes.data, out.ctypes.data,
+                                  counts.ctypes.data, arr, len(lists), None, 0, None))
+        return out[:n], counts, [(idx[:min(int(cnt[0]), cap)], int(cnt[0])) for (idx, cnt), cap in zip(res, caps)]
+    import torch
+
+    device = batch.device
+    for t, width in ((verdicts, 8), (cookie_status, 1), (route, 4)):
+        assert t is None or (t.is_contiguous() and t.numel() * t.element_size() >= width * n)
+    if stream is None:
+        stream = torch.cuda.current_stream(device).cuda_stream
+    out = torch.empty((max(1, n), 2), dtype=torch.int32, device=device)
+    counts = torch.empty(_abi.RESP_KINDS, dtype=torch.int64, device=device)
+    res = []
+    for l, (mask, cap) in enumerate(zip(lists, caps)):
+        idx, cnt = torch.empty(max(1, cap), dtype=torch.int32, device=device), torch.empty(1, dtype=torch.int32, device=device)
+        arr[l].kinds, arr[l].cap, arr[l].idx, arr[l].n = mask, cap, idx.data_ptr() if cap else None, cnt.data_ptr()
+        res.append((idx[:cap], cnt))
+    need = int(lib().pwaf_respond_scratch_bytes(n))
+    scratch = torch.empty(need, dtype=torch.uint8, device=device)
+    _check(lib().pwaf_respond(C.byref(st), verdicts.data_ptr(), None if cookie_status is None else cookie_status.data_ptr(), None if route is None else route.data_ptr(),
+                              out.data_ptr(), counts.data_ptr(), arr, len(lists), scratch.data_ptr(), need, C.c_void_p(stream)))
+    out = out[:n]
+    out.respond_scratch = scratch
+    return out, counts, res
+
+
+def respond_one(verdict, cookie_status=0, route=None, path=b""):
+    """The same decision for one request on the host (pwaf_respond_one) -> (kind, arg): verdict an (action, rule_idx) pair or a record of
+    VERDICT_DTYPE, cookie_status an _abi.COOKIE_*, route None (no route column), an index, or -1 / ROUTE_NONE (no route matches), path the
+    request's derived path. What a per-request closure calls behind verify_cookie and evaluate_routed."""
+    v = _abi.Verdict()
+    if isinstance(verdict, (tuple, list)):
+        v.action, v.rule_idx = int(verdict[0]), int(verdict[1]) & 0xFFFFFFFF
+    else:
+        v.action, v.rule_idx = int(verdict["action"]), int(verdict["rule_idx"])
+    p = path.encode() if isinstance(path, str) else bytes(path)
+    buf = (C.c_uint8 * max(1, len(p))).from_buffer_copy(p or b"\0")
+    out = _abi.Response()
+    _check(lib().pwaf_respond_one(C.byref(v), int(cookie_status), 0 if route is None else 1, 0 if route is None else int(route) & 0xFFFFFFFF, C.addressof(buf), len(p), C.byref(out)))
+    return int(out.kind), int(out.arg)
 
 
 DERIVED_FIELDS = (0, 2, 4)  # PWAF_FIELD_HOST, _PATH, _USER_AGENT: pwaf_derive_batch's out[0..2]
